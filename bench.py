@@ -22,6 +22,11 @@ distribution of configs[2] (C3: 300-1500 features per frame, ragged).  Both Dela
 on the host (they are inputs of the GPU path, like the optical flow itself); `e2e` in the line says what the whole
 drop-in call reaches with them included.  Weak scaling: every rank owns F frames.
 
+A plain run sets up, warms up, times the K steps and prints the line; ``--dump-outputs DIR`` also writes what the
+last timed step computed (see dump_outputs).  Everything below except `roofline` is measured only with ``--full``
+(the CPU baselines and the oracle parity sample, the two-stream probe, the end-to-end and latency legs, and for
+N > 1 the sharded leg).
+
 Prints ONE JSON line on rank 0 (contract in the task statement) with these extra objects:
   roofline      algorithmic bytes per launch (8*(3N+N)+12*(T1+T2)+12 per frame) / average duration of
                 the dominant kernel, measured with HIP events recorded on its launch stream around that kernel
@@ -569,6 +574,26 @@ def latency_leg(args, device, sizes, seed, frames=100):
     return out
 
 
+DUMP_LIMIT_BYTES = 64 << 20
+
+
+def dump_outputs(dirname, arrays, seed=2024):
+    """--dump-outputs: what the last timed step computed, as DIR/<name>.npy in float64 (status codes are small integers:
+    exact) — raw_scale, height_level, status (the whole sequence: gathered for N > 1), scale_filtered (the window median
+    over it) and height (this rank's frames).  Beyond 64 MB in all, every array keeps the same seeded sample of its frames,
+    whose indices go to DIR/<name>_index.npy."""
+    os.makedirs(dirname, exist_ok=True)
+    host = {k: v.double().cpu().numpy() for k, v in arrays.items()}
+    total = sum(a.nbytes for a in host.values())
+    for name, a in host.items():
+        if total > DUMP_LIMIT_BYTES:
+            k = int(a.size * DUMP_LIMIT_BYTES / (2 * total))           # (half the budget: the index files take the other half)
+            idx = np.sort(np.random.default_rng(seed).choice(a.size, k, replace=False))
+            np.save(os.path.join(dirname, name + "_index.npy"), idx.astype(np.float64))
+            a = a[idx]
+        np.save(os.path.join(dirname, name + ".npy"), a)
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
@@ -602,7 +627,14 @@ def main():
     ap.add_argument("--alias-pool", action="store_true",
                     help="diagnostic: every tile reads the feature planes of the SAME pool frames (cache-resident: 41 %% "
                          "less HBM traffic); the JSON line is marked and is not a benchmark result")
+    ap.add_argument("--full", action="store_true",
+                    help="also the secondary measurements: CPU baselines and the oracle parity sample, the two-stream probe, the "
+                         "end-to-end and latency legs, the sharded leg for N > 1 (off: the headline steps alone)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write what the last timed step computed as DIR/<name>.npy (float64)")
     args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
     if args.tile_above > 0:
         TILE_ABOVE[0] = args.tile_above
     if args.workload == "gridded":
@@ -621,7 +653,7 @@ def main():
     pool_n = min(pool_n, frames_req)
     sizes = frame_sizes(args, pool_n)
     rank_env = int(os.environ.get("RANK", "0"))
-    want_cpu = args.gpus == 1 and rank_env == 0 and not args.no_cpu_baseline
+    want_cpu = args.full and args.gpus == 1 and rank_env == 0 and not args.no_cpu_baseline
 
     # ---- everything that forks, before the GPU runtime exists -------------------------------------------------
     from mvoscalerecovery_amd import packing
@@ -776,12 +808,18 @@ def main():
     kernel_ms_avg = float(np.mean([p[0] for p in prof]))                               # scale kernel (+ its exact pass)
     road_ms_avg = float(np.mean([p[1] for p in prof]))                                 # road_model_kernel
     ctx.profile(False)
+    if rank == 0 and args.dump_outputs:
+        g = last_gather[0]
+        dump_outputs(args.dump_outputs, {"raw_scale": g.raw() if g is not None else rec.raw[:F],
+                                         "height_level": g.level() if g is not None else rec.level[:F],
+                                         "status": g.status() if g is not None else rec.status[:F],
+                                         "scale_filtered": filtered, "height": height[:F]})
 
     # ---- probe: the same K steps alternating between TWO streams (two contexts: a workspace and a record each),
     # so that the road model of step k — serial behind its scale kernel on one stream — can run under the scale kernel of step
     # k+1.  Reported beside the headline (whose config is "single stream"), never in its place.
     two_streams = None
-    if n_gpus == 1 and not args.c4 and not dense and not os.environ.get("MVOSR_BENCH_NO_TWO_STREAMS"):
+    if args.full and n_gpus == 1 and not args.c4 and not dense and not os.environ.get("MVOSR_BENCH_NO_TWO_STREAMS"):
         try:
             ctx2 = _lib.Context(local)
             stream2 = torch.cuda.Stream(device=local)
@@ -830,7 +868,7 @@ def main():
         st_all = whole_st.cpu().numpy()
 
     sharded = None
-    if not args.no_e2e and not args.c4 and pf_pool.max_feat <= 4000 and (n_gpus > 1 or args.e2e_sharded):
+    if not args.no_e2e and not args.c4 and pf_pool.max_feat <= 4000 and ((args.full and n_gpus > 1) or args.e2e_sharded):
         # every rank takes part (the leg has a collective); this context's streams go first (see below)
         torch.cuda.synchronize()
         keep.clear()
@@ -929,7 +967,8 @@ def main():
                 line["cpu_baseline_all_cores"] = {"error": "%s: %s" % (type(exc).__name__, exc)}
         if dense:
             line["host_tile_layout_ms_per_frame"] = getattr(build_pool, "host_layout_ms_per_frame", None)
-        if n_gpus == 1 and not args.no_e2e:
+        legs_e2e = args.full and n_gpus == 1 and not args.no_e2e
+        if legs_e2e:
             # The secondary legs run in their own context.  This one's two streams go first: with torch's two and the legs'
             # two the process would own six — more than ROCm's four hardware queues per process (GPU_MAX_HW_QUEUES), and
             # streams that share a queue serialise: the end-to-end leg's upload stream stopped overlapping its kernels
@@ -941,7 +980,7 @@ def main():
             line["e2e_sharded"] = sharded
         if two_streams is not None:
             line["two_streams"] = two_streams
-        if n_gpus == 1 and not args.no_e2e and dense:
+        if legs_e2e and dense:
             # dense frames end to end: host Qhull (~140 CPU-ms per call and frame) bounds it; the tile layout is included
             try:
                 line["e2e"] = e2e_leg(args, local, sizes, 2024, 96)
@@ -955,7 +994,7 @@ def main():
                 line["e2e_gpu_exact"] = e2e_gpu_leg(args, local, sizes, 2024, 1024, exact=True)
             except Exception as exc:                                    # noqa: BLE001
                 line["e2e_gpu_exact"] = {"error": "%s: %s" % (type(exc).__name__, exc)}
-        if n_gpus == 1 and not args.no_e2e and not dense and args.workload == "gridded":
+        if legs_e2e and not dense and args.workload == "gridded":
             # the decline path: a quarter of these frames goes to the host's SciPy (worker pool), the rest stays on the device
             for key, kw in (("e2e_gpu_exact", {"exact": True}), ("e2e_gpu_triangulation", {})):
                 try:
@@ -966,7 +1005,7 @@ def main():
                 line["e2e"] = e2e_leg(args, local, sizes, 2024, 2048)
             except Exception as exc:                                    # noqa: BLE001
                 line["e2e"] = {"error": "%s: %s" % (type(exc).__name__, exc)}
-        elif n_gpus == 1 and not args.no_e2e and not dense:
+        elif legs_e2e and not dense:
             try:
                 line["e2e"] = e2e_leg(args, local, sizes, 2024, 4096)
             except Exception as exc:                                    # noqa: BLE001

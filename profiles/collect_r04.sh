@@ -5,8 +5,8 @@ R=${GRAFT_REPO_ROOT:-$(cd "$(dirname "$0")/.." && pwd)}
 OUT=$R/gpurun_out
 mkdir -p $OUT
 cd $R
-timeout 600 python bench.py > $OUT/r04_bench.json 2> $OUT/r04_bench.err
-timeout 600 python bench.py --workload kitti > $OUT/r04_bench_kitti.json 2> $OUT/r04_bench_kitti.err
+timeout 600 python bench.py --full > $OUT/r04_bench.json 2> $OUT/r04_bench.err
+timeout 600 python bench.py --full --workload kitti > $OUT/r04_bench_kitti.json 2> $OUT/r04_bench_kitti.err
 : > $OUT/r04_delaunay_bench.jsonl
 for a in "" "--seeded --keep 0.95" "--seeded --keep 0.95 --no-carry" "--seeded --keep 0.85" "--seeded --keep 0.85 --no-carry" \
          "--points 900 --sets 8192" "--points 900 --sets 8192 --seeded --keep 0.95" "--ragged 300:1500 --sets 8192" "--ragged 300:1500 --sets 8192 --seeded --keep 0.95"; do

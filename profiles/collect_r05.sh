@@ -5,9 +5,9 @@ R=${GRAFT_REPO_ROOT:-$(cd "$(dirname "$0")/.." && pwd)}
 OUT=$R/gpurun_out
 mkdir -p $OUT
 cd $R
-timeout 900 python bench.py > $OUT/r05_bench.json 2> $OUT/r05_bench.err
-timeout 900 python bench.py --workload kitti > $OUT/r05_bench_kitti.json 2> $OUT/r05_bench_kitti.err
-timeout 900 python bench.py --features 20000 > $OUT/r05_bench_dense.json 2> $OUT/r05_bench_dense.err
+timeout 900 python bench.py --full > $OUT/r05_bench.json 2> $OUT/r05_bench.err
+timeout 900 python bench.py --full --workload kitti > $OUT/r05_bench_kitti.json 2> $OUT/r05_bench_kitti.err
+timeout 900 python bench.py --full --features 20000 > $OUT/r05_bench_dense.json 2> $OUT/r05_bench_dense.err
 # the Qhull-rows kernel alone (2000 points, ragged 300-1500) and its phase shares
 QH_FRAMES=512,4096,16384 timeout 300 python profiles/qhull_gpu_check.py 2048 2000 > $OUT/r05_qhull_check.txt 2>&1
 QH_FRAMES=8192,32768 timeout 300 python profiles/qhull_gpu_check.py 2048 0 | tail -2 >> $OUT/r05_qhull_check.txt 2>&1

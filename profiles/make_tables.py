@@ -4,7 +4,7 @@ round (profiles/r0N_*.json / .jsonl / .csv / .txt), so that no number in those d
 
     python profiles/make_tables.py [r04]        # rewrites the text between <!-- TAG-tables:begin --> and <!-- TAG-tables:end -->
 
-Sources: r0N_bench.json / r0N_bench_kitti.json (the bench lines: `python bench.py [--workload kitti]`), r0N_bench_c4_1gpu.json
+Sources: r0N_bench.json / r0N_bench_kitti.json (the bench lines: `python bench.py --full [--workload kitti]`), r0N_bench_c4_1gpu.json
 (BASELINE configs[3] literally, on one GPU), r0N_summary.md's source r0N_kernel_stats.csv (rocprofv3 --kernel-trace --stats),
 r0N_delaunay_bench.jsonl (profiles/bench_delaunay.py), r0N_e2e_{scale,rescale}_busy.txt (profiles/e2e_gpu_busy.py),
 r0N_fixed_mode_accuracy.json (profiles/fixed_mode_accuracy.py), traffic.json (PMC passes).

@@ -186,7 +186,7 @@ def test_bench_line_contract(gpu):
     for k in ("RANK", "LOCAL_RANK", "WORLD_SIZE", "MASTER_ADDR", "MASTER_PORT"):
         env.pop(k, None)
     p = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--frames", "8192", "--pool", "64", "--steps", "3", "--warmup", "1",
-                        "--no-e2e"], capture_output=True, text=True, env=env, timeout=600)
+                        "--no-e2e", "--full"], capture_output=True, text=True, env=env, timeout=600)
     assert p.returncode == 0, p.stderr[-2000:]
     lines = [ln for ln in p.stdout.splitlines() if ln.startswith("{")]
     assert len(lines) == 1
@@ -208,6 +208,42 @@ def test_bench_line_contract(gpu):
         p2 = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--gpus", "2", "--frames", "4096", "--pool", "32", "--steps", "1",
                              "--warmup", "1", "--no-e2e", "--no-cpu-baseline"], capture_output=True, text=True, env=env, timeout=600)
         assert p2.returncode != 0 and not [ln for ln in p2.stdout.splitlines() if ln.startswith("{")]
+
+
+def test_bench_plain_run_and_dumped_outputs(gpu, tmp_path):
+    """A plain bench.py run (no --full) times the headline steps alone: no CPU baseline, no parity sample, no probe or
+    end-to-end legs.  --dump-outputs writes what the last timed step computed, float64, one array per output; the raw
+    scales are the bytes raw_scale_crc32 was taken over, and a second run with the same arguments writes the same arrays."""
+    import json
+    import subprocess
+    import sys
+    import zlib
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    env = dict(os.environ)
+    for k in ("RANK", "LOCAL_RANK", "WORLD_SIZE", "MASTER_ADDR", "MASTER_PORT"):
+        env.pop(k, None)
+    dumps = []
+    for k in range(2):
+        out = tmp_path / ("out%d" % k)
+        p = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--gpus", "1", "--frames", "4096", "--pool", "64", "--steps", "2",
+                            "--warmup", "1", "--dump-outputs", str(out)], capture_output=True, text=True, env=env, timeout=600)
+        assert p.returncode == 0, p.stderr[-2000:]
+        lines = [ln for ln in p.stdout.splitlines() if ln.startswith("{")]
+        assert len(lines) == 1
+        d = json.loads(lines[0])
+        for key in ("cpu_baseline", "parity_mismatches_vs_oracle", "two_streams", "e2e", "e2e_gpu_triangulation", "e2e_gpu_exact",
+                    "e2e_rescale", "e2e_sharded", "latency"):
+            assert key not in d, key
+        assert d["steps"] == 2 and d["warmup"] == 1 and abs(d["value"] - 4096 / (d["ms_per_step"] * 1e-3)) < 1e-6 * d["value"]
+        arrs = {n: np.load(out / (n + ".npy")) for n in ("raw_scale", "height_level", "status", "scale_filtered", "height")}
+        for n, a in arrs.items():
+            assert a.dtype == np.float64 and a.shape == (4096,), (n, a.dtype, a.shape)
+        assert zlib.crc32(arrs["raw_scale"].tobytes()) == d["raw_scale_crc32"]
+        st, cnt = np.unique(arrs["status"].astype(np.int64), return_counts=True)
+        assert {str(s): int(c) for s, c in zip(st, cnt)} == d["status_histogram"]
+        dumps.append(arrs)
+    for n in dumps[0]:
+        assert np.array_equal(dumps[0][n], dumps[1][n], equal_nan=True), n
 
 
 def test_bench_multi_rank_dry_runs(gpu):
@@ -291,7 +327,7 @@ def test_bench_e2e_sharded_leg(gpu):
     env = dict(os.environ)
     for k in ("RANK", "LOCAL_RANK", "WORLD_SIZE", "MASTER_ADDR", "MASTER_PORT"):
         env.pop(k, None)
-    common = ["--steps", "2", "--warmup", "1", "--no-cpu-baseline", "--frames", "2048", "--pool", "64"]
+    common = ["--steps", "2", "--warmup", "1", "--no-cpu-baseline", "--frames", "2048", "--pool", "64", "--full"]
     for extra, world in ((["--gpus", "2", "--share-gpu"], 2), (["--e2e-sharded"], 1)):
         p = subprocess.run([sys.executable, os.path.join(root, "bench.py")] + extra + common, capture_output=True, text=True, env=env, timeout=1500)
         assert p.returncode == 0, p.stderr[-3000:]
