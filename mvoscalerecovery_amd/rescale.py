@@ -49,6 +49,7 @@ import numpy as np
 from . import _lib
 from . import constants as K
 from . import packing
+from . import stream
 from .engine import DeviceBatch, ScaleEngine, frame_tables, pack_upload_native
 
 EDGE_POTENTIAL = [[3, 1], [2, 2], [2, 2], [0, 4]]     # rescale.py:32
@@ -59,6 +60,7 @@ RANSAC_GOAL = 0.8                                     # estimate_road_norm.py:68
 RANSAC_MIN_POINTS = 12                                # rescale.py:152
 MIN_VALID_FOR_RETRI = 10                              # rescale.py:133
 SLEW = 0.3                                            # rescale.py:169-172
+_FIELDS = ("raw_scale", "height_level", "model", "best_ic", "used", "n_kept", "status")     # a chunk's results, per frame
 
 
 def good_bits(edge_potential=EDGE_POTENTIAL, prob_threshold=0.6):
@@ -85,7 +87,9 @@ def good_bits(edge_potential=EDGE_POTENTIAL, prob_threshold=0.6):
     return bits
 
 
-class ScaleEstimator:
+class ScaleEstimator(stream.StreamKnobs):
+    N_HYP = RANSAC_ITERATIONS
+
     def __init__(self, absolute_reference, window_size=6, device=0, ransac_seed=None, sampler=None,
                  delaunay_workers=None, verbose=False, triangulation=None, sampling=None):
         # reference attributes (rescale.py:24-35)
@@ -323,14 +327,6 @@ class ScaleEstimator:
         return self.scale_calculation_ransac_batch([s[0] for s in sel])
 
     # ---- the device-resident path ------------------------------------------------------------------------------
-    GPU_CHUNK = 8192            # frames per chunk, at most (a call of F frames uses chunks of F/4, 512 at least)
-    GPU_RESIDENT = 512          # frames the GPU works on at once (two 8-wavefront workgroups per CU)
-    GPU_CHUNK_POINTS = 10000000 # ... and features per chunk
-    GPU_RAMP_FRACTIONS = (1 / 6, 1 / 3, 1 / 2, 2 / 3, 5 / 6)   # the short first chunks, as fractions of a full one (scale_calculator.py)
-    GPU_PIPELINE = 2            # chunks queued on the device behind the one being collected
-    GPU_SIDE_DOWNLOADS = os.environ.get("MVOSR_SIDE_DOWNLOADS", "1") != "0"   # streamed batches: results to page-locked memory by a copy kernel, no copy engine (scale_calculator.ScaleEstimator.GPU_SIDE_DOWNLOADS)
-    N_HYP = RANSAC_ITERATIONS
-
     def _rescale_params(self, frame_base):
         return _lib.RescaleParams(self._good_bits, MIN_VALID_FOR_RETRI, -80.0, -85.0, 0.9, RANSAC_MIN_POINTS, self.N_HYP,
                                   RANSAC_THRESHOLD, RANSAC_GOAL, float(self.absolute_reference), self._seed, int(frame_base))
@@ -462,10 +458,6 @@ class ScaleEstimator:
                 return a + int(j), below
         return None
 
-    def _resident_frames(self, max_pts):
-        """Frames the triangulation kernel works on at a time (mvosr_delaunay_frames_per_cu x CUs)."""
-        return max(self.GPU_RESIDENT, int(self.ctx.lib.mvosr_delaunay_frames_per_cu(int(max_pts))) * int(self.ctx.n_cu))
-
     def _max_points(self):
         """Largest frame the device-resident kernels take (flat_selection + RANSAC hold a frame's survivors, rows'
         heights and flags in one workgroup's LDS: 42 B per feature + 12 KB)."""
@@ -482,23 +474,16 @@ class ScaleEstimator:
         return self._host_collect(rec, stage)
 
     # The host path in steps none of which waits for more than its own inputs (round 6: a deferred re-run advances through them while
-    # the call's later chunks run, _advance_deferred): packed + first triangulations started -> (those back) uploaded, the vote
+    # the call's later chunks run, stream.advance): packed + first triangulations started -> (those back) uploaded, the vote
     # launched, its keep words on their way -> (those back) second triangulations started -> (those back) uploaded, flat_selection +
     # RANSAC launched, results on their way -> collected.
-    def _host_begin(self, f3s, f2s, frame_base, slot=0, background=False, ctx=None):
+    def _host_begin(self, f3s, f2s, frame_base, slot=stream.SLOT_CHUNK, background=False, ctx=None):
         pf = packing.pack_features(f3s, f2s, self.vanish)                                   # rescale.py:115-117
         if pf.n_frames and pf.max_feat > self._max_points():
             self._refuse_oversized(pf, frame_base if np.isscalar(frame_base) else self._frame_counter)
         pf.extra["canonical"] = True
-        return {"pf": pf, "h1": packing.submit_tri1(pf, self.delaunay_workers, slot=slot, background=background), "step": 0,   # :124
+        return {"pf": pf, "h1": packing.submit_tri1(pf, self.delaunay_workers, slot=slot, background=background),   # :124
                 "ctx": ctx or self.ctx}
-
-    def _redo_context(self):
-        """A second context on the device (its own stream, workspace, caches) for the re-runs that advance while later chunks run: on the
-        estimator's own stream their few launches would sit BEHIND the chunks already queued — two chunks, 8 ms each — at every step."""
-        if getattr(self, "_redo_ctx", None) is None:
-            self._redo_ctx = _lib.Context(self.ctx.device)
-        return self._redo_ctx
 
     def _host_keep_start(self, rec):
         ctx, lib, pf = rec["ctx"], self.ctx.lib, rec["pf"]
@@ -509,15 +494,14 @@ class ScaleEstimator:
         _lib.check(lib.mvosr_graph_keep_batch(ctx.handle, C.byref(bs), C.c_uint32(self._good_bits), MIN_VALID_FOR_RETRI, None,
                                               aux["keep"].ptr, None, None), "mvosr_graph_keep_batch")
         aux.mark_done()
-        rec.update(db=db, aux=aux, step=1)
+        rec.update(db=db, aux=aux)
 
-    def _host_tri2_start(self, rec, slot=1, background=False):
+    def _host_tri2_start(self, rec, slot=stream.SLOT_CHUNK_TRI2, background=False):
         pf = rec["pf"]
         keep = rec["aux"]["keep"].download()
         rec["keep"] = keep
         rec["masks"] = [keep[pf.frame_slice(f)] >= 0 for f in range(pf.n_frames)]
         rec["h2"] = packing.submit_tri2(pf, rec["masks"], self.delaunay_workers, slot=slot, background=background)   # :134-137
-        rec["step"] = 2
 
     def _host_flat_start(self, rec, frame_base, frame_ids, id_triples, stage):
         pf, db = rec["pf"], rec["db"]
@@ -528,7 +512,6 @@ class ScaleEstimator:
         rec["out"], rec["flags"], side = self._launch_flat_ransac(db, rec["aux"]["keep"].ptr, None, frame_base, frame_ids, id_triples, stage,
                                                                   max(max_tri, 1), ctx=rec["ctx"])
         rec["side"] = side + [rec["aux"]]
-        rec["step"] = 3
 
     def _host_collect(self, rec, stage):
         pf = rec["pf"]
@@ -538,13 +521,13 @@ class ScaleEstimator:
         st = {"pf": pf, "db": rec["db"], "out": rec["out"], "flags": rec["flags"], "side": rec["side"], "host_errors": host_errors, "keep": rec["keep"]}
         if stage:
             res["stage"] = self._stage_outputs(st, host=True)
-        self._free_chunk(st)
+        stream.free_blocks(st)
         res["host_errors"] = host_errors
         return res
 
     @staticmethod
     def _collect(out, F):
-        return {k: out[k].download() for k in ("raw_scale", "height_level", "model", "best_ic", "used", "n_kept", "status")}
+        return {k: out[k].download() for k in _FIELDS}
 
     def _stage_outputs(self, st, host=False):
         """Per frame: the vote's mask (graph.py:35), the second triangulation's rows and flat_selection's flags."""
@@ -563,27 +546,15 @@ class ScaleEstimator:
             flags = [fl[toff[f]:toff[f] + cnt2[f]] for f in range(F)]
         return {"valid": [keep[pf.frame_slice(f)] > 0 for f in range(F)], "tris2": rows, "tri_flags": flags}
 
-    @staticmethod
-    def _free_chunk(st):
-        for k in ("out", "flags"):
-            if st.get(k) is not None:
-                st[k].free()
-        for blk in st.get("side") or []:
-            blk.free()
-        if st.get("db") is not None:
-            st["db"].free()
-
     def _chunk_dev_finish(self, st, f3s, f2s, frame_base, id_triples, stage, defer=None):
         """Results of a chunk started by ``_chunk_dev_gpu``; frames whose triangulation the device declined (degenerate point
         sets, fewer than 3 points) are redone on the host's triangulations with their own sample counters — at once, or, with
-        ``defer`` (a list; streamed batches), in ONE batch after the call's last chunk (``_finish_deferred``): the re-run is waited
-        for, and between the chunks that wait drained the pipeline (80 declined frames in 16 384: 529 -> 93 k frames/s in the
+        ``defer`` (the call's re-run records; streamed batches), after the call's last chunk (``stream.finish_all``): the re-run is
+        waited for, and between the chunks that wait drained the pipeline (80 declined frames in 16 384: 529 -> 93 k frames/s in the
         sibling estimator's fixed mode, scale_calculator._chunk_gpu_finish)."""
-        F = len(f3s)
         if not st["gpu"]:
             return self._chunk_dev_host(f3s, f2s, frame_base, None, id_triples, stage)
         db = st["db"]
-        early = None
         if defer is not None and not stage and self.GPU_REDO_EARLY:
             # the call's LAST chunk: the frames its first triangulation declined are known behind that kernel.  This thread has nothing
             # else to do: it takes them through their first triangulation (waited for — the chunk's other kernels are running), the
@@ -591,117 +562,84 @@ class ScaleEstimator:
             s1e = db.early_status()
             if s1e is not None and s1e.any() and int(np.count_nonzero(s1e)) <= self.GPU_REDO_EARLY_MAX:
                 ef = np.nonzero(s1e != 0)[0]
-                rec = self._host_begin([f3s[f] for f in ef], [f2s[f] for f in ef], 0, slot=24, background=True, ctx=self._redo_context())
-                rec["ids"] = frame_base + ef
-                rec["triples"] = None if id_triples is None else [id_triples[f] for f in ef]
-                self._host_keep_start(rec)
-                self._host_tri2_start(rec, slot=25, background=True)
-                early = (ef, rec)
+                early = st["early"] = self._rerun(None, ef, f3s, f2s, frame_base, id_triples, (stream.SLOT_EARLY, stream.SLOT_EARLY_TRI2))
+                self._host_keep_start(early.rec)
+                self._host_tri2_start(early.rec, slot=stream.SLOT_EARLY_TRI2, background=True)
+                early.step = 2
                 self.redo_early_status_hits = getattr(self, "redo_early_status_hits", 0) + 1
-        if defer and self.GPU_REDO_EARLY and not stage:
-            # (re-runs of earlier chunks are under way: the thread looks in on them every 0.2 ms instead of sleeping until this chunk's
-            # results arrive — each step of a record is taken the moment its inputs are there)
-            while any(item[6] is not None and item[6]["step"] < 3 for item in defer) and not (st["out"].ready() and db.info.ready()):
-                self._advance_deferred(defer)
-                time.sleep(2e-4)
-        res = self._collect(st["out"], F)
+        stream.advance_while(defer or (), lambda: not (st["out"].ready() and db.info.ready()))
+        res = self._collect(st["out"], len(f3s))
         s1, s2 = db.triangulation_status()
         redo = np.nonzero((s1 != 0) | (s2 != 0))[0]
         self.last_declined += len(redo)
         if stage:
             res["stage"] = self._stage_outputs(st)
-        self._free_chunk(st)
+        early = st.pop("early", None)
+        stream.free_blocks(st)
         res["host_errors"] = {}
         if early is not None:
-            if defer is not None and len(redo) == len(early[0]) and np.array_equal(redo, early[0]):
-                defer.append((res, redo, frame_base, f3s, f2s, id_triples, early[1]))      # (continues where the early steps left it)
+            if len(redo) == len(early.redo) and np.array_equal(redo, early.redo):
+                early.res = res
+                defer.append(early)                 # (continues where the early steps left it)
                 return res
-            self._free_chunk({"db": early[1].get("db"), "side": [early[1]["aux"]]})         # (more frames than the early read knew of: the merged way)
+            stream.free_blocks(early.rec)           # (more frames than the early read knew of: the merged way)
         if len(redo) and defer is not None:
-            rec = None
-            if self.GPU_REDO_EARLY and not stage and len(redo) <= self.GPU_REDO_EARLY_MAX and len(defer) < 8:
-                # (a few frames: their re-run starts now — first triangulations on the pool — and advances while later chunks run)
-                rec = self._host_begin([f3s[f] for f in redo], [f2s[f] for f in redo], 0, slot=8 + len(defer), background=True,
-                                       ctx=self._redo_context())
-                rec["ids"] = frame_base + redo
-                rec["triples"] = None if id_triples is None else [id_triples[f] for f in redo]
-                self.redo_early_started = getattr(self, "redo_early_started", 0) + 1
-            defer.append((res, redo, frame_base, f3s, f2s, id_triples, rec))
-            self._advance_deferred(defer)
+            started = self.GPU_REDO_EARLY and not stage and len(redo) <= self.GPU_REDO_EARLY_MAX and len(defer) < self.GPU_REDO_MAX_DEFERRED
+            # (a few frames: their re-run starts now — first triangulations on the pool — and advances while later chunks run)
+            defer.append(self._rerun(res, redo, f3s, f2s, frame_base, id_triples, (stream.SLOT_DEFER + len(defer), stream.SLOT_DEFER_TRI2 + len(defer)) if started else None))
+            self.redo_early_started = getattr(self, "redo_early_started", 0) + int(started)
+            stream.advance(defer)
             return res
-        if defer:
-            self._advance_deferred(defer)
+        stream.advance(defer or ())
         if len(redo):
             sub = self._chunk_dev_host([f3s[f] for f in redo], [f2s[f] for f in redo], 0, frame_base + redo,
                                        None if id_triples is None else [id_triples[f] for f in redo], stage)
-            for k in ("raw_scale", "height_level", "model", "best_ic", "used", "n_kept", "status"):
-                res[k][redo] = sub[k]
-            res["host_errors"] = {int(redo[j]): e for j, e in sub["host_errors"].items()}
-            if stage:
-                for k in ("valid", "tris2", "tri_flags"):
-                    for j, f in enumerate(redo):
-                        res["stage"][k][f] = sub["stage"][k][j]
+            self._scatter(res, redo, sub, 0, stage)
         return res
 
-    GPU_REDO_EARLY = True           # a deferred re-run of at most GPU_REDO_EARLY_MAX frames is started at once and advanced while later chunks run
-    GPU_REDO_EARLY_MAX = 16
+    def _scatter(self, res, frames, sub, first, stage):
+        stream.scatter(res, frames, sub, _FIELDS, "host_errors", first)
+        if stage:
+            for k in ("valid", "tris2", "tri_flags"):
+                for j, f in enumerate(frames):
+                    res["stage"][k][f] = sub["stage"][k][first + j]
 
-    def _advance_deferred(self, deferred):
-        """Started re-runs one step further wherever that step would not wait (see the _host_* steps); their launches go to a context of
-        their own (_redo_context) — nothing here blocks."""
-        for k, item in enumerate(deferred):
-            rec = item[6]
-            if rec is None:
-                continue
-            if rec["step"] == 0 and rec["h1"].ready():
-                self._host_keep_start(rec)
-            elif rec["step"] == 1 and rec["aux"].ready():
-                self._host_tri2_start(rec, slot=16 + k, background=True)
-            elif rec["step"] == 2 and rec["h2"].ready():
-                self._host_flat_start(rec, 0, rec["ids"], rec["triples"], False)
+    def _rerun(self, res, redo, f3s, f2s, frame_base, id_triples, slots=None):
+        """The re-run record of a chunk's frames ``redo``.  ``slots`` (the pool slots of its two triangulations): started now — its first
+        triangulations go to the pool, and stream.advance / stream.finish_all take it through the _host_* steps, launching on the
+        re-runs' own context; else it waits for the call's merged re-run (``_merged_rerun``)."""
+        r = stream.Rerun(res, redo, lambda: None, f3s=f3s, f2s=f2s, frame_base=frame_base, id_triples=id_triples)
+        if slots is None:
+            return r
+        rec = r.rec = self._host_begin([f3s[f] for f in redo], [f2s[f] for f in redo], 0, slot=slots[0], background=True,
+                                       ctx=self._redo_context())
+        rec["ids"] = frame_base + redo
+        rec["triples"] = None if id_triples is None else [id_triples[f] for f in redo]
+
+        def flat(wait):
+            self._host_flat_start(rec, 0, rec["ids"], rec["triples"], False)
+            if not wait:
                 self.redo_early_launched = getattr(self, "redo_early_launched", 0) + 1
+        r.chain = [(lambda: rec["h1"].ready(), lambda wait: self._host_keep_start(rec)),
+                   (lambda: rec["aux"].ready(), lambda wait: self._host_tri2_start(rec, slot=slots[1], background=not wait)),
+                   (lambda: rec["h2"].ready(), flat)]
+        r.collect, r.begun = (lambda: self._host_collect(rec, False)), True
+        r.free = lambda: (stream.free_blocks(rec), stream.wait_out(rec.get("h1"), rec.get("h2")))
+        return r
 
-    def _finish_deferred(self, deferred, stage):
-        """The declined frames of every chunk of a call through the host's triangulations, scattered back: the started re-runs each
-        finish their remaining steps (launches first, then the results), the others go in one merged batch."""
-        if not deferred:
-            return
-        self._advance_deferred(deferred)
-        started = [(k, item) for k, item in enumerate(deferred) if item[6] is not None]
-        for k, item in started:
-            if item[6]["step"] == 0:
-                self._host_keep_start(item[6])
-        for k, item in started:
-            if item[6]["step"] == 1:
-                self._host_tri2_start(item[6], slot=16 + k)
-        for k, item in started:
-            if item[6]["step"] == 2:
-                self._host_flat_start(item[6], 0, item[6]["ids"], item[6]["triples"], stage)
-        for k, item in started:
-            res, redo = item[0], item[1]
-            sub = self._host_collect(item[6], stage)
-            for key in ("raw_scale", "height_level", "model", "best_ic", "used", "n_kept", "status"):
-                res[key][redo] = sub[key]
-            for j, e in sub["host_errors"].items():
-                res["host_errors"][int(redo[j])] = e
-        deferred = [item[:6] for item in deferred if item[6] is None]
-        if not deferred:
-            return
-        f3_all, f2_all, ids, trs, where = [], [], [], [], []
-        for k, (res, redo, frame_base, f3s, f2s, id_triples) in enumerate(deferred):
-            for f in redo:
-                f3_all.append(f3s[f]); f2_all.append(f2s[f]); ids.append(frame_base + int(f)); where.append((k, int(f)))
-                trs.append(None if id_triples is None else id_triples[f])
-        sub = self._chunk_dev_host(f3_all, f2_all, 0, np.asarray(ids, dtype=np.int64), None if trs[0] is None else trs, stage)
-        for i, (k, f) in enumerate(where):
-            res = deferred[k][0]
-            for key in ("raw_scale", "height_level", "model", "best_ic", "used", "n_kept", "status"):
-                res[key][f] = sub[key][i]
-            if i in sub["host_errors"]:
-                res["host_errors"][f] = sub["host_errors"][i]
-            if stage:
-                for key in ("valid", "tris2", "tri_flags"):
-                    res["stage"][key][f] = sub["stage"][key][i]
+    def _finish_reruns(self, records, stage):
+        """The call's re-runs after its last chunk: the started ones finish their steps, the others' frames go in one batch."""
+        stream.finish_all(records, lambda rest: self._merged_rerun(rest, stage), _FIELDS, "host_errors")
+
+    def _merged_rerun(self, records, stage):
+        """The frames of the records whose re-run was not started, in ONE batch through the host's triangulations, scattered back."""
+        at = [(r, f) for r in records for f in r.redo]
+        sub = self._chunk_dev_host([r.f3s[f] for r, f in at], [r.f2s[f] for r, f in at], 0, np.array([r.frame_base + int(f) for r, f in at], dtype=np.int64),
+                                   None if records[0].id_triples is None else [r.id_triples[f] for r, f in at], stage)
+        first = 0
+        for r in records:
+            self._scatter(r.res, r.redo, sub, first, stage)
+            first += len(r.redo)
 
     def _stream_device(self, feature3ds, feature2ds, id_triples, stage, push=True):
         F = len(feature3ds)
@@ -709,7 +647,6 @@ class ScaleEstimator:
             return np.zeros(0), np.zeros(0)
         base = self._frame_counter
         self.last_declined = 0
-        results, bounds = [], []
         # A frame the device path has no kernel for (_oversized_error) ends the run like every other error (_push_device): the frames
         # before it go through the slew limiter, the window and the sample counter, nothing queued is dropped, then the exception —
         # what the reference's per-frame loop would have left behind.
@@ -718,70 +655,48 @@ class ScaleEstimator:
             oversized = self._first_oversized(feature2ds, [len(x) for x in feature2ds], 0)
             if oversized is not None:
                 F = oversized[0]
+        triples = lambda a, b: None if id_triples is None else id_triples[a:b]
         if self.triangulation == "gpu":
-            C_ = int(min(self.GPU_CHUNK, max(512, -(-F // 4))))
-            mean_pts = max(1, sum(len(x) for x in feature3ds[:64]) // min(F, 64))
-            C_ = int(max(512, min(C_, self.GPU_CHUNK_POINTS // mean_pts)))     # (the points cap as it will bite: the short first chunks are fractions of that)
-            # short first chunks (C/8, C/4, C/2): the GPU starts after the pack + upload of an eighth of a chunk
-            ramp = [int(C_ * x) for x in self.GPU_RAMP_FRACTIONS] if (C_ >= 2048 and F >= 3 * C_) else []
-            queue, a = [], 0
-            deferred = []                                  # chunks with declined frames: their re-run waits for the call's last chunk
-            # MVOSR_TRACE_CHUNKS=1: when this process started and finished each chunk's pack + launches and each collection
-            # (self.chunk_trace: (what, chunk, frames, seconds since the call began))
+            C, ramp = stream.chunk_size(F, self.GPU_CHUNK, self.GPU_MIN_CHUNK, self.GPU_CHUNK_POINTS, [len(x) for x in feature3ds[:64]],
+                                        self.GPU_RAMP_FRACTIONS if self.GPU_RAMP else ())
+            found = []
+
+            def stop(a, lens):                     # (the stream ends before the first oversized frame)
+                o = self._first_oversized(feature2ds, lens, a)
+                if o is not None:
+                    found.append(o)
+                    return o[0]
+            deferred = []
             self.chunk_trace = [] if os.environ.get("MVOSR_TRACE_CHUNKS") else None
             self._trace_t0 = time.perf_counter()
-            while a < F:
-                b = min(F, a + (ramp[len(bounds)] if len(bounds) < len(ramp) else C_))
-                tb = frame_tables(feature3ds[a:b], feature2ds[a:b])          # (sizes from the packer's pointer tables: one C loop)
-                lens = tb[2].astype(np.int64) if tb is not None else np.fromiter((len(x) for x in feature3ds[a:b]), dtype=np.int64, count=b - a)
-                if oversized is None:
-                    oversized = self._first_oversized(feature2ds, lens, a)
-                    if oversized is not None:
-                        F = oversized[0]                   # (the stream ends before that frame)
-                        if a >= F:
-                            break
-                        b, lens = min(b, F), lens[:F - a]
-                        tb = tuple(t[:F - a] for t in tb) if tb is not None else None
-                b = min(b, a + max(int(np.searchsorted(np.cumsum(lens), self.GPU_CHUNK_POINTS, side="right")), 1))
-                while b - a > 1 and (b - a) * int(lens[:b - a].max()) > 2 * self.GPU_CHUNK_POINTS:     # (workspace = frames x largest frame)
-                    b = a + max(1, (b - a) // 2)
-                res = self._resident_frames(int(lens[:b - a].max()))
-                if b < F and b - a >= 2 * res:                         # whole rounds of the GPU's resident frames: no partly filled last round
-                    b = a + ((b - a) // res) * res
-                tr = None if id_triples is None else id_triples[a:b]
-                self._trace("launch", len(bounds), b - a)
-                queue.append((self._chunk_dev_gpu(feature3ds[a:b], feature2ds[a:b], base + a, tr, stage,
-                                                  tables=(tuple(t[:b - a] for t in tb) if tb is not None else None),
-                                                  early_status=self.GPU_REDO_EARLY and not stage and b == F and a > 0), a, b))
-                bounds.append((a, b))
-                self._trace("launched", len(bounds) - 1, b - a)
-                while len(queue) > self.GPU_PIPELINE:
-                    st, pa, pb = queue.pop(0)
-                    self._trace("collect", len(results), pb - pa)
-                    results.append(self._chunk_dev_finish(st, feature3ds[pa:pb], feature2ds[pa:pb], base + pa,
-                                                          None if id_triples is None else id_triples[pa:pb], stage, defer=deferred))
-                a = b
-            while queue:
-                st, pa, pb = queue.pop(0)
-                results.append(self._chunk_dev_finish(st, feature3ds[pa:pb], feature2ds[pa:pb], base + pa,
-                                                      None if id_triples is None else id_triples[pa:pb], stage, defer=deferred))
-            self._finish_deferred(deferred, stage)
+            collected = iter(range(F))
+
+            def start(a, b, tables, k):
+                self._trace("launch", k, b - a)
+                st = self._chunk_dev_gpu(feature3ds[a:b], feature2ds[a:b], base + a, triples(a, b), stage, tables=tables,
+                                         early_status=self.GPU_REDO_EARLY and not stage and b == (found[0][0] if found else F) and a > 0)
+                self._trace("launched", k, b - a)
+                return st
+
+            def collect(st, a, b, last):
+                self._trace("collect", next(collected), b - a)
+                return self._chunk_dev_finish(st, feature3ds[a:b], feature2ds[a:b], base + a, triples(a, b), stage, defer=deferred)
+            chunks = stream.plan(F, stream.tables_of(feature3ds, feature2ds), C, ramp, self.GPU_CHUNK_POINTS, self._resident_frames, stop)
+            bounds, _, results = stream.run(chunks, start, collect, self.GPU_PIPELINE, stream.free_blocks, deferred,
+                                            lambda: self._finish_reruns(deferred, stage))
+            if found:
+                oversized, F = found[0], found[0][0]
         else:
-            C_ = 2048
-            for a in range(0, F, C_):          # (F: the frames before the first oversized one)
-                b = min(F, a + C_)
+            bounds, results = [], []
+            for a in range(0, F, 2048):          # (F: the frames before the first oversized one)
+                b = min(F, a + 2048)
                 bounds.append((a, b))
-                results.append(self._chunk_dev_host(feature3ds[a:b], feature2ds[a:b], base + a, None,
-                                                    None if id_triples is None else id_triples[a:b], stage))
+                results.append(self._chunk_dev_host(feature3ds[a:b], feature2ds[a:b], base + a, None, triples(a, b), stage))
         if oversized is not None and not results:
             raise self._oversized_error(*oversized)
-        cat = lambda k: np.concatenate([r[k] for r in results])
-        raw, status, level = cat("raw_scale"), cat("status"), cat("height_level")
-        host_errors = {}
-        for (a, _), r in zip(bounds, results):
-            host_errors.update({a + f: e for f, e in r["host_errors"].items()})
-        self.last = {"model": cat("model"), "best_ic": cat("best_ic"), "used": cat("used"), "n_kept": cat("n_kept"),
-                     "status": status, "height_level": level, "raw_scale": raw}
+        cat, host_errors = stream.concat(bounds, results, _FIELDS, "host_errors")
+        self.last = dict(zip(_FIELDS, cat))
+        raw, status, level = self.last["raw_scale"], self.last["status"], self.last["height_level"]
         if stage:
             for k in ("valid", "tris2", "tri_flags"):
                 self.last[k] = [x for r in results for x in r["stage"][k]]

@@ -24,13 +24,12 @@ from __future__ import annotations
 import os
 from collections import deque
 
-import time
-
 import numpy as np
 
 from . import _lib
 from . import constants as K
 from . import packing
+from . import stream
 from .engine import DeviceBatch, DeviceOutputs, ScaleEngine
 
 
@@ -49,7 +48,27 @@ def raise_for_status(status, frame=None):
         raise ValueError("frame without features below the vanishing row / without triangles" + where)
 
 
-class ScaleEstimator:
+class ScaleEstimator(stream.StreamKnobs):
+    # (the streamed path's shared knobs: stream.StreamKnobs)
+    PIPELINE_CHUNK = 512            # frames per chunk of the host-triangulation streaming path (_stream_chunks)
+    LAZY_FLAT_FEATURE = True        # after a batch: flat_feature / flat_feature_2d when they are read (see the properties)
+    GPU_EXACT_TWO_CONTEXTS = True   # check_triangle="reference": the chunks of a call alternate between two contexts (see _stream_gpu)
+    GPU_EXACT_STANDIN = True        # check_triangle="reference": the second triangulation by the fast kernel as a stand-in; Qhull's own rows only for
+                                    # the frames of the exact pass (engine.DeviceBatch.triangulate); False: Qhull's replay for every frame
+    GPU_SINGLE_HOT = True           # check_triangle="fixed", ONE frame per call: the product kernels only, height_level exact when read (see _single_exact_fast)
+    GPU_EXACT_SINGLE_FAST = True    # check_triangle="reference", ONE frame per call: SciPy for the first triangulation only (see _single_exact_fast)
+    GPU_EXACT_HOST_REPLAY = True    # check_triangle="reference" with triangulation="gpu": the estimator's host-side triangulations by mvosr_qhull_rows_host
+    GPU_EXACT_FORCE_DEVICE = False  # (tests) the device replay however few the frames
+    GPU_EXACT_MIN_FRAMES = 8        # ... calls of fewer frames (or fewer than ~3.7 per Delaunay worker) take SciPy's triangulations (same rows, lower latency)
+    GPU_EXACT_CHUNK = 16384         # check_triangle="reference" (the Qhull-rows kernel): frames per chunk, at most ...
+    GPU_EXACT_CHUNK_POINTS = 33000000   # ... and features per chunk (~0.75 KB each on the device: 25 GB at the cap)
+    GPU_EXACT_FIRST_CHUNK = 4096    # check_triangle="reference", two contexts: frames of a call's first chunk (0: a full chunk; 4096 = one round of resident wavefronts: profiles/r06_exact_first_chunk_ab.txt)
+    GPU_EXACT_HOST_REDO = True      # check_triangle="reference" batches: the exact pass's few frames through the host path (see _chunk_gpu)
+    GPU_EXACT_HOST_REDO_MAX = 64    # ... up to so many per chunk (16 per Delaunay worker at most); more: the device's exact pass (one masked relaunch)
+    GPU_EXACT_LAZY_LEVEL = True     # check_triangle="reference" batches: a chunk's last frame is not on the exact mask (see _stream_gpu)
+    GPU_REDO_CONTEXT = True         # streamed batches: the host-path re-run of declined frames on a context of its own (see _chunk_gpu_finish)
+    GPU_REDO_DEFER = True           # ... and finished after the call's last chunk (its SciPy calls start on the worker pool at once)
+
     def __init__(self, absolute_reference, window_size=6, vanish=K.VANISH, focus=K.FOCUS, device=0,
                  delaunay_workers=None, verbose=False, mutate_inputs=True, triangulation=None, check_triangle=None):
         # reference attributes (scale_calculator.py:23-40)
@@ -327,8 +346,6 @@ class ScaleEstimator:
         raise NotImplementedError("visualisation helper of the reference; not part of the hot path")
 
     # ---- batched surface ---------------------------------------------------------------------
-    PIPELINE_CHUNK = 512        # frames per chunk of the streaming batch path
-
     def scale_calculation_batch(self, feature3ds, feature2ds, tri1s=None, tri2s=None, _single=False, _raw_only=False):
         """Equivalent to calling ``scale_calculation`` once per frame, in order, on this
         estimator: returns ``(scales[F], stds[F])`` (filtered scales).  ``tri1s``/``tri2s`` may
@@ -393,7 +410,7 @@ class ScaleEstimator:
             last = st
         self.last_status, self.last_counts, self.last_raw_scale = status, counts, raw
         if _raw_only:
-            self._chunk_free(last)
+            stream.free_blocks(last)
             return raw, status, level, host_errors
         hint = None
         if stage and F == 1 and isinstance(last, dict) and last.get("filtered_queue") is not None and last.get("out") is not None \
@@ -411,12 +428,12 @@ class ScaleEstimator:
             self.__dict__["_flat_thunk"] = lambda: self._flat_feature_of(f3c, f2c, st_, mutate=mut_)
         elif n_ok:
             self._flat_feature_of(feature3ds[n_ok - 1], feature2ds[n_ok - 1], status[n_ok - 1])
-        self._chunk_free(last)
+        stream.free_blocks(last)
         raise_late()
         return filtered, stds
 
     # -- one chunk of frames through the stages; the Delaunay calls are submitted to the pool and collected later
-    def _chunk_begin(self, f3s, f2s, k, tri1s=None, _packed=None, _remapped=False, _exact_all=False, _fast=False, _eng=None, _slot=None):
+    def _chunk_begin(self, f3s, f2s, k, tri1s=None, _packed=None, _remapped=False, _exact_all=False, _fast=False, _eng=None):
         """Vanishing-row filter + packing (:252-254) and the start of the first triangulation (:257), on the host."""
         if _packed is not None:
             pf = _packed                                               # (packed — and the caller's arrays remapped — already)
@@ -434,7 +451,7 @@ class ScaleEstimator:
         if tri1s is not None:
             h1 = tri1s
         else:
-            h1 = packing.submit_tri1(pf, self.delaunay_workers, slot=(k % 4) if _slot is None else _slot, fast=_fast)
+            h1 = packing.submit_tri1(pf, self.delaunay_workers, slot=stream.SLOT_CHUNK + k % stream.CHUNK_SLOTS, fast=_fast)
         # (_fast: the host replay of Qhull's run instead of SciPy where it accepts the set — the default estimator's own host steps;
         # an estimator constructed with triangulation="scipy" never sets it)
         st = {"pf": pf, "h1": h1, "n": len(f3s), "out": None, "dbatch": None, "masks": None, "exact_all": bool(_exact_all),
@@ -449,7 +466,7 @@ class ScaleEstimator:
         """First triangulation in, vote on the GPU (:151-167), start of the second triangulation (:266)."""
         self._chunk_vote_start(st, tri2s)
         if tri2s is None:
-            self._chunk_vote_finish(st, 4 + k % 4)
+            self._chunk_vote_finish(st, stream.SLOT_CHUNK_TRI2 + k % stream.CHUNK_SLOTS)
 
     def _chunk_vote_start(self, st, tri2s=None):
         """The first half of ``_chunk_vote``: the first triangulation attached, the batch uploaded, the vote LAUNCHED and the download
@@ -516,7 +533,7 @@ class ScaleEstimator:
             res = (res[0], res[1], self._exact_after(eng, st["dbatch"], out, res[1], res[2], host_errors), res[3])
         st["out"] = out
         if not keep:
-            self._chunk_free(st)
+            stream.free_blocks(st)
         return res + (host_errors,)
 
     def _exact_after(self, eng, db, out, status, level, host_errors, skip=()):
@@ -553,17 +570,6 @@ class ScaleEstimator:
         level[mask != 0] = new[mask != 0]
         return level
 
-    @staticmethod
-    def _chunk_free(st):
-        if st is None:
-            return
-        if st.get("out") is not None:
-            st["out"].free()
-            st["out"] = None
-        if st.get("dbatch") is not None:
-            st["dbatch"].free()
-            st["dbatch"] = None
-
     def _stream_chunks(self, feature3ds, feature2ds, depth=2):
         F, C = len(feature3ds), self.PIPELINE_CHUNK
         bounds = [(a, min(F, a + C)) for a in range(0, F, C)]
@@ -594,27 +600,6 @@ class ScaleEstimator:
             host_errors.update({a + f: e for f, e in r[4].items()})
         return raw, status, level, counts, host_errors, S[n - 1]
 
-    GPU_RAMP = True                 # short first chunks (see _stream_gpu)
-    GPU_RAMP_FRACTIONS = (1 / 6, 1 / 3, 1 / 2, 2 / 3, 5 / 6)   # their sizes, as fractions of a full chunk: with 2000-feature frames one, two,
-                                    # three, four and five whole rounds of the triangulation kernel's resident frames (768) before the
-                                    # six-round chunks.  (The shape barely matters any more — every ramp tried gave 520-530 k
-                                    # frames/s —: the pipeline's stages are balanced, PCIe at 6.5 ms per chunk against the GPU's 7.2.)
-    GPU_PIPELINE = 2                # chunks queued on the device behind the one being collected (with the short first chunks 1 -> 2 is +3 % at 32 768 frames, +6 % at 16 384; 3: the same)
-    GPU_CHUNK = 8192            # frames per chunk of the device-triangulation path, at most (a call of F frames uses chunks of F/4, 512 at least: the pipeline needs a few)
-    GPU_MIN_CHUNK = 512         # ... and at least (tests lower it to put chunk boundaries everywhere)
-    GPU_RESIDENT = 512          # frames the GPU works on at once (two 8-wavefront workgroups per CU): chunks are multiples of it
-    GPU_CHUNK_POINTS = 10000000 # ... and features per chunk (40 B each in staging memory, ~180 B each on the device)
-    GPU_EXACT_TWO_CONTEXTS = True   # check_triangle="reference": the chunks of a call alternate between two contexts (see _stream_gpu)
-    GPU_EXACT_STANDIN = True    # check_triangle="reference": the second triangulation by the fast kernel as a stand-in; Qhull's own rows only for
-                                # the frames of the exact pass (engine.DeviceBatch.triangulate); False: Qhull's replay for every frame
-    GPU_SINGLE_HOT = True           # check_triangle="fixed", ONE frame per call: the product kernels only, height_level exact when read (see _single_exact_fast)
-    GPU_EXACT_SINGLE_FAST = True    # check_triangle="reference", ONE frame per call: SciPy for the first triangulation only (see _single_exact_fast)
-    GPU_EXACT_HOST_REPLAY = True    # check_triangle="reference" with triangulation="gpu": the estimator's host-side triangulations by mvosr_qhull_rows_host
-    GPU_EXACT_FORCE_DEVICE = False  # (tests) the device replay however few the frames
-    GPU_EXACT_MIN_FRAMES = 8    # ... calls of fewer frames (or fewer than ~3.7 per Delaunay worker) take SciPy's triangulations (same rows, lower latency)
-    GPU_EXACT_CHUNK = 16384     # check_triangle="reference" (the Qhull-rows kernel): frames per chunk, at most ...
-    GPU_EXACT_CHUNK_POINTS = 33000000   # ... and features per chunk (~0.75 KB each on the device: 25 GB at the cap)
-
     def _lower_points(self, f2):
         """A frame's pixels below the vanishing row (:252-254), contiguous — what the first Delaunay call sees."""
         f2 = np.asarray(f2, dtype=np.float64)
@@ -627,21 +612,22 @@ class ScaleEstimator:
                                         check_triangle=self.check_triangle)
         return self._engine2
 
-    GPU_REDO_CONTEXT = True         # streamed batches: the host-path re-run of declined frames on a context of its own (see _chunk_gpu_finish)
-    GPU_REDO_MAX_DEFERRED = 8       # ... at most so many chunks' re-runs pending (each keeps its device blocks and a shared-memory slot)
-    GPU_REDO_DEFER = True           # ... and finished after the call's last chunk (its SciPy calls start on the worker pool at once)
-
     def _redo_engine(self, remapped):
-        """The engine (on a third context: own streams, workspace, caches) for the re-runs of frames a device triangulation declined;
-        ``remapped``: the caller's arrays hold the remapped values already (:414), the engine's remap is the identity."""
-        if getattr(self, "_redo_ctx", None) is None:
-            self._redo_ctx = _lib.Context(self.engine.ctx.device)
-            self._redo_engines = {}
-        key = bool(remapped)
-        if key not in self._redo_engines:
-            self._redo_engines[key] = ScaleEngine(self.absolute_reference, ctx=self._redo_ctx,
-                                                  camera_pitch=0.0 if remapped else self.camera_pitch, check_triangle=self.check_triangle)
-        return self._redo_engines[key]
+        """The engine on the re-runs' context (_redo_context) for the frames a device triangulation declined; ``remapped``: the
+        caller's arrays hold the remapped values already (:414), the engine's remap is the identity."""
+        engines = self.__dict__.setdefault("_redo_engines", {})
+        if bool(remapped) not in engines:
+            engines[bool(remapped)] = ScaleEngine(self.absolute_reference, ctx=self._redo_context(), camera_pitch=0.0 if remapped else self.camera_pitch,
+                                                  check_triangle=self.check_triangle)
+        return engines[bool(remapped)]
+
+    def _redo_sub(self, f3s, f2s, rows, remapped):
+        """A re-run's batch of frames whose first triangulations (``rows``, canonical form from the workers) are back: packed, on the
+        re-runs' engine, every stage in the exact mode."""
+        sub = self._chunk_begin(f3s, f2s, 0, tri1s=rows, _remapped=remapped, _exact_all=True, _fast=self._host_replay,
+                                _eng=self._redo_engine(remapped) if self.GPU_REDO_CONTEXT else None)
+        sub["pf"].extra["tri1_is_canonical"] = self.check_triangle == "fixed"
+        return sub
 
     def _chunk_gpu(self, f3s, f2s, stage, tables=False, eng=None, single_exact=False, hot_only=False, lazy_last=False, host_exact=False,
                    early_status=False):
@@ -733,50 +719,42 @@ class ScaleEstimator:
     def _chunk_gpu_finish(self, st, f3s, f2s, keep=False, defer=None):
         """Results of a chunk started by ``_chunk_gpu``; frames whose triangulation the device stage declined (degenerate
         point sets, fewer than 3 points) are redone through the host's path (SciPy's rows, canonical form in "fixed" mode).
-        ``defer`` (a list; streamed batches): the re-run is only STARTED here — its first SciPy calls go to the worker pool — and a
-        record is appended; ``_chunk_gpu_complete`` finishes it once every chunk of the call has been collected.  Returns the
-        chunk's ``[raw, status, level, counts, host_errors]`` (a list: a deferred completion fills the declined frames' entries in)."""
+        ``defer`` (the call's re-run records; streamed batches): the re-run is only STARTED here — its first SciPy calls go to the
+        worker pool — and a record is appended; ``_finish_reruns`` finishes it.  Returns the chunk's ``[raw, status, level, counts,
+        host_errors]`` (a list: a deferred completion fills the declined frames' entries in)."""
         eng = st.get("engine") or self.engine
         pf = st["pf"]
         stage = st["stage"]
-        if defer:
-            self._advance_deferred(defer)        # (host work for earlier chunks' re-runs, before this chunk's results are waited for)
+        stream.advance(defer or ())         # (host work for earlier chunks' re-runs, before this chunk's results are waited for)
         if not st["gpu"]:
             sub = self._chunk_begin(f3s, f2s, 0, _remapped=st["remapped"])
             self._chunk_vote(sub, None, 0)
             res = self._chunk_scale(sub, None, stage, keep=True)
             st.update(out=sub["out"], dbatch=sub["dbatch"], masks=sub["masks"], pf=sub["pf"])
             if not keep:
-                self._chunk_free(st)
+                stream.free_blocks(st)
             return list(res)
         db, out = st["dbatch"], st["out"]
-        early = None
         if defer is not None and not stage:
             # (the call's last chunk: whatever its first triangulation declined is known behind THAT kernel — the frames' SciPy calls
             # start now, under the chunk's vote, second triangulation and product kernels, instead of after them)
             s1e = db.early_status()
             if s1e is not None and s1e.any():
                 ef = np.nonzero(s1e != 0)[0]
-                early = (ef, packing.delaunay_submit([self._lower_points(f2s[f]) for f in ef], self.delaunay_workers, slot=24,
-                                                     fast=self._host_replay, canonical=self.check_triangle == "fixed", background=True))
+                early = st["early"] = self._rerun(st, f3s, f2s, ef, packing.delaunay_submit(
+                    [self._lower_points(f2s[f]) for f in ef], self.delaunay_workers, slot=stream.SLOT_EARLY, fast=self._host_replay,
+                    canonical=self.check_triangle == "fixed", background=True))
                 self.redo_early_status_hits = getattr(self, "redo_early_status_hits", 0) + 1
                 if self.GPU_REDO_EARLY and len(ef) <= self.GPU_REDO_EARLY_MAX:
                     # ... and this thread has nothing else to do for the call's last chunk: it takes those frames through their first
                     # triangulation (waited for: the chunk's other kernels are running), the vote (on the re-runs' context) and the start
                     # of their second triangulation NOW, so that the call's end finds only their product kernels left to launch
-                    rows = early[1].get()
-                    sub = self._chunk_begin([f3s[f] for f in ef], [f2s[f] for f in ef], 0, tri1s=rows, _remapped=st["remapped"], _exact_all=True,
-                                            _fast=self._host_replay, _eng=self._redo_engine(st["remapped"]) if self.GPU_REDO_CONTEXT else None)
-                    sub["pf"].extra["tri1_is_canonical"] = self.check_triangle == "fixed"
-                    self._chunk_vote_start(sub)
-                    self._chunk_vote_finish(sub, 25, background=True)
-                    st["early_sub"] = sub
-        if defer and self.GPU_REDO_EARLY:
-            # re-runs of earlier chunks are under way: instead of sleeping until this chunk's results arrive (tens of ms with the
-            # reference's vote), the thread looks in on them every 0.2 ms — each step of a record is taken the moment its inputs are there
-            while any(p.get("early", 0) < 3 and 0 < len(p["redo"]) <= self.GPU_REDO_EARLY_MAX for p in defer) and not (db.info.ready() and out.ready()):
-                self._advance_deferred(defer)
-                time.sleep(2e-4)
+                    early.sub = self._redo_sub([f3s[f] for f in ef], [f2s[f] for f in ef], early.h1.get(), st["remapped"])
+                    self._chunk_vote_start(early.sub)
+                    self._chunk_vote_finish(early.sub, stream.SLOT_EARLY_TRI2, background=True)
+        # (re-runs of earlier chunks are under way: instead of sleeping until this chunk's results arrive — tens of ms with the
+        # reference's vote — the thread takes each step of a record the moment its inputs are there)
+        stream.advance_while(defer or (), lambda: not (db.info.ready() and out.ready()))
         s1, s2 = db.triangulation_status()
         redo = np.nonzero((s1 != 0) | (s2 != 0))[0]
         res = [out.get("raw_scale"), out.get("status"), out.get("height_level"), out.get("counts"), {}]
@@ -808,6 +786,7 @@ class ScaleEstimator:
             elif len(extra):
                 redo = np.union1d(redo, extra).astype(redo.dtype)
                 self.exact_redone_on_host = getattr(self, "exact_redone_on_host", 0) + len(extra)
+        early = st.pop("early", None)
         handle = None
         if len(redo) and defer is not None and not stage:
             # Streamed batches (round 6): only the declined frames' FIRST SciPy calls are started here — on the worker pool when the
@@ -817,130 +796,87 @@ class ScaleEstimator:
             # long for a slot: round 5 ran the re-run in each chunk's epilogue on the chunk's own stream (72 declined frames in
             # 16 384: 53 k -> 30 k frames/s); on its own context but still between the chunks 80 declined frames cost 96 -> 66 k
             # (and 529 -> 93 k in the fixed mode, whose chunks are short).
-            have = set(int(f) for f in early[0]) if early is not None else set()
+            have = set(int(f) for f in early.redo) if early is not None else set()
             rest = [k for k, f in enumerate(redo) if int(f) not in have]
             handle = packing.delaunay_submit([self._lower_points(f2s[redo[k]]) for k in rest], self.delaunay_workers,
-                                             slot=8 + len(defer) % self.GPU_REDO_MAX_DEFERRED,
+                                             slot=stream.SLOT_DEFER + len(defer),
                                              fast=self._host_replay, canonical=self.check_triangle == "fixed", background=True)
             if early is not None:
                 where = {int(f): k for k, f in enumerate(redo)}
-                handle = packing._JoinedHandle(len(redo), [([where[int(f)] for f in early[0]], early[1]), (rest, handle)])
-        pend = {"st": st, "redo": redo, "s12": (s1, s2), "f3s": f3s, "f2s": f2s, "res": res, "keep": keep, "h1": handle}
-        esub = st.pop("early_sub", None)
-        if esub is not None:
-            if handle is not None and early is not None and len(redo) == len(early[0]) and np.array_equal(redo, early[0]):
-                pend["sub"], pend["early"] = esub, 2          # (the record continues where the early steps left it: _advance_deferred)
-            else:                                              # (more frames to redo than the early read knew of: the merged way for all)
-                self._chunk_free(esub)
+                handle = packing._JoinedHandle(len(redo), [([where[int(f)] for f in early.redo], early.h1), (rest, handle)])
+        rec = self._rerun(st, f3s, f2s, redo, handle, res=res, s12=(s1, s2), keep=keep,
+                          slot2=stream.SLOT_DEFER_TRI2 + len(defer) if handle is not None else None)
+        if early is not None and early.sub is not None:
+            if handle is not None and len(redo) == len(early.redo) and np.array_equal(redo, early.redo):
+                rec.sub, rec.step, rec.begun = early.sub, 2, True      # (the record continues where the early steps left it)
+            else:                                                      # (more frames to redo than the early read knew of: the merged way for all)
+                stream.free_blocks(early.sub)
         if handle is not None:
-            defer.append(pend)
+            defer.append(rec)
             if len(defer) >= self.GPU_REDO_MAX_DEFERRED:       # (bounded: a deferred chunk keeps its device blocks and a pool slot)
-                self._chunk_gpu_complete_all(defer)
-                del defer[:]
+                self._finish_reruns(defer)
             else:
-                self._advance_deferred(defer)                  # (this chunk's results were waited for: earlier records may have moved on)
+                stream.advance(defer)                          # (this chunk's results were waited for: earlier records may have moved on)
             return res
-        if defer:
-            self._advance_deferred(defer)
-        self._chunk_gpu_complete(pend)
+        stream.advance(defer or ())
+        self._chunk_gpu_complete(rec)
         return res
 
-    GPU_SIDE_DOWNLOADS = os.environ.get("MVOSR_SIDE_DOWNLOADS", "1") != "0"       # streamed batches: a chunk's results reach page-locked memory through a copy KERNEL — not through a
-                                    # hipMemcpyAsync parked on a copy engine behind the chunk's kernels (False / MVOSR_SIDE_DOWNLOADS=0: as before round 6's second half; LABNOTES 10.14)
-    GPU_REDO_EARLY = True           # a deferred re-run's vote and second triangulation START while later chunks run (_advance_deferred) ...
-    GPU_REDO_EARLY_MAX = 16         # ... for chunks with at most so many frames to redo (more: the one merged re-run at the call's end)
+    def _rerun(self, st, f3s, f2s, redo, h1, slot2=None, **data):
+        """The re-run record of chunk ``st``'s frames ``redo`` whose first triangulations ``h1`` has started.  ``slot2`` (deferred
+        records of at most GPU_REDO_EARLY_MAX frames): its steps are taken while later chunks run (round 6, LABNOTES 10.11) — a chunk's
+        few declined frames (and, in the reference-exact mode, the few frames of its exact pass) need first triangulation -> vote ->
+        second triangulation -> product kernels, a chain of two host triangulations and two device round trips: at the call's end that
+        chain is 4-8 ms during which nothing else runs, a fifth of a 34 ms call for ONE declined frame.  Once its first triangulations
+        are back the record's batch is uploaded and its vote launched on the re-runs' context (the record has begun); once the counters
+        are back its second triangulations start on the pool; once those are back its product kernels are launched."""
+        rec = stream.Rerun(data.pop("res", None), redo, lambda: (stream.free_blocks(rec.sub), stream.free_blocks(st), stream.wait_out(
+            rec.h1, (rec.sub or {}).get("h2"))), st=st, f3s=f3s, f2s=f2s, h1=h1, sub=None, **data)
+        if slot2 is None or not (self.GPU_REDO_EARLY and 0 < len(redo) <= self.GPU_REDO_EARLY_MAX):
+            return rec
 
-    def _advance_deferred(self, pending):
-        """Deferred re-runs, one step further where that step does not WAIT (round 6, LABNOTES 10.11).  A chunk's few declined frames
-        (and, in the reference-exact mode, the few frames of its exact pass) need first triangulation -> vote -> second triangulation ->
-        product kernels, a chain of two host triangulations and two device round trips: at the call's end that chain is 4-8 ms during
-        which nothing else runs — a fifth of a 34 ms call for ONE declined frame.  Here, whenever the call collects a chunk: a record
-        whose first triangulations are back gets its batch uploaded and its vote launched (on the re-runs' own context, download of
-        the counters queued behind it); a record whose counters have arrived gets its second triangulations started on the worker pool.
-        ``_chunk_gpu_complete_all`` then finds only the product kernels left to do for every chunk but the call's last."""
-        if not self.GPU_REDO_EARLY:
-            return
-        for idx, p in enumerate(pending):
-            state = p.get("early", 0)
-            if state == 0 and 0 < len(p["redo"]) <= self.GPU_REDO_EARLY_MAX and p["h1"].ready():
-                rows = p["h1"].get()
-                remapped = p["st"]["remapped"]
-                sub = self._chunk_begin([p["f3s"][f] for f in p["redo"]], [p["f2s"][f] for f in p["redo"]], 0, tri1s=rows, _remapped=remapped,
-                                        _exact_all=True, _fast=self._host_replay,
-                                        _eng=self._redo_engine(remapped) if self.GPU_REDO_CONTEXT else None)
-                sub["pf"].extra["tri1_is_canonical"] = self.check_triangle == "fixed"   # (the workers brought the rows to canonical form)
-                self._chunk_vote_start(sub)
-                p["sub"], p["early"] = sub, 1
-                self.redo_early_started = getattr(self, "redo_early_started", 0) + 1
-            elif state == 1 and p["sub"]["vote_out"].ready():
-                # (slots 16..: a pair of shared-memory segments per record in flight)
-                self._chunk_vote_finish(p["sub"], 16 + idx % self.GPU_REDO_MAX_DEFERRED, background=True)
-                p["early"] = 2
-            elif state == 2 and p["sub"]["h2"].ready():
-                self._chunk_scale_start(p["sub"], False)
-                p["early"] = 3
+        def begin(wait):
+            rec.sub = self._redo_sub([f3s[f] for f in redo], [f2s[f] for f in redo], rec.h1.get(), st["remapped"])
+            self._chunk_vote_start(rec.sub)
+            rec.begun = True
+            self.redo_early_started = getattr(self, "redo_early_started", 0) + 1
+
+        def scale(wait):
+            self._chunk_scale_start(rec.sub, False)
+            if not wait:
                 self.redo_early_launched = getattr(self, "redo_early_launched", 0) + 1     # (only its results are left for the call's end)
+        rec.chain = [(lambda: rec.h1.ready(), begin),
+                     (lambda: rec.sub["vote_out"].ready(), lambda wait: self._chunk_vote_finish(rec.sub, slot2, background=not wait)),
+                     (lambda: rec.sub["h2"].ready(), scale)]
+        rec.collect = lambda: self._chunk_scale_finish(rec.sub, False)
+        return rec
 
-    def _chunk_gpu_complete_all(self, pending):
-        """The declined frames of several chunks through the host path (their first triangulations were started by
-        ``_chunk_gpu_finish``), results scattered back; then every chunk's own completion.  Chunks whose re-run ``_advance_deferred``
-        has started finish it here, each as its own small batch; the others' frames go through ONE merged re-run."""
-        if not pending:
-            return
-        self._advance_deferred(pending)
-        errs = [dict() for _ in pending]
-        for k, p in enumerate(pending):        # (every started re-run's remaining launches first, then their results)
-            if p.get("early") == 1:
-                self._chunk_vote_finish(p["sub"], 16 + k % self.GPU_REDO_MAX_DEFERRED)
-                p["early"] = 2
-        for k, p in enumerate(pending):
-            if p.get("early") == 2:
-                self._chunk_scale_start(p["sub"], False)
-                p["early"] = 3
-        for k, p in enumerate(pending):
-            if not p.get("early"):
-                continue
-            sub = p["sub"]
-            r_raw, r_status, r_level, r_counts, r_err = self._chunk_scale_finish(sub, False)
-            res = p["res"]
-            for i, f in enumerate(p["redo"]):
-                res[0][f], res[1][f], res[2][f], res[3][f] = r_raw[i], r_status[i], r_level[i], r_counts[i]
-                if i in r_err:
-                    errs[k][int(f)] = r_err[i]
-            p["sub"] = None
-        rest = [k for k, p in enumerate(pending) if not p.get("early")]
-        if rest:
-            f3_all, f2_all, tri1_all, where = [], [], [], []
-            for k in rest:
-                p = pending[k]
-                rows = p["h1"].get()
-                for j, f in enumerate(p["redo"]):
-                    f3_all.append(p["f3s"][f]); f2_all.append(p["f2s"][f]); tri1_all.append(rows[j]); where.append((k, int(f)))
-            remapped = pending[rest[0]]["st"]["remapped"]
-            sub = self._chunk_begin(f3_all, f2_all, 0, tri1s=tri1_all, _remapped=remapped, _exact_all=True, _fast=self._host_replay,
-                                    _eng=self._redo_engine(remapped) if self.GPU_REDO_CONTEXT else None)
-            sub["pf"].extra["tri1_is_canonical"] = self.check_triangle == "fixed"       # (the workers brought the rows to canonical form)
-            self._chunk_vote(sub, None, 0)
-            r_raw, r_status, r_level, r_counts, r_err = self._chunk_scale(sub, None, False)
-            for i, (k, f) in enumerate(where):
-                res = pending[k]["res"]
-                res[0][f], res[1][f], res[2][f], res[3][f] = r_raw[i], r_status[i], r_level[i], r_counts[i]
-                if i in r_err:
-                    errs[k][f] = r_err[i]
-        for k, p in enumerate(pending):
-            p["res"][4] = errs[k]
-            p["merged"] = True
-            self._chunk_gpu_complete(p)
+    def _finish_reruns(self, records):
+        """The declined frames of the records' chunks through the host path, results scattered back (stream.finish_all: the begun
+        re-runs each finish as their own small batch, the others' frames go through ONE merged re-run); then every chunk's own
+        completion."""
+        stream.finish_all(records, self._merged_rerun, range(4), 4, then=lambda rec: self._chunk_gpu_complete(rec, merged=True))
 
-    def _chunk_gpu_complete(self, pend):
-        """The rest of ``_chunk_gpu_finish``: the declined frames' re-run (unless ``_chunk_gpu_complete_all`` merged it in already);
-        the exact levels around the chunk's first real error; the per-frame call's stage outputs."""
-        st, redo, (s1, s2), f3s, f2s, res, keep = (pend[k] for k in ("st", "redo", "s12", "f3s", "f2s", "res", "keep"))
+    def _merged_rerun(self, records):
+        at = [(rec, f) for rec in records for f in rec.redo]
+        sub = self._redo_sub([rec.f3s[f] for rec, f in at], [rec.f2s[f] for rec, f in at], [t for rec in records for t in rec.h1.get()],
+                             records[0].st["remapped"])
+        self._chunk_vote(sub, None, 0)
+        out = self._chunk_scale(sub, None, False)
+        first = 0
+        for rec in records:
+            stream.scatter(rec.res, rec.redo, out, range(4), 4, first)
+            first += len(rec.redo)
+
+    def _chunk_gpu_complete(self, rec, merged=False):
+        """The rest of ``_chunk_gpu_finish``: the declined frames' re-run (unless ``_finish_reruns`` ``merged`` it in already); the
+        exact levels around the chunk's first real error; the per-frame call's stage outputs."""
+        st, redo, (s1, s2), f3s, f2s, res, keep = rec.st, rec.redo, rec.s12, rec.f3s, rec.f2s, rec.res, rec.keep
         eng = st.get("engine") or self.engine
         pf, stage = st["pf"], st["stage"]
         db, out = st["dbatch"], st["out"]
         raw, status, level, counts, host_errors = res
-        if len(redo) and not pend.get("merged"):
+        if len(redo) and not merged:
             # (every frame of the small re-run in the exact mode: a declined frame's level may be the one a later frame reads)
             sub = self._chunk_begin([f3s[f] for f in redo], [f2s[f] for f in redo], 0, _remapped=st["remapped"], _exact_all=True,
                                     _fast=self._host_replay)
@@ -972,16 +908,11 @@ class ScaleEstimator:
                 one = self._chunk_begin(f3s, f2s, 0, _remapped=st["remapped"])
                 self._chunk_vote(one, None, 0)
                 self._chunk_scale(one, None, True, keep=True)
-                self._chunk_free(st)
+                stream.free_blocks(st)
                 st.update(out=one["out"], dbatch=one["dbatch"], masks=one["masks"], pf=one["pf"], filtered_queue=None)
         if not keep:
-            self._chunk_free(st)
+            stream.free_blocks(st)
         res[2], res[4] = level, host_errors
-
-    GPU_EXACT_FIRST_CHUNK = 4096    # check_triangle="reference", two contexts: frames of a call's first chunk (0: a full chunk; 4096 = one round of resident wavefronts: profiles/r06_exact_first_chunk_ab.txt)
-    GPU_EXACT_HOST_REDO = True      # check_triangle="reference" batches: the exact pass's few frames through the host path (see _chunk_gpu)
-    GPU_EXACT_HOST_REDO_MAX = 64    # ... up to so many per chunk (16 per Delaunay worker at most); more: the device's exact pass (one masked relaunch)
-    GPU_EXACT_LAZY_LEVEL = True     # check_triangle="reference" batches: a chunk's last frame is not on the exact mask (see _stream_gpu)
 
     def _exact_level_of(self, f3, f2, remapped):
         """NumPy's own ``height_level`` (:239-241) of ONE frame: Qhull's rows (the host replay, SciPy where it declines), every stage in
@@ -1007,33 +938,24 @@ class ScaleEstimator:
         self._lazy_levels = set()
         # Larger chunks leave fewer launch tails (32 768 frames of 2000 features: 347 k frames/s in chunks of 2048, 356 k in
         # chunks of 4096; 900 features: 710 k / 756 k, and with the short first chunks 764 k / 807 k in chunks of 4096 / 8192 —
-        # profiles/e2e_chunk_sweep.py; the points cap keeps 2000-feature frames at 5000 per chunk), but a call that is ONE chunk packs,
-        # uploads and computes one after the other: at least four chunks per call, of 512 frames or more
-        C = int(min(self.GPU_CHUNK, max(self.GPU_MIN_CHUNK, -(-F // 4))))
+        # profiles/e2e_chunk_sweep.py; the points cap keeps 2000-feature frames at 5000 per chunk)
         exact = self.check_triangle == "reference"
         engines = [self.engine]
-        chunk_points = self.GPU_CHUNK_POINTS
+        points, full = self.GPU_CHUNK_POINTS, None
         if exact:
             # The Qhull-rows kernel is a chain of ~n dependent insertions per frame (one wavefront each): a launch lasts ~25 ms
             # whether it holds 500 frames or 4 000, and only resident wavefronts fill the GPU — chunks as large as the workspace
             # allows (0.56 KB per point of frames x largest frame), no short first chunks: the host's packing is 1 % of the time
-            C = int(min(self.GPU_EXACT_CHUNK, F))
-            chunk_points = self.GPU_EXACT_CHUNK_POINTS
+            full, points = int(min(self.GPU_EXACT_CHUNK, F)), self.GPU_EXACT_CHUNK_POINTS
             if self.GPU_EXACT_TWO_CONTEXTS and not stage and F >= 2 * 4096:
                 # ... and two contexts (a stream, a workspace and caches each) taking the chunks in turn: while one chunk is in the
                 # thin parts of its chain (the launch's tail, the stand-in triangulation, Qhull's rows for the exact pass's few frames
                 # — 20 ms at a few hundred wavefronts), the other chunk's replay fills the machine
                 engines.append(self._second_engine())
-                C = int(min(self.GPU_EXACT_CHUNK // 2, max(4096, ((-(-F // 2)) // 4096) * 4096)))
-                chunk_points //= 2
-        # (the points cap as it will bite, from the first frames' sizes: the short first chunks are fractions of THAT chunk)
-        mean_pts = max(1, sum(len(x) for x in feature3ds[:64]) // min(F, 64))
-        C = int(max(self.GPU_MIN_CHUNK, min(C, chunk_points // mean_pts)))
-        # chunks of at most GPU_CHUNK frames and GPU_CHUNK_POINTS features (a chunk's planes, rows and staging memory
-        # scale with its points: dense frames travel in smaller chunks)
-        # the first chunks are short (C/8, C/4, C/2): the GPU starts after the pack + upload of 1/8 chunk instead of a whole
-        # one, and the host, which prepares a frame in less time than the GPU spends on it, is ahead from then on
-        ramp = [int(C * x) for x in self.GPU_RAMP_FRACTIONS] if (self.GPU_RAMP and not exact and C >= 2048 and F >= 3 * C) else []
+                full = int(min(self.GPU_EXACT_CHUNK // 2, max(4096, ((-(-F // 2)) // 4096) * 4096)))
+                points //= 2
+        C, ramp = stream.chunk_size(F, self.GPU_CHUNK, self.GPU_MIN_CHUNK, points, [len(x) for x in feature3ds[:64]],
+                                    self.GPU_RAMP_FRACTIONS if self.GPU_RAMP and not exact else (), full=full)
         if exact and len(engines) == 2 and self.GPU_EXACT_FIRST_CHUNK and C >= 2 * self.GPU_EXACT_FIRST_CHUNK and self.GPU_EXACT_HOST_REDO:
             # the exact path's head: nothing runs before the first chunk is packed and uploaded (16 ms for 8 192 frames of 2000 features).
             # A short first chunk was a loss while every chunk ended in a 23 ms list replay (LABNOTES 9.14); with the exact pass's
@@ -1045,74 +967,34 @@ class ScaleEstimator:
             head = np.fromiter((len(x) for x in feature3ds[:256]), dtype=np.int64, count=min(F, 256))
             if head.max() <= 1.3 * max(head.mean(), 1.0):
                 ramp = [int(self.GPU_EXACT_FIRST_CHUNK)]
-
-        from .engine import frame_tables
-
-        def chunk_bounds():
-            # (a chunk's sizes are looked at when its turn comes — one pass over the whole call's frames before the first
-            # chunk was 5 ms at 32 768 frames, with an idle GPU)
-            a_, k_ = 0, 0
-            while a_ < F:
-                b_ = min(F, a_ + (ramp[k_] if k_ < len(ramp) else C))
-                # (the frames' sizes from the pointer tables the C packer wants anyway — one C loop over the lists — where the
-                # frames are packable in place; a Python loop over them was 7 ms per 32 768 frames)
-                tb = frame_tables(feature3ds[a_:b_], feature2ds[a_:b_], remap_in_place=bool(self.mutate_inputs))
-                lens = tb[2].astype(np.int64) if tb is not None else np.fromiter((len(x) for x in feature3ds[a_:b_]), dtype=np.int64, count=b_ - a_)
-                over = int(np.searchsorted(np.cumsum(lens), chunk_points, side="right"))
-                b_ = min(b_, a_ + max(over, 1))
-                # the triangulation's workspace is sized frames x LARGEST frame (mvosr_delaunay_batch): one 20 000-point frame
-                # among thousands of small ones must not turn into a 20 GB request — such a chunk is cut short
-                while b_ - a_ > 1 and (b_ - a_) * int(lens[:b_ - a_].max()) > 2 * chunk_points:
-                    b_ = a_ + max(1, (b_ - a_) // 2)
-                # a chunk is a whole number of the GPU's resident sets of frames (512 eight-wavefront workgroups on 256 CUs):
-                # the triangulation kernels then have no partly filled last round (32 768 frames of 2000 features in chunks of
-                # 5000: 349-388 k frames/s, of 4096: 379-408 k)
-                ctx_ = self.engine.ctx
-                res = (16 * int(ctx_.n_cu)) if exact else \
-                    max(self.GPU_RESIDENT, int(ctx_.lib.mvosr_delaunay_frames_per_cu(int(lens[:b_ - a_].max()))) * int(ctx_.n_cu))
-                if b_ < F and b_ - a_ >= 2 * res:
-                    b_ = a_ + ((b_ - a_) // res) * res
-                yield a_, b_, (tuple(t[:b_ - a_] for t in tb) if tb is not None else None)
-                a_, k_ = b_, k_ + 1
-
-        bounds = []
-        results, queue = [], []
-        self._chunk_states = []
+        # (the exact path: whole rounds of 16 resident wavefronts per CU, whatever the frames' sizes)
+        resident = (lambda n: 16 * int(self.engine.ctx.n_cu)) if exact else self._resident_frames
+        chunks = stream.plan(F, stream.tables_of(feature3ds, feature2ds, remap_in_place=bool(self.mutate_inputs)), C, ramp, points, resident)
         deferred = [] if (self.GPU_REDO_DEFER and not stage) else None      # declined frames' re-runs: finished after the last chunk
-        for k, (a, b, tb) in enumerate(chunk_bounds()):
-            bounds.append((a, b))
-            queue.append((self._chunk_gpu(feature3ds[a:b], feature2ds[a:b], stage, tables=tb, eng=engines[k % len(engines)],
-                                          lazy_last=lazy_last and not (eager_final and b == F),
-                                          host_exact=exact and not stage and self.GPU_EXACT_HOST_REDO and self.GPU_EXACT_STANDIN,
-                                          early_status=self.GPU_REDO_EARLY and deferred is not None and b == F and k > 0), a, b))
-            # GPU_PIPELINE chunks stay queued behind the one whose results are collected: this process packs and uploads
-            # the next chunk meanwhile (the kernel timeline shows the GPU 98 % busy between a call's first and last chunk
-            # with one: what a call pays beyond its kernels is its first chunk's pack + upload and the host's epilogue)
-            while len(queue) > self.GPU_PIPELINE + (1 if len(engines) == 2 else 0):
-                # (two contexts taking the chunks in turn: one more chunk in flight — each context then has its next chunk queued behind
-                # the one it is working on: 65 536 frames 116.3-117.0 -> 119.7-120.3 k frames/s, 16 384 frames unchanged:
-                # profiles/r06_exact_shape_sweep.txt)
-                ps, pa, pb = queue.pop(0)
-                self._chunk_states.append((ps, pa, pb))
-                results.append(self._chunk_gpu_finish(ps, feature3ds[pa:pb], feature2ds[pa:pb], defer=deferred))
-        while queue:
-            ps, pa, pb = queue.pop(0)
-            self._chunk_states.append((ps, pa, pb))
-            results.append(self._chunk_gpu_finish(ps, feature3ds[pa:pb], feature2ds[pa:pb], keep=not queue, defer=deferred))
-        self._chunk_gpu_complete_all(deferred)
-        raw = np.concatenate([r[0] for r in results])
-        status = np.concatenate([r[1] for r in results])
-        level = np.concatenate([r[2] for r in results])
-        counts = np.concatenate([r[3] for r in results])
-        host_errors = {}
-        for (a, _), r in zip(bounds, results):
-            host_errors.update({a + f: e for f, e in r[4].items()})
+
+        def start(a, b, tables, k):
+            return self._chunk_gpu(feature3ds[a:b], feature2ds[a:b], stage, tables=tables, eng=engines[k % len(engines)],
+                                   lazy_last=lazy_last and not (eager_final and b == F),
+                                   host_exact=exact and not stage and self.GPU_EXACT_HOST_REDO and self.GPU_EXACT_STANDIN,
+                                   early_status=self.GPU_REDO_EARLY and deferred is not None and b == F and k > 0)
+
+        def collect(st, a, b, last):
+            return self._chunk_gpu_finish(st, feature3ds[a:b], feature2ds[a:b], keep=last, defer=deferred)
+        # GPU_PIPELINE chunks stay queued behind the one whose results are collected (the kernel timeline shows the GPU 98 % busy between
+        # a call's first and last chunk with one: what a call pays beyond its kernels is its first chunk's pack + upload and the host's
+        # epilogue).  Two contexts taking the chunks in turn: one more chunk in flight — each context then has its next chunk queued
+        # behind the one it is working on (65 536 frames 116.3-117.0 -> 119.7-120.3 k frames/s, 16 384 frames unchanged:
+        # profiles/r06_exact_shape_sweep.txt)
+        records = deferred if deferred is not None else []
+        bounds, states, results = stream.run(chunks, start, collect, self.GPU_PIPELINE + len(engines) - 1, stream.free_blocks, records,
+                                             lambda: self._finish_reruns(records))
+        (raw, status, level, counts), host_errors = stream.concat(bounds, results, range(4), 4)
         if lazy_last:
             # the frames whose level is the product kernels' own sum although a later chunk might read it: every chunk's last frame
             # with more than three features below the vanishing row, unless the mask held it for another reason or an exact pass
             # redid it anyway (a re-run, a level that is the result).  A three-feature frame of THIS call that reads one: finished now.
             lazy = set()
-            for (a, b), (ps_, _, _) in zip(bounds, self._chunk_states):
+            for (a, b), ps_ in zip(bounds, states):
                 cnt = np.asarray(ps_["pf"].feat_cnt) if ps_.get("gpu") else None
                 if cnt is not None and not (eager_final and b == F):
                     ok = np.nonzero(cnt > 3)[0]
@@ -1135,8 +1017,7 @@ class ScaleEstimator:
                     lazy.discard(g)
                 self.lazy_levels_finished = getattr(self, "lazy_levels_finished", 0) + len(need)
             self._lazy_levels = lazy
-        self._chunk_states = []
-        return raw, status, level, counts, host_errors, ps
+        return raw, status, level, counts, host_errors, states[-1]
 
     def _single_exact_fast(self, feature3ds, feature2ds, fixed=False):
         """ONE frame of the reference-exact path (the per-frame call of /root/reference/src/main.py:110-113) with ONE SciPy call
@@ -1166,7 +1047,7 @@ class ScaleEstimator:
             return raw, status, level, counts, host_errors, st, None          # (final as it is: no level of this frame is read)
         if not sets_level:
             # marked (_lib.ST_REDO), or a status whose level is read at once: the frame again, through the host's path
-            self._chunk_free(st)
+            stream.free_blocks(st)
             sub = self._chunk_begin([f3], [f2], 0, tri1s=st.get("tri1_rows"), _remapped=st["remapped"], _fast=self._host_replay)
             self._chunk_vote(sub, None, 0)
             raw, status, level, counts, host_errors = self._chunk_scale(sub, None, True, keep=True)
@@ -1181,7 +1062,7 @@ class ScaleEstimator:
             try:
                 if fixed:               # (the device's own triangulations again, the frame on the exact mask this time)
                     _, _, lvl, _, _, ps = self._stream_gpu([raw_in], [f2_in], False)
-                    self._chunk_free(ps)
+                    stream.free_blocks(ps)
                 else:
                     sub = self._chunk_begin([raw_in], [f2_in], 0, tri1s=rows1, _exact_all=True, _fast=self._host_replay)
                     self._chunk_vote(sub, None, 0)
@@ -1191,8 +1072,6 @@ class ScaleEstimator:
             self.single_fast_levels = getattr(self, "single_fast_levels", 0) + 1
             return lvl[0]
         return raw, status, level, counts, host_errors, st, exact_level
-
-    LAZY_FLAT_FEATURE = True        # after a batch: flat_feature / flat_feature_2d when they are read (see the properties)
 
     def _flat_feature_of(self, feature3d, feature2d, st, mutate=None):
         """``self.flat_feature`` / ``flat_feature_2d`` after a batch: the selected points of its last processed frame
@@ -1213,7 +1092,7 @@ class ScaleEstimator:
                 one = self._chunk_gpu([f3], [f2], True)
                 _, status, _, _, _ = self._chunk_gpu_finish(one, [f3], [f2], keep=True)
                 self._store_flat_feature(one["pf"], one["out"], [f3], [f2], one["masks"], 0, status[0])
-                self._chunk_free(one)
+                stream.free_blocks(one)
                 return
             one = self._chunk_begin([f3], [f2], 0, _fast=self._host_replay)
             one["eng"] = self._plain_engine() if mutate else self.engine
@@ -1222,7 +1101,7 @@ class ScaleEstimator:
             if mutate:
                 self.mutate_inputs = True              # (_store_flat_feature then takes f3 as already remapped)
             self._store_flat_feature(one["pf"], one["out"], [f3], [f2], one["masks"], 0, status[0])
-            self._chunk_free(one)
+            stream.free_blocks(one)
         finally:
             self.mutate_inputs = keep_mutate
 

@@ -57,7 +57,7 @@ def main():
                                  check_triangle="reference" if exact else "fixed")
         est.GPU_REDO_EARLY = early
         acc = {}
-        for nm in ("_chunk_gpu_complete_all", "_chunk_begin", "_chunk_vote", "_chunk_scale", "_chunk_gpu", "_chunk_gpu_finish", "_finish_deferred"):
+        for nm in ("_finish_reruns", "_chunk_begin", "_chunk_vote", "_chunk_scale", "_chunk_gpu", "_chunk_gpu_finish"):
             if hasattr(est, nm):
                 timed(est, nm, acc)
         from mvoscalerecovery_amd import engine as _eng
@@ -126,8 +126,8 @@ def main():
             est.redo_early_started = est.redo_early_launched = est.redo_early_status_hits = 0
             print("%-9s %-9s: %7.2f ms per call (%+6.2f), %6.1f k frames/s, declined %3d; re-run %5.2f ms = begin %5.2f + vote %5.2f + scale %5.2f + rest %5.2f; launch side %6.2f, collect side %6.2f ms; hipMalloc %d hipFree %d; status waits %6.2f ms in %d, submits %5.2f ms in %d" % (
                 leg, label, med * 1e3, (med - ref) * 1e3, F / med / 1e3, getattr(est, "declined_total", getattr(est, "last_declined", 0)),
-                (p.get("_chunk_gpu_complete_all", 0.0) + p.get("_finish_deferred", 0.0)) * 1e3, p.get("_chunk_begin", 0.0) * 1e3, p.get("_chunk_vote", 0.0) * 1e3, p.get("_chunk_scale", 0.0) * 1e3,
-                (p.get("_chunk_gpu_complete_all", 0.0) - p.get("_chunk_begin", 0.0) - p.get("_chunk_vote", 0.0) - p.get("_chunk_scale", 0.0)) * 1e3,
+                p.get("_finish_reruns", 0.0) * 1e3, p.get("_chunk_begin", 0.0) * 1e3, p.get("_chunk_vote", 0.0) * 1e3, p.get("_chunk_scale", 0.0) * 1e3,
+                (p.get("_finish_reruns", 0.0) - p.get("_chunk_begin", 0.0) - p.get("_chunk_vote", 0.0) - p.get("_chunk_scale", 0.0)) * 1e3,
                 p.get("_chunk_gpu", 0.0) * 1e3, p.get("_chunk_gpu_finish", 0.0) * 1e3, p.get("mallocs", 0), p.get("frees", 0),
                 p.get("triangulation_status", 0.0) * 1e3, p.get("triangulation_status_calls", 0), p.get("delaunay_submit", 0.0) * 1e3, p.get("delaunay_submit_calls", 0)), flush=True)
 

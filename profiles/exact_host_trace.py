@@ -31,7 +31,7 @@ def wrap(obj, name, label):
 
 wrap(est, "_chunk_gpu", "launch")
 wrap(est, "_chunk_gpu_finish", "collect")
-wrap(est, "_chunk_gpu_complete_all", "re-runs")
+wrap(est, "_finish_reruns", "re-runs")
 wrap(engine, "pack_upload_native", "  pack+upload")
 _tri = engine.DeviceBatch.triangulate
 

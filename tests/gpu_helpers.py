@@ -140,3 +140,51 @@ def _check_rescale_device_against_oracle(est, ref, frames, batch):
 def _device_count():
     from mvoscalerecovery_amd import _lib
     return int(_lib.load().mvosr_device_count())
+
+
+def _declining(frames, at):
+    """``frames`` with the frames ``at`` on a quarter-pixel grid with a repeated site: both device triangulations decline them."""
+    frames = list(frames)
+    for f in at:
+        a3, a2 = frames[f][0].copy(), np.ascontiguousarray(np.round(frames[f][1] * 4) / 4)
+        low = np.nonzero(a2[:, 1] > 200.0)[0]
+        a2[low[1]], a3[low[1]] = a2[low[0]], a3[low[0]]
+        frames[f] = (a3, a2)
+    return frames
+
+
+def _check_error_mid_call_is_released(make, frames, contexts, monkeypatch):
+    """A host step that raises while a streamed call collects its third chunk, with re-runs of earlier chunks pending: the exception
+    leaves the call, every context's live blocks are back to their count before the call, every pool job the call submitted is done,
+    and the estimator's next call equals a fresh estimator's."""
+    from mvoscalerecovery_amd import engine, packing
+    f3s, f2s = [f[0] for f in frames], [f[1] for f in frames]
+    est = make()
+    est.raw_scale_batch(f3s, f2s)                          # (the estimator's contexts exist from here on)
+    ctxs = contexts(est)
+    before = [c.alloc_stats()["live_blocks"] for c in ctxs]
+    submitted, calls = [], [0]
+    submit, status = packing.delaunay_submit, engine.DeviceBatch.triangulation_status
+
+    def submit_(*a, **k):
+        h = submit(*a, **k)
+        submitted.append((k.get("slot", a[2] if len(a) > 2 else 0), h))
+        return h
+
+    def status_(self):
+        calls[0] += 1
+        if calls[0] == 3:
+            raise RuntimeError("host step failed")
+        return status(self)
+    monkeypatch.setattr(packing, "delaunay_submit", submit_)
+    monkeypatch.setattr(engine.DeviceBatch, "triangulation_status", status_)
+    with pytest.raises(RuntimeError, match="host step failed"):
+        est.raw_scale_batch(f3s, f2s)
+    monkeypatch.undo()
+    assert any(8 <= slot < 24 for slot, _ in submitted), [s for s, _ in submitted]     # (re-runs were pending)
+    assert all(h.ready() for _, h in submitted)
+    assert [c.alloc_stats()["live_blocks"] for c in ctxs] == before
+    got, want = est.raw_scale_batch(f3s, f2s), make().raw_scale_batch(f3s, f2s)
+    for g, w in zip(got[:3], want[:3]):
+        assert np.array_equal(np.asarray(g), np.asarray(w), equal_nan=True)
+    assert sorted(got[3]) == sorted(want[3])

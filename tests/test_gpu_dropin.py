@@ -9,7 +9,7 @@ import numpy as np
 import pytest
 
 from conftest import load_json, load_npz
-from gpu_helpers import _oracle
+from gpu_helpers import _check_error_mid_call_is_released, _declining, _oracle
 
 pytestmark = pytest.mark.gpu
 
@@ -1002,3 +1002,17 @@ def test_side_downloads_equal_queued_downloads(gpu, mode):
         got[side] = (np.asarray(s), np.asarray(d), est.height_level, est.declined_total)
     assert np.array_equal(got[True][0], got[False][0]) and np.array_equal(got[True][1], got[False][1])
     assert got[True][2] == got[False][2] and got[True][3] == got[False][3] >= 1
+
+
+def test_stream_error_mid_call_releases_chunks_and_reruns(gpu, monkeypatch):
+    """A host step raising while the streamed call collects its third of six chunks, re-runs of the first two pending: nothing of
+    the call stays alive on any of the estimator's contexts or in the Delaunay pool's slots, and the next call is unaffected."""
+    from mvoscalerecovery_amd import synth
+    from mvoscalerecovery_amd.scale_calculator import ScaleEstimator
+    frames = _declining([synth.synth_frame(i, 220 + (i * 37) % 160, base_seed=4242, upper_fraction=0.1) for i in range(768)], [3, 130, 700])
+
+    def make():
+        est = ScaleEstimator(1.75, window_size=5, mutate_inputs=False, triangulation="gpu", check_triangle="fixed", delaunay_workers=3)
+        est.GPU_CHUNK, est.GPU_RAMP, est.GPU_MIN_CHUNK = 128, False, 1
+        return est
+    _check_error_mid_call_is_released(make, frames, lambda e: [e.engine.ctx, e._redo_ctx], monkeypatch)

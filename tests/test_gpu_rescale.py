@@ -9,7 +9,7 @@ import numpy as np
 import pytest
 
 from conftest import load_json, load_npz
-from gpu_helpers import _check_rescale_device_against_oracle, _ransac_triples, _rescale_frames
+from gpu_helpers import _check_error_mid_call_is_released, _check_rescale_device_against_oracle, _declining, _ransac_triples, _rescale_frames
 
 pytestmark = pytest.mark.gpu
 
@@ -376,3 +376,16 @@ def test_rescale_deferred_reruns_started_early(gpu):
         assert (getattr(a, "redo_early_started", 0) >= 3) == early, getattr(a, "redo_early_started", 0)
         # (the LAST chunk's declined frame: found by the early read of the first triangulation's status)
         assert getattr(a, "redo_early_status_hits", 0) == (1 if early else 0)
+
+
+def test_rescale_stream_error_mid_call_releases_chunks_and_reruns(gpu, monkeypatch):
+    """rescale's streamed call: a host step raising while its third of six chunks is collected, re-runs of the first two pending —
+    nothing of the call stays alive on the estimator's contexts or in the Delaunay pool's slots, and the next call is unaffected."""
+    from mvoscalerecovery_amd.rescale import ScaleEstimator
+    frames = _declining(_rescale_frames([150 + (i * 29) % 200 for i in range(768)], base_seed=91), [5, 130, 700])
+
+    def make():
+        est = ScaleEstimator(1.75, window_size=5, triangulation="gpu", ransac_seed=99, delaunay_workers=3)
+        est.GPU_CHUNK, est.GPU_RAMP, est.GPU_MIN_CHUNK = 128, False, 1
+        return est
+    _check_error_mid_call_is_released(make, frames, lambda e: [e.ctx, e._redo_ctx], monkeypatch)

@@ -658,3 +658,122 @@ def test_joined_delaunay_handle():
         assert np.array_equal(r, packing.delaunay_simplices(p))
     assert packing._JoinedHandle(2, [([0], packing.delaunay_submit([sets[0]], 0, canonical=True)),
                                      ([1], packing.delaunay_submit([sets[1]], 0, canonical=True))]).canonical
+
+
+def _plan_bounds(F, lens, C, ramp=(), points=10 ** 9, resident=lambda n: 1, stop=None):
+    from mvoscalerecovery_amd import stream
+    lens = np.asarray(lens, dtype=np.int64)
+    out = []
+    for a, b, tb in stream.plan(F, lambda a, b: ((np.arange(a, b),), lens[a:b]), C, list(ramp), points, resident, stop):
+        assert np.array_equal(tb[0], np.arange(a, b))          # (the packer's tables cut to the chunk)
+        out.append((a, b))
+    return out
+
+
+def test_chunk_planner_ramp_points_workspace_resident():
+    """stream.chunk_size + stream.plan, the chunk bounds both estimators' streamed batches use, on synthetic frame sizes."""
+    from mvoscalerecovery_amd import stream
+    fr = stream.StreamKnobs.GPU_RAMP_FRACTIONS
+    # chunks of a quarter of the call (8192 at most, 512 at least); the short first chunks at C >= 2048 and F >= 3 C
+    C, ramp = stream.chunk_size(30000, 8192, 512, 10 ** 9, [100] * 64, fr)
+    assert (C, ramp) == (7500, [1250, 2500, 3750, 5000, 6250])
+    assert _plan_bounds(30000, [100] * 30000, C, ramp) == [(0, 1250), (1250, 3750), (3750, 7500), (7500, 12500), (12500, 18750),
+                                                           (18750, 26250), (26250, 30000)]
+    assert stream.chunk_size(8000, 8192, 512, 10 ** 9, [100] * 64, fr) == (2000, [])                 # (C < 2048: no ramp)
+    assert stream.chunk_size(6000, 2048, 512, 10 ** 9, [100] * 64, fr) == (1500, [])
+    assert stream.chunk_size(30000, 8192, 512, 10 ** 9, [100] * 64, ()) == (7500, [])                # (GPU_RAMP off)
+    assert stream.chunk_size(30000, 8192, 512, 2000000, [1000] * 64, fr) == (2000, [])               # (the points cap as it bites)
+    assert stream.chunk_size(100, 8192, 512, 5500, [1000] * 64, fr) == (512, [])                     # (... never below the minimum)
+    assert stream.chunk_size(65536, 8192, 512, 10 ** 9, [100] * 64, fr, full=16384)[0] == 16384       # (a size given: the exact mode's)
+    # the points cap: 5500 features are five 1000-feature frames
+    assert _plan_bounds(20, [1000] * 20, 512, points=5500) == [(0, 5), (5, 10), (10, 15), (15, 20)]
+    # one 20 000-point frame among small ones: chunks halved while frames x largest frame is above twice the cap
+    lens = [100] * 64
+    lens[10] = 20000
+    assert _plan_bounds(64, lens, 64, points=100000) == [(0, 8), (8, 15), (15, 64)]
+    # whole rounds of resident frames, except for the call's last chunk; resident() sees the chunk's largest frame
+    seen = []
+    assert _plan_bounds(1000, [10] * 1000, 300, resident=lambda n: seen.append(n) or 64) == [(0, 256), (256, 512), (512, 768),
+                                                                                            (768, 1000)]
+    assert set(seen) == {10}
+    assert _plan_bounds(1000, [10] * 1000, 300, resident=lambda n: 200) == [(0, 300), (300, 600), (600, 900), (900, 1000)]
+
+
+def test_chunk_planner_stop_before_oversized_frame():
+    """stream.plan's ``stop``: the call ends before the frame it names (rescale's frame the device path does not take), whether that
+    frame is inside a chunk or at its start; once it has named one it is not asked again."""
+    lens = np.full(400, 10)
+    lens[150] = 5000
+    calls = []
+
+    def stop(a, sizes):
+        calls.append(a)
+        over = np.nonzero(np.asarray(sizes) > 1000)[0]
+        return a + int(over[0]) if len(over) else None
+    assert _plan_bounds(400, lens, 100, stop=stop) == [(0, 100), (100, 150)]
+    assert calls == [0, 100]
+    lens = np.full(400, 10)
+    lens[200] = 5000
+    assert _plan_bounds(400, lens, 100, stop=stop) == [(0, 100), (100, 200)]
+    assert _plan_bounds(400, np.full(400, 10), 100, stop=stop) == [(0, 100), (100, 200), (200, 300), (300, 400)]
+
+
+def test_rerun_records_slots_in_flight_are_distinct():
+    """stream.Rerun / advance / finish_all with stub steps shaped like the estimators' (first triangulations on the pool -> launch ->
+    second triangulations on the pool -> launch -> results): two started records, the last chunk's early one and a host-path chunk in
+    flight at once use distinct slots of the map; finish_all forces the chains in stage order, merges the record that had not begun
+    and scatters every result into its chunk's results."""
+    from mvoscalerecovery_amd import stream
+    in_flight, used, log = set(), set(), []
+    legal = set(range(stream.SLOT_CHUNK, stream.SLOT_CHUNK_TRI2 + stream.CHUNK_SLOTS)) | set(range(stream.SLOT_DEFER, stream.SLOT_DEFER_TRI2 + 8)) \
+        | {stream.SLOT_EARLY, stream.SLOT_EARLY_TRI2}
+
+    def submit(slot):
+        assert slot in legal and slot not in in_flight, (slot, in_flight)
+        in_flight.add(slot)
+        used.add(slot)
+
+    def record(name, slots, n, begun):
+        res = {"v": np.zeros(6), "e": {}}
+        r = stream.Rerun(res, np.arange(n) * 2, lambda: None, ready=[False, False, False])
+        submit(slots[0])
+
+        def step(s):
+            def take(wait):
+                log.append((name, s, wait))
+                if s == 0:
+                    in_flight.discard(slots[0])
+                    r.begun = True
+                elif s == 1:
+                    submit(slots[1])
+                else:
+                    in_flight.discard(slots[1])
+            return take
+        r.chain = [(lambda s=s: r.ready[s], step(s)) for s in range(3)]
+        r.collect = lambda: {"v": np.full(n, 7.0), "e": {0: ValueError(name)}}
+        r.begun = begun
+        return r
+
+    recs = [record("a", (stream.SLOT_DEFER, stream.SLOT_DEFER_TRI2), 2, True), record("b", (stream.SLOT_DEFER + 1, stream.SLOT_DEFER_TRI2 + 1), 3, False)]
+    submit(stream.SLOT_CHUNK + 5 % stream.CHUNK_SLOTS)                    # (a host-path chunk's first triangulations, in flight meanwhile)
+    recs[0].ready[0] = True
+    stream.advance(recs)
+    assert [r.step for r in recs] == [1, 0] and log == [("a", 0, False)]
+    early = record("e", (stream.SLOT_EARLY, stream.SLOT_EARLY_TRI2), 1, True)
+    early.ready[0] = early.ready[1] = True
+    stream.advance([early])
+    stream.advance([early])
+    assert early.step == 2 and stream.SLOT_EARLY_TRI2 in in_flight
+    recs.append(early)
+    stream.advance_while(recs, lambda: False)              # (nothing outstanding: no wait)
+    merged = []
+
+    def merge(rest):
+        merged.extend(rest)
+        for r in rest:
+            stream.scatter(r.res, r.redo, {"v": np.full(len(r.redo), 3.0), "e": {}}, ["v"], "e")
+    stream.finish_all(recs, merge, ["v"], "e")
+    assert recs == [] and [r.redo.tolist() for r in merged] == [[0, 2, 4]]
+    # forced: a's second step, then the third steps of a and e — every launch before any result
+    assert log[-3:] == [("a", 1, True), ("a", 2, True), ("e", 2, True)]
+    assert len(used) == 6 and in_flight == {stream.SLOT_CHUNK + 1, stream.SLOT_DEFER + 1}     # (b's merged; the chunk's own)
