@@ -811,10 +811,10 @@ __device__ __forceinline__ SelectResult phase_select(const Smem &s, int n_valid,
 // ---------------------------------------------------------------------------------------------
 // Phase C (its own kernel, one frame per WAVEFRONT): road model on a dense list of y' values —
 // the selected points the scale kernel wrote to the workspace, or caller-supplied lists.
-// No barriers: a wave keeps up to 16 values per lane in registers, builds the 169-bin histogram
-// with wave-local LDS atomics, evaluates remove_single / modes / local minima on 64-bit ballots
-// and reduces mean / std with DPP.  Runs at full occupancy, so its latency chains are hidden by
-// other waves instead of holding a 53 KB LDS allocation idle.
+// No barriers: a wave reads its list once, building the 169-bin histogram with wave-local LDS
+// atomics and the shifted sums of mean / std in the same loop, evaluates remove_single / modes /
+// local minima on 64-bit ballots and reduces with DPP.  Its latency chains are hidden by other
+// waves instead of holding a 53 KB LDS allocation idle.
 //                                                (road_model_calculation_static, :324-354)
 // ---------------------------------------------------------------------------------------------
 struct RoadResult {
@@ -842,12 +842,18 @@ __device__ __forceinline__ bool dropped_by_single(double y, int bin, const Bits1
     return d;
 }
 
+#ifdef MVOSR_ROAD_EXACT_COUNT
+// Diagnostic build only (profiles/road_exact_count.py): lists that reach the skewness decision, and how many of them the
+// earlier two-pass band alone / the band in use send to NumPy's exact order (without the statistics output).
+__device__ unsigned long long g_road_exact_count[3];
+#endif
 #ifndef MVOSR_ROAD_RC
 #define MVOSR_ROAD_RC 20
 #endif
-constexpr int kRoadRC = MVOSR_ROAD_RC;   // deepest register cache: values per lane kept in registers (lists up to 64*RC values; longer ones
-                                         // re-read).  20 keeps the kernel at 4 wavefronts per SIMD (121 VGPRs); 32 was measured: 2 per SIMD, slower
-constexpr int kDropStride = 32;          // verdict bytes per lane in LDS (two 16-byte words)
+constexpr int kRoadRC = MVOSR_ROAD_RC;   // deepest tier: rows of 64 values whose bins stay in registers (one byte each, four per VGPR); longer
+                                         // lists (dense frames) re-read their tail once, for the suspects
+constexpr int kRoadSub = 4;              // lane-interleaved copies of the histogram (lane & 3): a clustered row's same-bin ds_add_u32 serialise
+                                         // four times less; the copies of a bin are adjacent ints, summed with one ds_read_b128
 constexpr int kRoadWaves = 4;          // frames (wavefronts) per workgroup
 constexpr int kTrash = 175;            // histogram slot for values that are not binned (bins are 0..168)
 constexpr int kStPending = -1;         // scale kernel -> road kernel: "road model still to run"
@@ -885,15 +891,24 @@ __device__ __forceinline__ int bin_of_table(double y, const double2 *edges) {
 
 // WW = 1: the whole list in one wavefront.  WW = kRoadWaves (dense frames, lists of thousands of values, too few
 // frames to fill the GPU with one wavefront each): the workgroup's wavefronts share the frame — each takes a
-// contiguous part `[lo, hi)` of the list through the per-value passes (histogram into the SHARED `hist`, suspects,
-// sums; partial sums meet in `part`, added in wavefront order), every wavefront evaluates the histogram logic
-// redundantly (same inputs, same result), and wavefront 0 alone finishes the frame (modes, the decision, the cold
+// contiguous part `[lo, hi)` of the list through the per-value pass (histogram into the SHARED `hist`, sums) and
+// through its suspects; partial sums meet in `part`, added in wavefront order; every wavefront evaluates the histogram
+// logic redundantly (same inputs, same result), and wavefront 0 alone finishes the frame (modes, the decision, the cold
 // exact branches over the whole list).  `Mall` is the whole list's length; `yv` its first value.
+//
+// ONE pass over the values: it bins a value, adds it to the histogram and to the lane's shifted sums
+// S1 = sum(y - sh), S2 = sum((y - sh)^2) (sh: the list's first value, a frame-uniform shift close to the data).  Which
+// values remove_single drops is known only once the histogram is complete: those few are re-read (their bin or a
+// neighbour has count 1 — the "suspects") and their terms subtracted from the lane's sums.  No value is kept in registers,
+// only the bins of the first RC rows (a byte each), for the suspect test.
+// hist: kRoadSub lane-interleaved copies, bin b of copy c at int 4*b + c; comb: the summed counts (176 ints);
+// nearflag: 176 bytes, 1 for a bin that is single or next to a single one.
 template <int RC, int WW = 1>
-__device__ __forceinline__ RoadResult road_wave(int *hist, int *nearflag, uint16_t *slots, uint8_t *dropb, const double2 *edges,
+__device__ __forceinline__ RoadResult road_wave(int *hist, int *comb, uint8_t *nearflag, const double2 *edges,
                                                 const double *yv_all, double *scratch,
                                                 int Mall, double height_level, const mvosr_params &P, int32_t *g_hist, bool exact_stats,
                                                 int part_lo, int part_hi, double *part, int *np_stack MVOSR_STAMP_ARG) {
+    static_assert(RC <= 32 && kRoadSub == 4, "32-bit row masks; one int4 per bin");
     const int lane = lane_id();
     RoadResult R;
     R.height = nan(""); R.status = MVOSR_ST_MODE; R.n_sel = Mall; R.n_kept = 0; R.n_modes = 0; R.mode_left = -1; R.mode_right = -1;
@@ -902,47 +917,63 @@ __device__ __forceinline__ RoadResult road_wave(int *hist, int *nearflag, uint16
     const double *yv = yv_all + (part_hi > part_lo ? part_lo : 0);     // my part of the list (WW == 1: all of it; an empty part: any legal address)
     const int M = part_hi - part_lo;                    // (may be 0 for the last wavefronts of a short list)
     if (WW == 1 || wave_id() == 0) {
+        int4 z; z.x = z.y = z.z = z.w = 0;
 #pragma unroll
-        for (int c = 0; c < 3; ++c) { const int b = lane + 64 * c; if (b < 176) hist[b] = 0; }
+        for (int c = 0; c < 3; ++c) { const int b = lane + 64 * c; if (b < 176) reinterpret_cast<int4 *>(hist)[b] = z; }
     }
     if constexpr (WW > 1) __syncthreads();
+    const double y0 = yv_all[0];
+    const double sh = (y0 - y0 == 0.0) ? y0 : 0.0;      // (finite; a non-finite value makes the sums NaN whatever the shift)
+    int *hsub = hist + (lane & (kRoadSub - 1));
 
-    // histogram (np.histogram, :326); the first RC values of every lane stay in registers
-    double yc[RC];
-    int binc[RC];
-    // Branch-free on purpose: with no control flow between them the 16 loads, table reads and
-    // atomics of a lane are scheduled in batches instead of one dependent round trip per value.
-    // Values that take no part (beyond the list, or outside [0,16.9]) go to the trash bin kTrash.
+    // histogram (np.histogram, :326) and the shifted sums; the bins of the first RC rows stay in registers.
+    // Branch-free on purpose: with no control flow between them the loads, table reads and atomics of a lane are
+    // scheduled in batches instead of one dependent round trip per value.  Values that take no part (beyond the list,
+    // or outside [0,16.9]) go to the trash bin kTrash; outside [0,16.9] they still count for the mean (as in NumPy).
     const int nfull = M / kWave;
     const unsigned valid = (nfull >= RC) ? (unsigned)((1ull << RC) - 1ull)     // bit k: value k*64+lane exists
                                               : (((1u << nfull) - 1u) | ((lane < M - nfull * kWave ? 1u : 0u) << nfull));
+    double s1 = 0.0, s2 = 0.0;
+    unsigned pk[(RC + 3) / 4];
+    constexpr int kG = 4;                               // loads in flight per lane
 #pragma unroll
-    for (int k = 0; k < RC; ++k) {
-        const int i = max(min(k * kWave + lane, M - 1), 0);                               // clamped: always a legal address
-        yc[k] = yv[i];
-    }
+    for (int k0 = 0; k0 < RC; k0 += kG) {
+        double yg[kG];
 #pragma unroll
-    for (int k = 0; k < RC; ++k) {
-        const double y = yc[k];
-        const bool inr = ((valid >> k) & 1u) && (y >= 0.0) && (y <= bin_edge(kBins));
-        const int g = inr ? min((int)(y * 10.0), kBins - 1) : 0;
-        const double2 e = edges[g];
-        int bin = g + ((g < kBins - 1 && y >= e.y) ? 1 : 0) - ((y < e.x) ? 1 : 0);
-        bin = inr ? bin : kTrash;
-        atomicAdd(&hist[bin], 1);
-        binc[k] = bin;
+        for (int j = 0; j < kG && k0 + j < RC; ++j) yg[j] = yv[max(min((k0 + j) * kWave + lane, M - 1), 0)];   // clamped: always a legal address
+#pragma unroll
+        for (int j = 0; j < kG && k0 + j < RC; ++j) {
+            const int k = k0 + j;
+            const double y = yg[j];
+            const bool vk = (valid >> k) & 1u;
+            const bool inr = vk && (y >= 0.0) && (y <= bin_edge(kBins));
+            const int g = inr ? min((int)(y * 10.0), kBins - 1) : 0;
+            const double2 e = edges[g];
+            int bin = g + ((g < kBins - 1 && y >= e.y) ? 1 : 0) - ((y < e.x) ? 1 : 0);
+            bin = inr ? bin : kTrash;
+            atomicAdd(&hsub[4 * bin], 1);
+            const double d = vk ? y - sh : 0.0;
+            s1 += d;
+            s2 = __builtin_fma(d, d, s2);
+            pk[k >> 2] = (k & 3) ? (pk[k >> 2] | ((unsigned)bin << (8 * (k & 3)))) : (unsigned)bin;
+        }
+        __builtin_amdgcn_sched_barrier(0);              // (the next group's loads stay behind this one: kG values in flight, not RC)
     }
-    // (lists longer than the register cache — dense frames: four loads in flight per trip instead of one dependent
-    // round trip per value; the same in the two passes further down)
-    constexpr int kLongUnroll = 8;
+    // (lists longer than the register tier — dense frames: two loads in flight per trip instead of one dependent
+    // round trip per value; the same in the suspects' pass further down)
+    constexpr int kLongUnroll = 2;
     for (int i0 = RC * kWave + lane; i0 < M; i0 += kLongUnroll * kWave) {
         double yl[kLongUnroll];
 #pragma unroll
         for (int j = 0; j < kLongUnroll; ++j) yl[j] = yv[max(min(i0 + j * kWave, M - 1), 0)];
 #pragma unroll
         for (int j = 0; j < kLongUnroll; ++j) {
-            const int bin = (i0 + j * kWave < M) ? bin_of_table(yl[j], edges) : -1;
-            if (bin >= 0) atomicAdd(&hist[bin], 1);
+            if (i0 + j * kWave >= M) continue;
+            const int bin = bin_of_table(yl[j], edges);
+            if (bin >= 0) atomicAdd(&hsub[4 * bin], 1);
+            const double d = yl[j] - sh;
+            s1 += d;
+            s2 = __builtin_fma(d, d, s2);
         }
     }
     MVOSR_RSTAMP(2);
@@ -954,7 +985,10 @@ __device__ __forceinline__ RoadResult road_wave(int *hist, int *nearflag, uint16
 #pragma unroll
     for (int c = 0; c < 3; ++c) {
         const int b = lane + 64 * c;
-        hraw[c] = (b < kBins) ? hist[b] : 0;
+        int h = 0;
+        if (b < kBins) { const int4 q = reinterpret_cast<const int4 *>(hist)[b]; h = (q.x + q.y) + (q.z + q.w); }
+        if (b < 176) comb[b] = h;
+        hraw[c] = h;
         hz[c] = (hraw[c] == 1) ? 0 : hraw[c];                                  // dis[dis==1]=0, :328
         single.w[c] = __ballot(b < kBins && hraw[c] == 1);
         mx = max(mx, hz[c]);
@@ -974,52 +1008,31 @@ __device__ __forceinline__ RoadResult road_wave(int *hist, int *nearflag, uint16
     near.w[1] = single.w[1] | (single.w[1] << 1) | (single.w[1] >> 1) | (single.w[0] >> 63) | (single.w[2] << 63);
     near.w[2] = single.w[2] | (single.w[2] << 1) | (single.w[2] >> 1) | (single.w[1] >> 63);
 #pragma unroll
-    for (int c = 0; c < 3; ++c) { const int b = lane + 64 * c; if (b < 176) nearflag[b] = (b < kBins) ? (int)((near.w[c] >> lane) & 1ull) : 0; }
+    for (int c = 0; c < 3; ++c) { const int b = lane + 64 * c; if (b < 176) nearflag[b] = (b < kBins) ? (uint8_t)((near.w[c] >> lane) & 1ull) : 0; }
     // check_mode returns no modes iff max <= 2 (:451-452); otherwise the maximum bin itself is one
     const bool have_modes = mx > P.mode_min;
 
-    // second pass: drop the points inside a single bin's interval (:284-293), accumulate the mean.
-    // Only values whose own or neighbouring bin has count 1 can be dropped: they are flagged here
-    // (one LDS read each) and examined in a rolled loop below, which most iterations skip.
-    // The few suspects of the whole list are packed into one dense list (slot numbers, ballot prefix)
-    // and examined with full lanes — row by row almost every row would run the whole interval test
-    // for one or two lanes.  Verdicts return through a byte per slot, 16 contiguous bytes per lane.
-    unsigned kept = valid;
+    // the values remove_single drops (:284-293): only a suspect — own or neighbouring bin of count 1 — can be.  Each lane
+    // re-reads its own suspects (a cache hit) and subtracts the terms of those the interval test drops, in row order.
+    double t1 = 0.0, t2 = 0.0;
+    int nd = 0;
     {
-        uint4 zero; zero.x = zero.y = zero.z = zero.w = 0u;
-        reinterpret_cast<uint4 *>(dropb)[2 * lane] = zero;
-        if (RC > 16) reinterpret_cast<uint4 *>(dropb)[2 * lane + 1] = zero;
-        int ns = 0;
+        unsigned sus = 0u;
 #pragma unroll
-        for (int k = 0; k < RC; ++k) {
-            const bool sus = nearflag[binc[k]] != 0;                          // nearflag[kTrash] == 0
-            const unsigned long long m = __ballot(sus);
-            if (sus) slots[ns + __popcll(m & ((1ull << lane) - 1ull))] = (uint16_t)(k * kWave + lane);
-            ns += __popcll(m);
-        }
-        for (int i = lane; i < ns; i += kWave) {
-            const int e = slots[i];
-            const double y = yv[e];                                           // (a cache hit; avoids indexing the register array)
-            if (dropped_by_single(y, bin_of_table(y, edges), single, first_single)) dropb[(e & (kWave - 1)) * kDropStride + (e >> 6)] = 1;
-        }
-        if (ns > 0) {
-#pragma unroll
-            for (int j = 0; j < (RC + 15) / 16; ++j) {
-                const uint4 d = reinterpret_cast<const uint4 *>(dropb)[2 * lane + j];
-#pragma unroll
-                for (int k = 16 * j; k < RC && k < 16 * j + 16; ++k) {
-                    const int kk = k & 15;
-                    const unsigned w = (kk >> 2) == 0 ? d.x : ((kk >> 2) == 1 ? d.y : ((kk >> 2) == 2 ? d.z : d.w));
-                    if ((w >> (8 * (kk & 3))) & 0xFFu) kept &= ~(1u << k);
-                }
+        for (int k = 0; k < RC; ++k) sus |= (nearflag[(pk[k >> 2] >> (8 * (k & 3))) & 0xFFu] ? 1u : 0u) << k;   // nearflag[kTrash] == 0
+        while (sus) {
+            const int k = __ffs(sus) - 1;
+            sus &= sus - 1u;
+            const double y = yv[k * kWave + lane];
+            if (dropped_by_single(y, bin_of_table(y, edges), single, first_single)) {
+                const double d = y - sh;
+                t1 += d;
+                t2 = __builtin_fma(d, d, t2);
+                ++nd;
             }
         }
     }
-    double sum = 0.0;
-#pragma unroll
-    for (int k = 0; k < RC; ++k) sum += ((kept >> k) & 1u) ? yc[k] : 0.0;
-    double cntd = (double)__popc(kept);
-    for (int i0 = RC * kWave + lane; i0 < M; i0 += kLongUnroll * kWave) {   // lists longer than the register cache
+    for (int i0 = RC * kWave + lane; i0 < M; i0 += kLongUnroll * kWave) {   // lists longer than the register tier
         double yl[kLongUnroll];
 #pragma unroll
         for (int j = 0; j < kLongUnroll; ++j) yl[j] = yv[max(min(i0 + j * kWave, M - 1), 0)];
@@ -1028,22 +1041,28 @@ __device__ __forceinline__ RoadResult road_wave(int *hist, int *nearflag, uint16
             if (i0 + j * kWave >= M) continue;
             const double y = yl[j];
             const int bin = bin_of_table(y, edges);
-            if (bin >= 0 && nearflag[bin] && dropped_by_single(y, bin, single, first_single)) continue;
-            sum += y; cntd += 1.0;
+            if (bin >= 0 && nearflag[bin] && dropped_by_single(y, bin, single, first_single)) {
+                const double d = y - sh;
+                t1 += d;
+                t2 = __builtin_fma(d, d, t2);
+                ++nd;
+            }
         }
     }
-    sum = wave_sum(sum);
-    cntd = wave_sum(cntd);
+    double S1 = wave_sum(s1 - t1), S2 = wave_sum(s2 - t2), Q = wave_sum(s2);
+    nd = wave_sum(nd);
     if constexpr (WW > 1) {
-        if (lane == 0) { part[2 * wave_id()] = sum; part[2 * wave_id() + 1] = cntd; }
+        if (lane == 0) { part[4 * wave_id()] = S1; part[4 * wave_id() + 1] = S2; part[4 * wave_id() + 2] = Q; part[4 * wave_id() + 3] = (double)nd; }
         __syncthreads();
-        sum = 0.0; cntd = 0.0;
+        S1 = 0.0; S2 = 0.0; Q = 0.0;
+        double ndd = 0.0;
 #pragma unroll
-        for (int i = 0; i < WW; ++i) { sum += part[2 * i]; cntd += part[2 * i + 1]; }
-        __syncthreads();                                // (the slots are used again for the squares)
+        for (int i = 0; i < WW; ++i) { S1 += part[4 * i]; S2 += part[4 * i + 1]; Q += part[4 * i + 2]; ndd += part[4 * i + 3]; }
+        nd = (int)ndd;
     }
     MVOSR_RSTAMP(4);
-    const int nkept = (int)cntd;
+    const int nkept = Mall - nd;
+    const double cntd = (double)nkept;
     R.n_kept = nkept;
 
     // the kept values in list order, packed into `scratch` (for the median fallback and the exact sums)
@@ -1094,38 +1113,7 @@ __device__ __forceinline__ RoadResult road_wave(int *hist, int *nearflag, uint16
         R.height = R.median; R.status = MVOSR_ST_MEDIAN;
         return R;
     }
-
-    // third pass: standard deviation around the mean (np.std, :496)
-    const double mean = sum / cntd;                                             // np.mean
-    double ss = 0.0;
-#pragma unroll
-    for (int k = 0; k < RC; ++k) {
-        const double d = ((kept >> k) & 1u) ? yc[k] - mean : 0.0;
-        ss += d * d;
-    }
-    for (int i0 = RC * kWave + lane; i0 < M; i0 += kLongUnroll * kWave) {
-        double yl[kLongUnroll];
-#pragma unroll
-        for (int j = 0; j < kLongUnroll; ++j) yl[j] = yv[max(min(i0 + j * kWave, M - 1), 0)];
-#pragma unroll
-        for (int j = 0; j < kLongUnroll; ++j) {
-            if (i0 + j * kWave >= M) continue;
-            const double y = yl[j];
-            const int bin = bin_of_table(y, edges);
-            if (bin >= 0 && nearflag[bin] && dropped_by_single(y, bin, single, first_single)) continue;
-            const double d = y - mean;
-            ss += d * d;
-        }
-    }
-    ss = wave_sum(ss);
-    if constexpr (WW > 1) {
-        if (lane == 0) part[wave_id()] = ss;
-        __syncthreads();
-        if (wave_id() != 0) return R;                   // wavefront 0 finishes the frame
-        ss = 0.0;
-#pragma unroll
-        for (int i = 0; i < WW; ++i) ss += part[i];
-    }
+    if constexpr (WW > 1) { if (wave_id() != 0) return R; }                                 // wavefront 0 finishes the frame
     MVOSR_RSTAMP(5);
 
 #pragma unroll
@@ -1138,7 +1126,7 @@ __device__ __forceinline__ RoadResult road_wave(int *hist, int *nearflag, uint16
                 is_mode = (h == mx);                                            // :454-458
                 is_min = (h == mn);                                             // :433-437
             } else {
-                const int lraw = hist[b - 1], rraw = hist[b + 1];
+                const int lraw = comb[b - 1], rraw = comb[b + 1];
                 const int hl_ = (lraw == 1) ? 0 : lraw, hr_ = (rraw == 1) ? 0 : rraw;
                 is_mode = (h >= hl_) && (h >= hr_) && ((double)h >= P.mode_rel * (double)mx) && (h >= P.mode_min);   // :459-463
                 is_min = (h <= hl_) && (h <= hr_) && !((h == hr_) && (h == hl_));                                   // :438-442
@@ -1160,16 +1148,48 @@ __device__ __forceinline__ RoadResult road_wave(int *hist, int *nearflag, uint16
     const int ir = mins.lowest_from(mr);                                        // :342,:344  bins mr..168
     if (ir < 0) { R.status = MVOSR_ST_ERR_RIGHT; return R; }
     const double right = bin_edge(ir + 1);
+    // np.mean / np.std from the shifted sums
+    const double m1 = S1 / cntd;
+    const double mean = sh + m1;
+    const double var = S2 / cntd - m1 * m1;
     double mean_o = mean;
-    double sd = sqrt(ss / cntd);                                                // np.std
-    // The sums above run in the wavefront's order, NumPy's in its pairwise order: mean and std agree to
-    // ~1e-15 relative, which decides `skew > 0.3` the same way unless the two sides are that close — in
-    // practice only for (nearly) constant lists, where std is rounding noise.  Then, and when exact
-    // statistics are asked for, both sums are redone in NumPy's own order on the packed list.
+    double sd = sqrt(var);
+    // The sums above run in the wavefront's order and in one pass, NumPy's in its pairwise order and in two: mean and std
+    // differ in the last bits, which decides `skew > thr` differently only when both sides of
+    //     (mean - mode/10) - thr*sd
+    // are within `bound` of each other — in practice for (nearly) constant lists, where std is rounding noise.  Then, and
+    // when exact statistics are asked for, both sums are redone in NumPy's own order on the packed list.
+    //   The bound (u = 2^-53; N = Mall values, n = nkept; Q = sum over ALL values of (y-sh)^2; a2 = Q/n, r = sqrt(a2) >=
+    // |S1/n|, rho = sqrt(N/n), Mg = |sh| + r >= mean|y| of the kept values).  A sum evaluated along a tree of height h is off
+    // by at most h*u*sum|terms| (to first order).  Ours: a lane adds <= ceil(N/64) values and subtracts <= as many, then
+    // the DPP tree and the readlanes (7), the wide variant's parts (4), the d = y - sh and the square (2): h <= 2*ceil(N/64)
+    // + 16.  NumPy's (np_pairwise_sum_cold): <= 16 adds per leaf accumulator, 3 to combine them, 7 for the leaf's
+    // remainder, 6 levels of halves within an 8192-value chunk, one per chunk: h_np <= 32 + N/8192.  So with
+    // g = 2u * (2*ceil(N/64) + 64 + N/8192) >= twice the sum of both heights and the handful of single roundings:
+    //   |S1 err|/n <= g*sum|y-sh|/n <= g*sqrt(N*Q)/n = g*rho*r;   NumPy's mean: g*Mg          => d(mean) <= g*(Mg + rho*r)
+    //   S2 - the dropped terms: g*Q (both sums of positive terms), m1^2: 2*r*g*(rho + 1)*r;
+    //   NumPy's two-pass variance: g*var + d(mean_np)^2 (sum of (y - m')^2 = sum of (y - m)^2 + n*(m - m')^2)
+    //                                                                                => d(var) <= g*a2*(6 + 2*rho) + (g*Mg)^2
+    //   |sqrt(a) - sqrt(b)| <= |a - b| / sqrt(a):   d(sd) <= d(var) / sd;  and the rounding of the margin's own terms and of
+    //   the division in skew: g*(Mg + |mode/10| + thr*sd).
+    // The band below is the earlier two-pass band plus this one: a list the old band sent to the exact path still goes.
     {
-        const double var = ss / cntd, rms = sqrt(mean * mean + var);
+        const double thr = fabs(P.skew_threshold);
+        const double N = (double)Mall;
+        const double g = 0x1p-52 * (2.0 * (double)((Mall + kWave - 1) / kWave) + 64.0 + N / (double)kNpBufSize);
+        const double a2 = Q / cntd, r = sqrt(a2), rho = sqrt(N / cntd), Mg = fabs(sh) + r;
+        const double rms = sqrt(mean * mean + var);
         const double margin = fabs((mean - mode / 10.0) - P.skew_threshold * sd);
-        const double bound = 1e-11 * (rms + sd) + 1e-22 * rms * rms / sd;
+        const double bound_two_pass = 1e-11 * (rms + sd) + 1e-22 * rms * rms / sd;
+        const double bound = bound_two_pass
+                           + g * ((Mg + rho * r) + fabs(mode / 10.0) + (1.0 + thr) * sd + (1.0 + thr) * (a2 * (6.0 + 2.0 * rho) + g * Mg * Mg) / sd);
+#ifdef MVOSR_ROAD_EXACT_COUNT
+        if (lane == 0) {
+            atomicAdd(&g_road_exact_count[0], 1ull);
+            if (!(margin > bound_two_pass)) atomicAdd(&g_road_exact_count[1], 1ull);
+            if (!(margin > bound)) atomicAdd(&g_road_exact_count[2], 1ull);
+        }
+#endif
         if (!(margin > bound) || exact_stats) {
             const int nl = pack_kept();
             __threadfence_block();               // the wave's own stores, visible to all its lanes
@@ -1187,17 +1207,22 @@ __device__ __forceinline__ RoadResult road_wave(int *hist, int *nearflag, uint16
 #ifndef MVOSR_ROAD_MINW
 #define MVOSR_ROAD_MINW 1
 #endif
+#ifndef MVOSR_ROAD_OCC
+#define MVOSR_ROAD_OCC 6                 // wavefronts per SIMD the product variants are compiled for (their VGPR budget)
+#endif
 // LIST: the frames of a.list, grid-strided (the rare second pass over the frames that ended on the fallback level); otherwise
 // frame first_frame + wavefront index, no loop (a loop around the body costs the product variant 57 VGPRs, i.e. half its occupancy)
+// LDS per workgroup ~18 KB; the launch bound gives the product variants MVOSR_ROAD_OCC wavefronts per SIMD (6: at most
+// 80 VGPRs, six workgroups per CU; 8 needs 64 VGPRs and spills inside the loops, 5 runs without spills but slower).
 template <bool LIST, int WW = 1>
-__global__ __launch_bounds__(kRoadWaves *kWave, (LIST ? 1 : 4)) void road_model_kernel(const RoadArgs a) {
-    static_assert(kRoadRC >= 16 && kRoadRC <= kDropStride, "verdict bytes per lane; the keep masks are 32 bits");
+__global__ __launch_bounds__(kRoadWaves *kWave, (LIST ? 1 : MVOSR_ROAD_OCC)) void road_model_kernel(const RoadArgs a) {
+    static_assert(kRoadRC >= 16 && kRoadRC <= 32, "the row masks are 32 bits");
     static_assert(WW == 1 || (WW == kRoadWaves && !LIST), "wide variant: the whole workgroup on one frame");
-    __shared__ int hist_all[kRoadWaves][2][176];
+    __shared__ __attribute__((aligned(16))) int hist_all[kRoadWaves][kRoadSub * 176];
+    __shared__ int comb_all[kRoadWaves][176];
+    __shared__ uint8_t near_all[kRoadWaves][176];
     __shared__ double2 edges[kBins + 1];
-    __shared__ uint16_t slots_all[kRoadWaves][kRoadRC * kWave];
-    __shared__ __attribute__((aligned(16))) uint8_t drop_all[kRoadWaves][kDropStride * kWave];
-    __shared__ double part[2 * kRoadWaves];
+    __shared__ double part[4 * kRoadWaves];
     __shared__ __attribute__((aligned(8))) int np_stack_all[kRoadWaves][kNpStackInts];
     for (int k = threadIdx.x; k < kBins; k += kRoadWaves * kWave) { double2 e; e.x = bin_edge(k); e.y = bin_edge(k + 1); edges[k] = e; }
     __syncthreads();
@@ -1210,9 +1235,9 @@ __global__ __launch_bounds__(kRoadWaves *kWave, (LIST ? 1 : 4)) void road_model_
     const int64_t off = a.off[f];
     const double hl = a.height_level ? a.height_level[f] : nan("");
     MVOSR_RSTAMP(1);
-    // values per lane kept in registers: as few as the list (wide: this wavefront's part of it) needs (the passes over
-    // them are branch-free, so a short list would otherwise pay for sixteen rows of padding)
-    int *h0 = hist_all[WW > 1 ? 0 : wave_id()][0], *h1 = hist_all[wave_id()][1];
+    // rows of bins kept in registers: as few as the list (wide: this wavefront's part of it) needs (the pass over
+    // them is branch-free, so a short list would otherwise pay for rows of padding)
+    int *h0 = hist_all[WW > 1 ? 0 : wave_id()];
     int32_t *gh = a.o.hist ? a.o.hist + f * 2 * kBins : nullptr;
     const bool ex = a.o.stats != nullptr;
     int lo = 0, hi = M;
@@ -1222,11 +1247,12 @@ __global__ __launch_bounds__(kRoadWaves *kWave, (LIST ? 1 : 4)) void road_model_
         hi = min(M, lo + q);
     }
     const int Mp = hi - lo;
-#define MVOSR_ROAD_CALL(RC_) road_wave<RC_, WW>(h0, h1, slots_all[wave_id()], drop_all[wave_id()], edges, a.y + off, a.scratch + off, M, hl, a.P, gh, ex, lo, hi, part, np_stack_all[wave_id()] MVOSR_STAMP_PASS)
+#define MVOSR_ROAD_CALL(RC_) road_wave<RC_, WW>(h0, comb_all[wave_id()], near_all[wave_id()], edges, a.y + off, a.scratch + off, M, hl, a.P, gh, ex, lo, hi, part, np_stack_all[wave_id()] MVOSR_STAMP_PASS)
     const RoadResult R = (Mp <= 4 * kWave) ? MVOSR_ROAD_CALL(4)
                        : (Mp <= 8 * kWave) ? MVOSR_ROAD_CALL(8)
                        : (Mp <= 12 * kWave) ? MVOSR_ROAD_CALL(12)
                        : (kRoadRC == 16 || Mp <= 16 * kWave) ? MVOSR_ROAD_CALL(16)
+                       : (kRoadRC <= 20 || Mp <= 20 * kWave) ? MVOSR_ROAD_CALL(kRoadRC <= 20 ? kRoadRC : 20)
                                           : MVOSR_ROAD_CALL(kRoadRC);
 #undef MVOSR_ROAD_CALL
     MVOSR_RSTAMP(6);
@@ -3011,5 +3037,18 @@ extern "C" int mvosr_debug_redo_list(mvosr_ctx *ctx, int64_t n_frames, int32_t *
     (void)hipStreamSynchronize(ctx_stream(ctx));
     const hipError_t e = hipMemcpy(out, ctx->ws_nsel + n_frames, sizeof(int32_t) * (size_t)cap, hipMemcpyDeviceToHost);
     return e == hipSuccess ? MVOSR_OK : MVOSR_ERR_HIP;
+}
+#endif
+
+#ifdef MVOSR_ROAD_EXACT_COUNT
+// (diagnostic build only) the road model's decision counters: out[3] as above; reset: zero them afterwards
+extern "C" int mvosr_debug_road_exact_count(unsigned long long *out, int reset) {
+    if (hipDeviceSynchronize() != hipSuccess) return MVOSR_ERR_HIP;
+    if (hipMemcpyFromSymbol(out, HIP_SYMBOL(mvosr::g_road_exact_count), 3 * sizeof(unsigned long long)) != hipSuccess) return MVOSR_ERR_HIP;
+    if (reset) {
+        const unsigned long long z[3] = {0ull, 0ull, 0ull};
+        if (hipMemcpyToSymbol(HIP_SYMBOL(mvosr::g_road_exact_count), z, sizeof z) != hipSuccess) return MVOSR_ERR_HIP;
+    }
+    return MVOSR_OK;
 }
 #endif
