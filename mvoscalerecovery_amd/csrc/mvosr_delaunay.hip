@@ -47,50 +47,16 @@ namespace mvosr {
 
 constexpr int kDtWaves = 8;
 constexpr int kDtBlock = kDtWaves * kWave;
-#ifndef MVOSR_DT_SMALL_LADDER
-#define MVOSR_DT_SMALL_LADDER 1
-#endif
 constexpr int kDtLadderMinFrames = 512;      // two eight-wavefront frames on each of 256 CUs
-constexpr bool kDtSmallLadder = MVOSR_DT_SMALL_LADDER != 0;
-#ifndef MVOSR_DT_ARENA_OUT
-#define MVOSR_DT_ARENA_OUT 1
-#endif
-constexpr bool kDtArenaOut = MVOSR_DT_ARENA_OUT != 0;
-#ifndef MVOSR_DT_WIDE16
-#define MVOSR_DT_WIDE16 1
-#endif
-constexpr bool kDtWide16 = MVOSR_DT_WIDE16 != 0;          // sixteen wavefronts per frame for launches of a few frames (see the launcher)
-constexpr int kDtWide16MaxFrames = 128;   // three four-wavefront frames per CU with the rows' arena in global memory (see the launcher)   // 2- and 4-wavefront instantiations for small frames (see the launcher)
-#ifndef MVOSR_DT_R
-#define MVOSR_DT_R 2
-#endif
-#ifndef MVOSR_DT_PER_CELL
-#define MVOSR_DT_PER_CELL 1.5
-#endif
-constexpr int kDtR = MVOSR_DT_R;         // a point's candidates: the (2R+1)^2 cell block around its cell
-#ifndef MVOSR_DT_COLOUR
-#define MVOSR_DT_COLOUR 1
-#endif
-constexpr bool kDtColour = MVOSR_DT_COLOUR != 0;    // points taken colour by colour of their cells ((x & 1, y & 1)): see the kernel
-constexpr double kDtPerCell = MVOSR_DT_PER_CELL;   // target points per cell (measured trade-off: profiles/micro/dt_proto.py)
+constexpr int kDtWide16MaxFrames = 128;  // sixteen wavefronts per frame for launches of a few frames (see the launcher)
+constexpr int kDtR = 2;                  // a point's candidates: the (2R+1)^2 cell block around its cell
+constexpr double kDtPerCell = 1.5;       // target points per cell (measured trade-off: profiles/micro/dt_proto.py)
 constexpr int kDtMaxCells = 4096;
-#ifndef MVOSR_DT_LANE_ROWS
-#define MVOSR_DT_LANE_ROWS 12
-#endif
-constexpr int kDtLaneRows = MVOSR_DT_LANE_ROWS;   // rows a point may own on the lane path (more: the group pass)
+constexpr int kDtLaneRows = 12;          // rows a point may own on the lane path (more: the group pass)
 constexpr int kDtLaneDeg = 24;           // star degree on the lane path
-#ifndef MVOSR_DT_BUDGET
-#define MVOSR_DT_BUDGET 48
-#endif
-#ifndef MVOSR_DT_RWIDE
-#define MVOSR_DT_RWIDE 8
-#endif
-constexpr int kDtBudget = MVOSR_DT_BUDGET;   // candidates per lane and scan step
-#ifndef MVOSR_DT_COOP_CELLS
-#define MVOSR_DT_COOP_CELLS 36
-#endif
-constexpr int kDtCoopCells = MVOSR_DT_COOP_CELLS;    // a circumcircle's cell box larger than this is scanned by the whole wavefront
-constexpr int kDtRWide = MVOSR_DT_RWIDE;              // the block a search is widened to before it takes the whole frame
+constexpr int kDtBudget = 48;            // candidates per lane and scan step
+constexpr int kDtCoopCells = 36;         // a circumcircle's cell box larger than this is scanned by the whole wavefront
+constexpr int kDtRWide = 8;              // the block a search is widened to before it takes the whole frame
 constexpr int kDtWaveRows = 32;          // rows a point may own at all
 constexpr int kDtWaveDeg = 60;
 constexpr int kDtHardCap = 256;          // points left to the group pass
@@ -157,36 +123,10 @@ static unsigned long long *g_dt_stamps = nullptr;
 // that published it (its circumcircle lay within the cells that lane had scanned).  Relaxed device-scope loads and stores:
 // a hint that is not visible yet is a search done twice, nothing else.  Measured at 2000 points: 43 % of the 11 936
 // triangle corners of a set are taken from a hint, 5.7 busy scan steps per point instead of 9.0.
-#ifndef MVOSR_DT_HINTS
-#define MVOSR_DT_HINTS 16
-#endif
-constexpr int kDtHintK = MVOSR_DT_HINTS;       // 0: no hints
-#ifndef MVOSR_DT_SCOPE
-#define MVOSR_DT_SCOPE __HIP_MEMORY_SCOPE_WORKGROUP
-#endif
-constexpr int kDtScope = MVOSR_DT_SCOPE;
-#ifndef MVOSR_DT_CHAIN
-#define MVOSR_DT_CHAIN 8
-#endif
-#ifndef MVOSR_DT_HINT_START
-#define MVOSR_DT_HINT_START 1
-#endif
-#ifndef MVOSR_DT_SERVE_ROWS
-#define MVOSR_DT_SERVE_ROWS 4
-#endif
-constexpr int kDtServeRows = MVOSR_DT_SERVE_ROWS;      // (a power of two)
-#ifndef MVOSR_DT_COOP
-#define MVOSR_DT_COOP 1
-#endif
-constexpr int kDtHintChain = MVOSR_DT_CHAIN;
-#ifndef MVOSR_DT_GLOBAL_HINTS
-#define MVOSR_DT_GLOBAL_HINTS 1
-#endif
-template <bool GLOBAL> constexpr bool kDtHintsOn = kDtHintK > 0 && (!GLOBAL || MVOSR_DT_GLOBAL_HINTS);
-#ifndef MVOSR_DT_GLOBAL_COOP
-#define MVOSR_DT_GLOBAL_COOP 0
-#endif
-template <bool GLOBAL> constexpr bool kDtCoop = MVOSR_DT_COOP && (!GLOBAL || MVOSR_DT_GLOBAL_COOP);    // (frames in global memory: 26 k -> 19 k sets/s with it at 20 000 points)   // hinted triangles taken in a row before the lane goes back to searching
+constexpr int kDtHintK = 16;
+constexpr int kDtScope = __HIP_MEMORY_SCOPE_WORKGROUP;
+constexpr int kDtHintChain = 8;           // hinted triangles taken in a row before the lane goes back to searching
+constexpr int kDtServeRows = 4;           // (a power of two)
 
 struct DtPlan { uint32_t S, oid, od, astart, cs, arena, big, hard, wrows, red, misc, wsl, aff, total, out_bytes; int max_cells, arena_cap; };
 constexpr int kDtMaxCellsGlobal = 32768;
@@ -549,10 +489,10 @@ __global__ __launch_bounds__(WAVES *kWave, PARTS ? 1 : ((ARENA_OUT && WAVES == 4
     int *wsl = reinterpret_cast<int *>(small + L.wsl);
     uint8_t *aff = reinterpret_cast<uint8_t *>(small + L.aff);
     const size_t hint_pts = (size_t)((a.max_pts + 7) & ~7);
-    uint32_t *hints = (kDtHintsOn<GLOBAL> && a.hints) ? a.hints + (size_t)hslice * ((size_t)(kDtHintK + 3) * hint_pts) : nullptr;
+    uint32_t *hints = a.hints ? a.hints + (size_t)hslice * ((size_t)(kDtHintK + 3) * hint_pts) : nullptr;
     uint32_t *start = hints ? hints + (size_t)(kDtHintK + 1) * hint_pts : nullptr;               // one known triangle per point: its star starts there
     uint32_t *inv = (hints && a.seed_tri) ? hints + (size_t)kDtHintK * hint_pts : nullptr;       // position in u/v -> sorted index (seeds only)
-    uint32_t *order = (hints && kDtColour && !GLOBAL) ? hints + (size_t)(kDtHintK + 2) * hint_pts : nullptr; // the order in which the points are taken
+    uint32_t *order = (hints && !GLOBAL) ? hints + (size_t)(kDtHintK + 2) * hint_pts : nullptr; // the order in which the points are taken
     if (hints) {
         // all ones = empty.  (One hipMemsetAsync over the launch's caches instead held the HOST for the GPU's queue above
         // 256 MB: the chunk loop around this kernel ran at 146 k instead of 228 k frames/s.)
@@ -956,25 +896,21 @@ __global__ __launch_bounds__(WAVES *kWave, PARTS ? 1 : ((ARENA_OUT && WAVES == 4
         // wavefront scans it together (below) instead of the lane on its own
         auto begin_search = [&](const DtBox &b_, int w_, int c_ = -1) {
             box = b_; wide = w_; y_next = b_.ya; j_resume = 0; A.reset();
-            coop = (kDtCoop<GLOBAL> && mode == 1 && (c_ < 0 ? w_ : c_)) ? 1 : 0;
+            coop = (!GLOBAL && mode == 1 && (c_ < 0 ? w_ : c_)) ? 1 : 0;
         };
         // A point that already holds a triangle of its star — "after `from` comes `to`" (a seed, or a neighbour's find) — starts
         // there: both are Delaunay neighbours, the nearest-neighbour search (a scan step or two) is not needed.  The state is
         // that of a finished final search whose answer is `to`: the completion code takes it from there.
         auto start_from_hint = [&]() {
-#if MVOSR_DT_HINT_START
-            if constexpr (kDtHintsOn<GLOBAL>) {
-                if (hints && i >= 0) {
-                    const uint32_t h = start_get((uint32_t)i);
-                    const int from = (int)(h >> 16), to = (int)(h & 0xFFFFu);
-                    if (h != 0xFFFFFFFFu && from < n && to < n && from != to && from != i && to != i) {
-                        mode = 1; q0 = from; iq = from; nn_level = 0;
-                        box.xa = 0; box.xb = 0; box.ya = 0; box.yb = -1; wide = 1; coop = 0; y_next = 0; j_resume = 0;
-                        A.reset(); A.b1 = to;
-                    }
+            if (hints && i >= 0) {
+                const uint32_t h = start_get((uint32_t)i);
+                const int from = (int)(h >> 16), to = (int)(h & 0xFFFFu);
+                if (h != 0xFFFFFFFFu && from < n && to < n && from != to && from != i && to != i) {
+                    mode = 1; q0 = from; iq = from; nn_level = 0;
+                    box.xa = 0; box.xb = 0; box.ya = 0; box.yb = -1; wide = 1; coop = 0; y_next = 0; j_resume = 0;
+                    A.reset(); A.b1 = to;
                 }
             }
-#endif
         };
         if (i >= 0) { p = S[i]; oi = oid[i]; begin_search(block_r(p, 1), 0); start_from_hint(); }
         // A WIDE search of a star (the cell box of a circumcircle that leaves the point's block, the frame's half beside
@@ -984,7 +920,7 @@ __global__ __launch_bounds__(WAVES *kWave, PARTS ? 1 : ((ARENA_OUT && WAVES == 4
         // such search after the other, each lane taking every 64th candidate of a cell row.
         auto serve_wide = [&]() -> bool {
             bool any = false;
-            if constexpr (kDtCoop<GLOBAL>) {
+            if constexpr (!GLOBAL) {       // (frames in global memory: 26 k -> 19 k sets/s with it at 20 000 points)
             for (unsigned long long todo = __ballot(i >= 0 && mode == 1 && coop); todo; todo &= todo - 1ull) {
                 const int src = (int)__ffsll((long long)todo) - 1;
                 const int bi = __builtin_amdgcn_readlane(i, src), biq = __builtin_amdgcn_readlane(iq, src);
@@ -1181,24 +1117,20 @@ __global__ __launch_bounds__(WAVES *kWave, PARTS ? 1 : ((ARENA_OUT && WAVES == 4
                 // nothing on that side within the block: the frame's half beside the edge, scanned by the wavefront (an
                 // intermediate 17 x 17 block first was measured: equal at 2000 points, 20 % slower at 300-600); the lane
                 // on its own (global-memory variant) looks at 17 x 17 cells first
-                else if (!kDtCoop<GLOBAL> && nn_level == 0) { nn_level = 1; begin_search(block_r(p, kDtRWide), 0); }
+                else if (GLOBAL && nn_level == 0) { nn_level = 1; begin_search(block_r(p, kDtRWide), 0); }
                 else begin_search(all, 1);
                 DT_SEC(4);
                 DT_MARK(c_accept);
                 if (accept >= 0) {
                     if (A.tie && dt_confirm_tie(S, cs, G.gx, box.xa, box.xb, box.ya, box.yb, E.px, E.py, E.ax, E.ay, E.sgn, E.a2col, E.i, E.iq, A.b1, A.n1, A.c1))
                         degenerate |= DT_WHY_TIE;
-                    if constexpr (kDtHintsOn<GLOBAL>) {
-                        if (hints) {
-                            // counter-clockwise walk: (p, iq, accept) is the triangle; clockwise: (p, accept, iq)
-                            const uint32_t a_ = (uint32_t)(sgn > 0.0 ? iq : accept), c_ = (uint32_t)(sgn > 0.0 ? accept : iq);
-                            hint_put(a_, c_, (c_ << 16) | (uint32_t)i);                  // in a's star: after c comes p
-                            hint_put(c_, (uint32_t)i, ((uint32_t)i << 16) | a_);         // in c's star: after p comes a
-#if MVOSR_DT_HINT_START
-                            start_put(a_, (c_ << 16) | (uint32_t)i);
-                            start_put(c_, ((uint32_t)i << 16) | a_);
-#endif
-                        }
+                    if (hints) {
+                        // counter-clockwise walk: (p, iq, accept) is the triangle; clockwise: (p, accept, iq)
+                        const uint32_t a_ = (uint32_t)(sgn > 0.0 ? iq : accept), c_ = (uint32_t)(sgn > 0.0 ? accept : iq);
+                        hint_put(a_, c_, (c_ << 16) | (uint32_t)i);                  // in a's star: after c comes p
+                        hint_put(c_, (uint32_t)i, ((uint32_t)i << 16) | a_);         // in c's star: after p comes a
+                        start_put(a_, (c_ << 16) | (uint32_t)i);
+                        start_put(c_, ((uint32_t)i << 16) | a_);
                     }
                     int chain = 0;
 #ifdef MVOSR_STAMPS
@@ -1232,11 +1164,9 @@ __global__ __launch_bounds__(WAVES *kWave, PARTS ? 1 : ((ARENA_OUT && WAVES == 4
                         if (go && sgn > 0.0 && iq == q0) { state = 1; go = false; }      // closed
                         // the next edge of the star: already known from a neighbour's star?
                         int nxt = -1;
-                        if constexpr (kDtHintsOn<GLOBAL>) {
-                            if (go && hints && sgn > 0.0 && chain < kDtHintChain) {
-                                const uint32_t h = hint_get((uint32_t)i, (uint32_t)iq);
-                                if ((h >> 16) == (uint32_t)iq && (int)(h & 0xFFFFu) < n) nxt = (int)(h & 0xFFFFu);
-                            }
+                        if (go && hints && sgn > 0.0 && chain < kDtHintChain) {
+                            const uint32_t h = hint_get((uint32_t)i, (uint32_t)iq);
+                            if ((h >> 16) == (uint32_t)iq && (int)(h & 0xFFFFu) < n) nxt = (int)(h & 0xFFFFu);
                         }
                         search_on = search_on || (go && nxt < 0);
                         in_chain = go && nxt >= 0;
@@ -1539,13 +1469,13 @@ static void dt_ladder(int max_pts, int &waves, bool &arena_out, int &per_cu) {
         // four-wavefront frames against two eight-wavefront ones: 12 wavefronts per CU with 170 registers each (no spills), a
         // quarter fewer points of a frame in flight at once (more triangles arrive as hints), and a third frame's work
         // under the dependent steps of the second triangulation, which is bound by its longest star
-        else if (kDtArenaOut && fits(3u, dt_plan(max_pts, false, 4, true).total)) { waves = 4; arena_out = true; }
+        else if (fits(3u, dt_plan(max_pts, false, 4, true).total)) { waves = 4; arena_out = true; }
         // beyond that, two eight-wavefront frames per CU as long as they fit — with the arena in global memory up to ~3 100
         // points instead of ~2 350 (one frame per CU is half the wavefronts)
-        else if (kDtArenaOut && !fits(2u, dt_plan(max_pts, false, 8).total) && fits(2u, dt_plan(max_pts, false, 8, true).total)) arena_out = true;
+        else if (!fits(2u, dt_plan(max_pts, false, 8).total) && fits(2u, dt_plan(max_pts, false, 8, true).total)) arena_out = true;
         // (where three four-wavefront frames fit a CU either way — 1 100 to 1 480 points — the arena-out build, which is compiled
         // for three wavefronts per SIMD: 154 registers, no spills: +3-5 %)
-        if (kDtArenaOut && waves == 4 && !arena_out && !fits(4u, dt_plan(max_pts, false, 4).total)) arena_out = true;
+        if (waves == 4 && !arena_out && !fits(4u, dt_plan(max_pts, false, 4).total)) arena_out = true;
     }
     auto fits_n = [](uint32_t frames, uint32_t bytes) { return frames * ((bytes + 1279u) / 1280u) <= 128u; };
     const uint32_t bytes = dt_plan(max_pts, false, waves, arena_out).total;
@@ -1614,7 +1544,7 @@ extern "C" int mvosr_delaunay_batch_ex(mvosr_ctx *ctx, int64_t n_frames, const i
         // frames beyond the LDS capacity: the big arrays in the context's workspace, one slice per frame
         void *ws = nullptr;
         const size_t big_bytes = ((size_t)n_frames * L.big + 255) & ~(size_t)255;
-        const size_t hint_bytes = kDtHintsOn<true> ? (size_t)n_frames * (size_t)(kDtHintK + 3) * (size_t)((max_pts + 7) & ~7) * sizeof(uint32_t) : 0;
+        const size_t hint_bytes = (size_t)n_frames * (size_t)(kDtHintK + 3) * (size_t)((max_pts + 7) & ~7) * sizeof(uint32_t);
         if ((rc = ctx_workspace_bytes(ctx, big_bytes + hint_bytes, &ws))) return rc;
         a.ws = reinterpret_cast<char *>(ws);
         if (hint_bytes) a.hints = reinterpret_cast<uint32_t *>(a.ws + big_bytes);
@@ -1637,7 +1567,7 @@ extern "C" int mvosr_delaunay_batch_ex(mvosr_ctx *ctx, int64_t n_frames, const i
     // one frame on one CU (276 us at 2000 points, 95 % of it the stars): several workgroups per frame instead, each with the
     // whole frame in its LDS and a strip of the cells to build the stars of — four wavefronts, at most a star per lane —, the last one to
     // finish writing the rows (the PARTS instantiation)
-    if (kDtHintK > 0 && kDtColour && n_frames <= kDtPartsMaxFrames && max_pts >= 2 * kDtPartsPoints && dt_parts_env() &&
+    if (n_frames <= kDtPartsMaxFrames && max_pts >= 2 * kDtPartsPoints && dt_parts_env() &&
         dt_plan(max_pts, false, 4).total <= 160u * 1024u) {
         const int parts = dt_parts_env() > 0 ? dt_parts_env() : min(kDtPartsMax, (max_pts + kDtPartsPoints - 1) / kDtPartsPoints);
         const DtPlan LQ = dt_plan(max_pts, false, 4);
@@ -1661,11 +1591,11 @@ extern "C" int mvosr_delaunay_batch_ex(mvosr_ctx *ctx, int64_t n_frames, const i
         hipLaunchKernelGGL((delaunay_kernel<false, 4, false, true>), dim3((unsigned)(n_frames * parts)), dim3(4 * kWave), plds, ctx_stream(ctx), a);
         return check_launch("delaunay_kernel (parts)");
     }
-    if (kDtSmallLadder && n_frames >= kDtLadderMinFrames) dt_ladder(max_pts, waves, arena_out, per_cu);
+    if (n_frames >= kDtLadderMinFrames) dt_ladder(max_pts, waves, arena_out, per_cu);
     // A launch of a few frames (the per-frame call of /root/reference/src/main.py:110-113: ONE) leaves most CUs idle and its length is
     // one frame's: sixteen wavefronts per frame — four per SIMD instead of two: the lanes' dependent steps overlap, and a
     // lane walks two stars instead of four
-    else if (kDtWide16 && n_frames <= kDtWide16MaxFrames && max_pts >= 256 && dt_plan(max_pts, false, 16).total <= 160u * 1024u) waves = 16;   // (its phase-2 rows are 6 KB more: the largest LDS frames keep eight)
+    else if (n_frames <= kDtWide16MaxFrames && max_pts >= 256 && dt_plan(max_pts, false, 16).total <= 160u * 1024u) waves = 16;   // (its phase-2 rows are 6 KB more: the largest LDS frames keep eight)
     const DtPlan LP = dt_plan(max_pts, false, waves, arena_out);
     lds = LP.total;
     const void *kfn = waves == 16 ? reinterpret_cast<const void *>(delaunay_kernel<false, 16>)
@@ -1682,7 +1612,7 @@ extern "C" int mvosr_delaunay_batch_ex(mvosr_ctx *ctx, int64_t n_frames, const i
         const size_t out_bytes = arena_out ? (size_t)n_frames * LP.out_bytes : 0;
         if (hint_bytes + out_bytes) {
             if ((rc = ctx_workspace_bytes(ctx, hint_bytes + out_bytes, &ws))) return rc;
-            if (kDtHintK > 0) a.hints = reinterpret_cast<uint32_t *>(ws);   // (every workgroup empties its own frame's caches: no memset of the whole block)
+            a.hints = reinterpret_cast<uint32_t *>(ws);   // (every workgroup empties its own frame's caches: no memset of the whole block)
             a.aws = reinterpret_cast<char *>(ws) + hint_bytes;
         }
     }

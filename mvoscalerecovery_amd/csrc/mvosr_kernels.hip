@@ -51,43 +51,6 @@ namespace mvosr {
 // ---------------------------------------------------------------------------------------------
 // LDS carve-up (byte offsets, all multiples of 16)
 // ---------------------------------------------------------------------------------------------
-// Experiment (review item 4 ii): an XOR swizzle of the vertex records' slots.  -DMVOSR_PSWZ=k permutes the slots inside
-// aligned groups of 8 by bits k.. of the index.  The gathers address the records through triangle rows, i.e. at random
-// with respect to the banks, so no fixed permutation changes how many of a ds_read_b128's 16 lanes collide
-// (measured: profiles/r03_ab_swizzle.txt); the product build has no swizzle.
-// -DMVOSR_PSPLIT keeps the records as two 8-byte planes an odd number of doubles apart instead (LDS-resident variants
-// only: an experiment build, not a product one).
-#if defined(MVOSR_PSWZ)
-#define PSW(i) ((i) ^ ((((unsigned)(i)) >> MVOSR_PSWZ) & 7u))
-#define MVOSR_NPAD(n) ((uint32_t)(((n) + 7) & ~7))
-#elif defined(MVOSR_PSPLIT)
-#define PSW(i) (i)
-#define MVOSR_NPAD(n) ((uint32_t)(((n) + 3) & ~1))
-#else
-#define PSW(i) (i)
-#define MVOSR_NPAD(n) ((uint32_t)(((n) + 1) & ~1))
-#endif
-#ifdef MVOSR_PSPLIT
-__device__ __forceinline__ int p_stride(const double2 *P, const double *Y) {
-    return (int)((Y - reinterpret_cast<const double *>(P)) >> 1) - 1;      // npad - 1: odd
-}
-__device__ __forceinline__ double2 p_ld(const double2 *P, const double *Y, int i) {
-    const double *d = reinterpret_cast<const double *>(P);
-    double2 r; r.x = d[i]; r.y = d[p_stride(P, Y) + i]; return r;
-}
-__device__ __forceinline__ double p_ldy(const double2 *P, const double *Y, int i) {
-    return reinterpret_cast<const double *>(P)[p_stride(P, Y) + i];
-}
-__device__ __forceinline__ void p_st(double2 *P, const double *Y, int i, double2 v) {
-    double *d = reinterpret_cast<double *>(P);
-    d[i] = v.x; d[p_stride(P, Y) + i] = v.y;
-}
-#else
-__device__ __forceinline__ double2 p_ld(const double2 *P, const double *, int i) { return P[PSW(i)]; }
-__device__ __forceinline__ double p_ldy(const double2 *P, const double *, int i) { return P[PSW(i)].y; }
-__device__ __forceinline__ void p_st(double2 *P, const double *, int i, double2 v) { P[PSW(i)] = v; }
-#endif
-
 struct LdsPlan {
     uint32_t p, y, c, hist, red, misc, total;
 };
@@ -96,7 +59,7 @@ constexpr int kRedSlots = 6;                       // one scratch slot per block
 enum { R_SEL_H = 0, R_SEL_CNT = 1, R_SEL_ABS = 2, R_ROAD_SUM = 3, R_ROAD_SS = 4, R_MISC = 5 };
 __host__ __device__ inline LdsPlan lds_plan(int n, int waves) {
     LdsPlan p;
-    const uint32_t npad = MVOSR_NPAD(n);
+    const uint32_t npad = (uint32_t)((n + 1) & ~1);
     p.p = 0;                                      // double2 {v|x, z'} per feature
     p.y = p.p + 16u * npad;                       // y' per feature
     p.c = p.y + 8u * npad;                        // 16-bit vote counter per feature; later the selected bit-set
@@ -140,10 +103,7 @@ enum { M_WCNT = 0 /* [0..15] per-wave survivor counts */, M_LIST = 16, M_MEDLO =
 // flight together, and the first chunk of each sweep is issued a phase early (tri1 with the
 // feature loads, tri2 before the compaction barriers) so that its latency is off the sweep.
 // ---------------------------------------------------------------------------------------------
-#ifndef MVOSR_TC
-#define MVOSR_TC 2
-#endif
-constexpr int kTC = MVOSR_TC;   // triangles per thread per chunk (3 VGPRs each)
+constexpr int kTC = 2;   // triangles per thread per chunk (3 VGPRs each)
 
 
 // Inputs that are read exactly once are loaded non-temporally: measured, the L2-miss traffic of the
@@ -209,14 +169,11 @@ __device__ __forceinline__ int phase_vote(const Smem &s, int n, const double *gx
                                           const double *gv, const int32_t *tri1, int64_t t1_begin, int t1_count,
                                           double cp, double sp, int32_t *g_counters, int &bad,
                                           const int32_t *tri2, int64_t t2_begin, int t2_count, TriChunk<WAVES * kWave> &next,
-                                          bool fixed, int dbg = 0 MVOSR_STAMP_ARG) {
+                                          bool fixed MVOSR_STAMP_ARG) {
     constexpr int B = WAVES * kWave;
     const int tid = threadIdx.x;
     const int npad2 = (n + 1) >> 1;
     TriChunk<B> tc;
-#ifdef MVOSR_PRIO_LOAD
-    __builtin_amdgcn_s_setprio(MVOSR_PRIO_LOAD);                       // (experiment: the streaming phase ahead of other workgroups' sweeps)
-#endif
     tc.template load<true>(tri1, t1_begin, t1_count, 0, tid);          // in flight while the features stream in
     // planes are 16-byte aligned per frame: two features per lane and load, two loads per plane in flight
     const double2 *gy2 = reinterpret_cast<const double2 *>(gy);
@@ -234,17 +191,14 @@ __device__ __forceinline__ int phase_vote(const Smem &s, int n, const double *gx
         yr.x = ya.x * cp - za.x * sp;  yr.y = ya.y * cp - za.y * sp;      // :391
         p0.x = va.x; p0.y = ya.x * sp + za.x * cp;                        // :392
         p1.x = va.y; p1.y = ya.y * sp + za.y * cp;
-        sY2[i0] = yr; p_st(s.P, s.Y, 2 * i0, p0); p_st(s.P, s.Y, 2 * i0 + 1, p1); s.c32[i0] = ones;
+        sY2[i0] = yr; s.P[2 * i0] = p0; s.P[2 * i0 + 1] = p1; s.c32[i0] = ones;
         if (two) {
             yr.x = yb.x * cp - zb.x * sp;  yr.y = yb.y * cp - zb.y * sp;
             p0.x = vb.x; p0.y = yb.x * sp + zb.x * cp;
             p1.x = vb.y; p1.y = yb.y * sp + zb.y * cp;
-            sY2[i1] = yr; p_st(s.P, s.Y, 2 * i1, p0); p_st(s.P, s.Y, 2 * i1 + 1, p1); s.c32[i1] = ones;
+            sY2[i1] = yr; s.P[2 * i1] = p0; s.P[2 * i1 + 1] = p1; s.c32[i1] = ones;
         }
     }
-#ifdef MVOSR_PRIO_LOAD
-    __builtin_amdgcn_s_setprio(0);
-#endif
     __syncthreads();
     MVOSR_STAMP(1);
 
@@ -259,10 +213,9 @@ __device__ __forceinline__ int phase_vote(const Smem &s, int n, const double *gx
     }
 
     // the vote: +1 on a vertex the triangle does not flag, -1 on one it flags (:160-163)
-    const int t1c = (dbg & 1) ? 0 : t1_count;
     TriChunk<B> tn;                                   // the next chunk streams in while this one is processed
-    for (int base = 0; base < t1c; base += kTC * B) {
-        const bool more = base + kTC * B < t1c;
+    for (int base = 0; base < t1_count; base += kTC * B) {
+        const bool more = base + kTC * B < t1_count;
         if (more) tn.template load<true>(tri1, t1_begin, t1_count, base + kTC * B, tid);
         // all vertex reads of the chunk first: the reads of one triangle cannot be moved across the
         // LDS atomics of another by the compiler, and issued together their latencies overlap
@@ -273,7 +226,7 @@ __device__ __forceinline__ int phase_vote(const Smem &s, int n, const double *gx
             const TriIds q = tc.q[k];
             vok[k] = base + k * B + tid < t1_count;
             if (vok[k] && ((unsigned)q.a >= (unsigned)n || (unsigned)q.b >= (unsigned)n || (unsigned)q.c >= (unsigned)n)) { bad = 1; vok[k] = false; }
-            if (vok[k]) { vp[k][0] = p_ld(s.P, s.Y, q.a); vp[k][1] = p_ld(s.P, s.Y, q.b); vp[k][2] = p_ld(s.P, s.Y, q.c); }      // {v, z'}
+            if (vok[k]) { vp[k][0] = s.P[q.a]; vp[k][1] = s.P[q.b]; vp[k][2] = s.P[q.c]; }      // {v, z'}
         }
 #pragma unroll
         for (int k = 0; k < kTC; ++k) {
@@ -312,7 +265,7 @@ __device__ __forceinline__ int phase_vote(const Smem &s, int n, const double *gx
             keep = c >= 0;                                                    // :166
             if (g_counters) g_counters[i] = c;
             yk[k] = s.Y[i];
-            zk[k] = p_ldy(s.P, s.Y, i);
+            zk[k] = s.P[i].y;
         }
         if (keep) keepmask |= 1u << k;
         cnt += __popcll(__ballot(keep));
@@ -330,7 +283,7 @@ __device__ __forceinline__ int phase_vote(const Smem &s, int n, const double *gx
         if (keep) {
             const int pos = base + __popcll(m & ((1ull << lane) - 1ull));
             double2 pv; pv.x = xs[k]; pv.y = zk[k];
-            p_st(s.P, s.Y, pos, pv);
+            s.P[pos] = pv;
             s.Y[pos] = yk[k];
         }
         base += __popcll(m);
@@ -691,7 +644,7 @@ struct LdsFetch {            // rows of tri2 index the compacted survivors in LD
     __device__ __forceinline__ bool operator()(const TriIds q, double &x0, double &y0, double &z0, double &x1, double &y1, double &z1,
                                                double &x2, double &y2, double &z2) const {
         if ((unsigned)q.a >= (unsigned)n_valid || (unsigned)q.b >= (unsigned)n_valid || (unsigned)q.c >= (unsigned)n_valid) return false;
-        const double2 p0 = p_ld(P, Y, q.a), p1 = p_ld(P, Y, q.b), p2 = p_ld(P, Y, q.c);
+        const double2 p0 = P[q.a], p1 = P[q.b], p2 = P[q.c];
         x0 = p0.x; z0 = p0.y; x1 = p1.x; z1 = p1.y; x2 = p2.x; z2 = p2.y;
         y0 = Y[q.a]; y1 = Y[q.b]; y2 = Y[q.c];
         return true;
@@ -709,7 +662,7 @@ template <int WAVES, int MODE, int FW = 1>
 __device__ __forceinline__ SelectResult phase_select(const Smem &s, int n_valid, const int32_t *tri2, int64_t t2_begin,
                                                      int t2_count, TriChunk<WAVES * kWave> &tc, PitchTest pt,
                                                      double *g_normals, double *g_pitch, double *g_heights, int bad_in,
-                                                     double *scratch, int scratch_cap, int dbg = 0 MVOSR_STAMP_ARG) {
+                                                     double *scratch, int scratch_cap MVOSR_STAMP_ARG) {
     constexpr int B = WAVES * kWave;
     constexpr bool FULL = MODE == MODE_FULL;
     const int tid = threadIdx.x;
@@ -723,7 +676,7 @@ __device__ __forceinline__ SelectResult phase_select(const Smem &s, int n_valid,
     // One triangle of the first sweep (:229-240).
     auto test_triangle = [&](int t, int kk, const TriIds q) {
     if ((unsigned)q.a >= (unsigned)n_valid || (unsigned)q.b >= (unsigned)n_valid || (unsigned)q.c >= (unsigned)n_valid) { bad = 1; return; }
-    const double2 p0 = p_ld(s.P, s.Y, q.a), p1 = p_ld(s.P, s.Y, q.b), p2 = p_ld(s.P, s.Y, q.c);      // {x, z'}
+    const double2 p0 = s.P[q.a], p1 = s.P[q.b], p2 = s.P[q.c];      // {x, z'}
     const double y0 = s.Y[q.a], y1 = s.Y[q.b], y2 = s.Y[q.c];
     const double x0 = p0.x, z0 = p0.y, x1 = p1.x, z1 = p1.y, x2 = p2.x, z2 = p2.y;
     // :238.  The product path works on 3h = (y0+y1)+y2: its level is only trusted outside the guard band anyway (a frame
@@ -742,23 +695,21 @@ __device__ __forceinline__ SelectResult phase_select(const Smem &s, int n_valid,
     };
     // `tc` arrives with the first chunk of tri2 already loaded (phase_vote); the next chunk streams
     // in while the current one is processed.
-    const int t2c = (dbg & 2) ? 0 : t2_count;
     TriChunk<B> tn;
-    for (int base = 0; base < t2c; base += kTC * B) {
-        const bool more = base + kTC * B < t2c;
+    for (int base = 0; base < t2_count; base += kTC * B) {
+        const bool more = base + kTC * B < t2_count;
         if (more) tn.load(tri2, t2_begin, t2_count, base + kTC * B, tid);
 #pragma unroll
         for (int k = 0; k < kTC; ++k) {
             const int t = base + k * B + tid;
-            if (t < t2c) test_triangle(t, base / B + k, tc.q[k]);
+            if (t < t2_count) test_triangle(t, base / B + k, tc.q[k]);
         }
         if (more) tc = tn;
     }
     // second sweep: its first chunk is re-read now, under the reduction's barrier (unless the whole
     // triangulation was one chunk and is still in registers)
-    const int t2d = (dbg & 4) ? 0 : t2_count;
     const bool in_regs = t2_count <= kTC * B;
-    if (!in_regs && t2d > 0) tc.template load<true>(tri2, t2_begin, t2_count, 0, tid);
+    if (!in_regs && t2_count > 0) tc.template load<true>(tri2, t2_begin, t2_count, 0, tid);
     if constexpr (MODE == MODE_HOT) block_sum3<WAVES>(hsum, hcnt, habs, s.red + R_SEL_H * 2 * WAVES, s.red + R_SEL_ABS * 2 * WAVES);
     else block_sum2<WAVES>(hsum, hcnt, s.red + R_SEL_H * 2 * WAVES);
     MVOSR_STAMP(4);
@@ -787,12 +738,12 @@ __device__ __forceinline__ SelectResult phase_select(const Smem &s, int n_valid,
             atomicOr(&s.sel[qc >> 5], 1u << (qc & 31));
         }
     };
-    for (int base = 0; base < t2d; base += kTC * B) {
-        const bool more = base + kTC * B < t2d;
+    for (int base = 0; base < t2_count; base += kTC * B) {
+        const bool more = base + kTC * B < t2_count;
         if (more) tn.template load<true>(tri2, t2_begin, t2_count, base + kTC * B, tid);
 #pragma unroll
         for (int k = 0; k < kTC; ++k) {
-            if (base + k * B + tid < t2d) mark_triangle(base / B + k, tc.q[k].a, tc.q[k].b, tc.q[k].c);
+            if (base + k * B + tid < t2_count) mark_triangle(base / B + k, tc.q[k].a, tc.q[k].b, tc.q[k].c);
         }
         if (more) tc = tn;
     }
@@ -847,10 +798,7 @@ __device__ __forceinline__ bool dropped_by_single(double y, int bin, const Bits1
 // earlier two-pass band alone / the band in use send to NumPy's exact order (without the statistics output).
 __device__ unsigned long long g_road_exact_count[3];
 #endif
-#ifndef MVOSR_ROAD_RC
-#define MVOSR_ROAD_RC 20
-#endif
-constexpr int kRoadRC = MVOSR_ROAD_RC;   // deepest tier: rows of 64 values whose bins stay in registers (one byte each, four per VGPR); longer
+constexpr int kRoadRC = 20;              // deepest tier: rows of 64 values whose bins stay in registers (one byte each, four per VGPR); longer
                                          // lists (dense frames) re-read their tail once, for the suspects
 constexpr int kRoadSub = 4;              // lane-interleaved copies of the histogram (lane & 3): a clustered row's same-bin ds_add_u32 serialise
                                          // four times less; the copies of a bin are adjacent ints, summed with one ds_read_b128
@@ -1204,18 +1152,13 @@ __device__ __forceinline__ RoadResult road_wave(int *hist, int *comb, uint8_t *n
     return R;
 }
 
-#ifndef MVOSR_ROAD_MINW
-#define MVOSR_ROAD_MINW 1
-#endif
-#ifndef MVOSR_ROAD_OCC
-#define MVOSR_ROAD_OCC 6                 // wavefronts per SIMD the product variants are compiled for (their VGPR budget)
-#endif
+constexpr int kRoadOcc = 6;              // wavefronts per SIMD the product variants are compiled for (their VGPR budget)
 // LIST: the frames of a.list, grid-strided (the rare second pass over the frames that ended on the fallback level); otherwise
 // frame first_frame + wavefront index, no loop (a loop around the body costs the product variant 57 VGPRs, i.e. half its occupancy)
-// LDS per workgroup ~18 KB; the launch bound gives the product variants MVOSR_ROAD_OCC wavefronts per SIMD (6: at most
+// LDS per workgroup ~18 KB; the launch bound gives the product variants kRoadOcc wavefronts per SIMD (6: at most
 // 80 VGPRs, six workgroups per CU; 8 needs 64 VGPRs and spills inside the loops, 5 runs without spills but slower).
 template <bool LIST, int WW = 1>
-__global__ __launch_bounds__(kRoadWaves *kWave, (LIST ? 1 : MVOSR_ROAD_OCC)) void road_model_kernel(const RoadArgs a) {
+__global__ __launch_bounds__(kRoadWaves *kWave, (LIST ? 1 : kRoadOcc)) void road_model_kernel(const RoadArgs a) {
     static_assert(kRoadRC >= 16 && kRoadRC <= 32, "the row masks are 32 bits");
     static_assert(WW == 1 || (WW == kRoadWaves && !LIST), "wide variant: the whole workgroup on one frame");
     __shared__ __attribute__((aligned(16))) int hist_all[kRoadWaves][kRoadSub * 176];
@@ -1251,9 +1194,8 @@ __global__ __launch_bounds__(kRoadWaves *kWave, (LIST ? 1 : MVOSR_ROAD_OCC)) voi
     const RoadResult R = (Mp <= 4 * kWave) ? MVOSR_ROAD_CALL(4)
                        : (Mp <= 8 * kWave) ? MVOSR_ROAD_CALL(8)
                        : (Mp <= 12 * kWave) ? MVOSR_ROAD_CALL(12)
-                       : (kRoadRC == 16 || Mp <= 16 * kWave) ? MVOSR_ROAD_CALL(16)
-                       : (kRoadRC <= 20 || Mp <= 20 * kWave) ? MVOSR_ROAD_CALL(kRoadRC <= 20 ? kRoadRC : 20)
-                                          : MVOSR_ROAD_CALL(kRoadRC);
+                       : (Mp <= 16 * kWave) ? MVOSR_ROAD_CALL(16)
+                                            : MVOSR_ROAD_CALL(kRoadRC);
 #undef MVOSR_ROAD_CALL
     MVOSR_RSTAMP(6);
 #ifdef MVOSR_STAMPS
@@ -1303,7 +1245,6 @@ struct KArgs {
     PitchTest pt;
     int64_t first_frame;
     const double *height_level_in;
-    int debug_skip;          // ablation bits for profiling runs (env MVOSR_DEBUG_SKIP); 0 in production
     int32_t *redo;           // workspace: redo[0] = number of frames the HOT kernel left for the EXACT pass, redo[1..] their indices
     int redo_pass;           // EXACT kernels: 1 = process the redo list (grid-strided), 0 = frame first_frame + blockIdx.x
     double *ysel;            // workspace plane (laid out like x): the selected y' of every frame, dense
@@ -1429,15 +1370,9 @@ __device__ __forceinline__ void for_frames(const KArgs &a, Body body) {
     body(a.first_frame + blockIdx.x);
 }
 
-#ifndef MVOSR_MINW
-#define MVOSR_MINW 1
-#endif
-#ifndef MVOSR_HOTW
-#define MVOSR_HOTW 6
-#endif
 // (the 8-wavefront product variants must stay within 80 VGPRs: three workgroups per CU are six wavefronts per SIMD)
 template <int WAVES, int SC, int MODE, bool LIST = false>
-__global__ __launch_bounds__(WAVES *kWave, (WAVES == 8 && MODE == MODE_HOT ? MVOSR_HOTW : MVOSR_MINW)) void scale_frames_kernel(const KArgs a) {
+__global__ __launch_bounds__(WAVES *kWave, (WAVES == 8 && MODE == MODE_HOT ? 6 : 1)) void scale_frames_kernel(const KArgs a) {
     extern __shared__ __attribute__((aligned(16))) char smem[];
     for_frames<MODE, LIST>(a, [&](const int64_t f) {
     constexpr int B = WAVES * kWave;
@@ -1448,15 +1383,6 @@ __global__ __launch_bounds__(WAVES *kWave, (WAVES == 8 && MODE == MODE_HOT ? MVO
     const int64_t t1b = a.b.tri1_off[f], t2b = a.b.tri2_off[f];
     const int t1n = tri_rows(a.b.tri1_off, a.b.tri1_cnt, f), t2n = tri_rows(a.b.tri2_off, a.b.tri2_cnt, f);
     const Smem s = carve(smem, n, WAVES);
-#ifdef MVOSR_STAGGER
-    // Experiment (round 6, LABNOTES 10.10): the launch's first generation of workgroups starts spread over MVOSR_STAGGER
-    // ticks of s_memtime (100 MHz) instead of all at once, so that equal-length frames do not march through their phases in step.
-    if (MODE == MODE_HOT && !LIST && blockIdx.x < 768u) {
-        const unsigned long long t0 = __builtin_amdgcn_s_memtime();
-        const unsigned long long wait = ((blockIdx.x * 2654435761u) >> 12) % (unsigned)(MVOSR_STAGGER);
-        while (__builtin_amdgcn_s_memtime() - t0 < wait) __builtin_amdgcn_s_sleep(8);
-    }
-#endif
 #ifdef MVOSR_STAMPS
     if (n < 0) return;                             // (never: makes the stamp below wait for the frame's counts)
 #endif
@@ -1476,7 +1402,7 @@ __global__ __launch_bounds__(WAVES *kWave, (WAVES == 8 && MODE == MODE_HOT ? MVO
     const int nvalid = phase_vote<WAVES, SC>(s, n, a.b.x + off, a.b.y + off, a.b.z + off, a.b.v + off, a.b.tri1, t1b, t1n,
                                              a.P.cos_pitch, a.P.sin_pitch,
                                              a.o.vote_counters ? a.o.vote_counters + off : nullptr, bad,
-                                             a.b.tri2, t2b, t2n, tc2, a.P.vote_mode == MVOSR_VOTE_FIXED, a.debug_skip MVOSR_STAMP_PASS);
+                                             a.b.tri2, t2b, t2n, tc2, a.P.vote_mode == MVOSR_VOTE_FIXED MVOSR_STAMP_PASS);
     const bool mask_mismatch = a.b.n2_expected && a.b.n2_expected[f] != nvalid;
 
     SelectResult S;
@@ -1485,8 +1411,7 @@ __global__ __launch_bounds__(WAVES *kWave, (WAVES == 8 && MODE == MODE_HOT ? MVO
     const bool too_many_rows = t1n > kMaxVoteRows;
     if (!mask_mismatch && !too_many_rows)
         S = phase_select<WAVES, MODE>(s, nvalid, a.b.tri2, t2b, t2n, tc2, a.pt, a.o.tri_normals, a.o.tri_pitch_deg,
-                                      a.o.tri_heights, bad, a.ysel ? a.ysel + off : nullptr, n, a.debug_skip MVOSR_STAMP_PASS);
-    if (a.debug_skip & 8) S.bad = 1;
+                                      a.o.tri_heights, bad, a.ysel ? a.ysel + off : nullptr, n MVOSR_STAMP_PASS);
     frame_tail<WAVES, MODE>(a, s, f, off, nvalid, mask_mismatch || too_many_rows, S, R);
     MVOSR_STAMP(9);
 #ifdef MVOSR_STAMPS
@@ -1630,7 +1555,7 @@ __global__ __launch_bounds__(DW *kWave) void scale_frames_dense_kernel(const Den
         TriChunk<B> tc2;
         tc2.load(a.b.tri2, t2b, t2n, 0, tid);
         S = phase_select<DW, MODE, 2>(s, nvalid, a.b.tri2, t2b, t2n, tc2, a.pt, a.o.tri_normals, a.o.tri_pitch_deg,
-                                      a.o.tri_heights, bad, nullptr, 0, 0);
+                                      a.o.tri_heights, bad, nullptr, 0);
     }
     frame_tail<DW, MODE>(a, s, f, off, nvalid, mask_mismatch, S, R);
     });
@@ -1831,26 +1756,12 @@ __global__ __launch_bounds__(DW *kWave) void scale_frames_dense_feat_kernel(cons
 // scale_frames_dense_feat_kernel on it; stage outputs select that kernel too.
 // ---------------------------------------------------------------------------------------------
 constexpr int kTileW = 512;                 // features per tile (MVOSR_TILE_W in the header; the host's index uses the same)
-#ifndef MVOSR_TILED_WAVES
-#define MVOSR_TILED_WAVES 8
-#endif
-constexpr int kTiledWaves = MVOSR_TILED_WAVES;
-#ifndef MVOSR_TILED_RING
-#define MVOSR_TILED_RING 3
-#endif
-constexpr int kRing = MVOSR_TILED_RING;     // tiles in the LDS ring: 2 = two barriers per tile (a tile retires and its successor is stored between them),
-                                            // 3 = one (tile k-1 retires and tile k+2 takes its slot while the rows of tile k are still being walked)
+constexpr int kTiledWaves = 8;
+constexpr int kRing = 3;                    // tiles in the LDS ring: one barrier per tile (tile k-1 retires and tile k+2 takes its slot while the
+                                            // rows of tile k are still being walked)
 constexpr int kPendCap = 1024;              // pending votes for vertices whose tile has not arrived yet (4 B each) ...
-constexpr int kPendCapH = kRing == 3 ? 576 : 1024;      // ... and pending heights (12 B each): what fits two workgroups per CU
-#ifndef MVOSR_TILE_ROWS
-#define MVOSR_TILE_ROWS 2
-#endif
-constexpr int kTileRows = MVOSR_TILE_ROWS;  // rows per thread and triangulation prefetched for the coming step
-#ifndef MVOSR_TILED_SUBC
-#define MVOSR_TILED_SUBC 1
-#endif
-constexpr int kSubC = MVOSR_TILED_SUBC;     // vote counters per ring vertex (a lane adds to counter lane % kSubC): rows are sorted by smallest vertex, so the
-                                            // lanes of one LDS atomic name the same vertices again and again, and updates of one word are serialised
+constexpr int kPendCapH = 576;              // ... and pending heights (12 B each): what fits two workgroups per CU
+constexpr int kTileRows = 2;                // rows per thread and triangulation prefetched for the coming step
 
 struct TiledPlan { uint32_t ringA, ringB, ringH, ringC, used, pendV, pendH, toff, red, misc, total; };
 __host__ __device__ inline TiledPlan tiled_plan(int n, int waves) {
@@ -1860,8 +1771,8 @@ __host__ __device__ inline TiledPlan tiled_plan(int n, int waves) {
     p.ringA = 0;                                                 // double2 {v, z'}
     p.ringB = p.ringA + 16u * RW;                                // double2 {x, y'}
     p.ringH = p.ringB + 16u * RW;                                // uint64 key of the largest flat height
-    p.ringC = p.ringH + 8u * RW;                                 // int32 vote counters (kSubC per vertex)
-    p.used = p.ringC + 4u * RW * kSubC;                          // uint8 "a tri2 row names this vertex"
+    p.ringC = p.ringH + 8u * RW;                                 // int32 vote counters
+    p.used = p.ringC + 4u * RW;                                  // uint8 "a tri2 row names this vertex"
     p.pendV = align16(p.used + RW);                              // vertex << 1 | (vote is -1)
     p.pendH = p.pendV + 4u * kPendCap;                           // key64 x kPendCapH, then vertex x kPendCapH
     p.toff = align16(p.pendH + 12u * kPendCapH);                 // the frame's tile index: 2 x (ntiles + 1) ints
@@ -1948,13 +1859,10 @@ __global__ __launch_bounds__(DW *kWave, (DW == 8 ? 4 : 1)) void scale_frames_til
             tv[j] = stream_load(gv + i); tx[j] = stream_load(gx + i); ty[j] = stream_load(gy + i); tz[j] = stream_load(gz + i);
         }
     };
-    // ring slots.  Two tiles: feature i sits at i mod 2W.  Three: at i mod 3W — for a feature at distance d <= 2W - 1 from the
-    // start of a tile whose slot begins at sb that is sb + d, wrapped once.
-    auto tile_slot = [&](int t) { return kRing == 2 ? (t & 1) * W : (t % 3) * W; };
-    auto slot_at = [&](int sb, int d) {
-        if constexpr (kRing == 2) return (sb + d) & M;
-        else { const int s_ = sb + d; return s_ >= 3 * W ? s_ - 3 * W : s_; }
-    };
+    // ring slots: feature i sits at i mod 3W — for a feature at distance d <= 2W - 1 from the start of a tile whose slot begins
+    // at sb that is sb + d, wrapped once.
+    auto tile_slot = [&](int t) { return (t % 3) * W; };
+    auto slot_at = [&](int sb, int d) { const int s_ = sb + d; return s_ >= 3 * W ? s_ - 3 * W : s_; };
     auto tile_store = [&](int t) {
         const int sb = tile_slot(t);
 #pragma unroll
@@ -1965,8 +1873,7 @@ __global__ __launch_bounds__(DW *kWave, (DW == 8 ? 4 : 1)) void scale_frames_til
             pa.x = tv[j]; pa.y = ty[j] * sp + tz[j] * cp;          // {v, z'}
             pb.x = tx[j]; pb.y = ty[j] * cp - tz[j] * sp;          // {x, y'}
             if (i < n) { ringA[slot] = pa; ringB[slot] = pb; }
-#pragma unroll
-            for (int c = 0; c < kSubC; ++c) ringC[slot * kSubC + c] = c == 0 ? 1 : 0;      // np.ones, :153 (the sub-counters add up)
+            ringC[slot] = 1;                                        // np.ones, :153
             ringH[slot] = 0ull;
             used[slot] = 0;
         }
@@ -2063,7 +1970,7 @@ __global__ __launch_bounds__(DW *kWave, (DW == 8 ? 4 : 1)) void scale_frames_til
         const int nv = min(n_pendV[0], kPendCap), nh = min(n_pendH[0], kPendCapH), sb = tile_slot(tile);
         for (int e = tid; e < nv; e += B) {
             const int p = pendV[e], vtx = p >> 1;
-            if (vtx / W == tile) atomicAdd(&ringC[(sb + vtx - tile * W) * kSubC], (p & 1) ? -1 : 1);
+            if (vtx / W == tile) atomicAdd(&ringC[sb + vtx - tile * W], (p & 1) ? -1 : 1);
         }
         for (int e = tid; e < nh; e += B) {
             const int vtx = pendHv[e];
@@ -2108,10 +2015,7 @@ __global__ __launch_bounds__(DW *kWave, (DW == 8 ? 4 : 1)) void scale_frames_til
             bool survivor = false, is_cand = false;
             double cy = 0.0, ch = 0.0;
             if (i < n) {
-                int csum = 0;
-#pragma unroll
-                for (int c = 0; c < kSubC; ++c) csum += ringC[slot * kSubC + c];
-                survivor = csum >= 0;                                                  // :166
+                survivor = ringC[slot] >= 0;                                                 // :166
                 if (used[slot] && !survivor) bad = 1;                                  // tri2 names a feature the vote dropped
                 const unsigned long long hk = ringH[slot];
                 is_cand = hk != 0ull;
@@ -2147,9 +2051,9 @@ __global__ __launch_bounds__(DW *kWave, (DW == 8 ? 4 : 1)) void scale_frames_til
             const bool pb = (p0.x - p2.x) * (p0.y - p2.y) > 0.0;       // :108,:113  (marks vertices 0 and 1, as the reference does)
             const bool pc = (p1.x - p2.x) * (p1.y - p2.y) > 0.0;       // :109,:116
             const VoteFlags vf = vote_flags(pa, pb, pc, fixed);
-            atomicAdd(&ringC[(S(q.a)) * kSubC], vf.f0 ? -1 : 1);
-            atomicAdd(&ringC[(S(q.b)) * kSubC], vf.f1 ? -1 : 1);
-            atomicAdd(&ringC[(S(q.c)) * kSubC], vf.f2 ? -1 : 1);
+            atomicAdd(&ringC[S(q.a)], vf.f0 ? -1 : 1);
+            atomicAdd(&ringC[S(q.b)], vf.f1 ? -1 : 1);
+            atomicAdd(&ringC[S(q.c)], vf.f2 ? -1 : 1);
         };
         {
             // the prefetched rows: every ring read first (the compiler cannot move the reads of one row across the LDS
@@ -2173,9 +2077,9 @@ __global__ __launch_bounds__(DW *kWave, (DW == 8 ? 4 : 1)) void scale_frames_til
                 const bool pb = (p0.x - p2.x) * (p0.y - p2.y) > 0.0;       // :108,:113  (marks vertices 0 and 1, as the reference does)
                 const bool pc = (p1.x - p2.x) * (p1.y - p2.y) > 0.0;       // :109,:116
                 const VoteFlags vf = vote_flags(pa, pb, pc, fixed);
-                atomicAdd(&ringC[(S(q.a)) * kSubC], vf.f0 ? -1 : 1);
-                atomicAdd(&ringC[(S(q.b)) * kSubC], vf.f1 ? -1 : 1);
-                atomicAdd(&ringC[(S(q.c)) * kSubC], vf.f2 ? -1 : 1);
+                atomicAdd(&ringC[S(q.a)], vf.f0 ? -1 : 1);
+                atomicAdd(&ringC[S(q.b)], vf.f1 ? -1 : 1);
+                atomicAdd(&ringC[S(q.c)], vf.f2 ? -1 : 1);
             }
         }
         for (int t = b1 + kTileRows * B + rid; t < e1; t += B) vote_row(load_tri(rows1, t));
@@ -2205,18 +2109,14 @@ __global__ __launch_bounds__(DW *kWave, (DW == 8 ? 4 : 1)) void scale_frames_til
         for (int j = 0; j < kTileRows; ++j) { if (b2 + j * B + rid < e2) select_row(c2[j]); }
         for (int t = b2 + kTileRows * B + rid; t < e2; t += B) select_row(load_tri(rows2, t));
         MVOSR_TSTAMP(3);
-        if constexpr (kRing == 2) {
-            __syncthreads();                           // every row that names a vertex of tile k has been processed
-            MVOSR_TSTAMP(4);
-            retire(k);                                 // tile k+2 takes the slot
-        } else if (k > 0) retire(k - 1);               // (final since the barrier that ended the last step; tile k+2 takes ITS slot)
+        if (k > 0) retire(k - 1);                      // (final since the barrier that ended the last step; tile k+2 takes ITS slot)
         tile_store(k + 2);
         tile_load(k + 3);
         MVOSR_TSTAMP(5);
         __syncthreads();
         MVOSR_TSTAMP(6);
     }
-    if constexpr (kRing == 3) retire(ntiles - 1);
+    retire(ntiles - 1);
 
     block_sum2<DW>(hsum, hcnt, red + R_SEL_H * 2 * DW);
     {
@@ -2360,7 +2260,7 @@ __global__ __launch_bounds__(WAVES *kWave) void outlier_vote_kernel(const KArgs 
     TriChunk<WAVES * kWave> unused;
     const int nvalid = phase_vote<WAVES, SC>(s, n, nullptr, a.b.y + off, a.b.z + off, a.b.v + off, a.b.tri1, t1b, t1n,
                                              a.P.cos_pitch, a.P.sin_pitch, a.o.vote_counters + off, bad, nullptr, 0, 0, unused,
-                                             a.P.vote_mode == MVOSR_VOTE_FIXED, 0 MVOSR_STAMP_PASS);
+                                             a.P.vote_mode == MVOSR_VOTE_FIXED MVOSR_STAMP_PASS);
     int b0 = bad | (t1n > kMaxVoteRows ? 1 : 0), b1 = 0, b2 = 0, b3 = 0;
     block_sum4i<WAVES>(b0, b1, b2, b3, s.red + R_MISC * 2 * WAVES);
     if (threadIdx.x == 0) {
@@ -2436,33 +2336,6 @@ static PitchTest make_pitch_test(double thr_deg) {
         pt.s2_lo = -INFINITY;
     }
     return pt;
-}
-
-// Ablation / A-B switches of profiling runs: ONLY in builds with -DMVOSR_ABLATE (profiles/ab_build.sh); the shipped library
-// ignores the variable (tested).  Env MVOSR_DEBUG_SKIP, a bit mask — results with any bit of 1..16 set are NOT the path's
-// results: 1 / 2 / 4 skip the vote sweep / first / second selection sweep, 8 forces the refused-frame tail, 16 skips the
-// road-model launches, 32 ignores a batch's tile index (two-sweep dense kernel), 64 launches a ragged batch with one
-// variant instead of per size class, 256 keeps the one-wavefront road model for dense batches.
-static int debug_skip_env() {
-#ifdef MVOSR_ABLATE
-    static int v = -1;
-    if (v < 0) { const char *e = getenv("MVOSR_DEBUG_SKIP"); v = e ? atoi(e) : 0; }
-    return v;
-#else
-    return 0;
-#endif
-}
-
-// MVOSR_LDS_PAD (same builds only): bytes added to the LDS request of scale_frames_kernel so that fewer workgroups fit a CU
-// — the kernel lays its arrays out from the frame size, the padding is never touched (profiles/ab_occupancy.sh).
-static size_t lds_pad_env() {
-#ifdef MVOSR_ABLATE
-    static long v = -1;
-    if (v < 0) { const char *e = getenv("MVOSR_LDS_PAD"); v = e ? atol(e) : 0; }
-    return (size_t)v;
-#else
-    return 0;
-#endif
 }
 
 // Size classes of a ragged batch (the crossovers of pick_waves): the frames of a launch are split into up to three
@@ -2577,15 +2450,15 @@ static int launch_append_mask(mvosr_ctx *ctx, const KArgs &ka, int64_t nl, bool 
 }
 
 // One step of a scale-kernel family (its HOT / EXACT / FULL instantiations): FULL and EXACT run every frame of the
-// range in that mode; HOT runs the product variant and then the EXACT variant over the redo list the HOT kernel
-// filled (a short persistent grid: the list's length is only known on the device, and is almost always zero).
+// range in that mode; HOT runs the product variant, and mvosr_scale_batch runs ONE exact pass over the redo list it
+// filled, after the road model has added its frames (kModeExactList: a short persistent grid, the list's length is only
+// known on the device, and is almost always zero).
 constexpr int kRedoGrid = 512;
 constexpr int kModeExactList = 3;
 static inline KArgs &kargs_of(KArgs &a) { return a; }
 static inline KArgs &kargs_of(DenseArgs &a) { return a.k; }
 
-// set by mvosr_scale_batch around its HOT dispatch: the exact pass over the redo list is left to the caller
-static thread_local bool g_defer_exact = false;
+// set by mvosr_scale_batch around its HOT dispatch
 static thread_local bool g_hot_only = false;      // MVOSR_WAVES_HOT_ONLY: no exact_mask frames on the redo list either
 
 template <class Args>
@@ -2618,16 +2491,12 @@ static int launch_modes(mvosr_ctx *ctx, void (*k_hot)(const Args), void (*k_exac
     hipLaunchKernelGGL(k_hot, dim3((unsigned)nl), dim3(threads_hot), lds_hot, ctx_stream(ctx), args);
     if ((rc = check_launch(name))) return rc;
     if (!g_hot_only && (rc = launch_append_mask(ctx, kargs_of(args), nl, true))) return rc;
-    if (g_defer_exact) return MVOSR_OK;           // mvosr_scale_batch runs ONE exact pass, after the road model has added its frames to the list
-    kargs_of(args).redo_pass = 1;
-    const unsigned grid = (unsigned)(nl < (int64_t)kRedoGrid ? nl : (int64_t)kRedoGrid);
-    hipLaunchKernelGGL(k_exact, dim3(grid), dim3(threads), lds, ctx_stream(ctx), args);
-    return check_launch(name);
+    return MVOSR_OK;
 }
 
 template <int WAVES, int SC>
 static int launch_scale(mvosr_ctx *ctx, const KArgs &ka, int64_t nl, int mode) {
-    const size_t lds = lds_plan(ka.b.max_feat, WAVES).total + lds_pad_env();
+    const size_t lds = lds_plan(ka.b.max_feat, WAVES).total;
     int rc = check_fit(&ka.b, WAVES, SC, lds);
     if (rc) return rc;
     return launch_modes<KArgs>(ctx, scale_frames_kernel<WAVES, SC, MODE_HOT>, scale_frames_kernel<WAVES, SC, MODE_EXACT>,
@@ -2661,7 +2530,7 @@ static int launch_scale_dense_w(mvosr_ctx *ctx, const KArgs &ka, int64_t nl, int
     int rc = MVOSR_OK;
     // the tiled variant: feature-numbered rows with the host's tile index, frames small enough for its LDS plan
     const bool tiled = !vote_only && ka.b.tri2_ids == MVOSR_TRI2_FEATURES && ka.b.tile_w == kTileW && ka.b.tile_base &&
-                       ka.b.tile1_off && ka.b.tile2_off && !(debug_skip_env() & 32) &&
+                       ka.b.tile1_off && ka.b.tile2_off &&
                        (int64_t)tiled_plan(ka.b.max_feat, kTiledWaves).total <= (int64_t)g_max_dyn_lds;
     if (!vote_only && (ka.b.tri2_ids != MVOSR_TRI2_FEATURES || tiled)) {    // (the vote alone and the two-sweep feature-numbered variant need no workspace)
         void *p[2];
@@ -2826,13 +2695,12 @@ int mvosr_scale_batch(mvosr_ctx *ctx, const mvosr_params *p, const mvosr_batch *
     if ((rc = ctx_activate(ctx))) return rc;
     KArgs ka;
     ka.P = *p; ka.b = *b; ka.o = *o; ka.pt = make_pitch_test(p->pitch_threshold_deg);
-    ka.first_frame = first_frame; ka.height_level_in = nullptr; ka.debug_skip = debug_skip_env();
+    ka.first_frame = first_frame; ka.height_level_in = nullptr;
     ka.redo_pass = 0; ka.cls_list = nullptr; ka.cls_cnt = nullptr;
     if (b->total_feat <= 0) return set_error(MVOSR_ERR_ARG, "scale_batch: batch.total_feat (length of the feature planes) not set");
     if (b->n_frames >= ((int64_t)1 << 31) - 1) return set_error(MVOSR_ERR_TOO_LARGE, "scale_batch: more than 2^31-2 frames in one batch");
     if ((rc = ctx_workspace(ctx, b->n_frames, b->total_feat, &ka.ysel, &ka.nsel))) return rc;
-    ka.redo = ka.nsel + b->n_frames;            // [1 + n_frames] ints behind the nsel array
-    int32_t *redo2 = ka.redo + b->n_frames + 1; // a second list: frames the road model ends on the fallback level
+    ka.redo = ka.nsel + b->n_frames;            // [1 + n_frames] ints behind the nsel array; the [1 + n_frames] behind it are unused
     // FULL: per-triangle debug outputs; EXACT: stage outputs requested (height_level bit-equal to NumPy's for every
     // frame); HOT: the product path + its exact pass over the frames that need it
     const int mode = hot_only ? MODE_HOT : (o->tri_normals || o->tri_pitch_deg || o->tri_heights) ? MODE_FULL
@@ -2858,7 +2726,7 @@ int mvosr_scale_batch(mvosr_ctx *ctx, const mvosr_params *p, const mvosr_batch *
     // ragged batch: the HOT pass per size class (each class with its own variant and LDS request), then the EXACT pass
     // over the redo list as usual
     const bool by_class = mode == MODE_HOT && !dense && waves_per_frame == 0 && n_launch >= kClassMinFrames &&
-                          b->max_feat > kClassThr0 && !(debug_skip_env() & 64) &&
+                          b->max_feat > kClassThr0 &&
                           (b->min_feat <= 0 || pick_waves(0, b->min_feat) != waves);
     // stand-in rows (mvosr_batch.standin_*): the frames of the exact pass's list get SciPy's own rows before the pass reads them
     const bool standin = b->standin_u != nullptr;
@@ -2866,9 +2734,18 @@ int mvosr_scale_batch(mvosr_ctx *ctx, const mvosr_params *p, const mvosr_batch *
         if (!b->standin_keep || !b->standin_rows || !b->standin_cnt || !b->standin_status || !b->tri2_cnt || b->tri2_ids != MVOSR_TRI2_SURVIVORS)
             return set_error(MVOSR_ERR_ARG, "scale_batch: stand-in rows need standin_keep/_rows/_cnt/_status, tri2_cnt and survivor-numbered rows");
         if (dense) return set_error(MVOSR_ERR_TOO_LARGE, "scale_batch: stand-in rows are for frames that fit the LDS-resident kernels");
-        if (!(want_masked || hot_only || (mode == MODE_HOT && !(debug_skip_env() & (16 | 512)))))
+        if (!(want_masked || mode == MODE_HOT))
             return set_error(MVOSR_ERR_ARG, "scale_batch: stand-in rows need the HOT mode (no stage outputs, no EXACT-for-all)");
     }
+    // (a -DMVOSR_STAMPS build launches no road model: the scale kernel's stamps are written over outputs.hist, where the road
+    // model writes its histograms)
+    auto road = [&]() {
+#ifdef MVOSR_STAMPS
+        return MVOSR_OK;
+#else
+        return launch_road(ctx, ra, ctx_stream(ctx));
+#endif
+    };
     auto standin_rows = [&](const int32_t *list) {
         return qh_rows_for_list(ctx, b->n_frames, b->feat_off, b->feat_cnt, b->standin_u, b->v, b->standin_keep, b->max_feat, b->tri2_off,
                                 b->standin_rows, b->standin_cnt, b->standin_status, list);
@@ -2883,56 +2760,36 @@ int mvosr_scale_batch(mvosr_ctx *ctx, const mvosr_params *p, const mvosr_batch *
         if (standin && (rc = standin_rows(ka.redo))) return rc;
         if ((rc = dense ? launch_scale_dense(ctx, ka, n_launch, kModeExactList, false) : dispatch_scale(ctx, ka, waves, n_launch, kModeExactList))) return rc;
         ra.first_frame = first_frame; ra.n_frames = n_launch; ra.list = ka.redo;
-        ra.wide = (dense && !(debug_skip_env() & 256)) ? 1 : 0;
-        return launch_road(ctx, ra, ctx_stream(ctx));
+        ra.wide = dense ? 1 : 0;
+        return road();
     }
     // HOT: ONE exact pass per call (round 5; two before: one behind the HOT kernel, one behind the road model).  The HOT kernel
     // and the exact mask put their frames on the redo list; the road model runs over every other frame and APPENDS the frames that
     // end on the fallback level (:334-335; rare) to the same list; then the EXACT variant over the list, then the road model over it.
-    const bool fold = mode == MODE_HOT && (hot_only || (!(debug_skip_env() & 16) && !(debug_skip_env() & 512)));
     if (by_class) {
         if ((rc = launch_scale_classes(ctx, ka, n_launch))) return rc;
         if (!hot_only && (rc = launch_append_mask(ctx, ka, n_launch, true))) return rc;
-        if (!fold && (rc = dispatch_scale(ctx, ka, waves, n_launch, kModeExactList))) return rc;
     } else {
-        g_defer_exact = fold;
         g_hot_only = hot_only;
         rc = dense ? launch_scale_dense(ctx, ka, n_launch, mode, false) : dispatch_scale(ctx, ka, waves, n_launch, mode);
-        g_defer_exact = false;
         g_hot_only = false;
         if (rc) return rc;
     }
     if (pev && (ee = hipEventRecord(pev[1], ctx_stream(ctx))) != hipSuccess) return set_hip_error("hipEventRecord(profile)", ee);
     ra.first_frame = first_frame; ra.n_frames = n_launch;
-    ra.wide = (dense && !(debug_skip_env() & 256)) ? 1 : 0;     // dense batches: thousands of values per list, few frames
-    if (!(debug_skip_env() & 16)) {
-        if (fold) {
-            ra.level_redo = ka.redo;
-            ra.listed_mask = hot_only ? nullptr : b->exact_mask;    // (hot_only: append_mask_kernel did not run)
-            if ((rc = launch_road(ctx, ra, ctx_stream(ctx)))) return rc;
-            ra.listed_mask = nullptr;
-            if (hot_only) return MVOSR_OK;            // (the list's frames stay MVOSR_ST_REDO: the caller's)
-            if (standin && (rc = standin_rows(ka.redo))) return rc;          // SciPy's own rows for the frames the exact pass redoes
-            if ((rc = dense ? launch_scale_dense(ctx, ka, n_launch, kModeExactList, false) : dispatch_scale(ctx, ka, waves, n_launch, kModeExactList))) return rc;
-            ra.level_redo = nullptr; ra.list = ka.redo;
-            if ((rc = launch_road(ctx, ra, ctx_stream(ctx)))) return rc;
-        } else {
-            if (mode == MODE_HOT) {
-                // frames whose road model ends on the fallback level come back on a second list: the EXACT variant redoes them
-                // (height_level in NumPy's order), then the road model runs on that list alone
-                const hipError_t e2 = hipMemsetAsync(redo2, 0, sizeof(int32_t), ctx_stream(ctx));
-                if (e2 != hipSuccess) return set_hip_error("hipMemsetAsync(redo list 2)", e2);
-                ra.level_redo = redo2;
-            }
-            if ((rc = launch_road(ctx, ra, ctx_stream(ctx)))) return rc;
-            if (mode == MODE_HOT) {
-                KArgs k2 = ka;
-                k2.redo = redo2;
-                if ((rc = dense ? launch_scale_dense(ctx, k2, n_launch, kModeExactList, false) : dispatch_scale(ctx, k2, waves, n_launch, kModeExactList))) return rc;
-                ra.level_redo = nullptr; ra.list = redo2;
-                if ((rc = launch_road(ctx, ra, ctx_stream(ctx)))) return rc;
-            }
-        }
+    ra.wide = dense ? 1 : 0;                    // dense batches: thousands of values per list, few frames
+    if (mode == MODE_HOT) {
+        ra.level_redo = ka.redo;
+        ra.listed_mask = hot_only ? nullptr : b->exact_mask;    // (hot_only: append_mask_kernel did not run)
+        if ((rc = road())) return rc;
+        ra.listed_mask = nullptr;
+        if (hot_only) return MVOSR_OK;            // (the list's frames stay MVOSR_ST_REDO: the caller's)
+        if (standin && (rc = standin_rows(ka.redo))) return rc;          // SciPy's own rows for the frames the exact pass redoes
+        if ((rc = dense ? launch_scale_dense(ctx, ka, n_launch, kModeExactList, false) : dispatch_scale(ctx, ka, waves, n_launch, kModeExactList))) return rc;
+        ra.level_redo = nullptr; ra.list = ka.redo;
+        if ((rc = road())) return rc;
+    } else if ((rc = road())) {
+        return rc;
     }
     if (pev) {
         if ((ee = hipEventRecord(pev[2], ctx_stream(ctx))) != hipSuccess) return set_hip_error("hipEventRecord(profile)", ee);
@@ -2969,7 +2826,7 @@ int mvosr_outlier_vote_batch(mvosr_ctx *ctx, const mvosr_params *p, const mvosr_
     if ((rc = ctx_activate(ctx))) return rc;
     KArgs ka;
     ka.P = *p; ka.b = *b; ka.o = *o; ka.pt = make_pitch_test(p->pitch_threshold_deg);
-    ka.first_frame = 0; ka.height_level_in = nullptr; ka.debug_skip = 0; ka.ysel = nullptr; ka.nsel = nullptr; ka.redo = nullptr; ka.redo_pass = 0;
+    ka.first_frame = 0; ka.height_level_in = nullptr; ka.ysel = nullptr; ka.nsel = nullptr; ka.redo = nullptr; ka.redo_pass = 0;
     ka.cls_list = nullptr; ka.cls_cnt = nullptr;
     if ((waves_per_frame == 0 || waves_per_frame == 16) && b->max_feat > lds_capacity_features()) {
         if (b->total_feat <= 0) return set_error(MVOSR_ERR_ARG, "outlier_vote: batch.total_feat not set");
@@ -3028,17 +2885,6 @@ int mvosr_window_median_blocked(mvosr_ctx *ctx, const double *blocks, int64_t n,
 }
 
 }  // extern "C"
-
-#ifdef MVOSR_ABLATE
-// diagnostic builds only (profiles/ab_build.sh ... -DMVOSR_ABLATE): the exact pass's list of the context's last mvosr_scale_batch —
-// out[0] = how many frames, out[1..] = which (profiles/redo_list_census.py)
-extern "C" int mvosr_debug_redo_list(mvosr_ctx *ctx, int64_t n_frames, int32_t *out, int cap) {
-    if (!ctx || !out || cap < 1 || !ctx->ws_nsel) return MVOSR_ERR_ARG;
-    (void)hipStreamSynchronize(ctx_stream(ctx));
-    const hipError_t e = hipMemcpy(out, ctx->ws_nsel + n_frames, sizeof(int32_t) * (size_t)cap, hipMemcpyDeviceToHost);
-    return e == hipSuccess ? MVOSR_OK : MVOSR_ERR_HIP;
-}
-#endif
 
 #ifdef MVOSR_ROAD_EXACT_COUNT
 // (diagnostic build only) the road model's decision counters: out[3] as above; reset: zero them afterwards

@@ -24,8 +24,9 @@ namespace {
 
 constexpr int kQhMaxPoints = 8000;        // facet ids are 16-bit: 7 * (n + 1) + 64 facets per run
 constexpr int kQhMaxPointsWide = 60000;   // 32-bit facet ids (80-byte records); point ids stay 16-bit
-// table entries per insertion: 64 (one frame per wavefront) or 32 (packed kernels) — cone facets 5.6 on average, 35 the most seen
-// in 512 frames of 2000 points; visible facets 3.6 on average, 33 the most seen; horizon facets about as many
+// table entries per insertion — cone facets 5.6 on average, 35 the most seen in 512 frames of 2000 points; visible facets 3.6 on
+// average, 33 the most seen; horizon facets about as many
+constexpr int kQhTab = 64;
 constexpr int kQhPickWindow = 16;
 constexpr double kQhEps = 2.220446049250313e-16;
 constexpr double kQhHuge = 1.797e308;
@@ -84,7 +85,6 @@ struct QhArgs {
     const int64_t *pts_off; const int32_t *pts_cnt; const double *u; const double *v; const int32_t *keep;
     const int64_t *tri_off; int32_t *tri; int32_t *tri_cnt; int32_t *n_used; int32_t *status; int32_t *order_out;
     unsigned long long *stamps;
-    int32_t *redo;               // packed kernels: frames that overflowed a table ([0] = how many), for the list kernel
     const int32_t *list;         // null, or: list[0] frames list[1..] (a redo list of the scale kernels), walked by a persistent grid
     const int32_t *launch_order; // null, or: workgroup b runs frame launch_order[b] — the largest frames first (qh_order_kernel)
     char *ws; size_t ws_stride; int cap_pts;      // per-frame slice, laid out by QhPlan for cap_pts = max_pts + 1 points
@@ -119,58 +119,41 @@ struct QhCoord {
     __device__ __forceinline__ double &operator[](int i) const { return (&p[i].x)[k]; }
 };
 
-// The tables of one insertion, TAB entries each (a frame whose insertion needs more is declined — or, from the packed kernel,
-// redone by the 64-entry one).
-template <typename FID, int TAB> struct QhLdsT {
-    double npl[TAB][4];        // the cone's planes (n0, n1, n2, offset)
-    double nxy[TAB][6];        // coordinates of a cone facet's two horizon vertices (convexity test between cone facets)
-    uint16_t nva[TAB], nvb[TAB];     // a cone facet's horizon vertices (point ids)
-    uint8_t nnb[TAB][4];       // cone neighbours 1, 2 as cone-local indices; [0] = top-oriented, [3] = upper flag
-    FID visq[TAB];             // visible facets in Qhull's breadth-first order
-    FID visnb[TAB][4];         // (a stride of four: the entry/neighbour pair of a lane is a shift and a mask)
-    uint16_t visrep[TAB];      // cone-local index of the visible facet's replacement (kQhNone: the first cone facet)
-    uint32_t visoff[TAB];
-    uint16_t viscnt[TAB];      // points of its outside set without the furthest
-    uint16_t visbest[TAB];
-    uint32_t viscum[TAB + 1];
-    FID nhz[TAB];              // a cone facet's horizon neighbour (facet id)
-    FID hzq[TAB];              // horizon facets tested in this insertion, and their records (p0 p1 p2 flags nb0 nb1 nb2)
-    FID hzr[TAB][8];
-    uint32_t t_off[TAB]; uint32_t t_total[TAB]; uint32_t t_cnt[TAB]; uint16_t t_bestp[TAB]; double t_bestd[TAB];
+// The tables of one insertion, kQhTab entries each (a frame whose insertion needs more is declined).
+template <typename FID> struct QhLdsT {
+    double npl[kQhTab][4];                // the cone's planes (n0, n1, n2, offset)
+    double nxy[kQhTab][6];                // coordinates of a cone facet's two horizon vertices (convexity test between cone facets)
+    uint16_t nva[kQhTab], nvb[kQhTab];    // a cone facet's horizon vertices (point ids)
+    uint8_t nnb[kQhTab][4];               // cone neighbours 1, 2 as cone-local indices; [0] = top-oriented, [3] = upper flag
+    FID visq[kQhTab];                     // visible facets in Qhull's breadth-first order
+    FID visnb[kQhTab][4];                 // (a stride of four: the entry/neighbour pair of a lane is a shift and a mask)
+    uint16_t visrep[kQhTab];              // cone-local index of the visible facet's replacement (kQhNone: the first cone facet)
+    uint32_t visoff[kQhTab];
+    uint16_t viscnt[kQhTab];              // points of its outside set without the furthest
+    uint16_t visbest[kQhTab];
+    uint32_t viscum[kQhTab + 1];
+    FID nhz[kQhTab];                      // a cone facet's horizon neighbour (facet id)
+    FID hzq[kQhTab];                      // horizon facets tested in this insertion, and their records (p0 p1 p2 flags nb0 nb1 nb2)
+    FID hzr[kQhTab][8];
+    uint32_t t_off[kQhTab]; uint32_t t_total[kQhTab]; uint32_t t_cnt[kQhTab]; uint16_t t_bestp[kQhTab]; double t_bestd[kQhTab];
 };
-struct QhArrival { int tgt, p; double d; };      // (packed kernels: a chunk of arrivals staged over `nxy`, which placement no longer needs)
-
-// A frame's lanes: the whole wavefront (G = 64), or an aligned group of G = 32 / 16 lanes — then 64 / G frames share a wavefront
-// and every vector instruction serves all of them (one insertion is ~1 200 vector instructions whether it feeds one frame or
-// four).  The run is written for "the G lanes of a frame": ballots, shuffles and reductions stay inside the group; a loop whose
-// trip count differs between the groups of a wavefront diverges and reconverges like any SIMT loop; the lanes of a declined
-// frame drop out.  LDS instructions of a wavefront execute in order, so a group's writes are seen by its later reads.
-template <int G> struct Sg {
-    static_assert(G == 64 || G == 32 || G == 16, "lanes per frame");
-    static constexpr uint64_t kMask = ~0ull >> (64 - G);
-    static __device__ __forceinline__ int sl() { return lane_id() & (G - 1); }
-    static __device__ __forceinline__ int sub() { return lane_id() / G; }
-    static __device__ __forceinline__ int first() { return lane_id() & ~(G - 1); }
-    static __device__ __forceinline__ uint64_t ballot(bool p) {
-        const uint64_t b = __ballot(p);
-        if constexpr (G == 64) return b; else return (b >> first()) & kMask;
-    }
-    static __device__ __forceinline__ bool any(bool p) { if constexpr (G == 64) return __any(p); else return ballot(p) != 0ull; }
-    static __device__ __forceinline__ uint64_t below() { return (1ull << sl()) - 1ull; }
-    template <typename T> static __device__ __forceinline__ T shfl(T v, int i) {
-        if constexpr (G == 64) return __shfl(v, i); else return __shfl(v, first() + i);
-    }
-    static __device__ __forceinline__ int uni(int v) { if constexpr (G == 64) return __builtin_amdgcn_readfirstlane(v); else return v; }
-    // (i: uniform over the wavefront when G = 64)
-    static __device__ __forceinline__ double bcast_d(double v, int i) { if constexpr (G == 64) return readlane_d(v, i); else return __shfl(v, first() + i); }
+// One frame per wavefront: ballots, shuffles and reductions over the whole wavefront.
+struct Wf {
+    static __device__ __forceinline__ uint64_t ballot(bool p) { return __ballot(p); }
+    static __device__ __forceinline__ bool any(bool p) { return __any(p); }
+    static __device__ __forceinline__ uint64_t below() { return (1ull << lane_id()) - 1ull; }
+    template <typename T> static __device__ __forceinline__ T shfl(T v, int i) { return __shfl(v, i); }
+    static __device__ __forceinline__ int uni(int v) { return __builtin_amdgcn_readfirstlane(v); }
+    // (i: uniform over the wavefront)
+    static __device__ __forceinline__ double bcast_d(double v, int i) { return readlane_d(v, i); }
     static __device__ __forceinline__ double max_d(double v) {
 #pragma unroll
-        for (int o = G / 2; o >= 1; o >>= 1) { const double w = __shfl_xor(v, o); v = w > v ? w : v; }
+        for (int o = kWave / 2; o >= 1; o >>= 1) { const double w = __shfl_xor(v, o); v = w > v ? w : v; }
         return v;
     }
     static __device__ __forceinline__ double min_d(double v) {
 #pragma unroll
-        for (int o = G / 2; o >= 1; o >>= 1) { const double w = __shfl_xor(v, o); v = w < v ? w : v; }
+        for (int o = kWave / 2; o >= 1; o >>= 1) { const double w = __shfl_xor(v, o); v = w < v ? w : v; }
         return v;
     }
 };
@@ -303,62 +286,35 @@ template <typename L_t> __device__ __forceinline__ QhWalk qh_walk_cone(const L_t
     return R;
 }
 
-// One chunk (<= G arrivals, lanes 0 .. count-1 of the frame's group in Qhull's processing order) appended to the targets' outside
+// One chunk (<= 64 arrivals, lanes 0 .. count-1 in Qhull's processing order) appended to the targets' outside
 // sets: qh_partitionpoint's list rule.  A target's list is arena[t_off .. t_off + t_cnt) + [t_bestp]; the furthest point stays
 // last, a point that arrives further than it takes over and the old one enters the list in the arrival's place.  Lane j keeps
-// target j's state in registers and the arrivals are broadcast one by one (v_readlane; from LDS in the packed kernels):
-// ~14 instructions per arrival.
-template <int G, typename L_t> __device__ __forceinline__ void qh_place_chunk(L_t &L, uint16_t *arena, int count, int m, int tgt, int p, double d) {
-    const int sl = Sg<G>::sl();
-    if constexpr (G == 64) {
-        uint32_t base = 0, cnt = 0; int bestp = kQhNone; double bestd = -kQhHuge;
-        if (sl < m) { base = L.t_off[sl]; cnt = L.t_cnt[sl]; bestp = L.t_bestp[sl]; bestd = L.t_bestd[sl]; }
-        for (int i = 0; i < count; ++i) {
-            const int ti = __builtin_amdgcn_readlane(tgt, i);
-            const int pi = __builtin_amdgcn_readlane(p, i);
-            const double di = readlane_d(d, i);
-            if (sl == ti) {
-                if (bestp == kQhNone) { bestp = pi; bestd = di; }
-                else {
-                    const bool further = di > bestd;
-                    arena[base + cnt] = (uint16_t)(further ? bestp : pi);
-                    ++cnt;
-                    if (further) { bestp = pi; bestd = di; }
-                }
+// target j's state in registers and the arrivals are broadcast one by one (v_readlane): ~14 instructions per arrival.
+template <typename L_t> __device__ __forceinline__ void qh_place_chunk(L_t &L, uint16_t *arena, int count, int m, int tgt, int p, double d) {
+    const int sl = lane_id();
+    uint32_t base = 0, cnt = 0; int bestp = kQhNone; double bestd = -kQhHuge;
+    if (sl < m) { base = L.t_off[sl]; cnt = L.t_cnt[sl]; bestp = L.t_bestp[sl]; bestd = L.t_bestd[sl]; }
+    for (int i = 0; i < count; ++i) {
+        const int ti = __builtin_amdgcn_readlane(tgt, i);
+        const int pi = __builtin_amdgcn_readlane(p, i);
+        const double di = readlane_d(d, i);
+        if (sl == ti) {
+            if (bestp == kQhNone) { bestp = pi; bestd = di; }
+            else {
+                const bool further = di > bestd;
+                arena[base + cnt] = (uint16_t)(further ? bestp : pi);
+                ++cnt;
+                if (further) { bestp = pi; bestd = di; }
             }
         }
-        if (sl < m) { L.t_cnt[sl] = cnt; L.t_bestp[sl] = (uint16_t)bestp; L.t_bestd[sl] = bestd; }
-    } else {
-        QhArrival *A = reinterpret_cast<QhArrival *>(&L.nxy[0][0]);
-        { QhArrival a; a.tgt = tgt; a.p = p; a.d = d; A[sl] = a; }
-        qh_lds_sync();
-        for (int jb = 0; jb < m; jb += G) {
-            const int j = jb + sl;
-            uint32_t base = 0, cnt = 0; int bestp = kQhNone; double bestd = -kQhHuge;
-            if (j < m) { base = L.t_off[j]; cnt = L.t_cnt[j]; bestp = L.t_bestp[j]; bestd = L.t_bestd[j]; }
-            for (int i = 0; i < count; ++i) {
-                const QhArrival a = A[i];
-                if (j == a.tgt) {
-                    if (bestp == kQhNone) { bestp = a.p; bestd = a.d; }
-                    else {
-                        const bool further = a.d > bestd;
-                        arena[base + cnt] = (uint16_t)(further ? bestp : a.p);
-                        ++cnt;
-                        if (further) { bestp = a.p; bestd = a.d; }
-                    }
-                }
-            }
-            if (j < m) { L.t_cnt[j] = cnt; L.t_bestp[j] = (uint16_t)bestp; L.t_bestd[j] = bestd; }
-        }
-        qh_lds_sync();
     }
+    if (sl < m) { L.t_cnt[sl] = cnt; L.t_bestp[sl] = (uint16_t)bestp; L.t_bestd[sl] = bestd; }
 }
 
-// One frame, G lanes.  Returns the reason the frame was declined (QH_OK: rows written, `nrows` of them).
-template <typename FID, int G, int TAB> __device__ __forceinline__ int qh_run(const QhArgs &a, QhLdsT<FID, TAB> &L, const int64_t f, const int64_t slot, int &nrows) {
+// One frame, one wavefront.  Returns the reason the frame was declined (QH_OK: rows written, `nrows` of them).
+template <typename FID> __device__ __forceinline__ int qh_run(const QhArgs &a, QhLdsT<FID> &L, const int64_t f, const int64_t slot, int &nrows) {
     typedef QhFacetT<FID> QhFacet;
-    typedef Sg<G> S_;
-    const int lane = S_::sl();
+    const int lane = lane_id();
     const QhPlan P = qh_plan(a.cap_pts, sizeof(FID) == 4);
     char *ws = a.ws + (size_t)slot * a.ws_stride;
     double4 *PT = reinterpret_cast<double4 *>(ws + P.pts);
@@ -377,13 +333,13 @@ template <typename FID, int G, int TAB> __device__ __forceinline__ int qh_run(co
     int perm0 = 1;                // the initial facet moved to the head of the list (qh_furthestnext)
 
     // ---- 0. the sites: kept points compacted, lifted; the point 'at infinity'; extremes ----
-    for (int base = 0; base < cnt; base += G) {
+    for (int base = 0; base < cnt; base += kWave) {
         const int i = base + lane;
         bool k = i < cnt;
         if (k && a.keep) k = a.keep[off + i] >= 0;
-        const uint64_t m = S_::ballot(k);
+        const uint64_t m = Wf::ballot(k);
         if (k) {
-            const int r = n + popc64(m & S_::below());
+            const int r = n + popc64(m & Wf::below());
             if (r < a.cap_pts - 1) {
                 const double x = a.u[off + i], y = a.v[off + i];
                 X[r] = x; Y[r] = y; Z[r] = x * x + y * y;
@@ -391,19 +347,19 @@ template <typename FID, int G, int TAB> __device__ __forceinline__ int qh_run(co
         }
         n += popc64(m);
     }
-    n = S_::uni(n);
+    n = Wf::uni(n);
     if (a.n_used) { if (lane == 0) a.n_used[f] = n; }
     if (n < 3 || n > a.cap_pts - 1 || n > (sizeof(FID) == 4 ? kQhMaxPointsWide : kQhMaxPoints)) return QH_FEW_POINTS;
     qh_mem_sync();
     {
         // sums in input order (the point at infinity sits over the mean), the largest lifted height
         double sx = 0.0, sy = 0.0, mz = -kQhHuge;
-        for (int base = 0; base < n; base += G) {
+        for (int base = 0; base < n; base += kWave) {
             const int i = base + lane;
             const double x = i < n ? X[i] : 0.0, y = i < n ? Y[i] : 0.0, z = i < n ? Z[i] : -kQhHuge;
-            const int c = min(G, n - base);
-            for (int j = 0; j < c; ++j) { sx += S_::bcast_d(x, j); sy += S_::bcast_d(y, j); }
-            mz = fmax(mz, S_::max_d(z));
+            const int c = min(kWave, n - base);
+            for (int j = 0; j < c; ++j) { sx += Wf::bcast_d(x, j); sy += Wf::bcast_d(y, j); }
+            mz = fmax(mz, Wf::max_d(z));
         }
         if (lane == 0) { X[n] = sx / (double)n; Y[n] = sy / (double)n; Z[n] = mz * 1.1; }
     }
@@ -415,12 +371,12 @@ template <typename FID, int G, int TAB> __device__ __forceinline__ int qh_run(co
         for (int k = 0; k < 3; ++k) {
             const QhCoord C{PT, k};
             double hi = -kQhHuge, lo = kQhHuge; int hii = 0, loi = 0;
-            for (int base = 0; base < m1; base += G) {
+            for (int base = 0; base < m1; base += kWave) {
                 const int i = base + lane;
                 const double c = i < m1 ? C[i] : 0.0;
-                const double cm = S_::max_d(i < m1 ? c : -kQhHuge), cn = S_::min_d(i < m1 ? c : kQhHuge);
-                if (cm > hi) { hi = cm; hii = base + ffs64(S_::ballot(i < m1 && c == cm)); }
-                if (cn < lo) { lo = cn; loi = base + ffs64(S_::ballot(i < m1 && c == cn)); }
+                const double cm = Wf::max_d(i < m1 ? c : -kQhHuge), cn = Wf::min_d(i < m1 ? c : kQhHuge);
+                if (cm > hi) { hi = cm; hii = base + ffs64(Wf::ballot(i < m1 && c == cm)); }
+                if (cn < lo) { lo = cn; loi = base + ffs64(Wf::ballot(i < m1 && c == cn)); }
             }
             double maxcoord;
             if (k == 2) { zlow = lo; zhigh = hi; maxcoord = maxabs; }
@@ -438,7 +394,7 @@ template <typename FID, int G, int TAB> __device__ __forceinline__ int qh_run(co
         // 'Qbb': the lifted coordinate scaled to [0, maxabs]
         const double scale = maxabs / (zhigh - zlow);
         const double shift = 0.0 - zlow * scale;
-        for (int i = lane; i <= n; i += G) Z[i] = Z[i] * scale + shift;
+        for (int i = lane; i <= n; i += kWave) Z[i] = Z[i] * scale + shift;
         const double maxdistsum = fmin(__builtin_sqrt(3.0) * maxabs, maxsum);
         K.distround = kQhEps * (3 * maxdistsum * 1.01 + maxabs);
         K.anground = 1.01 * 3 * kQhEps;
@@ -525,7 +481,7 @@ template <typename FID, int G, int TAB> __device__ __forceinline__ int qh_run(co
             fac[lane + 1] = Gf;
             L.t_total[lane] = 0;
         }
-        if (S_::any(gauss)) return QH_GAUSS;
+        if (Wf::any(gauss)) return QH_GAUSS;
         nfac = 4;
         qh_mem_sync();
         // narrow initial simplex: Qhull switches to another furthest-point rule
@@ -535,7 +491,7 @@ template <typename FID, int G, int TAB> __device__ __forceinline__ int qh_run(co
                 mina = fmin(mina, L.npl[lane][0] * L.npl[j][0] + L.npl[lane][1] * L.npl[j][1] + L.npl[lane][2] * L.npl[j][2]);
             gauss = mina < -0.99999999;
         }
-        if (S_::any(gauss)) return QH_NARROW;
+        if (Wf::any(gauss)) return QH_NARROW;
     }
     qh_mem_sync();
 
@@ -553,7 +509,7 @@ template <typename FID, int G, int TAB> __device__ __forceinline__ int qh_run(co
                 atop = L.t_total[0] + L.t_total[1] + L.t_total[2] + L.t_total[3];
                 qh_mem_sync();
             }
-            for (int base = 0; base < total; base += G) {
+            for (int base = 0; base < total; base += kWave) {
                 const int p = base + lane;
                 bool valid = p < total && p != simplex[0] && p != simplex[1] && p != simplex[2] && p != simplex[3];
                 int tgt = 0; double d = 0.0;
@@ -572,11 +528,11 @@ template <typename FID, int G, int TAB> __device__ __forceinline__ int qh_run(co
                         atomicAdd(&L.t_total[tgt], 1u);
                     } else { tgt = TT[p]; d = DD[p]; }
                 }
-                if (pass == 1) qh_place_chunk<G>(L, arena, min(G, total - base), 4, valid ? tgt : -1, p, d);
+                if (pass == 1) qh_place_chunk(L, arena, min(kWave, total - base), 4, valid ? tgt : -1, p, d);
             }
             qh_mem_sync();
-            if (S_::any(inside)) return QH_INSIDE_SIMPLEX;
-            if (S_::any(bad)) return QH_BAND;
+            if (Wf::any(inside)) return QH_INSIDE_SIMPLEX;
+            if (Wf::any(bad)) return QH_BAND;
         }
         if (lane < 4) {
             fac[lane + 1].off = L.t_off[lane]; fac[lane + 1].cnt = (uint16_t)L.t_cnt[lane];
@@ -610,18 +566,18 @@ template <typename FID, int G, int TAB> __device__ __forceinline__ int qh_run(co
                 if (id) { const uint4 *Gp = reinterpret_cast<const uint4 *>(&fac[id]); r0 = Gp[0]; r1 = Gp[1]; }
                 const QhHead<FID> h = qh_head(static_cast<const QhFacet *>(nullptr), r0, r1);
                 const bool has = id && !(h.flags & 4u) && h.bestp != kQhNone;
-                const uint64_t hm = S_::ballot(has);
+                const uint64_t hm = Wf::ballot(has);
                 if (hm) {
                     const int l = ffs64(hm);
                     pos += l; cur = pos2id(pos);
-                    H.bestp = S_::shfl(h.bestp, l); H.nb0 = S_::shfl(h.nb0, l); H.nb1 = S_::shfl(h.nb1, l); H.nb2 = S_::shfl(h.nb2, l);
-                    H.off = S_::shfl(h.off, l); H.cnt = S_::shfl(h.cnt, l);
+                    H.bestp = Wf::shfl(h.bestp, l); H.nb0 = Wf::shfl(h.nb0, l); H.nb1 = Wf::shfl(h.nb1, l); H.nb2 = Wf::shfl(h.nb2, l);
+                    H.off = Wf::shfl(h.off, l); H.cnt = Wf::shfl(h.cnt, l);
                     break;
                 }
                 pos += kQhPickWindow;
             }
             if (cur < 0) break;
-            cur = S_::uni(cur);
+            cur = Wf::uni(cur);
             ++step;
             const int p = (int)H.bestp;
             if (a.order_out) { if (lane == 0 && p < n) a.order_out[off + p] = step; }     // (compacted ids when `keep` is given)
@@ -637,7 +593,7 @@ template <typename FID, int G, int TAB> __device__ __forceinline__ int qh_run(co
             const double px = X[p], py = Y[p], pz = Z[p];        // (in flight together with the first round's facet records)
             bool bad = false, copl = false;
             while (head < nvis) {
-                const int ne = min(nvis - head, G / 4);            // four lanes per visible facet: neighbours 0..2 (the fourth lane idles)
+                const int ne = min(nvis - head, kWave / 4);            // four lanes per visible facet: neighbours 0..2 (the fourth lane idles)
                 const int e = head + (lane >> 2), k = lane & 3;
                 const bool act = (lane >> 2) < ne && k < 3;
                 int g = 0;
@@ -651,11 +607,11 @@ template <typename FID, int G, int TAB> __device__ __forceinline__ int qh_run(co
                     if (cand) Gf = fac[g];
                 }
                 // the same facet reached twice in this round: the earlier (entry, neighbour) pair tests it
-                const uint64_t cm = S_::ballot(cand);
+                const uint64_t cm = Wf::ballot(cand);
                 bool dup = false;
                 for (uint64_t r = cm; r; r &= r - 1) {
                     const int j = ffs64(r);
-                    const int gj = S_::shfl(g, j);
+                    const int gj = Wf::shfl(g, j);
                     if (cand && lane > j && gj == g) dup = true;
                 }
                 bool vis = false, hzn = false;
@@ -664,16 +620,16 @@ template <typename FID, int G, int TAB> __device__ __forceinline__ int qh_run(co
                     if (d > K.minvisible) { vis = true; if (d < K.guard) bad = true; }
                     else { hzn = true; if (d >= -K.guard) copl = true; }
                 }
-                const uint64_t vm = S_::ballot(vis), zm = S_::ballot(hzn);
+                const uint64_t vm = Wf::ballot(vis), zm = Wf::ballot(hzn);
                 const int add = popc64(vm), addz = popc64(zm);
-                if (nvis + add > TAB || nhz + addz > TAB) { why = QH_TOO_MANY_VISIBLE; break; }
+                if (nvis + add > kQhTab || nhz + addz > kQhTab) { why = QH_TOO_MANY_VISIBLE; break; }
                 if (vis) {
-                    const int q = nvis + popc64(vm & S_::below());
+                    const int q = nvis + popc64(vm & Wf::below());
                     L.visq[q] = (FID)g; L.visnb[q][0] = Gf.nb[0]; L.visnb[q][1] = Gf.nb[1]; L.visnb[q][2] = Gf.nb[2];
                     L.visoff[q] = Gf.off; L.viscnt[q] = Gf.cnt; L.visbest[q] = Gf.bestp;
                 }
                 if (hzn) {
-                    const int q = nhz + popc64(zm & S_::below());
+                    const int q = nhz + popc64(zm & Wf::below());
                     L.hzq[q] = (FID)g;
                     L.hzr[q][0] = Gf.p[0]; L.hzr[q][1] = Gf.p[1]; L.hzr[q][2] = Gf.p[2]; L.hzr[q][3] = Gf.flags;
                     L.hzr[q][4] = Gf.nb[0]; L.hzr[q][5] = Gf.nb[1]; L.hzr[q][6] = Gf.nb[2];
@@ -682,16 +638,12 @@ template <typename FID, int G, int TAB> __device__ __forceinline__ int qh_run(co
                 qh_lds_sync();
             }
             if (why) return why;
-            if (S_::any(copl)) return QH_COPLANAR_HORIZON;
-            if (S_::any(bad)) return QH_BAND;
+            if (Wf::any(copl)) return QH_COPLANAR_HORIZON;
+            if (Wf::any(bad)) return QH_BAND;
             QH_STAMP(1);
-            // The visible facets' points (what (e) partitions) are known as soon as the visible list is: their ids (a load from the
-            // arena) and then their coordinates (a dependent load) are two of an insertion's ~8 memory round trips.  The first chunk's
-            // ids can be asked for HERE, under the cone's own loads, and their coordinates before the matching, which is LDS work only:
-            // (e) then starts with its operands in registers.  MEASURED (round 6, same box, -DMVOSR_QH_PREFETCH against without): 34.75 /
-            // 34.94 against 34.86 / 34.84 ms per launch of 4 096 sets, 126.41 / 125.74 against 126.56 / 126.04 for 16 384 — nothing, like
-            // round 5's variant that only touched the sectors (LABNOTES §9.15): at four wavefronts per SIMD a wavefront's own round trips
-            // are hidden behind the others' instructions already.  Off by default; the prefix sum alone stays here.
+            // (Asking for the first chunk's ids and coordinates of (e) here, under the cone's own loads, was measured and gained
+            // nothing: at four wavefronts per SIMD a wavefront's own round trips are hidden behind the others' instructions already —
+            // DESIGN §3.6, LABNOTES "Retired switches".)
             int S = 0;
             {
                 if (lane == 0) {
@@ -703,21 +655,13 @@ template <typename FID, int G, int TAB> __device__ __forceinline__ int qh_run(co
                 S = (int)L.viscum[nvis];
             }
             if (atop + (uint32_t)S > P.acap) return QH_ARENA_FULL;
-#ifdef MVOSR_QH_PREFETCH
-            int q_pre = 0, e_pre = 0;
-            if (lane < S) {
-                while (e_pre + 1 < nvis && (int)L.viscum[e_pre + 1] <= lane) ++e_pre;
-                const int r = lane - (int)L.viscum[e_pre];
-                q_pre = r < (int)L.viscnt[e_pre] ? arena[L.visoff[e_pre] + r] : L.visbest[e_pre];
-            }
-#endif
             // (c) qh_makenewfacets: for each visible facet in order, for each horizon neighbour in order, a facet (apex first)
             int m = 0;
-            for (int e = lane; e < nvis; e += G) L.visrep[e] = kQhNone;
+            for (int e = lane; e < nvis; e += kWave) L.visrep[e] = kQhNone;
             qh_lds_sync();
             bool gauss = false, notconv = false;
-            for (int base = 0; base < nvis; base += G / 4) {
-                const int ne = min(nvis - base, G / 4);
+            for (int base = 0; base < nvis; base += kWave / 4) {
+                const int ne = min(nvis - base, kWave / 4);
                 const int e = base + (lane >> 2), k = lane & 3;
                 const bool act = (lane >> 2) < ne && k < 3;
                 int g = 0, hi = -1;
@@ -726,10 +670,10 @@ template <typename FID, int G, int TAB> __device__ __forceinline__ int qh_run(co
                     for (int i = 0; i < nhz; ++i) if (L.hzq[i] == g) hi = i;
                 }
                 const bool hz = hi >= 0;
-                const uint64_t hm = S_::ballot(hz);
-                const int j = m + popc64(hm & S_::below());
+                const uint64_t hm = Wf::ballot(hz);
+                const int j = m + popc64(hm & Wf::below());
                 const int add = popc64(hm);
-                if (m + add > TAB) { why = QH_CONE_TOO_LARGE; break; }
+                if (m + add > kQhTab) { why = QH_CONE_TOO_LARGE; break; }
                 if (nfac + m + add > (int)P.fcap) { why = QH_FACETS_FULL; break; }
                 if (hz) {
                     const int vid = L.visq[e];
@@ -759,13 +703,9 @@ template <typename FID, int G, int TAB> __device__ __forceinline__ int qh_run(co
             }
             if (why) return why;
             qh_lds_sync();
-            if (S_::any(gauss)) return QH_GAUSS;
-            if (S_::any(notconv)) return QH_NOT_CONVEX;
+            if (Wf::any(gauss)) return QH_GAUSS;
+            if (Wf::any(notconv)) return QH_NOT_CONVEX;
             if (m < 3) return QH_OPEN_CONE;
-#ifdef MVOSR_QH_PREFETCH
-            double x_pre = 0.0, y_pre = 0.0, z_pre = 0.0;
-            if (lane < S) { x_pre = X[q_pre]; y_pre = Y[q_pre]; z_pre = Z[q_pre]; }
-#endif
             QH_STAMP(2);
             // (d) qh_matchnewfacets: neighbour 1 shares the ridge {apex, b}, neighbour 2 the ridge {apex, a};
             //     qh_sharpnewfacets: the cone's normals in more than one orthant
@@ -773,7 +713,7 @@ template <typename FID, int G, int TAB> __device__ __forceinline__ int qh_run(co
             {
                 bool open = false, diff = false; notconv = false;
                 const int q0 = (L.npl[0][0] > 0 ? 1 : 0) | (L.npl[0][1] > 0 ? 2 : 0) | (L.npl[0][2] > 0 ? 4 : 0);
-                for (int jb = 0; jb < m; jb += G) {
+                for (int jb = 0; jb < m; jb += kWave) {
                     const int j = jb + lane;
                     if (j < m) {
                         const int va = L.nva[j], vb = L.nvb[j];
@@ -795,9 +735,9 @@ template <typename FID, int G, int TAB> __device__ __forceinline__ int qh_run(co
                         if (((L.npl[j][0] > 0 ? 1 : 0) | (L.npl[j][1] > 0 ? 2 : 0) | (L.npl[j][2] > 0 ? 4 : 0)) != q0) diff = true;
                     }
                 }
-                if (S_::any(open)) return QH_OPEN_CONE;
-                if (S_::any(notconv)) return QH_NOT_CONVEX;
-                sharp = S_::any(diff);
+                if (Wf::any(open)) return QH_OPEN_CONE;
+                if (Wf::any(notconv)) return QH_NOT_CONVEX;
+                sharp = Wf::any(diff);
                 qh_lds_sync();
             }
             QH_STAMP(3);
@@ -810,17 +750,11 @@ template <typename FID, int G, int TAB> __device__ __forceinline__ int qh_run(co
                 // a linear scan (qh.findbestnew stays set for the rest of this insertion)
                 bool mode = false, fail_band = false, fail_sharp = false, fail_none = false;
                 int q0 = 0, tgt0 = 0; double d0 = 0.0;
-                for (int base = 0; base < S; base += G) {
+                for (int base = 0; base < S; base += kWave) {
                     const int i = base + lane;
                     const bool valid = i < S;
                     int q = 0, start = 0;
                     double x = 0.0, y = 0.0, z = 0.0;
-#ifdef MVOSR_QH_PREFETCH
-                    if (valid && base == 0) {
-                        q = q_pre; x = x_pre; y = y_pre; z = z_pre;
-                        start = L.visrep[e_pre] == kQhNone ? 0 : L.visrep[e_pre];
-                    } else
-#endif
                     if (valid) {
                         int e = 0;
                         while (e + 1 < nvis && (int)L.viscum[e + 1] <= i) ++e;
@@ -833,7 +767,7 @@ template <typename FID, int G, int TAB> __device__ __forceinline__ int qh_run(co
                     if (valid) R = mode ? qh_scan_cone(L, m, start, x, y, z, K) : qh_walk_cone(L, start, x, y, z, K);
                     if (!mode) {
                         if (valid && R.state == 2) R = qh_scan_cone(L, m, 0, x, y, z, K);       // no best: all cone facets from the first
-                        const uint64_t trig = S_::ballot(valid && R.state == 1);
+                        const uint64_t trig = Wf::ballot(valid && R.state == 1);
                         if (trig) {
                             if (!sharp) fail_sharp = true;
                             const int t = ffs64(trig);
@@ -844,18 +778,18 @@ template <typename FID, int G, int TAB> __device__ __forceinline__ int qh_run(co
                     if (valid && R.state != 0) { if (R.state == 3) fail_band = true; else fail_none = true; }
                     if (valid) {
                         atomicAdd(&L.t_total[R.tgt], 1u);
-                        if (S > G) { TT[i] = (uint16_t)R.tgt; DD[i] = R.d; }
+                        if (S > kWave) { TT[i] = (uint16_t)R.tgt; DD[i] = R.d; }
                     }
                     if (base == 0) { q0 = q; tgt0 = R.tgt; d0 = R.d; }
                 }
-                if (S_::any(fail_band)) return QH_BAND;
+                if (Wf::any(fail_band)) return QH_BAND;
                 if (fail_sharp) return QH_NOT_SHARP;
-                if (S_::any(fail_none)) return QH_ABOVE_NONE;
+                if (Wf::any(fail_none)) return QH_ABOVE_NONE;
                 qh_lds_sync();
-                if (S > G) __threadfence_block();
+                if (S > kWave) __threadfence_block();
                 QH_STAMP(4);
                 // room for the cone's outside sets, then the placement in arrival order
-                for (int jb = 0; jb < m; jb += G) {
+                for (int jb = 0; jb < m; jb += kWave) {
                     const int j = jb + lane;
                     if (j < m) {
                         uint32_t o = atop;
@@ -865,8 +799,8 @@ template <typename FID, int G, int TAB> __device__ __forceinline__ int qh_run(co
                 }
                 atop += (uint32_t)S;
                 qh_lds_sync();
-                if (S > 0 && S <= G) qh_place_chunk<G>(L, arena, S, m, tgt0, q0, d0);
-                else for (int base = 0; base < S; base += G) {
+                if (S > 0 && S <= kWave) qh_place_chunk(L, arena, S, m, tgt0, q0, d0);
+                else for (int base = 0; base < S; base += kWave) {
                     const int i = base + lane;
                     const bool valid = i < S;
                     int q = 0, tgt = 0; double d = 0.0;
@@ -877,7 +811,7 @@ template <typename FID, int G, int TAB> __device__ __forceinline__ int qh_run(co
                         q = r < (int)L.viscnt[e] ? arena[L.visoff[e] + r] : L.visbest[e];
                         tgt = TT[i]; d = DD[i];
                     }
-                    qh_place_chunk<G>(L, arena, min(G, S - base), m, tgt, q, d);
+                    qh_place_chunk(L, arena, min(kWave, S - base), m, tgt, q, d);
                     qh_lds_sync();
                 }
                 qh_lds_sync();
@@ -887,7 +821,7 @@ template <typename FID, int G, int TAB> __device__ __forceinline__ int qh_run(co
             { const int c_ = S == 0 ? 0 : (S <= 64 ? 1 : 2); acc[8 + c_] += t_last - t_part0; acc[11 + c_] += 1; }
 #endif
             // (f) the cone's facet records; the visible facets die
-            for (int jb = 0; jb < m; jb += G) {
+            for (int jb = 0; jb < m; jb += kWave) {
                 const int j = jb + lane;
                 if (j < m) {
                     QhFacet Gf;
@@ -900,7 +834,7 @@ template <typename FID, int G, int TAB> __device__ __forceinline__ int qh_run(co
                     fac[nfac + 1 + j] = Gf;
                 }
             }
-            for (int e = lane; e < nvis; e += G) fac[L.visq[e]].flags |= 4;
+            for (int e = lane; e < nvis; e += kWave) fac[L.visq[e]].flags |= 4;
             nfac += m;
             qh_mem_sync();
             QH_STAMP(6);
@@ -910,13 +844,13 @@ template <typename FID, int G, int TAB> __device__ __forceinline__ int qh_run(co
 #endif
         // ---- 4. SciPy's rows: lower facets in list order; vertices by decreasing vertex id, first two swapped unless top ----
         const int64_t toff = a.tri_off[f];
-        for (int base = 0; base < nfac; base += G) {
+        for (int base = 0; base < nfac; base += kWave) {
             const int id = base + lane < nfac ? pos2id(base + lane) : 0;
             bool row = false; QhFacet Gf;
             if (id) { Gf = fac[id]; row = !(Gf.flags & 4) && !(Gf.flags & 2); }
-            const uint64_t rm = S_::ballot(row);
+            const uint64_t rm = Wf::ballot(row);
             if (row) {
-                int32_t *t = a.tri + 3 * (toff + nrows + popc64(rm & S_::below()));
+                int32_t *t = a.tri + 3 * (toff + nrows + popc64(rm & Wf::below()));
                 const bool top = Gf.flags & 1;
                 t[0] = top ? Gf.p[0] : Gf.p[1]; t[1] = top ? Gf.p[1] : Gf.p[0]; t[2] = Gf.p[2];
             }
@@ -926,16 +860,12 @@ template <typename FID, int G, int TAB> __device__ __forceinline__ int qh_run(co
     return why;
 }
 
-// G = 64 (one frame per wavefront): 119 registers and 9.7 KB of LDS, four wavefronts per SIMD.  (Compiled for five, six and eight
-// — 96 / 80 / 64 registers with spills, the LDS tables halved — the same launch of 4096 frames took 41 / 50 / 66 ms instead of
-// 34: LABNOTES §9.)  G = 32 / 16 (two / four frames per wavefront, 32-entry tables): a frame whose insertion overflows a table goes
-// to the `redo` list, which the G = 64 list kernel walks next.
-template <typename FID, int G, int TAB, bool LIST>
-__global__ __launch_bounds__(64, (G == 16 ? 2 : 4)) void qhull_rows_kernel(const QhArgs a) {
-    __shared__ QhLdsT<FID, TAB> Ls[64 / G];
-    QhLdsT<FID, TAB> &L = Ls[Sg<G>::sub()];
+// One frame per wavefront: 119 registers and 9.7 KB of LDS, four wavefronts per SIMD.  (Compiled for five, six and eight — 96 / 80
+// / 64 registers with spills, the LDS tables halved — the same launch of 4096 frames took 41 / 50 / 66 ms instead of 34: LABNOTES §9.)
+template <typename FID, bool LIST>
+__global__ __launch_bounds__(64, 4) void qhull_rows_kernel(const QhArgs a) {
+    __shared__ __attribute__((aligned(16))) QhLdsT<FID> L;      // (16: the wide LDS accesses to its tables)
     if constexpr (LIST) {
-        static_assert(G == 64, "the list walk is one frame per wavefront");
         // the frames of a list whose length is known on the device only: a persistent grid, one workspace slice per workgroup
         const int64_t todo = (int64_t)a.list[0];
         for (int64_t it = blockIdx.x; it < todo; it += gridDim.x) {
@@ -943,7 +873,7 @@ __global__ __launch_bounds__(64, (G == 16 ? 2 : 4)) void qhull_rows_kernel(const
             if (f < 0 || f >= a.n_frames) continue;
             int nrows = 0;
             __syncthreads();
-            const int why = qh_run<FID, G, TAB>(a, L, f, (int64_t)blockIdx.x, nrows);
+            const int why = qh_run<FID>(a, L, f, (int64_t)blockIdx.x, nrows);
             if (lane_id() == 0) {
                 if (why) { a.tri_cnt[f] = 0; a.status[f] = MVOSR_DT_DEGENERATE | (why << 8); }
                 else a.tri_cnt[f] = nrows;           // (status stays what the first attempt left: 0)
@@ -952,20 +882,14 @@ __global__ __launch_bounds__(64, (G == 16 ? 2 : 4)) void qhull_rows_kernel(const
         }
         return;
     } else {
-        int64_t f = (int64_t)blockIdx.x * (64 / G) + Sg<G>::sub();
+        int64_t f = (int64_t)blockIdx.x;
         if (f >= a.n_frames) return;
-        if (G == 64 && a.launch_order) f = (int64_t)a.launch_order[f];
+        if (a.launch_order) f = (int64_t)a.launch_order[f];
         int nrows = 0;
-        const int why = qh_run<FID, G, TAB>(a, L, f, f, nrows);
-        if (Sg<G>::sl() == 0) {
-            if (G < 64 && a.redo && (why == QH_TOO_MANY_VISIBLE || why == QH_CONE_TOO_LARGE)) {
-                const int k = atomicAdd(&a.redo[0], 1);
-                a.redo[1 + k] = (int32_t)f;
-                a.tri_cnt[f] = 0; a.status[f] = MVOSR_DT_OK;
-            } else {
-                a.tri_cnt[f] = why ? 0 : nrows;
-                a.status[f] = why ? (MVOSR_DT_DEGENERATE | (why << 8)) : MVOSR_DT_OK;
-            }
+        const int why = qh_run<FID>(a, L, f, f, nrows);
+        if (lane_id() == 0) {
+            a.tri_cnt[f] = why ? 0 : nrows;
+            a.status[f] = why ? (MVOSR_DT_DEGENERATE | (why << 8)) : MVOSR_DT_OK;
         }
     }
 }
@@ -986,33 +910,6 @@ __global__ __launch_bounds__(kQhOrderThreads) void qh_order_kernel(const int32_t
     if (tid == 0) { int b = 0; for (int c = 0; c < kQhOrderClasses; ++c) { base[c] = b; b += cnt[c]; } }
     __syncthreads();
     for (int64_t f = tid; f < n_frames; f += kQhOrderThreads) order[atomicAdd(&base[cls(pts_cnt[f])], 1)] = (int32_t)f;
-}
-
-// Lanes per frame of the product launch: 64.  The packed instantiations (two / four frames per wavefront) are measured A/B
-// variants of builds with -DMVOSR_ABLATE (env MVOSR_QH_GROUP = 32 | 16): rows identical, but a packed wavefront's insertion is
-// the LONGEST of its frames' steps (52.7 k clocks for four frames against 27.5 k for one, alone on a SIMD) and 20 KB of LDS
-// leave two wavefronts per SIMD: 113 k sets/s (G = 16), 103 k (G = 32) against 129 k (LABNOTES §9.8).
-// MVOSR_QH_NO_ORDER=1 (diagnostic builds, -DMVOSR_ABLATE): frames in index order, as before round 6
-bool qh_no_order() {
-#ifdef MVOSR_ABLATE
-    static const bool v = [] { const char *e = getenv("MVOSR_QH_NO_ORDER"); return e && e[0] == '1'; }();
-    return v;
-#else
-    return false;
-#endif
-}
-
-int qh_group() {
-#ifdef MVOSR_ABLATE
-    static const int g = [] {
-        const char *e = getenv("MVOSR_QH_GROUP");
-        const int v = e ? atoi(e) : 0;
-        return v == 32 || v == 16 ? v : 64;
-    }();
-    return g;
-#else
-    return 64;
-#endif
 }
 
 }  // namespace
@@ -1038,7 +935,7 @@ static int qh_launch(mvosr_ctx *ctx, int64_t n_frames, const int64_t *pts_off, c
     const bool wide = max_pts > kQhMaxPoints;
     QhArgs a;
     a.n_frames = n_frames; a.pts_off = pts_off; a.pts_cnt = pts_cnt; a.u = u; a.v = v; a.keep = keep; a.tri_off = tri_off; a.tri = tri;
-    a.tri_cnt = tri_cnt; a.n_used = n_used; a.status = status; a.order_out = order_out; a.list = list; a.redo = nullptr;
+    a.tri_cnt = tri_cnt; a.n_used = n_used; a.status = status; a.order_out = order_out; a.list = list;
     a.launch_order = nullptr;
     a.cap_pts = max_pts + 1;
 #ifdef MVOSR_QH_STAMPS
@@ -1049,43 +946,25 @@ static int qh_launch(mvosr_ctx *ctx, int64_t n_frames, const int64_t *pts_off, c
     const QhPlan P = qh_plan(a.cap_pts, wide);
     a.ws_stride = P.total;
     const int64_t slices = list ? (int64_t)(list_blocks < n_frames ? list_blocks : n_frames) : n_frames;
-    const int group = (list || wide) ? 64 : qh_group();
-    const size_t redo_bytes = group < 64 ? (((size_t)n_frames + 1) * sizeof(int32_t) + 255) & ~(size_t)255 : 0;
     // (a launch that holds more frames than the machine holds wavefronts — 16 per CU — and is not a list walk: largest frames first)
-    const bool ordered = !list && group == 64 && n_frames > (int64_t)16 * ctx->n_cu && n_frames < 0x7fffffff && !qh_no_order();
+    const bool ordered = !list && n_frames > (int64_t)16 * ctx->n_cu && n_frames < 0x7fffffff;
     const size_t order_bytes = ordered ? ((size_t)n_frames * sizeof(int32_t) + 255) & ~(size_t)255 : 0;
     void *ws = nullptr;
-    if ((rc = ctx_workspace_bytes(ctx, (size_t)slices * P.total + redo_bytes + order_bytes, &ws))) return rc;
+    if ((rc = ctx_workspace_bytes(ctx, (size_t)slices * P.total + order_bytes, &ws))) return rc;
     a.ws = reinterpret_cast<char *>(ws);
     hipStream_t st = ctx_stream(ctx);
     if (ordered) {
-        int32_t *ord = reinterpret_cast<int32_t *>(a.ws + (size_t)slices * P.total + redo_bytes);
+        int32_t *ord = reinterpret_cast<int32_t *>(a.ws + (size_t)slices * P.total);
         hipLaunchKernelGGL(qh_order_kernel, dim3(1), dim3(kQhOrderThreads), 0, st, pts_cnt, n_frames, max_pts, ord);
         if ((rc = check_launch("qh_order_kernel"))) return rc;
         a.launch_order = ord;
     }
     // (the list walk is an instantiation of its own: the loop around the run cost the product kernel registers — spills in its hot loop)
     if (list) {
-        if (wide) hipLaunchKernelGGL((qhull_rows_kernel<uint32_t, 64, 64, true>), dim3((unsigned)slices), dim3(64), 0, st, a);
-        else hipLaunchKernelGGL((qhull_rows_kernel<uint16_t, 64, 64, true>), dim3((unsigned)slices), dim3(64), 0, st, a);
-    } else if (wide) hipLaunchKernelGGL((qhull_rows_kernel<uint32_t, 64, 64, false>), dim3((unsigned)slices), dim3(64), 0, st, a);
-    else if (group == 64) hipLaunchKernelGGL((qhull_rows_kernel<uint16_t, 64, 64, false>), dim3((unsigned)slices), dim3(64), 0, st, a);
-#ifdef MVOSR_ABLATE
-    else {
-        // several frames per wavefront; the frames that overflowed a 32-entry table, next, one per wavefront
-        a.redo = reinterpret_cast<int32_t *>(a.ws + (size_t)slices * P.total);
-        if (hipMemsetAsync(a.redo, 0, sizeof(int32_t), st) != hipSuccess) return set_error(MVOSR_ERR_HIP, "delaunay_qhull_batch: memset");
-        const int per = 64 / group;
-        const unsigned blocks = (unsigned)((n_frames + per - 1) / per);
-        if (group == 32) hipLaunchKernelGGL((qhull_rows_kernel<uint16_t, 32, 32, false>), dim3(blocks), dim3(64), 0, st, a);
-        else hipLaunchKernelGGL((qhull_rows_kernel<uint16_t, 16, 32, false>), dim3(blocks), dim3(64), 0, st, a);
-        if ((rc = check_launch("qhull_rows_kernel"))) return rc;
-        QhArgs b = a;
-        b.list = a.redo; b.redo = nullptr;
-        const int64_t rb = n_frames < 256 ? n_frames : 256;
-        hipLaunchKernelGGL((qhull_rows_kernel<uint16_t, 64, 64, true>), dim3((unsigned)rb), dim3(64), 0, st, b);
-    }
-#endif
+        if (wide) hipLaunchKernelGGL((qhull_rows_kernel<uint32_t, true>), dim3((unsigned)slices), dim3(64), 0, st, a);
+        else hipLaunchKernelGGL((qhull_rows_kernel<uint16_t, true>), dim3((unsigned)slices), dim3(64), 0, st, a);
+    } else if (wide) hipLaunchKernelGGL((qhull_rows_kernel<uint32_t, false>), dim3((unsigned)slices), dim3(64), 0, st, a);
+    else hipLaunchKernelGGL((qhull_rows_kernel<uint16_t, false>), dim3((unsigned)slices), dim3(64), 0, st, a);
     return check_launch("qhull_rows_kernel");
 }
 

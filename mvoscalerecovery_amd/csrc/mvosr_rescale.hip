@@ -179,10 +179,7 @@ __device__ __forceinline__ void rs_draw3(uint64_t key, int h, int M, const uint1
     v0 = L[i0]; v1 = L[i1]; v2 = L[i2];
 }
 
-#ifndef MVOSR_FLAT_DEV_WAVES
-#define MVOSR_FLAT_DEV_WAVES 16
-#endif
-constexpr int kFlatDevWaves = MVOSR_FLAT_DEV_WAVES;   // the device-resident form holds 96 KB of LDS — one workgroup per CU —, so it brings its own occupancy: 16 wavefronts
+constexpr int kFlatDevWaves = 16;   // the device-resident form holds 96 KB of LDS — one workgroup per CU —, so it brings its own occupancy: 16 wavefronts
 
 template <bool DEV, int WAVES = kRsWaves>
 __global__ __launch_bounds__(WAVES *kWave) void flat_selection_kernel(const FlatArgs a) {

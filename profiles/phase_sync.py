@@ -4,8 +4,8 @@ Equal-sized frames, one frame per workgroup, three workgroups per CU: if the 768
 same time and all sweep at the same time, the phases' times ADD (which is what the ablation of LABNOTES 7 shows) although HBM, LDS and
 VALU could overlap.  s_memtime is one chip-wide 100 MHz counter, so the stamps of a -DMVOSR_STAMPS build place every workgroup's phases
 on one time axis.
-    bash profiles/ab_build.sh stamps "-DMVOSR_STAMPS -DMVOSR_ABLATE" [-DMVOSR_STAGGER=2000]
-    MVOSR_DEBUG_SKIP=16 MVOSR_LIB_PATH=profiles/ab/libmvosr_stamps.so python profiles/phase_sync.py [frames] [features]
+    bash profiles/ab_build.sh stamps -DMVOSR_STAMPS
+    MVOSR_LIB_PATH=profiles/ab/libmvosr_stamps.so python profiles/phase_sync.py [frames] [features]
 Prints, per phase, the mean number of resident workgroups in it and the standard deviation over 1 us bins against the binomial value
 (independent workgroups), the same per CU for the load phase, and the kernel's span."""
 import os, sys

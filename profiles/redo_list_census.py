@@ -1,9 +1,7 @@
 #!/usr/bin/env python3
-"""How many frames of a chunk does the exact pass redo, and which?  (the exact path's tail is the list replay of those frames: 23 ms
-however few).  (1) One chunk through the product kernels alone (MVOSR_WAVES_HOT_ONLY): the frames that come back MVOSR_ST_REDO are the
-ones the kernels themselves put on the list.  (2) With a diagnostic build (profiles/ab_build.sh ablate -DMVOSR_ABLATE; MVOSR_LIB_PATH):
-the list of the chunk's real launch, read back from the context's workspace.   python profiles/redo_list_census.py [frames] [features]"""
-import ctypes as C
+"""How many frames of a chunk does the exact pass redo?  (the exact path's tail is the list replay of those frames: 23 ms
+however few).  One chunk through the product kernels alone (MVOSR_WAVES_HOT_ONLY): the frames that come back MVOSR_ST_REDO are the
+ones the kernels themselves put on the list.   python profiles/redo_list_census.py [frames] [features]"""
 import os
 import sys
 
@@ -25,14 +23,6 @@ redo = int((status == _lib.ST_REDO).sum())
 hist = {int(k): int(v) for k, v in zip(*np.unique(status, return_counts=True))}
 print("%d frames of %d features through the product kernels alone: %d come back MVOSR_ST_REDO (%.2f %%); statuses %s; exact mask adds %d"
       % (F, N, redo, 100.0 * redo / F, hist, int(exact_mask_of(np.full(F, N)).sum())))
-lib = est.engine.ctx.lib
-if hasattr(lib, "mvosr_debug_redo_list"):
-    for lazy in (False, True):
-        st = est._chunk_gpu(f3s, f2s, False, lazy_last=lazy)
-        out = np.zeros(64, dtype=np.int32)
-        rc = lib.mvosr_debug_redo_list(est.engine.ctx.handle, C.c_int64(F), C.c_void_p(out.ctypes.data), 64)
-        est._chunk_gpu_finish(st, f3s, f2s)
-        print("real launch, lazy_last=%s: rc %d, the exact pass's list holds %d frame(s): %s" % (lazy, rc, out[0], out[1:1 + min(int(out[0]), 16)].tolist()))
 import time
 for lazy in (False, True, False, True):
     t = []

@@ -9,7 +9,6 @@ from mvoscalerecovery_amd.engine import DeviceBatch, DeviceOutputs, ScaleEngine
 
 F = int(sys.argv[1]) if len(sys.argv) > 1 else 1536
 N = int(sys.argv[2]) if len(sys.argv) > 2 else 20000
-os.environ["MVOSR_DEBUG_SKIP"] = "16"      # no road-model launch: it would write its histograms over the stamps
 packing.start_pool(None)
 ctx = _lib.default_context(0)
 eng = ScaleEngine(1.75, ctx=ctx)

@@ -31,12 +31,12 @@ def test_library_exports_every_declared_symbol():
 
 
 def test_shipped_library_has_no_ablation_switch():
-    """The ablation hook of the profiling builds (env MVOSR_DEBUG_SKIP: bits that switch sweeps off) exists only under
-    -DMVOSR_ABLATE: the product binary does not even contain the variable's name, nor the stamp hooks."""
+    """The retired ablation switches (environment variables that switched sweeps off or picked packed kernel variants, see
+    LABNOTES "Retired switches") stay out of the product binary: not even their names, nor the diagnostic hooks."""
     from mvoscalerecovery_amd import _lib
     blob = open(_lib.LIB_PATH, "rb").read()
     assert b"MVOSR_DEBUG_SKIP" not in blob
-    assert b"MVOSR_QH_GROUP" not in blob          # (the packed variants of qhull_rows_kernel: A/B builds only)
+    assert b"MVOSR_QH_GROUP" not in blob          # (the packed variants of qhull_rows_kernel)
     nm = subprocess.run(["nm", "-D", "--defined-only", _lib.LIB_PATH], capture_output=True, text=True).stdout
     assert "mvosr_debug" not in nm
 
