@@ -34,7 +34,7 @@
 extern "C" {
 #endif
 
-#define MVOSR_ABI_VERSION 12
+#define MVOSR_ABI_VERSION 13
 
 /* error codes (function return values) */
 enum mvosr_err {
@@ -565,6 +565,54 @@ int mvosr_triangle_batch(mvosr_ctx *ctx, const mvosr_batch *b, double focus, dou
  * plane model4 = (n, d) given on the HOST; px/py/pz/mask are device arrays of n elements. */
 int mvosr_plane_inliers(mvosr_ctx *ctx, int64_t n, const double *px, const double *py, const double *pz, const double *model4,
                         double threshold, uint8_t *mask);
+
+/* ---- dense depth maps from the triangle planes (/root/reference/src/reconstruct.py) ------------------ */
+
+/* The pinhole camera of the reference's PinholeCamera (/root/reference/src/reconstruct.py:21-36 reads these six). */
+typedef struct mvosr_camera { int32_t width, height; double fx, fy, cx, cy; } mvosr_camera;
+
+/* Outputs of mvosr_dense_depth_batch (device pointers; the optional ones may be NULL).  F = b->n_frames, H x W the camera's. */
+typedef struct mvosr_depth_outputs {
+    double  *depth;      /* [F*H*W] row-major per frame; 0 where uncovered                               */
+    int32_t *tri_id;     /* optional [F*H*W]: index of the pixel's row within the frame's rows, -1: none */
+    double  *tri_model;  /* optional [rows, laid out like the rows][4] = (nx, ny, nz, height), n the unit normal */
+    int32_t *covered;    /* optional [F] number of covered pixels                                        */
+    int32_t *status;     /* [F] 0, MVOSR_ST_ERR_SINGULAR, _MASK, _EMPTY                                   */
+} mvosr_depth_outputs;
+
+/*
+ * Reconstruct.triangle_model (/root/reference/src/reconstruct.py:70-90) for every frame: per row of the triangulation
+ * `which_tri` (1: b->tri1*, 2: b->tri2*; offsets and optional row counts read as the other entry points read them, so rows
+ * written by mvosr_delaunay_batch* go in without visiting the host) A = the three vertices' (x, y, z) in row order — RAW, no
+ * remap: reconstruct.py applies none —, n = A^-1.1, height = 1/|n|, n / |n|, both negated when n_y < 0 (:83-85);
+ * tri_model[(tri_off[f] + t)*4 ..] = (nx, ny, nz, height).  `keep` (optional, laid out like the planes) has the meaning it has
+ * for mvosr_delaunay_batch and mvosr_flat_ransac_batch: the rows' ids are ranks among the points with keep[i] >= 0.
+ * status [F]: 0, MVOSR_ST_ERR_SINGULAR (a pivot exactly zero: the reference raises LinAlgError, :78), MVOSR_ST_ERR_MASK (a
+ * vertex id out of range — that row's record is zero —, or more than 2 * feat_cnt[f] rows: none is read), MVOSR_ST_ERR_EMPTY.
+ */
+int mvosr_triangle_model_batch(mvosr_ctx *ctx, const mvosr_batch *b, int which_tri, const int32_t *keep, double *tri_model,
+                               int32_t *status);
+
+/*
+ * Reconstruct.depth_generate (/root/reference/src/reconstruct.py:91-117) for every frame, as a rasteriser: every pixel
+ * (col, row), col = 0..W-1, row = 0..H-1, is located in the triangulation of the frame's pixels (u, v) and gets
+ * height / ((nx*px + ny*py) + nz), p = ((col - cx)/fx, (row - cy)/fy, 1) (:31-36, :104; not clamped: a negative or infinite
+ * depth is kept), 0 where no triangle covers it.  `u`: the pixel columns, laid out like b->v (as the mvosr_delaunay_* entry
+ * points take them).  Point location is the closed, watertight rule: a pixel belongs to a row when its three edge functions,
+ * times the row's orientation sign, are >= 0; an edge is evaluated from its lower to its higher vertex id (negated for the
+ * triangle that sees it the other way), so the two triangles of an edge get exactly opposite values — no pixel inside the
+ * hull is left out by rounding, and only a pixel exactly on an edge is claimed twice —; a pixel claimed by several rows goes
+ * to the LOWEST row index.  Results do not depend on scheduling.  (SciPy's find_simplex, which the reference calls, is a
+ * directed walk: on such tie pixels it may name the other triangle of the edge.)
+ * Two launches on the context's stream: the planes and the rows' screen records (mvosr_triangle_model_batch's kernel), then
+ * one workgroup per band of image rows, which writes every byte of its part of depth (and tri_id) exactly once, 16 bytes per
+ * store.  covered[f] counts the covered pixels.  first_frame / n_launch restrict the call to a sub-range of the batch
+ * (n_launch <= 0: all); the other frames' outputs are not touched.  The context's grow-only workspace holds 212 bytes per
+ * element of the planes (b->total_feat) and 8 bytes per image column and row — nothing else is allocated.  A frame may have at most 2 * feat_cnt[f] rows; an image
+ * row must fit LDS twice (width <= ~20 000), else MVOSR_ERR_TOO_LARGE.
+ */
+int mvosr_dense_depth_batch(mvosr_ctx *ctx, const mvosr_batch *b, int which_tri, const double *u, const int32_t *keep,
+                            const mvosr_camera *cam, const mvosr_depth_outputs *o, int64_t first_frame, int64_t n_launch);
 
 /* ---- optional device stage for the triangulations themselves -------------------- */
 

@@ -13,7 +13,7 @@ import os
 import numpy as np
 
 LIB_PATH = os.environ.get("MVOSR_LIB_PATH") or os.path.join(os.path.dirname(os.path.abspath(__file__)), "libmvosr.so")   # (override: A/B builds in profiles/)
-ABI_VERSION = 12
+ABI_VERSION = 13
 VOTE_REFERENCE, VOTE_FIXED = 0, 1          # mvosr_params.vote_mode
 WAVES_EXACT = 0x100                        # MVOSR_WAVES_EXACT, or-ed into waves_per_frame
 WAVES_EXACT_MASKED = 0x200                 # MVOSR_WAVES_EXACT_MASKED: only the frames of mvosr_batch.exact_mask, in the exact mode
@@ -80,6 +80,16 @@ class RescaleOutputs(C.Structure):
                 ("tri_flags", C.c_void_p), ("hyp_counts", C.c_void_p)]
 
 
+class Camera(C.Structure):
+    """mvosr_camera"""
+    _fields_ = [("width", C.c_int32), ("height", C.c_int32), ("fx", C.c_double), ("fy", C.c_double), ("cx", C.c_double), ("cy", C.c_double)]
+
+
+class DepthOutputs(C.Structure):
+    """mvosr_depth_outputs"""
+    _fields_ = [("depth", C.c_void_p), ("tri_id", C.c_void_p), ("tri_model", C.c_void_p), ("covered", C.c_void_p), ("status", C.c_void_p)]
+
+
 # every symbol include/mvosr.h declares: name -> (restype, argtypes)
 _P = C.c_void_p
 SYMBOLS = {
@@ -142,6 +152,8 @@ SYMBOLS = {
     "mvosr_triangle_batch": (C.c_int, [_P, C.POINTER(Batch), C.c_double, C.c_double, C.c_double, C.c_double, C.c_double,
                                        _P, _P, _P]),
     "mvosr_plane_inliers": (C.c_int, [_P, C.c_int64, _P, _P, _P, _P, C.c_double, _P]),
+    "mvosr_triangle_model_batch": (C.c_int, [_P, C.POINTER(Batch), C.c_int, _P, _P, _P]),
+    "mvosr_dense_depth_batch": (C.c_int, [_P, C.POINTER(Batch), C.c_int, _P, _P, C.POINTER(Camera), C.POINTER(DepthOutputs), C.c_int64, C.c_int64]),
     "mvosr_delaunay_batch": (C.c_int, [_P, C.c_int64, _P, _P, _P, _P, _P, C.c_int, _P, _P, _P, _P, _P]),
     "mvosr_delaunay_batch_seeded": (C.c_int, [_P, C.c_int64, _P, _P, _P, _P, _P, C.c_int, _P, _P, _P, _P, _P, _P, _P, _P]),
     "mvosr_delaunay_batch_ex": (C.c_int, [_P, C.c_int64, _P, _P, _P, _P, _P, C.c_int, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P]),
