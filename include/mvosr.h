@@ -35,6 +35,9 @@ extern "C" {
 #endif
 
 #define MVOSR_ABI_VERSION 13
+/* (mvosr_point_cloud_batch and its three structs were added WITHOUT raising this number: the change is purely additive —
+ * no existing struct or signature moved — and a binding resolves every symbol it declares when it loads the library, so a
+ * library older than its binding fails loudly at load time anyway.) */
 
 /* error codes (function return values) */
 enum mvosr_err {
@@ -613,6 +616,48 @@ int mvosr_triangle_model_batch(mvosr_ctx *ctx, const mvosr_batch *b, int which_t
  */
 int mvosr_dense_depth_batch(mvosr_ctx *ctx, const mvosr_batch *b, int which_tri, const double *u, const int32_t *keep,
                             const mvosr_camera *cam, const mvosr_depth_outputs *o, int64_t first_frame, int64_t n_launch);
+
+/* ---- point clouds from the depth images (/root/reference/src/reconstruct.py:108-115) ---------------- */
+
+enum mvosr_cloud_flags {
+    MVOSR_CLOUD_RANGE = 1,       /* keep only near <= depth * scale <= far (NaN fails) */
+    MVOSR_CLOUD_F32 = 2          /* points and colours as float32: the float64 value, rounded once */
+};
+
+/* Device pointers.  depth [F*H*W] as mvosr_dense_depth_batch writes it; tri_id optional [F*H*W]; image optional uint8 [F*H*W*3],
+ * BGR as cv2 delivers it; scale optional [F]. */
+typedef struct mvosr_cloud_inputs  { const double *depth; const int32_t *tri_id /*opt*/; const uint8_t *image /*opt*/;
+                                     const double *scale /*opt [F]*/; int64_t n_frames; } mvosr_cloud_inputs;
+typedef struct mvosr_cloud_params  { double near, far; int32_t stride; int32_t flags; } mvosr_cloud_params;   /* MVOSR_CLOUD_RANGE, MVOSR_CLOUD_F32 */
+/* points / colors: [capacity][3] float64 (float32 with MVOSR_CLOUD_F32); capacity counts POINTS. */
+typedef struct mvosr_cloud_outputs { void *points; void *colors /*opt, requires image*/; int64_t *frame_off /*[F+1]*/;
+                                     int32_t *overflow /*[1]*/; int64_t capacity; } mvosr_cloud_outputs;
+
+/*
+ * The cloud Reconstruct.depth_generate builds from its depth image (/root/reference/src/reconstruct.py:108-115), for every
+ * frame of a batch of depth images, compacted on the device.  Per frame f the pixels (col, row) are visited in raster order
+ * (row-major, row outer); a pixel QUALIFIES when it is
+ *   covered:      tri_id[f,row,col] >= 0 when tri_id is given, else depth[f,row,col] != 0.0 (NaN counts as covered).  The two
+ *                 rules differ only for a covered pixel whose depth is exactly +-0, which needs an infinite normal: the id
+ *                 image keeps such a pixel, the depth image alone cannot tell it from an uncovered one;
+ *   on the grid:  row % stride == 0 && col % stride == 0 (stride >= 1);
+ *   in range:     only with MVOSR_CLOUD_RANGE: dm >= near && dm <= far, so NaN fails;
+ * where dm = depth * scale[f] — one multiplication, none when scale is NULL.  Its point is (px*dm, py*dm, dm) with
+ * px = (col - cx)/fx, py = (row - cy)/fy (:32, :35, :108; every operation rounded separately), its colour
+ * (image[..,2], image[..,1], image[..,0]) / 255.0 (:110).  Output: array of structures [K][3]; the frames' lists lie back to
+ * back in frame order; frame_off[f] is the index of frame f's first point, frame_off[F] the total — ALWAYS the true counts,
+ * whatever the capacity.  No byte beyond `capacity` points is written; *overflow (optional) = 1 when frame_off[F] > capacity,
+ * else 0: read frame_off[F] and call again with that capacity.  capacity = 0 (points may be NULL) only counts.
+ * With MVOSR_CLOUD_F32 every output value is the float64 value converted once (what .astype(float32) gives).
+ * Three launches on the context's stream (count per segment of 4096 pixels, scan, fill), no atomics on the outputs, no host
+ * synchronisation; results do not depend on scheduling.  The context's grow-only workspace holds 4 bytes per segment and
+ * frame and 8 per image column and row; a call of a shape seen before allocates nothing.
+ * MVOSR_ERR_ARG (before any device work): null ctx / in / cam / p / o / depth / frame_off, stride < 1, colours without an
+ * image, negative capacity or frame count, points NULL with capacity > 0, an empty camera.  n_frames == 0: MVOSR_OK.
+ * MVOSR_ERR_TOO_LARGE: a side above 2^21 pixels, a frame of 2^31 pixels, or 2^31 segments in one call.
+ */
+int mvosr_point_cloud_batch(mvosr_ctx *ctx, const mvosr_cloud_inputs *in, const mvosr_camera *cam,
+                            const mvosr_cloud_params *p, const mvosr_cloud_outputs *o);
 
 /* ---- optional device stage for the triangulations themselves -------------------- */
 

@@ -90,6 +90,24 @@ class DepthOutputs(C.Structure):
     _fields_ = [("depth", C.c_void_p), ("tri_id", C.c_void_p), ("tri_model", C.c_void_p), ("covered", C.c_void_p), ("status", C.c_void_p)]
 
 
+CLOUD_RANGE, CLOUD_F32 = 1, 2             # enum mvosr_cloud_flags
+
+
+class CloudInputs(C.Structure):
+    """mvosr_cloud_inputs"""
+    _fields_ = [("depth", C.c_void_p), ("tri_id", C.c_void_p), ("image", C.c_void_p), ("scale", C.c_void_p), ("n_frames", C.c_int64)]
+
+
+class CloudParams(C.Structure):
+    """mvosr_cloud_params"""
+    _fields_ = [("near", C.c_double), ("far", C.c_double), ("stride", C.c_int32), ("flags", C.c_int32)]
+
+
+class CloudOutputs(C.Structure):
+    """mvosr_cloud_outputs"""
+    _fields_ = [("points", C.c_void_p), ("colors", C.c_void_p), ("frame_off", C.c_void_p), ("overflow", C.c_void_p), ("capacity", C.c_int64)]
+
+
 # every symbol include/mvosr.h declares: name -> (restype, argtypes)
 _P = C.c_void_p
 SYMBOLS = {
@@ -154,6 +172,7 @@ SYMBOLS = {
     "mvosr_plane_inliers": (C.c_int, [_P, C.c_int64, _P, _P, _P, _P, C.c_double, _P]),
     "mvosr_triangle_model_batch": (C.c_int, [_P, C.POINTER(Batch), C.c_int, _P, _P, _P]),
     "mvosr_dense_depth_batch": (C.c_int, [_P, C.POINTER(Batch), C.c_int, _P, _P, C.POINTER(Camera), C.POINTER(DepthOutputs), C.c_int64, C.c_int64]),
+    "mvosr_point_cloud_batch": (C.c_int, [_P, C.POINTER(CloudInputs), C.POINTER(Camera), C.POINTER(CloudParams), C.POINTER(CloudOutputs)]),
     "mvosr_delaunay_batch": (C.c_int, [_P, C.c_int64, _P, _P, _P, _P, _P, C.c_int, _P, _P, _P, _P, _P]),
     "mvosr_delaunay_batch_seeded": (C.c_int, [_P, C.c_int64, _P, _P, _P, _P, _P, C.c_int, _P, _P, _P, _P, _P, _P, _P, _P]),
     "mvosr_delaunay_batch_ex": (C.c_int, [_P, C.c_int64, _P, _P, _P, _P, _P, C.c_int, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P]),

@@ -138,14 +138,6 @@ __global__ __launch_bounds__(kDpBlock) void triangle_model_kernel(const DepthArg
     }
 }
 
-// floor(i / d) and the remainder for 0 <= i < 2^22, d >= 1: a float estimate (off by at most one) and one correction each way
-__device__ __forceinline__ void divmod_small(int i, int d, float rd, int &q, int &r) {
-    q = (int)((float)i * rd);
-    q -= (q * d > i) ? 1 : 0;
-    q += ((q + 1) * d <= i) ? 1 : 0;
-    r = i - q * d;
-}
-
 __global__ __launch_bounds__(kDpBlock) void depth_raster_kernel(const DepthArgs a) {
     extern __shared__ __attribute__((aligned(16))) int tile[];
     __shared__ int s_cov[kDpWaves];

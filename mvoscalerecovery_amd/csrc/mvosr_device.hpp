@@ -30,6 +30,14 @@ __device__ __forceinline__ TriIds load_tri(const int32_t *tri, int t) {
     return r;
 }
 
+// floor(i / d) and the remainder for 0 <= i < 2^22, d >= 1: a float estimate (off by at most one) and one correction each way
+__device__ __forceinline__ void divmod_small(int i, int d, float rd, int &q, int &r) {
+    q = (int)((float)i * rd);
+    q -= (q * d > i) ? 1 : 0;
+    q += ((q + 1) * d <= i) ? 1 : 0;
+    r = i - q * d;
+}
+
 // ---- wave reductions on DPP (no LDS crossbar traffic) -----------------------------------------
 // Four DPP steps (quad xor 1, quad xor 2, row_half_mirror, row_mirror) leave every lane with the
 // sum of its row of 16; the four row sums are then read with v_readlane and added in a fixed
