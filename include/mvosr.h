@@ -450,6 +450,10 @@ int mvosr_flat_selection_batch(mvosr_ctx *ctx, const mvosr_batch *b, double loos
  * stops at the first improvement whose count exceeds goal_fraction * n_points.  Outputs: counts
  * [F][n_hyp] (optional), model [F][4] = unit (n, d) of the best plane with n_y >= 0
  * (/root/reference/src/rescale.py:159-161), best_ic [F], used [F] (hypotheses consumed).
+ * A sample that names a row outside [0, pts_cnt[f]) is treated like one that names a row twice: its
+ * model is NaN, its count 0, it can never be the best, and no point is read for it (one thread per
+ * hypothesis checks its own sample; the loop over the points is unchanged).  A frame with
+ * pts_cnt[f] <= 0 gets a NaN model, best_ic = used = 0 and, where counts is given, counts[f][0..n_hyp) = 0.
  */
 int mvosr_ransac_plane_batch(mvosr_ctx *ctx, int64_t n_frames, const int64_t *pts_off, const int32_t *pts_cnt,
                              const double *px, const double *py, const double *pz, const int32_t *triples, int n_hyp,
@@ -460,7 +464,8 @@ int mvosr_ransac_plane_batch(mvosr_ctx *ctx, int64_t n_frames, const int64_t *pt
  * The 2-D line variant, get_pitch_line_ransac (/root/reference/src/estimate_road_norm.py:60-64) with estimate_line /
  * is_inlier_line (:39-49): same kernel and replay rule; samples are pairs, stored like triples
  * (pairs[f][h][0..1] used, [2] ignored), points are (px, py); model [F][4] = unit (a, b, 0, c) of the best line
- * a x + b y + c = 0 with b >= 0 (the reference's SVD null vector has an arbitrary sign).
+ * a x + b y + c = 0 with b >= 0 (the reference's SVD null vector has an arbitrary sign).  The guard on the sample's
+ * indices covers the pair; the third column is not read at all.
  */
 int mvosr_ransac_line_batch(mvosr_ctx *ctx, int64_t n_frames, const int64_t *pts_off, const int32_t *pts_cnt,
                             const double *px, const double *py, const int32_t *pairs, int n_hyp,
@@ -559,7 +564,9 @@ int mvosr_slew_median_host(const double *raw, const int32_t *apply, int64_t n, d
  * triangle: back-projection with (focus, cx, cy) (:32-33), n = A^-1.1 (:36-37), s = n_y/|n| (:43),
  * h = mean y (:40); keep s > s_min (0.98) and h > 0 (:54-55); mean/std (:57-58); drop values outside
  * mean +- n_sigma (3) std (:60-61); height[f] = mean of the rest (:62).  counts [F][2] = kept / kept
- * after the clip; status [F] = 0, MVOSR_ST_ERR_SINGULAR, _MASK or _EMPTY.
+ * after the clip; status [F] = 0, MVOSR_ST_ERR_SINGULAR, _MASK or _EMPTY.  b->max_feat sizes the launch's LDS: a frame
+ * with feat_cnt[f] > b->max_feat (possible only where the counts live in device memory) is refused with MVOSR_ST_ERR_MASK,
+ * NaN height and counts (0, 0); the frames around it are processed as usual.
  */
 int mvosr_triangle_batch(mvosr_ctx *ctx, const mvosr_batch *b, double focus, double cx, double cy, double s_min,
                          double n_sigma, double *height, int32_t *counts, int32_t *status);

@@ -705,6 +705,7 @@ __global__ __launch_bounds__(kRsBlock) void ransac_plane_kernel(const RansacArgs
     double4 *mods = reinterpret_cast<double4 *>(smem);                    // [H] unit (n, d)
     int *cnts = reinterpret_cast<int *>(mods + H);                        // [H] inlier counts
     if (M <= 0) {
+        if (a.counts) for (int h = tid; h < H; h += kRsBlock) a.counts[(int64_t)f * H + h] = 0;     // no points: no inliers
         if (tid == 0) { a.best_ic[f] = 0; a.used[f] = 0; for (int k = 0; k < 4; ++k) a.model[4 * f + k] = nan(""); }
         return;
     }
@@ -712,7 +713,14 @@ __global__ __launch_bounds__(kRsBlock) void ransac_plane_kernel(const RansacArgs
     // the hypotheses' planes, one thread each
     for (int h = tid; h < H; h += kRsBlock) {
         const int32_t *t = a.triples + ((int64_t)f * H + h) * 3;
-        const int i0 = t[0], i1 = t[1], i2 = t[2];
+        const int i0 = t[0], i1 = t[1], i2 = a.line ? 0 : t[2];
+        // a sample that names a row outside [0, M) is spent like one that names a row twice: NaN model, no inliers, nothing read
+        if ((unsigned)i0 >= (unsigned)M || (unsigned)i1 >= (unsigned)M || (unsigned)i2 >= (unsigned)M) {
+            double4 m; m.x = m.y = m.z = m.w = nan("");
+            mods[h] = m;
+            cnts[h] = 0;
+            continue;
+        }
         double nx, ny, nz, d;
         if (a.line) {
             // the line a x + b y + c = 0 through two points: the null vector of [x y 1] (estimate_road_norm.py:44-46)
@@ -792,6 +800,7 @@ struct TriBatchArgs {
     const double *u, *v, *depth;
     const int64_t *tri_off; const int32_t *tri;
     double focus, cx, cy, s_min, n_sigma;
+    int32_t max_feat;              // what the launch's LDS was sized from
     double *height;                // [F]
     int32_t *counts;               // [F][2]: kept, kept after the clip
     int32_t *status;               // [F]
@@ -807,6 +816,10 @@ __global__ __launch_bounds__(kRsBlock) void triangle_batch_kernel(const TriBatch
     const int tid = threadIdx.x;
     if (n <= 0 || tn <= 0) {
         if (tid == 0) { a.status[f] = MVOSR_ST_ERR_EMPTY; a.height[f] = nan(""); a.counts[2 * f] = a.counts[2 * f + 1] = 0; }
+        return;
+    }
+    if (n > a.max_feat) {                                       // more features than the LDS has room for: refused, LDS untouched
+        if (tid == 0) { a.status[f] = MVOSR_ST_ERR_MASK; a.height[f] = nan(""); a.counts[2 * f] = a.counts[2 * f + 1] = 0; }
         return;
     }
     const uint32_t npad = (uint32_t)((n + 1) & ~1);
@@ -1073,6 +1086,7 @@ int mvosr_triangle_batch(mvosr_ctx *ctx, const mvosr_batch *b, double focus, dou
     TriBatchArgs a;
     a.n_frames = b->n_frames; a.feat_off = b->feat_off; a.feat_cnt = b->feat_cnt; a.u = b->x; a.v = b->v; a.depth = b->z;
     a.tri_off = b->tri1_off; a.tri = b->tri1; a.focus = focus; a.cx = cx; a.cy = cy; a.s_min = s_min; a.n_sigma = n_sigma;
+    a.max_feat = b->max_feat;
     a.height = height; a.counts = counts; a.status = status;
     const size_t lds = 24u * (size_t)((b->max_feat + 1) & ~1) + 8u * 3 * 2 * kRsWaves + 32;
     if ((rc = rs_prepare(triangle_batch_kernel, lds))) return rc;
