@@ -382,6 +382,10 @@ int mvosr_batch_size_hint(const int32_t *feat_cnt_host, int64_t n_frames, mvosr_
  * o->vote_counters (required) and counts[MVOSR_CNT_VALID] (optional).  Used by the per-frame
  * drop-in call and by the batch path when the second triangulation still has to be built on
  * the host from the surviving features.  Only b->feat_*, y, z, v, tri1* are read.
+ * b->max_feat sizes the launch's LDS (and chooses between the LDS-resident and the dense kernel): a frame with
+ * feat_cnt[f] > b->max_feat (possible only where the counts live in device memory) is refused before LDS is touched —
+ * status (where given) MVOSR_ST_ERR_MASK, counts[MVOSR_CNT_VALID] = 0, and every word of the frame's vote_counters slice -1:
+ * a counter >= 0 means "survives" (:166), so whoever reads the slice as `keep` finds no survivor and no stale word.
  */
 int mvosr_outlier_vote_batch(mvosr_ctx *ctx, const mvosr_params *p, const mvosr_batch *b,
                              const mvosr_outputs *o, int waves_per_frame);
@@ -425,7 +429,12 @@ int mvosr_window_median_blocked(mvosr_ctx *ctx, const double *blocks, int64_t n,
  * under the 8x8 triangle potential (graph.py:6-17,134-145) — 24 bits computed once on the host.
  * Reads feat_off/feat_cnt/z/v/tri1_off/tri1 of `b` (no remap: rescale.py:25 sets camera_pitch = 0).
  * total/good: int32 device arrays laid out like z.  status [F] (optional): 0 or MVOSR_ST_ERR_MASK.
+ * b->max_feat sizes the launch's LDS, and a vertex's two tallies are 16 bits each in LDS, where one row may name a vertex up
+ * to three times.  A frame with feat_cnt[f] > b->max_feat (possible only where the counts live in device memory), or with
+ * more than MVOSR_GRAPH_MAX_ROWS rows (no accepted frame can then wrap a tally: 3 * 21845 = 65535), is refused before LDS
+ * is touched: MVOSR_ST_ERR_MASK, and the frame's total and good slices are zero.
  */
+#define MVOSR_GRAPH_MAX_ROWS 21845
 int mvosr_graph_inliers_batch(mvosr_ctx *ctx, const mvosr_batch *b, uint32_t good_bits, int32_t *total, int32_t *good,
                               int32_t *status);
 
@@ -436,6 +445,9 @@ int mvosr_graph_inliers_batch(mvosr_ctx *ctx, const mvosr_batch *b, uint32_t goo
  * heights > height_factor (0.9) * median(heights[bit0]).  tri_height/tri_flags: per triangle of tri2;
  * height_level/n_kept/status: per frame (status 0, MVOSR_ST_ERR_SINGULAR, _MASK or _EMPTY).
  * max_tri: largest triangle count of a frame (sizes LDS; <= 0: 2*max_feat).
+ * b->max_feat and max_tri size the launch's LDS: a frame with feat_cnt[f] > b->max_feat or more rows than max_tri (possible
+ * only where the counts live in device memory) is refused before LDS is touched — status MVOSR_ST_ERR_MASK, height_level
+ * NaN, n_kept 0, its tri_height / tri_flags rows not written.
  */
 int mvosr_flat_selection_batch(mvosr_ctx *ctx, const mvosr_batch *b, double loose_deg, double tight_deg, double height_factor,
                                double *tri_height, uint8_t *tri_flags, double *height_level, int32_t *n_kept, int32_t *status,
@@ -498,6 +510,9 @@ typedef struct mvosr_rescale_params {
  * passed the vote.  Rows: b->tri1 at b->tri1_off[f], b->tri1_cnt[f] of them when tri1_cnt is given (the form
  * mvosr_delaunay_batch writes), else tri1_off[f+1] - tri1_off[f].  A frame whose first triangulation was declined
  * (dt_status[f] != 0, optional) is skipped.
+ * A frame mvosr_graph_inliers_batch refuses (feat_cnt[f] > b->max_feat, more than MVOSR_GRAPH_MAX_ROWS rows) is refused
+ * here too, with what a declined triangulation gets: every keep word of the frame -1, n_valid 0 — the second triangulation
+ * and the flat selection see an empty frame — and status MVOSR_ST_ERR_MASK.
  */
 int mvosr_graph_keep_batch(mvosr_ctx *ctx, const mvosr_batch *b, uint32_t good_bits, int32_t min_valid, const int32_t *dt_status,
                            int32_t *keep, int32_t *n_valid, int32_t *status);
@@ -535,6 +550,9 @@ typedef struct mvosr_rescale_outputs {
  * survivor-numbered VERTEX ids) replaces the draw: a recorded sample sequence of the reference mapped to point ids
  * replays its run whatever the row order.  `frame_ids` (optional, [F]) replaces frame_base + f (re-runs of single frames).
  * The replay rule is mvosr_ransac_plane_batch's.  max_tri: largest row count of a frame (<= 0: 2 * b->max_feat).
+ * b->max_feat (features BEFORE keep) and max_tri size the launch's LDS: a frame with feat_cnt[f] > b->max_feat or more rows
+ * than max_tri is refused before LDS is touched — status MVOSR_ST_ERR_MASK, raw_scale, height_level and model NaN, n_kept,
+ * best_ic and used 0; its tri_height / tri_flags / hyp_counts rows are not written.
  */
 int mvosr_flat_ransac_batch(mvosr_ctx *ctx, const mvosr_batch *b, const int32_t *keep, const mvosr_rescale_params *rp,
                             const int32_t *id_triples, const int64_t *frame_ids, const int32_t *dt_status,

@@ -2218,6 +2218,19 @@ __global__ __launch_bounds__(DW *kWave, (DW == 8 ? 4 : 1)) void scale_frames_til
     }
 }
 
+// The vote alone on a frame larger than the batch header says (max_feat sized this launch's LDS): refused before LDS is carved —
+// every counter of the frame -1 (nobody survives: a triangulation that reads the counters as `keep` builds nothing on them),
+// no survivors counted, MVOSR_ST_ERR_MASK.
+__device__ __forceinline__ bool vote_frame_oversize(const KArgs &a, int64_t f, int n, int64_t off) {
+    if (n <= a.b.max_feat) return false;
+    for (int i = threadIdx.x; i < n; i += blockDim.x) a.o.vote_counters[off + i] = -1;
+    if (threadIdx.x == 0) {
+        if (a.o.counts) a.o.counts[f * MVOSR_N_COUNTS + MVOSR_CNT_VALID] = 0;
+        if (a.o.status) a.o.status[f] = MVOSR_ST_ERR_MASK;
+    }
+    return true;
+}
+
 template <int DW>
 __global__ __launch_bounds__(DW *kWave) void outlier_vote_dense_kernel(const DenseArgs da) {
     extern __shared__ __attribute__((aligned(16))) char smem[];
@@ -2226,6 +2239,7 @@ __global__ __launch_bounds__(DW *kWave) void outlier_vote_dense_kernel(const Den
     const int n = a.b.feat_cnt[f];
     if (n <= 0) { if (threadIdx.x == 0 && a.o.counts) a.o.counts[f * MVOSR_N_COUNTS + MVOSR_CNT_VALID] = 0; return; }
     const int64_t off = a.b.feat_off[f];
+    if (vote_frame_oversize(a, f, n, off)) return;
     const int64_t t1b = a.b.tri1_off[f];
     const int t1n = tri_rows(a.b.tri1_off, a.b.tri1_cnt, f);
     const uint32_t npad = (uint32_t)((n + 1) & ~1);
@@ -2252,6 +2266,7 @@ __global__ __launch_bounds__(WAVES *kWave) void outlier_vote_kernel(const KArgs 
     const int n = a.b.feat_cnt[f];
     if (n <= 0) { if (threadIdx.x == 0 && a.o.counts) a.o.counts[f * MVOSR_N_COUNTS + MVOSR_CNT_VALID] = 0; return; }
     const int64_t off = a.b.feat_off[f];
+    if (vote_frame_oversize(a, f, n, off)) return;
     const int64_t t1b = a.b.tri1_off[f];
     const int t1n = tri_rows(a.b.tri1_off, a.b.tri1_cnt, f);
     const Smem s = carve(smem, n, WAVES);

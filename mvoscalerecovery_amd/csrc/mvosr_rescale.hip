@@ -43,7 +43,14 @@ struct GraphArgs {
     int32_t min_valid;             // rescale.py:133
     int32_t *keep;                 // [like z] 1 passed / 0 failed but the frame stays whole / -1 dropped
     int32_t *n_valid;              // [F] features that passed (null: not wanted)
+    int32_t max_feat;              // what the launch's LDS was sized from
 };
+
+// A vertex's two tallies share one 32-bit LDS word, 16 bits each, and one row may name a vertex up to three times: with at most
+// this many rows no tally can reach 2^16 (3 * 21845 = 65535) whatever the rows say.  (The rows are in global memory: nothing
+// else bounds their number.  A triangulation has fewer than two rows per point, and the LDS holds ~8 000 points.)
+constexpr int kGraphMaxRows = MVOSR_GRAPH_MAX_ROWS;
+static_assert(3 * kGraphMaxRows <= 0xFFFF, "graph_inliers_kernel: a 16-bit tally must hold three times the row count");
 
 template <bool KEEP>
 __global__ __launch_bounds__(kRsBlock) void graph_inliers_kernel(const GraphArgs a) {
@@ -62,6 +69,15 @@ __global__ __launch_bounds__(kRsBlock) void graph_inliers_kernel(const GraphArgs
     const int64_t off = a.feat_off[f];
     const int64_t tb = a.tri_off[f];
     const int tn = a.tri_cnt ? a.tri_cnt[f] : (int)(a.tri_off[f + 1] - tb);
+    if (n > a.max_feat || tn > kGraphMaxRows) {
+        // more features than the LDS has room for, or enough rows for a 16-bit tally to carry into its neighbour: refused, LDS
+        // untouched.  Stage form: no tallies.  Keep form: what a declined triangulation gets — an empty frame downstream.
+        for (int i = threadIdx.x; i < n; i += kRsBlock) {
+            if constexpr (KEEP) a.keep[off + i] = -1; else { a.total[off + i] = 0; a.good[off + i] = 0; }
+        }
+        if (threadIdx.x == 0) { if (a.status) a.status[f] = MVOSR_ST_ERR_MASK; if (KEEP && a.n_valid) a.n_valid[f] = 0; }
+        return;
+    }
     double2 *P = reinterpret_cast<double2 *>(smem);                       // {v, z}
     uint32_t *cnt = reinterpret_cast<uint32_t *>(smem + 16u * (uint32_t)((n + 1) & ~1));
     int *flag = reinterpret_cast<int *>(cnt + n + 4);                     // [0] bad vertex id, [1] features that passed
@@ -136,7 +152,8 @@ struct FlatArgs {
     const int32_t *dt_status;      // [F] non-zero: declined triangulation, frame skipped (null: none)
     const int32_t *id_triples;     // [F][H][3] survivor-numbered vertex ids replacing the draw (null: draw)
     const int64_t *frame_ids;      // [F] sample-sequence counter of the frame (null: frame_base + f)
-    int32_t n_hyp, ransac_min_points, max_tri;
+    int32_t n_hyp, ransac_min_points;
+    int32_t max_feat, max_tri;     // what the launch's LDS was sized from (both forms)
     double threshold, goal_fraction, absolute_reference;
     uint64_t seed; int64_t frame_base;
     double *raw_scale, *model;     // [F], [F][4]
@@ -193,9 +210,11 @@ __global__ __launch_bounds__(WAVES *kWave) void flat_selection_kernel(const Flat
     const int tn = a.tri_cnt ? a.tri_cnt[f] : (int)(a.tri_off[f + 1] - tb);
     const int tid = threadIdx.x, lane = lane_id(), wave = wave_id();
     const bool skip = DEV && a.dt_status && a.dt_status[f] != 0;
-    if (n_all <= 0 || tn <= 0 || skip || (DEV && tn > a.max_tri)) {
+    // more features or rows than the launch's LDS was sized for (the header's max_feat, the call's max_tri): refused, LDS untouched
+    const bool oversize = n_all > a.max_feat || tn > a.max_tri;
+    if (n_all <= 0 || tn <= 0 || skip || oversize) {
         if (tid == 0) {
-            a.status[f] = (DEV && !skip && tn > a.max_tri && n_all > 0) ? MVOSR_ST_ERR_MASK : MVOSR_ST_ERR_EMPTY;
+            a.status[f] = (!skip && oversize && n_all > 0 && tn > 0) ? MVOSR_ST_ERR_MASK : MVOSR_ST_ERR_EMPTY;
             a.height_level[f] = nan(""); a.n_kept[f] = 0;
             if constexpr (DEV) {
                 a.raw_scale[f] = nan(""); a.best_ic[f] = 0; a.used[f] = 0;
@@ -945,7 +964,7 @@ static int launch_graph(mvosr_ctx *ctx, const mvosr_batch *b, GraphArgs &a, bool
     if (rc) return rc;
     g_rs_max_lds = ctx->max_lds_per_block;
     a.n_frames = b->n_frames; a.feat_off = b->feat_off; a.feat_cnt = b->feat_cnt; a.z = b->z; a.v = b->v;
-    a.tri_off = b->tri1_off; a.tri = b->tri1; a.tri_cnt = b->tri1_cnt;
+    a.tri_off = b->tri1_off; a.tri = b->tri1; a.tri_cnt = b->tri1_cnt; a.max_feat = b->max_feat;
     const size_t lds = 16u * (size_t)((b->max_feat + 1) & ~1) + 4u * ((size_t)b->max_feat + 4) + 16;
     if (keep) {
         if ((rc = rs_prepare(graph_inliers_kernel<true>, lds))) return rc;
@@ -987,6 +1006,8 @@ int mvosr_flat_selection_batch(mvosr_ctx *ctx, const mvosr_batch *b, double loos
     a.tri_off = b->tri2_off; a.tri = b->tri2; a.tri_cnt = b->tri2_cnt; a.loose_deg = loose_deg; a.tight_deg = tight_deg; a.height_factor = height_factor;
     a.tri_height = tri_height; a.tri_flags = tri_flags; a.height_level = height_level; a.status = status; a.n_kept = n_kept;
     if (max_tri <= 0) max_tri = 2 * (int64_t)b->max_feat;
+    if (max_tri > INT32_MAX) return set_error(MVOSR_ERR_TOO_LARGE, "flat_selection: max_tri does not fit 32 bits");
+    a.max_feat = b->max_feat; a.max_tri = (int32_t)max_tri;
     size_t lds = 24u * (size_t)((b->max_feat + 1) & ~1);
     if (lds < 4u * 2048) lds = 4u * 2048;                        // (the histogram of the median search reuses the vertex planes)
     lds += 9u * (size_t)max_tri + 32 + 4u * 48 + 16;
@@ -1016,7 +1037,7 @@ int mvosr_flat_ransac_batch(mvosr_ctx *ctx, const mvosr_batch *b, const int32_t 
     a.loose_deg = rp->loose_deg; a.tight_deg = rp->tight_deg; a.height_factor = rp->height_factor;
     a.tri_height = o->tri_height; a.tri_flags = o->tri_flags; a.height_level = o->height_level; a.status = o->status; a.n_kept = o->n_kept;
     a.keep = keep; a.dt_status = dt_status; a.id_triples = id_triples; a.frame_ids = frame_ids;
-    a.n_hyp = rp->n_hyp; a.ransac_min_points = rp->ransac_min_points; a.max_tri = (int32_t)max_tri;
+    a.n_hyp = rp->n_hyp; a.ransac_min_points = rp->ransac_min_points; a.max_feat = b->max_feat; a.max_tri = (int32_t)max_tri;
     a.threshold = rp->threshold; a.goal_fraction = rp->goal_fraction; a.absolute_reference = rp->absolute_reference;
     a.seed = rp->seed; a.frame_base = rp->frame_base;
     a.raw_scale = o->raw_scale; a.model = o->model; a.best_ic = o->best_ic; a.used = o->used; a.hyp_counts = o->hyp_counts;

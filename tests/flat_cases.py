@@ -518,13 +518,36 @@ def _free(bufs):
         v.free()
 
 
-def run_stage(ctx, frames, height_factor=0.9):
-    """mvosr_flat_selection_batch over `frames` (survivors compacted on the host, as its header says) -> one dict per frame."""
+def _alloc(ctx, spec, sentinel):
+    """Output buffers, name -> (shape, dtype).  sentinel None: zeros.  Else every byte is `sentinel` and every buffer has one more
+    leading element than the launch may write: the guard."""
+    o = {}
+    for k, (shape, dt) in spec.items():
+        shape = shape if isinstance(shape, tuple) else (shape,)
+        o[k] = ctx.zeros(shape, dt) if sentinel is None else ctx.empty((shape[0] + 1,) + shape[1:], dt).fill(sentinel)
+    return o
+
+
+def _tails(r, lead):
+    """What lies behind the last element a launch may write, per output (lead: name -> elements it may write)."""
+    return {k: v[lead[k]:] for k, v in r.items()}
+
+
+def all_bytes(a, byte):
+    return bool(np.all(np.ascontiguousarray(a).view(np.uint8) == byte))
+
+
+def run_stage(ctx, frames, height_factor=0.9, max_feat=None, max_tri=None, sentinel=None):
+    """mvosr_flat_selection_batch over `frames` (survivors compacted on the host, as its header says) -> one dict per frame.
+    max_feat / max_tri: what the header and the call state (None: the largest frame's).  sentinel: the outputs are pre-filled
+    with that byte and carry one guard element each; -> (one dict per frame, the guards)."""
     from mvoscalerecovery_amd import _lib
-    b, d, toff, max_tri = _batch(ctx, frames, compact=True)
+    b, d, toff, true_max_tri = _batch(ctx, frames, compact=True)
+    b.max_feat = b.max_feat if max_feat is None else int(max_feat)
+    max_tri = true_max_tri if max_tri is None else int(max_tri)
     F, T = len(frames), max(int(toff[-1]), 1)
-    o = {"tri_height": ctx.zeros(T, np.float64), "tri_flags": ctx.zeros(T, np.uint8), "height_level": ctx.zeros(F, np.float64),
-         "n_kept": ctx.zeros(F, np.int32), "status": ctx.zeros(F, np.int32)}
+    o = _alloc(ctx, {"tri_height": (T, np.float64), "tri_flags": (T, np.uint8), "height_level": (F, np.float64),
+                     "n_kept": (F, np.int32), "status": (F, np.int32)}, sentinel)
     _lib.check(ctx.lib.mvosr_flat_selection_batch(ctx.handle, C.byref(b), LOOSE_DEG, TIGHT_DEG, float(height_factor), o["tri_height"].ptr,
                                                   o["tri_flags"].ptr, o["height_level"].ptr, o["n_kept"].ptr, o["status"].ptr, max_tri),
                "mvosr_flat_selection_batch")
@@ -532,17 +555,23 @@ def run_stage(ctx, frames, height_factor=0.9):
     r = {k: v.download() for k, v in o.items()}
     _free(list(o.values()) + list(d.values()))
     hs, fs = _split(r["tri_height"], toff), _split(r["tri_flags"], toff)
-    return [{"tri_height": hs[i], "tri_flags": fs[i], "height_level": r["height_level"][i], "n_kept": int(r["n_kept"][i]),
-             "status": int(r["status"][i])} for i in range(F)]
+    res = [{"tri_height": hs[i], "tri_flags": fs[i], "height_level": r["height_level"][i], "n_kept": int(r["n_kept"][i]),
+            "status": int(r["status"][i])} for i in range(F)]
+    if sentinel is None:
+        return res
+    return res, _tails(r, {k: (int(toff[-1]) if k.startswith("tri_") else F) for k in r})
 
 
 def run_dev(ctx, frames, height_factor=0.9, n_hyp=100, use_keep=True, id_triples=None, frame_ids=None, seed=5, frame_base=0,
-            min_points=MIN_POINTS, threshold=THRESHOLD, goal=GOAL):
+            min_points=MIN_POINTS, threshold=THRESHOLD, goal=GOAL, max_feat=None, max_tri=None, sentinel=None):
     """mvosr_flat_ransac_batch over `frames` with tri_height, tri_flags and hyp_counts requested.  use_keep: the frames' keep
     words are passed (frames without them: all ones) — else the survivors are compacted on the host and keep is NULL.
-    id_triples: per frame an (n_hyp, 3) array of survivor-numbered vertex ids, or None for the drawn path."""
+    id_triples: per frame an (n_hyp, 3) array of survivor-numbered vertex ids, or None for the drawn path.
+    max_feat / max_tri / sentinel: as run_stage."""
     from mvoscalerecovery_amd import _lib
-    b, d, toff, max_tri = _batch(ctx, frames, compact=not use_keep)
+    b, d, toff, true_max_tri = _batch(ctx, frames, compact=not use_keep)
+    b.max_feat = b.max_feat if max_feat is None else int(max_feat)
+    max_tri = true_max_tri if max_tri is None else int(max_tri)
     F, T, H = len(frames), max(int(toff[-1]), 1), int(n_hyp)
     extra = []
     keep_ptr = tr_ptr = ids_ptr = None
@@ -556,10 +585,11 @@ def run_dev(ctx, frames, height_factor=0.9, n_hyp=100, use_keep=True, id_triples
     if frame_ids is not None:
         extra.append(ctx.to_device(np.asarray(frame_ids, dtype=np.int64)))
         ids_ptr = extra[-1].ptr
-    o = {"raw_scale": ctx.zeros(F, np.float64), "height_level": ctx.zeros(F, np.float64), "model": ctx.zeros((F, 4), np.float64),
-         "best_ic": ctx.zeros(F, np.int32), "used": ctx.zeros(F, np.int32), "n_kept": ctx.zeros(F, np.int32),
-         "status": ctx.zeros(F, np.int32), "tri_height": ctx.zeros(T, np.float64), "tri_flags": ctx.zeros(T, np.uint8),
-         "hyp_counts": ctx.empty((F, H), np.int32).fill(0xFF)}
+    o = _alloc(ctx, {"raw_scale": (F, np.float64), "height_level": (F, np.float64), "model": ((F, 4), np.float64),
+                     "best_ic": (F, np.int32), "used": (F, np.int32), "n_kept": (F, np.int32), "status": (F, np.int32),
+                     "tri_height": (T, np.float64), "tri_flags": (T, np.uint8), "hyp_counts": ((F, H), np.int32)}, sentinel)
+    if sentinel is None:
+        o["hyp_counts"].fill(0xFF)
     ro = _lib.RescaleOutputs(*[o[k].ptr for k in ("raw_scale", "height_level", "model", "best_ic", "used", "n_kept", "status",
                                                    "tri_height", "tri_flags", "hyp_counts")])
     rp = _lib.RescaleParams(0, 10, LOOSE_DEG, TIGHT_DEG, float(height_factor), int(min_points), H, float(threshold), float(goal),
@@ -570,9 +600,12 @@ def run_dev(ctx, frames, height_factor=0.9, n_hyp=100, use_keep=True, id_triples
     r = {k: v.download() for k, v in o.items()}
     _free(list(o.values()) + list(d.values()) + extra)
     hs, fs = _split(r["tri_height"], toff), _split(r["tri_flags"], toff)
-    return [{"tri_height": hs[i], "tri_flags": fs[i], "height_level": r["height_level"][i], "n_kept": int(r["n_kept"][i]),
-             "status": int(r["status"][i]), "raw_scale": r["raw_scale"][i], "model": r["model"][i], "best_ic": int(r["best_ic"][i]),
-             "used": int(r["used"][i]), "hyp_counts": r["hyp_counts"][i]} for i in range(F)]
+    res = [{"tri_height": hs[i], "tri_flags": fs[i], "height_level": r["height_level"][i], "n_kept": int(r["n_kept"][i]),
+            "status": int(r["status"][i]), "raw_scale": r["raw_scale"][i], "model": r["model"][i], "best_ic": int(r["best_ic"][i]),
+            "used": int(r["used"][i]), "hyp_counts": r["hyp_counts"][i]} for i in range(F)]
+    if sentinel is None:
+        return res
+    return res, _tails(r, {k: (int(toff[-1]) if k.startswith("tri_") else F) for k in r})
 
 
 def max_points(ctx):
@@ -627,8 +660,10 @@ def graph_cases():
     return cases
 
 
-def run_graph(ctx, cases, min_valid=10):
-    """mvosr_graph_keep_batch and mvosr_graph_inliers_batch over the cases as one batch -> per case keep, n_valid, total, good."""
+def run_graph(ctx, cases, min_valid=10, max_feat=None, sentinel=None):
+    """mvosr_graph_keep_batch and mvosr_graph_inliers_batch over the cases as one batch -> per case keep, n_valid, total, good and
+    the two calls' status words.  max_feat: what the header states (None: the largest frame's).  sentinel: the outputs are
+    pre-filled with that byte and carry one guard element each; -> (one dict per case, the guards)."""
     from mvoscalerecovery_amd import _lib
     from mvoscalerecovery_amd.rescale import good_bits
     cnt = np.array([len(c["v"]) for c in cases], dtype=np.int32)
@@ -640,16 +675,23 @@ def run_graph(ctx, cases, min_valid=10):
          ctx.to_device(np.array([7 if c["declined"] else 0 for c in cases], dtype=np.int32))]
     b = _lib.Batch()
     b.n_frames, b.feat_off, b.feat_cnt, b.z, b.v, b.x, b.y = len(cases), d[0].ptr, d[1].ptr, d[2].ptr, d[3].ptr, d[2].ptr, d[2].ptr
-    b.tri1_off, b.tri1, b.max_feat, b.total_feat = d[4].ptr, d[5].ptr, int(cnt.max()), int(off[-1])
+    b.tri1_off, b.tri1, b.max_feat, b.total_feat = d[4].ptr, d[5].ptr, int(cnt.max() if max_feat is None else max_feat), int(off[-1])
     N, F = int(off[-1]), len(cases)
-    o = {"keep": ctx.empty(N, np.int32).fill(0x55), "n_valid": ctx.empty(F, np.int32).fill(0x55), "status": ctx.zeros(F, np.int32),
-         "total": ctx.zeros(N, np.int32), "good": ctx.zeros(N, np.int32)}
+    o = _alloc(ctx, {"keep": (N, np.int32), "n_valid": (F, np.int32), "status": (F, np.int32), "total": (N, np.int32), "good": (N, np.int32),
+                     "status_inliers": (F, np.int32)}, sentinel)
+    if sentinel is None:
+        o["keep"].fill(0x55)
+        o["n_valid"].fill(0x55)
     bits = C.c_uint32(good_bits())
     _lib.check(ctx.lib.mvosr_graph_keep_batch(ctx.handle, C.byref(b), bits, int(min_valid), d[6].ptr, o["keep"].ptr, o["n_valid"].ptr,
                                               o["status"].ptr), "mvosr_graph_keep_batch")
-    _lib.check(ctx.lib.mvosr_graph_inliers_batch(ctx.handle, C.byref(b), bits, o["total"].ptr, o["good"].ptr, None), "mvosr_graph_inliers_batch")
+    _lib.check(ctx.lib.mvosr_graph_inliers_batch(ctx.handle, C.byref(b), bits, o["total"].ptr, o["good"].ptr, o["status_inliers"].ptr),
+               "mvosr_graph_inliers_batch")
     ctx.sync()
     r = {k: v.download() for k, v in o.items()}
     _free(list(o.values()) + d)
-    return [{"keep": r["keep"][off[i]:off[i + 1]], "n_valid": int(r["n_valid"][i]), "total": r["total"][off[i]:off[i + 1]],
-             "good": r["good"][off[i]:off[i + 1]]} for i in range(F)]
+    res = [{"keep": r["keep"][off[i]:off[i + 1]], "n_valid": int(r["n_valid"][i]), "total": r["total"][off[i]:off[i + 1]],
+            "good": r["good"][off[i]:off[i + 1]], "status": int(r["status"][i]), "status_inliers": int(r["status_inliers"][i])} for i in range(F)]
+    if sentinel is None:
+        return res
+    return res, _tails(r, {k: (N if k in ("keep", "total", "good") else F) for k in r})
