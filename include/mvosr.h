@@ -558,6 +558,57 @@ int mvosr_flat_ransac_batch(mvosr_ctx *ctx, const mvosr_batch *b, const int32_t 
                             const int32_t *id_triples, const int64_t *frame_ids, const int32_t *dt_status,
                             const mvosr_rescale_outputs *o, int64_t max_tri);
 
+/* ---- GraphGrow: the road region grown over triangle adjacency (/root/reference/src/graph.py:39-107) ---------------- */
+
+typedef struct mvosr_grow_params {
+    double threshold_angle;      /* 8: two neighbours join when their pitch differs by less (graph.py:40,74)             */
+    double seed_deg;             /* -85: a flat seed has pitch below this (graph.py:90)                                  */
+    double level_deg;            /* -80: ... and 1/height below median(1/height[pitch < level_deg]) (graph.py:91)         */
+    double height_factor;        /* 0.4: ... and their 1/height by less than height_factor * median(1/height) (:74,93)    */
+} mvosr_grow_params;
+
+/* outputs of mvosr_region_grow_batch (device pointers; the optional ones may be NULL).  "rows": laid out like tri2. */
+typedef struct mvosr_grow_outputs {
+    uint8_t *region;             /* [rows of tri2] 1 = in the grown region */
+    int32_t *n_region, *n_flat, *status;      /* [F] rows in the region, flat seeds (graph.py:92), status */
+    double  *level, *threshold_height;        /* [F] median(hinv[angle<level_deg]), height_factor*median(hinv) (graph.py:91,93) */
+    int32_t *label;              /* optional [rows] smallest row index of the row's component */
+    int32_t *neighbors;          /* optional [rows][3] row across edge (a,b),(a,c),(b,c); -1: none */
+    double  *tri_height, *tri_angle;          /* optional [rows]: what the from-points form computed */
+} mvosr_grow_outputs;
+
+/*
+ * GraphGrow.process (graph.py:85-107) for every frame, one workgroup each (region_grow_kernel).  Rows: b->tri2 at
+ * b->tri2_off[f], b->tri2_cnt[f] of them when tri2_cnt is given, else tri2_off[f+1] - tri2_off[f]; ids in [0, feat_cnt[f]).
+ *   hinv = 1/heights (:88, an IEEE division);  flat = angle < seed_deg and hinv < median(hinv[angle < level_deg]) (:90-92);
+ *   threshold_height = height_factor * median(hinv) (:93); rows i, j that share an edge (:47-72) are joined iff
+ *   |angle_i - angle_j| < threshold_angle and |hinv_i - hinv_j| < threshold_height, both strict (:73-77).
+ * Medians are np.median's: the mean (a + b) / 2 of the two middle order statistics of an even count, NaN for an empty
+ * subset (then nothing is flat).  A NaN angle is never flat, never joined and outside the first median's subset.
+ * `expend` (:79-83) compares a row with the row it came from, so a proposal is the connected component of its seed in the
+ * joined graph over ALL rows; the reference draws 100 seeds at random and keeps the longest proposal (:97-103).  Declared
+ * rule here: the region is the largest component that holds a flat row; among equally large ones the one with the smallest
+ * row index; region[] marks its rows (the reference's list order is its random walk's).  Nothing flat: all-zero region,
+ * n_region 0 (:95-96).  label[] is the smallest row index of each row's component, whether seeded or not.
+ * Two forms: tri_height_in and tri_angle_in both given ([rows], `process`'s own arguments; x/y/z are not read), or both
+ * NULL: heights and angles are computed from the frame's x/y/z with mvosr_flat_selection_batch's expressions
+ * (/root/reference/src/rescale.py:78-89: n = A^-1.1, height = 1/|n|, angle = asin(-n_y/|n|) * 180/pi) and written to
+ * tri_height / tri_angle when asked for; a zero pivot gives MVOSR_ST_ERR_SINGULAR (rescale.py:79 raises) and an all-zero
+ * region.  Exactly one of the two given: MVOSR_ERR_ARG.
+ * Refused with MVOSR_ST_ERR_MASK, an all-zero region, n_region = n_flat = 0, NaN level / threshold_height, label and
+ * neighbors -1 (what graph.py:59's list(intersect)[0] would pick arbitrarily, or raise on): an edge named by more than two
+ * rows, a row that names a vertex twice, an id outside [0, feat_cnt[f]), a given height that is not finite and positive.
+ * b->max_feat and max_tri (largest row count of a frame; <= 0: 2 * b->max_feat) size the launch's LDS: a frame with
+ * feat_cnt[f] > b->max_feat or more rows than max_tri is refused before LDS is touched — MVOSR_ST_ERR_MASK, level and
+ * threshold_height NaN, n_region and n_flat 0, its per-row outputs not written.  A frame with no rows: MVOSR_ST_ERR_EMPTY,
+ * the same per-frame values.
+ * LDS, with T = max_tri and N = b->max_feat:  16 T + 64 + max(12 T + 4 (N + 2), from-points ? 24 (N rounded up to even) : 0)
+ * (rounded up to 8) + 1152 + 6 T (rounded up to 16) bytes — 144 KB for 3 980 rows of 2 000 points; a launch beyond the
+ * device's limit returns MVOSR_ERR_TOO_LARGE, as does b->max_feat > 65535 or max_tri >= 65535 (16-bit ids in LDS).
+ */
+int mvosr_region_grow_batch(mvosr_ctx *ctx, const mvosr_batch *b, const double *tri_height_in, const double *tri_angle_in,
+                            const mvosr_grow_params *gp, const mvosr_grow_outputs *o, int64_t max_tri);
+
 /*
  * The cross-frame tail of scale_calculation_ransac (rescale.py:169-178) over a run of frames, on the device: the slew
  * limiter — a frame with apply[i] != 0 moves the running scale towards raw[i] by at most `slew` (0.3), any other frame

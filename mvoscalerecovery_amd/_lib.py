@@ -80,6 +80,18 @@ class RescaleOutputs(C.Structure):
                 ("tri_flags", C.c_void_p), ("hyp_counts", C.c_void_p)]
 
 
+class GrowParams(C.Structure):
+    """mvosr_grow_params"""
+    _fields_ = [("threshold_angle", C.c_double), ("seed_deg", C.c_double), ("level_deg", C.c_double), ("height_factor", C.c_double)]
+
+
+class GrowOutputs(C.Structure):
+    """mvosr_grow_outputs"""
+    _fields_ = [("region", C.c_void_p), ("n_region", C.c_void_p), ("n_flat", C.c_void_p), ("status", C.c_void_p), ("level", C.c_void_p),
+                ("threshold_height", C.c_void_p), ("label", C.c_void_p), ("neighbors", C.c_void_p), ("tri_height", C.c_void_p),
+                ("tri_angle", C.c_void_p)]
+
+
 class Camera(C.Structure):
     """mvosr_camera"""
     _fields_ = [("width", C.c_int32), ("height", C.c_int32), ("fx", C.c_double), ("fy", C.c_double), ("cx", C.c_double), ("cy", C.c_double)]
@@ -161,6 +173,7 @@ SYMBOLS = {
     "mvosr_graph_keep_batch": (C.c_int, [_P, C.POINTER(Batch), C.c_uint32, C.c_int32, _P, _P, _P, _P]),
     "mvosr_flat_ransac_batch": (C.c_int, [_P, C.POINTER(Batch), _P, C.POINTER(RescaleParams), _P, _P, _P, C.POINTER(RescaleOutputs),
                                           C.c_int64]),
+    "mvosr_region_grow_batch": (C.c_int, [_P, C.POINTER(Batch), _P, _P, C.POINTER(GrowParams), C.POINTER(GrowOutputs), C.c_int64]),
     "mvosr_slew_median": (C.c_int, [_P, _P, _P, C.c_int64, C.c_double, C.c_double, C.c_int, _P, C.c_int, _P, _P]),
     "mvosr_slew_median_host": (C.c_int, [_P, _P, C.c_int64, C.c_double, C.c_double, C.c_int, _P, C.c_int, _P, _P, _P]),
     "mvosr_ransac_plane_batch": (C.c_int, [_P, C.c_int64, _P, _P, _P, _P, _P, _P, C.c_int, C.c_double, C.c_double,

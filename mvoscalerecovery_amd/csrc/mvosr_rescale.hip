@@ -941,6 +941,325 @@ __global__ __launch_bounds__(256) void plane_inliers_kernel(int64_t n, const dou
     if (i < n) mask[i] = fabs(((px[i] * m0 + py[i] * m1) + pz[i] * m2) + m3) < threshold;
 }
 
+// ---------------------------------------------------------------------------------------------
+// GraphGrow.process, /root/reference/src/graph.py:85-107, with its random loop made deterministic (include/mvosr.h,
+// mvosr_region_grow_batch): rows that share an edge (graph.py:47-72) are joined when their pitch differs by less than
+// threshold_angle and their inverse height by less than height_factor * median(1/heights) (graph.py:73-77,93); `expend`
+// (graph.py:79-83) compares a row with the row it came from, so a proposal is the connected component of its seed in that
+// symmetric graph; the result is the largest component that holds a flat seed (graph.py:90-92,97-103), the one with the
+// smallest row index among equally large ones.
+//
+// One frame per workgroup, five phases:
+//   1  per row 1/height and pitch into LDS — given (PTS = false), or from the frame's points with flat_selection_kernel's
+//      expressions (PTS = true: the vertex planes are staged in the work area) —, the rows checked (ids, repeated vertices);
+//   2  the two medians (graph.py:91,93) by an 8-bit radix select on the bit patterns (1/height > 0: they order like the values);
+//   3  the rows as 16-bit ids and a vertex -> incident rows table (counts, block scan, fill) in the work area;
+//   4  per row and edge the row across it: the incident rows of the edge's lower-degree end that name the other end — two or
+//      more is an edge on more than two rows: refused —, and the join test made at once: three 16-bit joined neighbours per row;
+//   5  labels (smallest row index of the component) by hooking on the label's root and full pointer jumping, repeated until a
+//      round changes nothing — no iteration cap: a strip of T rows has diameter T —; sizes and seed flags at the roots.
+// LDS: [1/height 8 T][pitch 8 T][8 x 8 B][work][32 + 256 words][joined neighbours 6 T], T = max_tri, with
+// work = max(12 T + 4 (max_feat + 2), PTS ? 24 * (max_feat rounded up to even) : 0); the labels and sizes (8 T) take the
+// work area over once the joined neighbours exist.  grow_lds_bytes() is that sum; 3 980 rows of 2 000 points: 144 KB.
+// ---------------------------------------------------------------------------------------------
+struct GrowArgs {
+    int64_t n_frames;
+    const int64_t *feat_off; const int32_t *feat_cnt;
+    const double *x, *y, *z;                 // read by the from-points form only
+    const int64_t *tri_off; const int32_t *tri; const int32_t *tri_cnt;
+    const double *h_in, *ang_in;             // [rows] the given form's heights and pitch (deg)
+    double threshold_angle, seed_deg, level_deg, height_factor;
+    int32_t max_feat, max_tri;               // what the launch's LDS was sized from
+    uint8_t *region;                         // [rows]
+    int32_t *n_region, *n_flat, *status;     // [F]
+    double *level, *threshold_height;        // [F]
+    int32_t *label, *neighbors;              // optional [rows], [rows][3]
+    double *tri_height, *tri_angle;          // optional [rows], from-points form
+};
+
+enum { GM_BAD = 0, GM_SINGULAR = 1, GM_KLEVEL = 2, GM_NFLAT = 3, GM_BIN = 4, GM_RANK = 5, GM_LE = 6 /* [2] */, GM_CHANGED = 8 /* [3] */,
+       GM_WSUM = 16 /* [kRsWaves] */, GM_N = 32 };
+constexpr int kGrowBins = 256;
+constexpr uint16_t kGrowNone = 0xFFFFu;      // "no joined neighbour": rows are numbered below it (the LDS holds a few thousand)
+
+__host__ __device__ inline size_t grow_work_bytes(bool pts, int64_t max_feat, int64_t max_tri) {
+    const size_t table = (12u * (size_t)max_tri + 4u * ((size_t)max_feat + 2) + 7u) & ~(size_t)7;
+    const size_t planes = pts ? 24u * (size_t)((max_feat + 1) & ~(int64_t)1) : 0u;
+    return table > planes ? table : planes;
+}
+__host__ __device__ inline size_t grow_lds_bytes(bool pts, int64_t max_feat, int64_t max_tri) {
+    return 16u * (size_t)max_tri + 64u + grow_work_bytes(pts, max_feat, max_tri) + 4u * (GM_N + kGrowBins) + ((6u * (size_t)max_tri + 15u) & ~(size_t)15);
+}
+
+// np.median of the k rows' 1/height that lie in the subset (SUB: pitch < level_deg; else every row): the lower middle order
+// statistic by eight passes of an 8-bit radix select from the top byte down, the upper one as flat_selection_kernel finds it.
+// `slot` (0 / 1): the call's own pre-set scalars (misc[GM_LE + slot] = 0, ext[slot] = ~0).  Every thread returns the same value.
+template <bool SUB>
+__device__ double grow_median(const unsigned long long *U, const double *Ang, double level_deg, int tn, int k, int *hist, int *misc,
+                              unsigned long long *ext, int slot) {
+    if (k <= 0) return nan("");                                  // np.median of an empty array
+    const int tid = threadIdx.x, lane = lane_id(), wave = wave_id();
+    const int klo = (k - 1) >> 1, khi = k >> 1;
+    unsigned long long prefix = 0ull;
+    int rank = klo;
+    for (int shift = 56; shift >= 0; shift -= 8) {
+        if (tid < kGrowBins) hist[tid] = 0;
+        __syncthreads();
+        for (int t = tid; t < tn; t += kRsBlock) {
+            if (SUB && !(Ang[t] < level_deg)) continue;
+            const unsigned long long u = U[t];
+            if (shift == 56 || (u >> (shift + 8)) == (prefix >> (shift + 8))) atomicAdd(&hist[(int)((u >> shift) & 255ull)], 1);
+        }
+        __syncthreads();
+        if (wave == 0) {                                         // four bins per lane, wave scan: the bin whose cumulative count passes the rank
+            const int b0 = hist[4 * lane], b1 = hist[4 * lane + 1], b2 = hist[4 * lane + 2], b3 = hist[4 * lane + 3];
+            const int mine = (b0 + b1) + (b2 + b3);
+            int incl = mine;
+#pragma unroll
+            for (int o = 1; o < kWave; o <<= 1) { const int up = __shfl_up(incl, o); if (lane >= o) incl += up; }
+            const int excl = incl - mine;
+            if (rank >= excl && rank < incl) {                   // exactly one lane
+                int r = rank - excl, bin = 4 * lane;
+                if (r >= b0) { r -= b0; ++bin; if (r >= b1) { r -= b1; ++bin; if (r >= b2) { r -= b2; ++bin; } } }
+                misc[GM_BIN] = bin; misc[GM_RANK] = r;
+            }
+        }
+        __syncthreads();
+        prefix |= (unsigned long long)misc[GM_BIN] << shift;
+        rank = misc[GM_RANK];
+    }
+    const double vlo = __longlong_as_double((long long)prefix);
+    if (khi == klo) return vlo;
+    // the next order statistic: vlo again if it occurs often enough, else the smallest value above it
+    int le = 0;
+    unsigned long long above = ~0ull;
+    for (int t = tid; t < tn; t += kRsBlock) {
+        if (SUB && !(Ang[t] < level_deg)) continue;
+        const unsigned long long u = U[t];
+        if (u <= prefix) ++le; else above = u < above ? u : above;
+    }
+    le = wave_sum(le);
+#pragma unroll
+    for (int o = 1; o < kWave; o <<= 1) { const unsigned long long other = __shfl_xor(above, o); above = other < above ? other : above; }
+    if (lane == 0) { atomicAdd(&misc[GM_LE + slot], le); atomicMin(&ext[slot], above); }
+    __syncthreads();
+    const double vhi = misc[GM_LE + slot] < khi + 1 ? __longlong_as_double((long long)ext[slot]) : vlo;
+    return (vlo + vhi) / 2.0;
+}
+
+template <bool PTS>
+__global__ __launch_bounds__(kRsBlock) void region_grow_kernel(const GrowArgs a) {
+    extern __shared__ __attribute__((aligned(16))) char smem[];
+    const int64_t f = blockIdx.x;
+    const int n_all = a.feat_cnt[f];
+    const int64_t tb = a.tri_off[f];
+    const int tn = a.tri_cnt ? a.tri_cnt[f] : (int)(a.tri_off[f + 1] - tb);
+    const int tid = threadIdx.x, lane = lane_id(), wave = wave_id();
+    if (tn <= 0 || n_all > a.max_feat || tn > a.max_tri) {
+        // no rows; or more features or rows than the launch's LDS was sized for: refused, LDS untouched, no per-row output written
+        if (tid == 0) {
+            a.status[f] = tn <= 0 ? MVOSR_ST_ERR_EMPTY : MVOSR_ST_ERR_MASK;
+            a.level[f] = nan(""); a.threshold_height[f] = nan(""); a.n_region[f] = 0; a.n_flat[f] = 0;
+        }
+        return;
+    }
+    const int n = max(n_all, 0);
+    const int64_t off = a.feat_off[f];
+    const uint32_t T = (uint32_t)a.max_tri;
+    double *Hi = reinterpret_cast<double *>(smem);                              // 1/height by row
+    const unsigned long long *U = reinterpret_cast<const unsigned long long *>(Hi);
+    double *Ang = Hi + T;                                                       // pitch by row
+    unsigned long long *ext = reinterpret_cast<unsigned long long *>(Ang + T);  // [0], [1] the medians' "smallest above", [2] the best root's key
+    char *work = reinterpret_cast<char *>(ext + 8);
+    int *misc = reinterpret_cast<int *>(work + grow_work_bytes(PTS, a.max_feat, a.max_tri));
+    int *hist = misc + GM_N;
+    uint16_t *NB = reinterpret_cast<uint16_t *>(hist + kGrowBins);              // [T][3] joined neighbours
+    const int32_t *rows = a.tri + 3 * tb;
+    if (tid < GM_N) misc[tid] = 0;
+    if (tid < 3) ext[tid] = tid < 2 ? ~0ull : 0ull;
+    // a frame refused for what its rows or heights say: all-zero region, nothing else
+    auto refuse = [&](int status) {
+        for (int t = tid; t < tn; t += kRsBlock) {
+            a.region[tb + t] = 0;
+            if (a.label) a.label[tb + t] = -1;
+            if (a.neighbors) { int32_t *nb = a.neighbors + 3 * (tb + t); nb[0] = -1; nb[1] = -1; nb[2] = -1; }
+        }
+        if (tid == 0) { a.status[f] = status; a.level[f] = nan(""); a.threshold_height[f] = nan(""); a.n_region[f] = 0; a.n_flat[f] = 0; }
+    };
+    // ---- phase 1: 1/height and pitch of every row, the rows checked
+    if constexpr (PTS) {
+        double *X = reinterpret_cast<double *>(work), *Y = X + ((a.max_feat + 1) & ~1), *Z = Y + ((a.max_feat + 1) & ~1);
+        for (int i = tid; i < n; i += kRsBlock) { X[i] = a.x[off + i]; Y[i] = a.y[off + i]; Z[i] = a.z[off + i]; }
+    }
+    __syncthreads();
+    {
+        int bad = 0, singular = 0, k_level = 0;
+        for (int t = tid; t < tn; t += kRsBlock) {
+            const TriIds q = load_tri(rows, t);
+            const bool in_range = (unsigned)q.a < (unsigned)n && (unsigned)q.b < (unsigned)n && (unsigned)q.c < (unsigned)n;
+            if (!in_range || q.a == q.b || q.a == q.c || q.b == q.c) bad = 1;
+            double h, ang;
+            if constexpr (PTS) {
+                h = nan(""); ang = nan("");
+                if (in_range) {
+                    const double *X = reinterpret_cast<const double *>(work), *Y = X + ((a.max_feat + 1) & ~1), *Z = Y + ((a.max_feat + 1) & ~1);
+                    double nx, ny, nz;
+                    if (!plane_normal(X[q.a], Y[q.a], Z[q.a], X[q.b], Y[q.b], Z[q.b], X[q.c], Y[q.c], Z[q.c], nx, ny, nz)) singular = 1;   // rescale.py:79-80
+                    const double len = sqrt((nx * nx + ny * ny) + nz * nz);                // :81
+                    const double mu = -(ny / len);                                         // :82
+                    h = 1.0 / len;                                                         // :89
+                    ang = asin(mu) * 180.0 / 3.141592653589793;                            // :83
+                }
+                if (a.tri_height) a.tri_height[tb + t] = h;
+                if (a.tri_angle) a.tri_angle[tb + t] = ang;
+            } else {
+                h = a.h_in[tb + t]; ang = a.ang_in[tb + t];
+                if (!(h > 0.0) || h == __longlong_as_double(0x7FF0000000000000ll)) bad = 1;   // non-finite or non-positive: 1/h would not order by its bits
+            }
+            const double hinv = 1.0 / h;                                                   // graph.py:88
+            if (PTS && !(hinv > 0.0)) singular = 1;                                       // (a NaN normal behind non-zero pivots: no height either)
+            Hi[t] = hinv; Ang[t] = ang;
+            k_level += (ang < a.level_deg) ? 1 : 0;                                        // graph.py:91
+        }
+        if (bad) misc[GM_BAD] = 1;
+        if (singular) misc[GM_SINGULAR] = 1;
+        k_level = wave_sum(k_level);
+        if (lane == 0 && k_level) atomicAdd(&misc[GM_KLEVEL], k_level);
+    }
+    __syncthreads();
+    if (misc[GM_BAD]) { refuse(MVOSR_ST_ERR_MASK); return; }
+    if (PTS && misc[GM_SINGULAR]) { refuse(MVOSR_ST_ERR_SINGULAR); return; }
+    // ---- phase 2: the medians (the vertex planes are dead)
+    const double level = grow_median<true>(U, Ang, a.level_deg, tn, misc[GM_KLEVEL], hist, misc, ext, 0);   // graph.py:91
+    const double thr_h = a.height_factor * grow_median<false>(U, Ang, a.level_deg, tn, tn, hist, misc, ext, 1);   // :93
+    // ---- phase 3: the rows in 16 bits, and per vertex its incident rows
+    uint16_t *R16 = reinterpret_cast<uint16_t *>(work);                         // [T][3]
+    uint16_t *It = R16 + 3u * T;                                                // [3 T] incident rows, vertex by vertex
+    int *St = reinterpret_cast<int *>(work + 12u * T);                          // [n + 1] where a vertex's rows start ([n]: 3 tn)
+    for (int v = tid; v <= n; v += kRsBlock) St[v] = 0;
+    __syncthreads();
+    for (int t = tid; t < tn; t += kRsBlock) {
+        const TriIds q = load_tri(rows, t);
+        R16[3 * t] = (uint16_t)q.a; R16[3 * t + 1] = (uint16_t)q.b; R16[3 * t + 2] = (uint16_t)q.c;
+        atomicAdd(&St[q.a], 1); atomicAdd(&St[q.b], 1); atomicAdd(&St[q.c], 1);
+    }
+    __syncthreads();
+    {   // inclusive scan of the counts: a contiguous chunk per thread, wave scan, wave totals through LDS
+        const int cnt = n + 1, chunk = (cnt + kRsBlock - 1) / kRsBlock;
+        const int i0 = tid * chunk, i1 = min(cnt, i0 + chunk);
+        int s = 0;
+        for (int i = i0; i < i1; ++i) s += St[i];
+        int incl = s;
+#pragma unroll
+        for (int o = 1; o < kWave; o <<= 1) { const int up = __shfl_up(incl, o); if (lane >= o) incl += up; }
+        if (lane == kWave - 1) misc[GM_WSUM + wave] = incl;
+        __syncthreads();
+        int run = incl - s;
+#pragma unroll
+        for (int w = 0; w < kRsWaves; ++w) if (w < wave) run += misc[GM_WSUM + w];
+        for (int i = i0; i < i1; ++i) { run += St[i]; St[i] = run; }
+    }
+    __syncthreads();
+    for (int t = tid; t < tn; t += kRsBlock) {
+#pragma unroll
+        for (int e = 0; e < 3; ++e) It[atomicSub(&St[R16[3 * t + e]], 1) - 1] = (uint16_t)t;   // (the ends count down to the starts)
+    }
+    __syncthreads();
+    // ---- phase 4: the row across each edge (graph.py:55-68) and the join test (graph.py:73-77)
+    {
+        int bad = 0;
+        for (int t = tid; t < tn; t += kRsBlock) {
+            const int v[3] = {R16[3 * t], R16[3 * t + 1], R16[3 * t + 2]};
+            const double ht = Hi[t], at = Ang[t];
+#pragma unroll
+            for (int e = 0; e < 3; ++e) {                                        // (a,b), (a,c), (b,c)
+                int p = v[e == 2 ? 1 : 0], q = v[e == 0 ? 1 : 2];
+                if (St[p + 1] - St[p] > St[q + 1] - St[q]) { const int s = p; p = q; q = s; }
+                int found = 0, other = -1;
+                for (int i = St[p], i1 = St[p + 1]; i < i1; ++i) {
+                    const int r = It[i];
+                    if (r == t) continue;
+                    if (R16[3 * r] == q || R16[3 * r + 1] == q || R16[3 * r + 2] == q) { ++found; other = r; }
+                }
+                if (found > 1) bad = 1;                                          // an edge on more than two rows
+                if (found != 1) other = -1;
+                if (a.neighbors) a.neighbors[3 * (tb + t) + e] = other;
+                bool joined = false;
+                if (other >= 0) joined = fabs(at - Ang[other]) < a.threshold_angle && fabs(ht - Hi[other]) < thr_h;
+                NB[3 * t + e] = joined ? (uint16_t)other : kGrowNone;
+            }
+        }
+        if (bad) misc[GM_BAD] = 1;
+    }
+    __syncthreads();
+    if (misc[GM_BAD]) { refuse(MVOSR_ST_ERR_MASK); return; }
+    // ---- phase 5: labels.  A round: every row hooks its label's root (and itself) to the smallest label among its joined
+    // neighbours, then every row jumps to its root; a round in which no row hooked ends the loop: labels are then equal
+    // along every joined edge and are roots, and a label is a row of the component not above any of its rows.
+    int *L = reinterpret_cast<int *>(work);                                     // [T] (the table is dead)
+    int *S = L + T;                                                             // [T] at a root: size, bit 30: holds a flat row
+    volatile int *Lv = L;
+    for (int t = tid; t < tn; t += kRsBlock) { L[t] = t; S[t] = 0; }
+    __syncthreads();
+    for (int it = 0;; ++it) {
+        if (tid == 0) misc[GM_CHANGED + (it + 1) % 3] = 0;                       // (read last two rounds ago)
+        int changed = 0;
+        for (int t = tid; t < tn; t += kRsBlock) {
+            const int l = Lv[t];
+            int m = l;
+#pragma unroll
+            for (int e = 0; e < 3; ++e) { const uint16_t r = NB[3 * t + e]; if (r != kGrowNone) m = min(m, Lv[r]); }
+            if (m < l) { atomicMin(&L[l], m); atomicMin(&L[t], m); changed = 1; }
+        }
+        if (changed) misc[GM_CHANGED + it % 3] = 1;
+        __syncthreads();
+        for (int t = tid; t < tn; t += kRsBlock) {
+            int l = Lv[t];
+            for (;;) { const int up = Lv[l]; if (up == l) break; l = up; }       // (labels only decrease: the chain ends)
+            Lv[t] = l;
+        }
+        __syncthreads();
+        if (!misc[GM_CHANGED + it % 3]) break;
+    }
+    // ---- sizes and seeds at the roots, the largest seeded component (smallest root among equals)
+    {
+        int n_flat = 0;
+        for (int t = tid; t < tn; t += kRsBlock) {
+            const bool flat = Ang[t] < a.seed_deg && Hi[t] < level;              // graph.py:90-92
+            const int l = L[t];
+            atomicAdd(&S[l], 1);
+            if (flat) { atomicOr(&S[l], 1 << 30); ++n_flat; }
+        }
+        n_flat = wave_sum(n_flat);
+        if (lane == 0 && n_flat) atomicAdd(&misc[GM_NFLAT], n_flat);
+    }
+    __syncthreads();
+    {
+        unsigned long long best = 0ull;
+        for (int t = tid; t < tn; t += kRsBlock) {
+            const int s = S[t];
+            if (L[t] == t && (s & (1 << 30))) {
+                const unsigned long long key = ((unsigned long long)(s & ((1 << 30) - 1)) << 32) | (unsigned long long)(0x7FFFFFFF - t);
+                best = key > best ? key : best;
+            }
+        }
+#pragma unroll
+        for (int o = 1; o < kWave; o <<= 1) { const unsigned long long other = __shfl_xor(best, o); best = other > best ? other : best; }
+        if (lane == 0 && best) atomicMax(&ext[2], best);
+    }
+    __syncthreads();
+    const unsigned long long key = ext[2];
+    const int root = key ? 0x7FFFFFFF - (int)(key & 0xFFFFFFFFull) : -1;         // nothing flat: graph.py:95-96
+    for (int t = tid; t < tn; t += kRsBlock) {
+        a.region[tb + t] = L[t] == root ? 1 : 0;
+        if (a.label) a.label[tb + t] = L[t];
+    }
+    if (tid == 0) {
+        a.status[f] = 0; a.level[f] = level; a.threshold_height[f] = thr_h;
+        a.n_region[f] = (int)(key >> 32); a.n_flat[f] = misc[GM_NFLAT];
+    }
+}
+
 static int g_rs_max_lds = 160 * 1024;
 
 template <typename K>
@@ -1047,6 +1366,43 @@ int mvosr_flat_ransac_batch(mvosr_ctx *ctx, const mvosr_batch *b, const int32_t 
     if ((rc = rs_prepare(flat_selection_kernel<true, kFlatDevWaves>, lds))) return rc;
     hipLaunchKernelGGL((flat_selection_kernel<true, kFlatDevWaves>), dim3((unsigned)b->n_frames), dim3(kFlatDevWaves * kWave), lds, ctx_stream(ctx), a);
     return check_launch("flat_selection_kernel<device>");
+}
+
+int mvosr_region_grow_batch(mvosr_ctx *ctx, const mvosr_batch *b, const double *tri_height_in, const double *tri_angle_in,
+                            const mvosr_grow_params *gp, const mvosr_grow_outputs *o, int64_t max_tri) {
+    if (!ctx || !b || !gp || !o) return set_error(MVOSR_ERR_ARG, "region_grow: null argument");
+    if (!o->region || !o->n_region || !o->n_flat || !o->status || !o->level || !o->threshold_height)
+        return set_error(MVOSR_ERR_ARG, "region_grow: a required output is null");
+    if ((tri_height_in == nullptr) != (tri_angle_in == nullptr)) return set_error(MVOSR_ERR_ARG, "region_grow: heights and angles are given together or not at all");
+    const bool pts = tri_height_in == nullptr;
+    if (!b->feat_off || !b->feat_cnt || !b->tri2_off || !b->tri2) return set_error(MVOSR_ERR_ARG, "region_grow: missing feat_off/feat_cnt/tri2");
+    if (pts && (!b->x || !b->y || !b->z)) return set_error(MVOSR_ERR_ARG, "region_grow: the from-points form needs x/y/z");
+    if (b->max_feat < 0) return set_error(MVOSR_ERR_ARG, "region_grow: max_feat < 0");
+    if (b->max_feat > 65535) return set_error(MVOSR_ERR_TOO_LARGE, "region_grow: vertex ids are 16-bit in LDS");
+    if (b->n_frames <= 0) return MVOSR_OK;
+    if (max_tri <= 0) max_tri = 2 * (int64_t)b->max_feat;
+    if (max_tri < 1) max_tri = 1;
+    if (max_tri >= 65535) return set_error(MVOSR_ERR_TOO_LARGE, "region_grow: row numbers are 16-bit in LDS");
+    int rc = ctx_activate(ctx);
+    if (rc) return rc;
+    g_rs_max_lds = ctx->max_lds_per_block;
+    GrowArgs a = {};
+    a.n_frames = b->n_frames; a.feat_off = b->feat_off; a.feat_cnt = b->feat_cnt; a.x = b->x; a.y = b->y; a.z = b->z;
+    a.tri_off = b->tri2_off; a.tri = b->tri2; a.tri_cnt = b->tri2_cnt; a.h_in = tri_height_in; a.ang_in = tri_angle_in;
+    a.threshold_angle = gp->threshold_angle; a.seed_deg = gp->seed_deg; a.level_deg = gp->level_deg; a.height_factor = gp->height_factor;
+    a.max_feat = b->max_feat; a.max_tri = (int32_t)max_tri;
+    a.region = o->region; a.n_region = o->n_region; a.n_flat = o->n_flat; a.status = o->status; a.level = o->level;
+    a.threshold_height = o->threshold_height; a.label = o->label; a.neighbors = o->neighbors;
+    a.tri_height = o->tri_height; a.tri_angle = o->tri_angle;
+    const size_t lds = grow_lds_bytes(pts, b->max_feat, max_tri);
+    if (pts) {
+        if ((rc = rs_prepare(region_grow_kernel<true>, lds))) return rc;
+        hipLaunchKernelGGL(region_grow_kernel<true>, dim3((unsigned)b->n_frames), dim3(kRsBlock), lds, ctx_stream(ctx), a);
+    } else {
+        if ((rc = rs_prepare(region_grow_kernel<false>, lds))) return rc;
+        hipLaunchKernelGGL(region_grow_kernel<false>, dim3((unsigned)b->n_frames), dim3(kRsBlock), lds, ctx_stream(ctx), a);
+    }
+    return check_launch("region_grow_kernel");
 }
 
 int mvosr_slew_median(mvosr_ctx *ctx, const double *raw, const int32_t *apply, int64_t n, double slew, double scale_in,

@@ -48,6 +48,7 @@ import numpy as np
 
 from . import _lib
 from . import constants as K
+from . import graph
 from . import packing
 from . import stream
 from .engine import DeviceBatch, ScaleEngine, frame_tables, pack_upload_native
@@ -91,7 +92,18 @@ class ScaleEstimator(stream.StreamKnobs):
     N_HYP = RANSAC_ITERATIONS
 
     def __init__(self, absolute_reference, window_size=6, device=0, ransac_seed=None, sampler=None,
-                 delaunay_workers=None, verbose=False, triangulation=None, sampling=None):
+                 delaunay_workers=None, verbose=False, triangulation=None, sampling=None, region="threshold"):
+        # region "threshold": the road rows are the reference's two thresholds (rescale.py:94-96); "grow": GraphGrow's region over
+        # the rows' adjacency (graph.py:85-107, the call rescale.py:99 leaves commented out) — on the staged path only, which it
+        # selects (checked first: no device is needed to refuse a combination).
+        if region not in ("threshold", "grow"):
+            raise ValueError("region must be 'threshold' or 'grow'")
+        if region == "grow":
+            if triangulation not in (None, "scipy") or sampling not in (None, "host"):
+                raise ValueError("region='grow' runs on the staged path: triangulation='scipy', sampling='host' (the fused "
+                                 "device-resident kernel keeps the threshold selection)")
+            triangulation, sampling = "scipy", "host"
+        self.region = region
         # reference attributes (rescale.py:24-35)
         self.absolute_reference = absolute_reference
         self.camera_pitch = 0
@@ -136,6 +148,7 @@ class ScaleEstimator(stream.StreamKnobs):
         self.triangulation, self.sampling = triangulation, sampling
         self._seed = int.from_bytes(os.urandom(8), "little") if ransac_seed is None else int(ransac_seed) & ((1 << 64) - 1)
         self._frame_counter = 0                     # frames this estimator has processed: the sample sequence's counter
+        self.grow_threshold_angle = 8               # graph.py:40 (rescale.py:33 builds GraphGrow with its default)
         self.stage_outputs = False                  # device path, per-frame calls: keep masks / rows / flags in self.last
         self.last_declined = 0
 
@@ -184,6 +197,12 @@ class ScaleEstimator(stream.StreamKnobs):
         out = tri_h.download(), tri_f.download(), level.download(), status.download()
         for buf in (tri_h, tri_f, level, nkept, status):
             buf.free()
+        if self.region == "grow":                                                           # rescale.py:99
+            try:
+                self.last_grow = graph.launch(ctx, b, pf2.n_frames, nt, max(max_tri, 1), self.grow_threshold_angle, values=True)
+            finally:
+                db.free()
+            return out
         db.free()
         return out
 
@@ -255,10 +274,18 @@ class ScaleEstimator(stream.StreamKnobs):
                 raise np.linalg.LinAlgError("Singular matrix")                              # :79
             t0, t1 = int(pf2.tri2_off[f]), int(pf2.tri2_off[f + 1])
             fl = tri_f[t0:t1]
-            ids = tris[f][(fl & 4) != 0].reshape(-1)                                          # :101
+            if self.region == "grow":
+                if self.last_grow["status"][f] == K.ST_ERR_MASK:
+                    raise ValueError("region='grow': frame %d has an edge on more than two rows or a row that names a vertex twice" % f)
+                keep = self.last_grow["region"][t0:t1] != 0                                    # :99
+            else:
+                keep = (fl & 4) != 0                                                           # :94-96
+            ids = tris[f][keep].reshape(-1)                                                    # :101
             out.append((low3[f][ids], tri_h[t0:t1][(fl & 1) != 0]))                           # :140,:102
             self.height_level = level[f]                                                    # :92
         self.last = {"valid": valids, "tris2": tris, "height_level": level, "pf2": pf2, "tri_flags": tri_f}
+        if self.region == "grow":
+            self.last["grow"] = self.last_grow
         return out
 
     def feature_selection(self, feature3d, feature2d):
