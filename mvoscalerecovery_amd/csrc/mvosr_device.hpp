@@ -30,6 +30,11 @@ __device__ __forceinline__ TriIds load_tri(const int32_t *tri, int t) {
     return r;
 }
 
+// three ids (a row's vertices, a sample's rows) all in [0, n)
+__device__ __forceinline__ bool ids_in_range(int a, int b, int c, int n) {
+    return (unsigned)a < (unsigned)n && (unsigned)b < (unsigned)n && (unsigned)c < (unsigned)n;
+}
+
 // floor(i / d) and the remainder for 0 <= i < 2^22, d >= 1: a float estimate (off by at most one) and one correction each way
 __device__ __forceinline__ void divmod_small(int i, int d, float rd, int &q, int &r) {
     q = (int)((float)i * rd);
@@ -85,6 +90,24 @@ __device__ __forceinline__ int wave_min(int v) {
     v = min(v, dpp_mov<kDppMirror>(v));
     return min(min(__builtin_amdgcn_readlane(v, 0), __builtin_amdgcn_readlane(v, 16)),
                min(__builtin_amdgcn_readlane(v, 32), __builtin_amdgcn_readlane(v, 48)));
+}
+
+// 64-bit keys (bit patterns of non-negative doubles, packed (size, index) pairs): every lane ends with the wave's smallest / largest
+__device__ __forceinline__ unsigned long long wave_min_u64(unsigned long long v) {
+#pragma unroll
+    for (int o = 1; o < kWave; o <<= 1) { const unsigned long long other = __shfl_xor(v, o); v = other < v ? other : v; }
+    return v;
+}
+__device__ __forceinline__ unsigned long long wave_max_u64(unsigned long long v) {
+#pragma unroll
+    for (int o = 1; o < kWave; o <<= 1) { const unsigned long long other = __shfl_xor(v, o); v = other > v ? other : v; }
+    return v;
+}
+// inclusive scan over the wave's lanes: lane l ends with the sum of lanes 0..l (lane 63: the wave's total)
+__device__ __forceinline__ int wave_scan_incl(int v) {
+#pragma unroll
+    for (int o = 1; o < kWave; o <<= 1) { const int up = __shfl_up(v, o); if (lane_id() >= o) v += up; }
+    return v;
 }
 
 // ---- block reductions over WAVES wavefronts, fixed order => run-to-run bit-identical ---------
@@ -255,6 +278,30 @@ __device__ __forceinline__ bool plane_normal(double a00, double a01, double a02,
     ny = __builtin_fma(-a12, nz, b1) * r1;
     nx = __builtin_fma(-a02, nz, __builtin_fma(-a01, ny, b0)) * r0;
     return ok;
+}
+
+// flat_selection's per-row arithmetic (rescale.py:79-89) on the vertex planes X, Y, Z: with n = A^-1 . 1, mu = -n_y/|n| — the sine
+// of the pitch: the caller compares on it or takes its asin — and the height 1/|n|.  False: a zero pivot.
+__device__ __forceinline__ bool row_height_pitch(const double *X, const double *Y, const double *Z, const TriIds q, double &mu, double &h) {
+    double nx, ny, nz;
+    const bool ok = plane_normal(X[q.a], Y[q.a], Z[q.a], X[q.b], Y[q.b], Z[q.b], X[q.c], Y[q.c], Z[q.c], nx, ny, nz);   // rescale.py:79-80
+    const double len = sqrt((nx * nx + ny * ny) + nz * nz);                          // :81
+    mu = -(ny / len);                                                                // :82
+    h = 1.0 / len;                                                                   // :89
+    return ok;
+}
+
+// The upper middle order statistic of a set of 64-bit patterns, given the lower one, `vlo`: vlo again if it occurs often enough,
+// else the smallest value above it.  Every thread passes the tallies of the members it visited (le: how many are <= vlo, above:
+// the smallest one > vlo, ~0 if none); `le_slot` / `above_slot` are LDS words pre-set to 0 / ~0 that no other call uses.  Holds a
+// barrier: every thread of the workgroup calls it, and every thread returns the same pattern.
+__device__ __forceinline__ unsigned long long next_order_statistic(int le, unsigned long long above, unsigned long long vlo, int khi,
+                                                                   int *le_slot, unsigned long long *above_slot) {
+    le = wave_sum(le);
+    above = wave_min_u64(above);
+    if (lane_id() == 0) { atomicAdd(le_slot, le); atomicMin(above_slot, above); }
+    __syncthreads();
+    return *le_slot < khi + 1 ? *above_slot : vlo;
 }
 
 }  // namespace mvosr

@@ -16,11 +16,12 @@
 #include "../../include/mvosr.h"
 #include "mvosr_device.hpp"
 #include "mvosr_host.hpp"
+#include "mvosr_rescale_plan.hpp"
 
 namespace mvosr {
 
-constexpr int kRsWaves = 8;
 constexpr int kRsBlock = kRsWaves * kWave;
+static_assert(sizeof(double4) == kPlaneBytes && 2 * sizeof(double2) == kPlaneBytes, "a hypothesis' plane in the LDS plans");
 
 // ---------------------------------------------------------------------------------------------
 // GraphChecker.find_inliers: per triangle the edge-order code a*4+b*2+c with
@@ -78,9 +79,10 @@ __global__ __launch_bounds__(kRsBlock) void graph_inliers_kernel(const GraphArgs
         if (threadIdx.x == 0) { if (a.status) a.status[f] = MVOSR_ST_ERR_MASK; if (KEEP && a.n_valid) a.n_valid[f] = 0; }
         return;
     }
-    double2 *P = reinterpret_cast<double2 *>(smem);                       // {v, z}
-    uint32_t *cnt = reinterpret_cast<uint32_t *>(smem + 16u * (uint32_t)((n + 1) & ~1));
-    int *flag = reinterpret_cast<int *>(cnt + n + 4);                     // [0] bad vertex id, [1] features that passed
+    const auto lds = graph_plan<uint32_t>(n);
+    double2 *P = reinterpret_cast<double2 *>(smem + lds.p);               // {v, z}
+    uint32_t *cnt = reinterpret_cast<uint32_t *>(smem + lds.cnt);
+    int *flag = reinterpret_cast<int *>(smem + lds.flag);                 // [0] bad vertex id, [1] features that passed
     const int tid = threadIdx.x;
     if (tid < 2) flag[tid] = 0;
     for (int i = tid; i < n; i += kRsBlock) {
@@ -92,7 +94,7 @@ __global__ __launch_bounds__(kRsBlock) void graph_inliers_kernel(const GraphArgs
     int bad = 0;
     for (int t = tid; t < tn; t += kRsBlock) {
         const TriIds q = load_tri(a.tri + 3 * tb, t);
-        if ((unsigned)q.a >= (unsigned)n || (unsigned)q.b >= (unsigned)n || (unsigned)q.c >= (unsigned)n) { bad = 1; continue; }
+        if (!ids_in_range(q.a, q.b, q.c, n)) { bad = 1; continue; }
         const double2 p0 = P[q.a], p1 = P[q.b], p2 = P[q.c];
         const int ca = (p0.x - p1.x) * (p0.y - p1.y) < 0.0;              // graph.py:125
         const int cb = (p1.x - p2.x) * (p1.y - p2.y) < 0.0;              // graph.py:126
@@ -160,14 +162,10 @@ struct FlatArgs {
     int32_t *best_ic, *used, *hyp_counts;
 };
 
-constexpr int kFlatBins = 2048;         // one histogram pass resolves 11 bits of the candidates' range
 constexpr int kFlatRows = 4;            // triangle rows a thread keeps in flight
 constexpr int kFlatDirect = 64;         // that few candidates left: wavefront 0 ranks them directly
 constexpr int kMaxHyp = 512;
 constexpr int kRansacPPT = 8;           // points per thread per chunk (chunks of 4096 points)
-// misc[] slots of flat_selection_kernel (slots below FM_WSUM are zeroed at the start)
-enum { FM_K = 0, FM_SINGULAR = 1, FM_BADID = 2, FM_KEPT = 3, FM_BIN = 4, FM_RANK = 5, FM_BINCNT = 6, FM_LE = 7, FM_LIST = 8, FM_ND = 9,
-       FM_WSUM = 16 /* [16] per-wave bin totals */, FM_CW = 32 /* [16] per-wave counts of the ordered compactions */, FM_N = 48 };
 
 // The sample sequence of the device-resident RANSAC (include/mvosr.h, mvosr_flat_ransac_batch): splitmix64's finaliser as a
 // counter-based generator.  oracle/rescale_oracle.py restates it.
@@ -223,20 +221,16 @@ __global__ __launch_bounds__(WAVES *kWave) void flat_selection_kernel(const Flat
         }
         return;
     }
-    // LDS: heights and flags of every triangle by row, the scalars, then the vertex planes.  Stage form: the planes are dead
-    // once the normals are done and the histogram of the median search takes their place.  Device-resident form: the planes
-    // live on for the RANSAC, the histogram has its own room, and the heights' room is reused by the point list.
-    const uint32_t npad = (uint32_t)((n_all + 1) & ~1);
-    double *Hh = reinterpret_cast<double *>(smem);               // every triangle's height, by row
+    const auto lds = flat_plan<uint32_t>(DEV, n_all, tn, a.n_hyp);   // (mvosr_rescale_plan.hpp: the layout, and what lives when)
+    double *Hh = reinterpret_cast<double *>(smem + lds.heights);
     unsigned long long *U = reinterpret_cast<unsigned long long *>(Hh);   // (heights are >= 0: the bit patterns order like the values)
-    unsigned long long *ext = U + tn;                            // [2] smallest / largest loose height (bits), [2] scratch
-    int *misc = reinterpret_cast<int *>(ext + 4);                // FM_N scalars
-    double *X = reinterpret_cast<double *>(misc + FM_N);
-    double *Y = X + npad;
-    double *Z = Y + npad;
-    int *hist = DEV ? reinterpret_cast<int *>(Z + npad) : reinterpret_cast<int *>(X);   // kFlatBins bins; later the short candidate list (64-bit)
-    const uint32_t planes = DEV ? 24u * npad + 4u * kFlatBins : (24u * npad > 4u * kFlatBins ? 24u * npad : 4u * kFlatBins);
-    uint8_t *Fl = reinterpret_cast<uint8_t *>(X) + planes;       // every triangle's flags, by row
+    unsigned long long *ext = reinterpret_cast<unsigned long long *>(smem + lds.ext);
+    int *misc = reinterpret_cast<int *>(smem + lds.misc);
+    double *X = reinterpret_cast<double *>(smem + lds.x);
+    double *Y = reinterpret_cast<double *>(smem + lds.y);
+    double *Z = reinterpret_cast<double *>(smem + lds.z);
+    int *hist = reinterpret_cast<int *>(smem + lds.hist);
+    uint8_t *Fl = reinterpret_cast<uint8_t *>(smem + lds.flags);
 #ifdef MVOSR_FS_STAMPS
     unsigned long long st[10];
 #define FS_STAMP(i) st[i] = __builtin_amdgcn_s_memtime()
@@ -323,14 +317,11 @@ __global__ __launch_bounds__(WAVES *kWave) void flat_selection_kernel(const Flat
         int k_mine = 0;
         unsigned long long umin = ~0ull, umax = 0ull;
         auto one_row = [&](const TriIds q, const int t) {
-            if ((unsigned)q.a >= (unsigned)n || (unsigned)q.b >= (unsigned)n || (unsigned)q.c >= (unsigned)n) {
+            if (!ids_in_range(q.a, q.b, q.c, n)) {
                 misc[FM_BADID] = 1; Fl[t] = 0; Hh[t] = nan(""); if (!DEV || a.tri_height) a.tri_height[tb + t] = nan(""); return;
             }
-            double nx, ny, nz;
-            if (!plane_normal(X[q.a], Y[q.a], Z[q.a], X[q.b], Y[q.b], Z[q.b], X[q.c], Y[q.c], Z[q.c], nx, ny, nz)) misc[FM_SINGULAR] = 1;   // rescale.py:79-80
-            const double len = sqrt((nx * nx + ny * ny) + nz * nz);                          // :81
-            const double mu = -(ny / len);                                                   // :82
-            const double h = 1.0 / len;                                                      // :89
+            double mu, h;
+            if (!row_height_pitch(X, Y, Z, q, mu, h)) misc[FM_SINGULAR] = 1;
             // pitch = asin(mu) * 180/pi (:83) is increasing in mu: away from the two thresholds the comparison is
             // made on mu itself, within 1e-12 of one (or for NaN) on the reference's own expression
             bool loose, tight;
@@ -356,11 +347,7 @@ __global__ __launch_bounds__(WAVES *kWave) void flat_selection_kernel(const Flat
             for (int j = 0; j < kFlatRows; ++j) if (t0 + j * BLK < tn) one_row(cur[j], t0 + j * BLK);
         }
         k_mine = wave_sum(k_mine);
-#pragma unroll
-        for (int o = 1; o < kWave; o <<= 1) {
-            const unsigned long long lo = __shfl_xor(umin, o), hi = __shfl_xor(umax, o);
-            umin = lo < umin ? lo : umin; umax = hi > umax ? hi : umax;
-        }
+        umin = wave_min_u64(umin); umax = wave_max_u64(umax);
         if (lane == 0 && k_mine) { atomicAdd(&misc[FM_K], k_mine); atomicMin(&ext[0], umin); atomicMax(&ext[1], umax); }
     }
     __syncthreads();
@@ -394,9 +381,7 @@ __global__ __launch_bounds__(WAVES *kWave) void flat_selection_kernel(const Flat
                 constexpr int BPT = kFlatBins / BLK;                // bins per thread (4 with 512 threads, 2 with 1024)
                 const int b0 = hist[BPT * tid], b1 = BPT > 1 ? hist[BPT * tid + 1] : 0, b2 = BPT > 2 ? hist[BPT * tid + 2] : 0, b3 = BPT > 3 ? hist[BPT * tid + 3] : 0;
                 const int mine = (b0 + b1) + (b2 + b3);
-                int incl = mine;
-#pragma unroll
-                for (int o = 1; o < kWave; o <<= 1) { const int up = __shfl_up(incl, o); if (lane >= o) incl += up; }
+                int incl = wave_scan_incl(mine);
                 if (lane == kWave - 1) misc[FM_WSUM + wave] = incl;
                 __syncthreads();
                 int before = 0;
@@ -441,7 +426,6 @@ __global__ __launch_bounds__(WAVES *kWave) void flat_selection_kernel(const Flat
         const double vlo = __longlong_as_double((long long)vlo_bits);
         double vhi = vlo;
         if (khi != klo) {
-            // the next order statistic: vlo again if it occurs often enough, else the smallest value above it
             int le = 0;
             unsigned long long above = ~0ull;
             #pragma unroll 4
@@ -450,12 +434,7 @@ __global__ __launch_bounds__(WAVES *kWave) void flat_selection_kernel(const Flat
                 const unsigned long long u = U[t];
                 if (u <= vlo_bits) ++le; else above = u < above ? u : above;
             }
-            le = wave_sum(le);
-#pragma unroll
-            for (int o = 1; o < kWave; o <<= 1) { const unsigned long long other = __shfl_xor(above, o); above = other < above ? other : above; }
-            if (lane == 0) { atomicAdd(&misc[FM_LE], le); atomicMin(&ext[2], above); }
-            __syncthreads();
-            if (misc[FM_LE] < khi + 1) vhi = __longlong_as_double((long long)ext[2]);
+            vhi = __longlong_as_double((long long)next_order_statistic(le, above, vlo_bits, khi, &misc[FM_LE], &ext[2]));
         }
         level = a.height_factor * ((klo == khi) ? vlo : (vlo + vhi) / 2.0);
     }
@@ -503,10 +482,10 @@ __global__ __launch_bounds__(WAVES *kWave) void flat_selection_kernel(const Flat
 #pragma unroll
         for (int w = 0; w < WAVES; ++w) { const int cw = misc[FM_CW + w]; K += cw; if (w < wave) base += cw; }
         const int M = 3 * K;                                     // len(point_selected), :140
-        uint16_t *L = reinterpret_cast<uint16_t *>(Hh);          // the point list as vertex ids
+        uint16_t *L = reinterpret_cast<uint16_t *>(smem + lds.list);   // the point list as vertex ids
         const int H = a.n_hyp;
-        double2 *mods = reinterpret_cast<double2 *>(smem + (((uint32_t)(Fl - reinterpret_cast<uint8_t *>(smem)) + (uint32_t)tn + 15u) & ~15u));   // [H][2] unit (n, d) as (nx, ny), (nz, d)
-        int *cnts = reinterpret_cast<int *>(mods + 2 * H);       // [H] inlier counts
+        double2 *mods = reinterpret_cast<double2 *>(smem + lds.mods);  // [H][2] unit (n, d) as (nx, ny), (nz, d)
+        int *cnts = reinterpret_cast<int *>(smem + lds.cnts);          // [H] inlier counts
         const bool bad = misc[FM_BADID] || misc[FM_SINGULAR];
         const bool fit = !bad && M >= a.ransac_min_points;       // :152
         if (fit) {
@@ -553,11 +532,11 @@ __global__ __launch_bounds__(WAVES *kWave) void flat_selection_kernel(const Flat
             // with ballots and popcounts — the points in registers — was two thirds of this kernel's instructions; the first
             // attempt at the multiplicities kept the ballots, bit-sliced, and was slower than the list.)
             FS_STAMP(5);
-            uint32_t *W2 = reinterpret_cast<uint32_t *>(hist);                   // [n / 2 + 1] two 16-bit counts per word
+            uint32_t *W2 = reinterpret_cast<uint32_t *>(smem + lds.w2);          // [n / 2 + 1] two 16-bit counts per word
             uint16_t *Dv = L + ((M + 1) & ~1);                                   // the distinct vertices, behind the list
-            // (the list and the vertices share the heights' 8 bytes per row: 6 per KEPT row + 2 per vertex — they fit unless
+            // (the list and the vertices share the heights' room: 6 bytes per KEPT row + 2 per vertex — they fit unless
             // nearly every row is kept in a frame of a few points; then the list itself is counted, entry by entry)
-            const bool dedup = 2 * ((M + 1) & ~1) + 2 * n <= 8 * tn && n <= 2 * kFlatBins - 2;
+            const bool dedup = 2 * ((M + 1) & ~1) + 2 * n <= (int)lds.heights_bytes && n <= 2 * kFlatBins - 2;
             int n_items = M;
             if (dedup) {
                 for (int v = tid; v < (n + 1) / 2 + 1; v += BLK) W2[v] = 0u;
@@ -573,8 +552,8 @@ __global__ __launch_bounds__(WAVES *kWave) void flat_selection_kernel(const Flat
             // ... and, where they fit the heights' room (28 bytes per distinct vertex: they do unless more than ~1 000 of a frame's
             // vertices lie on kept rows), the vertices' coordinates and multiplicities side by side, in the order of the list of
             // distinct vertices: the counting loop then reads four contiguous arrays instead of gathering by id
-            const bool packed = dedup && n_items <= 2 * BLK && 28 * n_items + 8 <= 8 * tn;
-            double *PX = Hh, *PY = PX + n_items, *PZ = PY + n_items;
+            const bool packed = dedup && n_items <= 2 * BLK && 28 * n_items + 8 <= (int)lds.heights_bytes;
+            double *PX = reinterpret_cast<double *>(smem + lds.packed), *PY = PX + n_items, *PZ = PY + n_items;
             int *PW = reinterpret_cast<int *>(PZ + n_items);
             if (packed) {
                 double gx[2], gy[2], gz[2];
@@ -721,8 +700,9 @@ __global__ __launch_bounds__(kRsBlock) void ransac_plane_kernel(const RansacArgs
     const int64_t off = a.pts_off[f];
     const int H = a.n_hyp;
     const int tid = threadIdx.x, lane = lane_id();
-    double4 *mods = reinterpret_cast<double4 *>(smem);                    // [H] unit (n, d)
-    int *cnts = reinterpret_cast<int *>(mods + H);                        // [H] inlier counts
+    const auto lds = ransac_plan<uint32_t>(H);
+    double4 *mods = reinterpret_cast<double4 *>(smem + lds.mods);         // [H] unit (n, d)
+    int *cnts = reinterpret_cast<int *>(smem + lds.cnts);                 // [H] inlier counts
     if (M <= 0) {
         if (a.counts) for (int h = tid; h < H; h += kRsBlock) a.counts[(int64_t)f * H + h] = 0;     // no points: no inliers
         if (tid == 0) { a.best_ic[f] = 0; a.used[f] = 0; for (int k = 0; k < 4; ++k) a.model[4 * f + k] = nan(""); }
@@ -734,7 +714,7 @@ __global__ __launch_bounds__(kRsBlock) void ransac_plane_kernel(const RansacArgs
         const int32_t *t = a.triples + ((int64_t)f * H + h) * 3;
         const int i0 = t[0], i1 = t[1], i2 = a.line ? 0 : t[2];
         // a sample that names a row outside [0, M) is spent like one that names a row twice: NaN model, no inliers, nothing read
-        if ((unsigned)i0 >= (unsigned)M || (unsigned)i1 >= (unsigned)M || (unsigned)i2 >= (unsigned)M) {
+        if (!ids_in_range(i0, i1, i2, M)) {
             double4 m; m.x = m.y = m.z = m.w = nan("");
             mods[h] = m;
             cnts[h] = 0;
@@ -841,12 +821,12 @@ __global__ __launch_bounds__(kRsBlock) void triangle_batch_kernel(const TriBatch
         if (tid == 0) { a.status[f] = MVOSR_ST_ERR_MASK; a.height[f] = nan(""); a.counts[2 * f] = a.counts[2 * f + 1] = 0; }
         return;
     }
-    const uint32_t npad = (uint32_t)((n + 1) & ~1);
-    double *X = reinterpret_cast<double *>(smem);
-    double *Y = X + npad;
-    double *Z = Y + npad;
-    double *red = Z + npad;                                     // 3 slots x 2*kRsWaves doubles
-    int *flag = reinterpret_cast<int *>(red + 3 * 2 * kRsWaves);
+    const auto lds = tribatch_plan<uint32_t>(n);
+    double *X = reinterpret_cast<double *>(smem + lds.x);
+    double *Y = reinterpret_cast<double *>(smem + lds.y);
+    double *Z = reinterpret_cast<double *>(smem + lds.z);
+    double *red = reinterpret_cast<double *>(smem + lds.red);   // 3 slots x 2*kRsWaves doubles
+    int *flag = reinterpret_cast<int *>(smem + lds.flag);
     if (tid == 0) { flag[0] = 0; flag[1] = 0; }
     for (int i = tid; i < n; i += kRsBlock) {
         const double d = a.depth[off + i];
@@ -858,7 +838,7 @@ __global__ __launch_bounds__(kRsBlock) void triangle_batch_kernel(const TriBatch
     // height of triangle t if it is kept, NaN otherwise
     auto kept_height = [&](int t) -> double {
         const TriIds q = load_tri(a.tri + 3 * tb, t);
-        if ((unsigned)q.a >= (unsigned)n || (unsigned)q.b >= (unsigned)n || (unsigned)q.c >= (unsigned)n) { flag[1] = 1; return nan(""); }
+        if (!ids_in_range(q.a, q.b, q.c, n)) { flag[1] = 1; return nan(""); }
         double nx, ny, nz;
         if (!plane_normal(X[q.a], Y[q.a], Z[q.a], X[q.b], Y[q.b], Z[q.b], X[q.c], Y[q.c], Z[q.c], nx, ny, nz)) flag[0] = 1;   // :36
         const double s = ny / sqrt((nx * nx + ny * ny) + nz * nz);                   // :38-39,:43
@@ -950,17 +930,15 @@ __global__ __launch_bounds__(256) void plane_inliers_kernel(int64_t n, const dou
 // smallest row index among equally large ones.
 //
 // One frame per workgroup, five phases:
-//   1  per row 1/height and pitch into LDS — given (PTS = false), or from the frame's points with flat_selection_kernel's
-//      expressions (PTS = true: the vertex planes are staged in the work area) —, the rows checked (ids, repeated vertices);
+//   1  per row 1/height and pitch into LDS — given (PTS = false), or from the frame's points by flat_selection_kernel's
+//      row_height_pitch (PTS = true: the vertex planes are staged in the work area) —, the rows checked (ids, repeated vertices);
 //   2  the two medians (graph.py:91,93) by an 8-bit radix select on the bit patterns (1/height > 0: they order like the values);
 //   3  the rows as 16-bit ids and a vertex -> incident rows table (counts, block scan, fill) in the work area;
 //   4  per row and edge the row across it: the incident rows of the edge's lower-degree end that name the other end — two or
 //      more is an edge on more than two rows: refused —, and the join test made at once: three 16-bit joined neighbours per row;
 //   5  labels (smallest row index of the component) by hooking on the label's root and full pointer jumping, repeated until a
 //      round changes nothing — no iteration cap: a strip of T rows has diameter T —; sizes and seed flags at the roots.
-// LDS: [1/height 8 T][pitch 8 T][8 x 8 B][work][32 + 256 words][joined neighbours 6 T], T = max_tri, with
-// work = max(12 T + 4 (max_feat + 2), PTS ? 24 * (max_feat rounded up to even) : 0); the labels and sizes (8 T) take the
-// work area over once the joined neighbours exist.  grow_lds_bytes() is that sum; 3 980 rows of 2 000 points: 144 KB.
+// LDS: grow_plan() (mvosr_rescale_plan.hpp), carved at the header's sizes; 3 980 rows of 2 000 points: 144 KB.
 // ---------------------------------------------------------------------------------------------
 struct GrowArgs {
     int64_t n_frames;
@@ -977,22 +955,10 @@ struct GrowArgs {
     double *tri_height, *tri_angle;          // optional [rows], from-points form
 };
 
-enum { GM_BAD = 0, GM_SINGULAR = 1, GM_KLEVEL = 2, GM_NFLAT = 3, GM_BIN = 4, GM_RANK = 5, GM_LE = 6 /* [2] */, GM_CHANGED = 8 /* [3] */,
-       GM_WSUM = 16 /* [kRsWaves] */, GM_N = 32 };
-constexpr int kGrowBins = 256;
 constexpr uint16_t kGrowNone = 0xFFFFu;      // "no joined neighbour": rows are numbered below it (the LDS holds a few thousand)
 
-__host__ __device__ inline size_t grow_work_bytes(bool pts, int64_t max_feat, int64_t max_tri) {
-    const size_t table = (12u * (size_t)max_tri + 4u * ((size_t)max_feat + 2) + 7u) & ~(size_t)7;
-    const size_t planes = pts ? 24u * (size_t)((max_feat + 1) & ~(int64_t)1) : 0u;
-    return table > planes ? table : planes;
-}
-__host__ __device__ inline size_t grow_lds_bytes(bool pts, int64_t max_feat, int64_t max_tri) {
-    return 16u * (size_t)max_tri + 64u + grow_work_bytes(pts, max_feat, max_tri) + 4u * (GM_N + kGrowBins) + ((6u * (size_t)max_tri + 15u) & ~(size_t)15);
-}
-
 // np.median of the k rows' 1/height that lie in the subset (SUB: pitch < level_deg; else every row): the lower middle order
-// statistic by eight passes of an 8-bit radix select from the top byte down, the upper one as flat_selection_kernel finds it.
+// statistic by eight passes of an 8-bit radix select from the top byte down, the upper one by next_order_statistic.
 // `slot` (0 / 1): the call's own pre-set scalars (misc[GM_LE + slot] = 0, ext[slot] = ~0).  Every thread returns the same value.
 template <bool SUB>
 __device__ double grow_median(const unsigned long long *U, const double *Ang, double level_deg, int tn, int k, int *hist, int *misc,
@@ -1014,9 +980,7 @@ __device__ double grow_median(const unsigned long long *U, const double *Ang, do
         if (wave == 0) {                                         // four bins per lane, wave scan: the bin whose cumulative count passes the rank
             const int b0 = hist[4 * lane], b1 = hist[4 * lane + 1], b2 = hist[4 * lane + 2], b3 = hist[4 * lane + 3];
             const int mine = (b0 + b1) + (b2 + b3);
-            int incl = mine;
-#pragma unroll
-            for (int o = 1; o < kWave; o <<= 1) { const int up = __shfl_up(incl, o); if (lane >= o) incl += up; }
+            const int incl = wave_scan_incl(mine);
             const int excl = incl - mine;
             if (rank >= excl && rank < incl) {                   // exactly one lane
                 int r = rank - excl, bin = 4 * lane;
@@ -1030,7 +994,6 @@ __device__ double grow_median(const unsigned long long *U, const double *Ang, do
     }
     const double vlo = __longlong_as_double((long long)prefix);
     if (khi == klo) return vlo;
-    // the next order statistic: vlo again if it occurs often enough, else the smallest value above it
     int le = 0;
     unsigned long long above = ~0ull;
     for (int t = tid; t < tn; t += kRsBlock) {
@@ -1038,12 +1001,7 @@ __device__ double grow_median(const unsigned long long *U, const double *Ang, do
         const unsigned long long u = U[t];
         if (u <= prefix) ++le; else above = u < above ? u : above;
     }
-    le = wave_sum(le);
-#pragma unroll
-    for (int o = 1; o < kWave; o <<= 1) { const unsigned long long other = __shfl_xor(above, o); above = other < above ? other : above; }
-    if (lane == 0) { atomicAdd(&misc[GM_LE + slot], le); atomicMin(&ext[slot], above); }
-    __syncthreads();
-    const double vhi = misc[GM_LE + slot] < khi + 1 ? __longlong_as_double((long long)ext[slot]) : vlo;
+    const double vhi = __longlong_as_double((long long)next_order_statistic(le, above, prefix, khi, &misc[GM_LE + slot], &ext[slot]));
     return (vlo + vhi) / 2.0;
 }
 
@@ -1066,14 +1024,15 @@ __global__ __launch_bounds__(kRsBlock) void region_grow_kernel(const GrowArgs a)
     const int n = max(n_all, 0);
     const int64_t off = a.feat_off[f];
     const uint32_t T = (uint32_t)a.max_tri;
-    double *Hi = reinterpret_cast<double *>(smem);                              // 1/height by row
+    const auto lds = grow_plan<uint32_t>(PTS, a.max_feat, a.max_tri);      // (mvosr_rescale_plan.hpp: the layout, and what lives when)
+    double *Hi = reinterpret_cast<double *>(smem + lds.hinv);                   // 1/height by row
     const unsigned long long *U = reinterpret_cast<const unsigned long long *>(Hi);
-    double *Ang = Hi + T;                                                       // pitch by row
-    unsigned long long *ext = reinterpret_cast<unsigned long long *>(Ang + T);  // [0], [1] the medians' "smallest above", [2] the best root's key
-    char *work = reinterpret_cast<char *>(ext + 8);
-    int *misc = reinterpret_cast<int *>(work + grow_work_bytes(PTS, a.max_feat, a.max_tri));
-    int *hist = misc + GM_N;
-    uint16_t *NB = reinterpret_cast<uint16_t *>(hist + kGrowBins);              // [T][3] joined neighbours
+    double *Ang = reinterpret_cast<double *>(smem + lds.ang);                   // pitch by row
+    unsigned long long *ext = reinterpret_cast<unsigned long long *>(smem + lds.ext);   // [0], [1] the medians' "smallest above", [2] the best root's key
+    int *misc = reinterpret_cast<int *>(smem + lds.misc);
+    int *hist = reinterpret_cast<int *>(smem + lds.hist);
+    uint16_t *NB = reinterpret_cast<uint16_t *>(smem + lds.nb);                 // [T][3] joined neighbours
+    double *X = reinterpret_cast<double *>(smem + lds.x), *Y = reinterpret_cast<double *>(smem + lds.y), *Z = reinterpret_cast<double *>(smem + lds.z);   // (PTS, phase 1)
     const int32_t *rows = a.tri + 3 * tb;
     if (tid < GM_N) misc[tid] = 0;
     if (tid < 3) ext[tid] = tid < 2 ? ~0ull : 0ull;
@@ -1088,7 +1047,6 @@ __global__ __launch_bounds__(kRsBlock) void region_grow_kernel(const GrowArgs a)
     };
     // ---- phase 1: 1/height and pitch of every row, the rows checked
     if constexpr (PTS) {
-        double *X = reinterpret_cast<double *>(work), *Y = X + ((a.max_feat + 1) & ~1), *Z = Y + ((a.max_feat + 1) & ~1);
         for (int i = tid; i < n; i += kRsBlock) { X[i] = a.x[off + i]; Y[i] = a.y[off + i]; Z[i] = a.z[off + i]; }
     }
     __syncthreads();
@@ -1096,19 +1054,15 @@ __global__ __launch_bounds__(kRsBlock) void region_grow_kernel(const GrowArgs a)
         int bad = 0, singular = 0, k_level = 0;
         for (int t = tid; t < tn; t += kRsBlock) {
             const TriIds q = load_tri(rows, t);
-            const bool in_range = (unsigned)q.a < (unsigned)n && (unsigned)q.b < (unsigned)n && (unsigned)q.c < (unsigned)n;
+            const bool in_range = ids_in_range(q.a, q.b, q.c, n);
             if (!in_range || q.a == q.b || q.a == q.c || q.b == q.c) bad = 1;
             double h, ang;
             if constexpr (PTS) {
                 h = nan(""); ang = nan("");
                 if (in_range) {
-                    const double *X = reinterpret_cast<const double *>(work), *Y = X + ((a.max_feat + 1) & ~1), *Z = Y + ((a.max_feat + 1) & ~1);
-                    double nx, ny, nz;
-                    if (!plane_normal(X[q.a], Y[q.a], Z[q.a], X[q.b], Y[q.b], Z[q.b], X[q.c], Y[q.c], Z[q.c], nx, ny, nz)) singular = 1;   // rescale.py:79-80
-                    const double len = sqrt((nx * nx + ny * ny) + nz * nz);                // :81
-                    const double mu = -(ny / len);                                         // :82
-                    h = 1.0 / len;                                                         // :89
-                    ang = asin(mu) * 180.0 / 3.141592653589793;                            // :83
+                    double mu;
+                    if (!row_height_pitch(X, Y, Z, q, mu, h)) singular = 1;
+                    ang = asin(mu) * 180.0 / 3.141592653589793;                            // rescale.py:83
                 }
                 if (a.tri_height) a.tri_height[tb + t] = h;
                 if (a.tri_angle) a.tri_angle[tb + t] = ang;
@@ -1133,9 +1087,9 @@ __global__ __launch_bounds__(kRsBlock) void region_grow_kernel(const GrowArgs a)
     const double level = grow_median<true>(U, Ang, a.level_deg, tn, misc[GM_KLEVEL], hist, misc, ext, 0);   // graph.py:91
     const double thr_h = a.height_factor * grow_median<false>(U, Ang, a.level_deg, tn, tn, hist, misc, ext, 1);   // :93
     // ---- phase 3: the rows in 16 bits, and per vertex its incident rows
-    uint16_t *R16 = reinterpret_cast<uint16_t *>(work);                         // [T][3]
-    uint16_t *It = R16 + 3u * T;                                                // [3 T] incident rows, vertex by vertex
-    int *St = reinterpret_cast<int *>(work + 12u * T);                          // [n + 1] where a vertex's rows start ([n]: 3 tn)
+    uint16_t *R16 = reinterpret_cast<uint16_t *>(smem + lds.r16);               // [T][3]
+    uint16_t *It = reinterpret_cast<uint16_t *>(smem + lds.inc);                // [3 T] incident rows, vertex by vertex
+    int *St = reinterpret_cast<int *>(smem + lds.start);                        // [n + 1] where a vertex's rows start ([n]: 3 tn)
     for (int v = tid; v <= n; v += kRsBlock) St[v] = 0;
     __syncthreads();
     for (int t = tid; t < tn; t += kRsBlock) {
@@ -1149,9 +1103,7 @@ __global__ __launch_bounds__(kRsBlock) void region_grow_kernel(const GrowArgs a)
         const int i0 = tid * chunk, i1 = min(cnt, i0 + chunk);
         int s = 0;
         for (int i = i0; i < i1; ++i) s += St[i];
-        int incl = s;
-#pragma unroll
-        for (int o = 1; o < kWave; o <<= 1) { const int up = __shfl_up(incl, o); if (lane >= o) incl += up; }
+        const int incl = wave_scan_incl(s);
         if (lane == kWave - 1) misc[GM_WSUM + wave] = incl;
         __syncthreads();
         int run = incl - s;
@@ -1196,7 +1148,7 @@ __global__ __launch_bounds__(kRsBlock) void region_grow_kernel(const GrowArgs a)
     // ---- phase 5: labels.  A round: every row hooks its label's root (and itself) to the smallest label among its joined
     // neighbours, then every row jumps to its root; a round in which no row hooked ends the loop: labels are then equal
     // along every joined edge and are roots, and a label is a row of the component not above any of its rows.
-    int *L = reinterpret_cast<int *>(work);                                     // [T] (the table is dead)
+    int *L = reinterpret_cast<int *>(smem + lds.label);                         // [T] (the table is dead)
     int *S = L + T;                                                             // [T] at a root: size, bit 30: holds a flat row
     volatile int *Lv = L;
     for (int t = tid; t < tn; t += kRsBlock) { L[t] = t; S[t] = 0; }
@@ -1243,8 +1195,7 @@ __global__ __launch_bounds__(kRsBlock) void region_grow_kernel(const GrowArgs a)
                 best = key > best ? key : best;
             }
         }
-#pragma unroll
-        for (int o = 1; o < kWave; o <<= 1) { const unsigned long long other = __shfl_xor(best, o); best = other > best ? other : best; }
+        best = wave_max_u64(best);
         if (lane == 0 && best) atomicMax(&ext[2], best);
     }
     __syncthreads();
@@ -1260,14 +1211,22 @@ __global__ __launch_bounds__(kRsBlock) void region_grow_kernel(const GrowArgs a)
     }
 }
 
-static int g_rs_max_lds = 160 * 1024;
-
-template <typename K>
-static int rs_prepare(K kernel, size_t lds) {
-    if ((int64_t)lds > (int64_t)g_rs_max_lds) return set_error(MVOSR_ERR_TOO_LARGE, "frame needs %zu B of LDS (> %d) in the rescale-variant kernels", lds, g_rs_max_lds);
-    hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void *>(kernel), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-    if (e != hipSuccess) return set_hip_error("hipFuncSetAttribute(MaxDynamicSharedMemorySize)", e);
-    return MVOSR_OK;
+// One launch of a frame-per-workgroup kernel on the context's device and stream, with `lds` bytes of dynamic LDS (its plan's
+// total).  `lds` is checked against the context's limit and the kernel's own limit raised to it — except for a kernel whose plan
+// stays below the 64 KB every kernel may have (raise_limit = false).
+template <typename Args>
+static int rs_launch(mvosr_ctx *ctx, void (*kernel)(Args), const char *name, int64_t n_frames, int block, size_t lds, const Args &a,
+                     bool raise_limit = true) {
+    int rc = ctx_activate(ctx);
+    if (rc) return rc;
+    if (raise_limit) {
+        if ((int64_t)lds > (int64_t)ctx->max_lds_per_block)
+            return set_error(MVOSR_ERR_TOO_LARGE, "frame needs %zu B of LDS (> %d) in the rescale-variant kernels", lds, ctx->max_lds_per_block);
+        hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void *>(kernel), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
+        if (e != hipSuccess) return set_hip_error("hipFuncSetAttribute(MaxDynamicSharedMemorySize)", e);
+    }
+    hipLaunchKernelGGL(kernel, dim3((unsigned)n_frames), dim3((unsigned)block), lds, ctx_stream(ctx), a);
+    return check_launch(name);
 }
 
 }  // namespace mvosr
@@ -1279,20 +1238,10 @@ extern "C" {
 static int launch_graph(mvosr_ctx *ctx, const mvosr_batch *b, GraphArgs &a, bool keep) {
     if (!b->feat_off || !b->feat_cnt || !b->z || !b->v || !b->tri1_off || !b->tri1) return set_error(MVOSR_ERR_ARG, "graph_inliers: missing z/v/tri1");
     if (b->n_frames <= 0) return MVOSR_OK;
-    int rc = ctx_activate(ctx);
-    if (rc) return rc;
-    g_rs_max_lds = ctx->max_lds_per_block;
     a.n_frames = b->n_frames; a.feat_off = b->feat_off; a.feat_cnt = b->feat_cnt; a.z = b->z; a.v = b->v;
     a.tri_off = b->tri1_off; a.tri = b->tri1; a.tri_cnt = b->tri1_cnt; a.max_feat = b->max_feat;
-    const size_t lds = 16u * (size_t)((b->max_feat + 1) & ~1) + 4u * ((size_t)b->max_feat + 4) + 16;
-    if (keep) {
-        if ((rc = rs_prepare(graph_inliers_kernel<true>, lds))) return rc;
-        hipLaunchKernelGGL(graph_inliers_kernel<true>, dim3((unsigned)b->n_frames), dim3(kRsBlock), lds, ctx_stream(ctx), a);
-    } else {
-        if ((rc = rs_prepare(graph_inliers_kernel<false>, lds))) return rc;
-        hipLaunchKernelGGL(graph_inliers_kernel<false>, dim3((unsigned)b->n_frames), dim3(kRsBlock), lds, ctx_stream(ctx), a);
-    }
-    return check_launch("graph_inliers_kernel");
+    return rs_launch(ctx, keep ? graph_inliers_kernel<true> : graph_inliers_kernel<false>, "graph_inliers_kernel", b->n_frames, kRsBlock,
+                     graph_plan<size_t>(b->max_feat).total, a);
 }
 
 int mvosr_graph_inliers_batch(mvosr_ctx *ctx, const mvosr_batch *b, uint32_t good_bits, int32_t *total, int32_t *good,
@@ -1317,9 +1266,6 @@ int mvosr_flat_selection_batch(mvosr_ctx *ctx, const mvosr_batch *b, double loos
     if (!ctx || !b || !tri_height || !tri_flags || !height_level || !n_kept || !status) return set_error(MVOSR_ERR_ARG, "flat_selection: null argument");
     if (!b->feat_off || !b->feat_cnt || !b->x || !b->y || !b->z || !b->tri2_off || !b->tri2) return set_error(MVOSR_ERR_ARG, "flat_selection: missing x/y/z/tri2");
     if (b->n_frames <= 0) return MVOSR_OK;
-    int rc = ctx_activate(ctx);
-    if (rc) return rc;
-    g_rs_max_lds = ctx->max_lds_per_block;
     FlatArgs a = {};
     a.n_frames = b->n_frames; a.feat_off = b->feat_off; a.feat_cnt = b->feat_cnt; a.x = b->x; a.y = b->y; a.z = b->z;
     a.tri_off = b->tri2_off; a.tri = b->tri2; a.tri_cnt = b->tri2_cnt; a.loose_deg = loose_deg; a.tight_deg = tight_deg; a.height_factor = height_factor;
@@ -1327,12 +1273,8 @@ int mvosr_flat_selection_batch(mvosr_ctx *ctx, const mvosr_batch *b, double loos
     if (max_tri <= 0) max_tri = 2 * (int64_t)b->max_feat;
     if (max_tri > INT32_MAX) return set_error(MVOSR_ERR_TOO_LARGE, "flat_selection: max_tri does not fit 32 bits");
     a.max_feat = b->max_feat; a.max_tri = (int32_t)max_tri;
-    size_t lds = 24u * (size_t)((b->max_feat + 1) & ~1);
-    if (lds < 4u * 2048) lds = 4u * 2048;                        // (the histogram of the median search reuses the vertex planes)
-    lds += 9u * (size_t)max_tri + 32 + 4u * 48 + 16;
-    if ((rc = rs_prepare(flat_selection_kernel<false>, lds))) return rc;
-    hipLaunchKernelGGL(flat_selection_kernel<false>, dim3((unsigned)b->n_frames), dim3(kRsBlock), lds, ctx_stream(ctx), a);
-    return check_launch("flat_selection_kernel");
+    return rs_launch(ctx, flat_selection_kernel<false>, "flat_selection_kernel", b->n_frames, kRsBlock,
+                     flat_plan<size_t>(false, b->max_feat, max_tri, 0).total, a);
 }
 
 int mvosr_flat_ransac_batch(mvosr_ctx *ctx, const mvosr_batch *b, const int32_t *keep, const mvosr_rescale_params *rp,
@@ -1346,9 +1288,6 @@ int mvosr_flat_ransac_batch(mvosr_ctx *ctx, const mvosr_batch *b, const int32_t 
     if (rp->ransac_min_points < 3) return set_error(MVOSR_ERR_ARG, "flat_ransac: ransac_min_points < 3");
     if (b->max_feat > 65535) return set_error(MVOSR_ERR_TOO_LARGE, "flat_ransac: vertex ids are 16-bit in the point list");
     if (b->n_frames <= 0) return MVOSR_OK;
-    int rc = ctx_activate(ctx);
-    if (rc) return rc;
-    g_rs_max_lds = ctx->max_lds_per_block;
     if (max_tri <= 0) max_tri = 2 * (int64_t)b->max_feat;
     FlatArgs a = {};
     a.n_frames = b->n_frames; a.feat_off = b->feat_off; a.feat_cnt = b->feat_cnt; a.x = b->x; a.y = b->y; a.z = b->z;
@@ -1360,12 +1299,8 @@ int mvosr_flat_ransac_batch(mvosr_ctx *ctx, const mvosr_batch *b, const int32_t 
     a.threshold = rp->threshold; a.goal_fraction = rp->goal_fraction; a.absolute_reference = rp->absolute_reference;
     a.seed = rp->seed; a.frame_base = rp->frame_base;
     a.raw_scale = o->raw_scale; a.model = o->model; a.best_ic = o->best_ic; a.used = o->used; a.hyp_counts = o->hyp_counts;
-    // heights (reused by the 16-bit point list: 6 B per row <= 8), scalars, planes, histogram, flags, hypotheses
-    const size_t lds = 8u * (size_t)max_tri + 32 + 4u * 48 + 24u * (size_t)((b->max_feat + 1) & ~1) + 4u * 2048 + (size_t)max_tri + 32
-                       + 36u * (size_t)rp->n_hyp + 16;
-    if ((rc = rs_prepare(flat_selection_kernel<true, kFlatDevWaves>, lds))) return rc;
-    hipLaunchKernelGGL((flat_selection_kernel<true, kFlatDevWaves>), dim3((unsigned)b->n_frames), dim3(kFlatDevWaves * kWave), lds, ctx_stream(ctx), a);
-    return check_launch("flat_selection_kernel<device>");
+    return rs_launch(ctx, flat_selection_kernel<true, kFlatDevWaves>, "flat_selection_kernel<device>", b->n_frames, kFlatDevWaves * kWave,
+                     flat_plan<size_t>(true, b->max_feat, max_tri, rp->n_hyp).total, a);
 }
 
 int mvosr_region_grow_batch(mvosr_ctx *ctx, const mvosr_batch *b, const double *tri_height_in, const double *tri_angle_in,
@@ -1383,9 +1318,6 @@ int mvosr_region_grow_batch(mvosr_ctx *ctx, const mvosr_batch *b, const double *
     if (max_tri <= 0) max_tri = 2 * (int64_t)b->max_feat;
     if (max_tri < 1) max_tri = 1;
     if (max_tri >= 65535) return set_error(MVOSR_ERR_TOO_LARGE, "region_grow: row numbers are 16-bit in LDS");
-    int rc = ctx_activate(ctx);
-    if (rc) return rc;
-    g_rs_max_lds = ctx->max_lds_per_block;
     GrowArgs a = {};
     a.n_frames = b->n_frames; a.feat_off = b->feat_off; a.feat_cnt = b->feat_cnt; a.x = b->x; a.y = b->y; a.z = b->z;
     a.tri_off = b->tri2_off; a.tri = b->tri2; a.tri_cnt = b->tri2_cnt; a.h_in = tri_height_in; a.ang_in = tri_angle_in;
@@ -1394,15 +1326,8 @@ int mvosr_region_grow_batch(mvosr_ctx *ctx, const mvosr_batch *b, const double *
     a.region = o->region; a.n_region = o->n_region; a.n_flat = o->n_flat; a.status = o->status; a.level = o->level;
     a.threshold_height = o->threshold_height; a.label = o->label; a.neighbors = o->neighbors;
     a.tri_height = o->tri_height; a.tri_angle = o->tri_angle;
-    const size_t lds = grow_lds_bytes(pts, b->max_feat, max_tri);
-    if (pts) {
-        if ((rc = rs_prepare(region_grow_kernel<true>, lds))) return rc;
-        hipLaunchKernelGGL(region_grow_kernel<true>, dim3((unsigned)b->n_frames), dim3(kRsBlock), lds, ctx_stream(ctx), a);
-    } else {
-        if ((rc = rs_prepare(region_grow_kernel<false>, lds))) return rc;
-        hipLaunchKernelGGL(region_grow_kernel<false>, dim3((unsigned)b->n_frames), dim3(kRsBlock), lds, ctx_stream(ctx), a);
-    }
-    return check_launch("region_grow_kernel");
+    return rs_launch(ctx, pts ? region_grow_kernel<true> : region_grow_kernel<false>, "region_grow_kernel", b->n_frames, kRsBlock,
+                     grow_plan<size_t>(pts, b->max_feat, max_tri).total, a);
 }
 
 int mvosr_slew_median(mvosr_ctx *ctx, const double *raw, const int32_t *apply, int64_t n, double slew, double scale_in,
@@ -1424,15 +1349,12 @@ static int launch_ransac(mvosr_ctx *ctx, int64_t n_frames, const int64_t *pts_of
         return set_error(MVOSR_ERR_ARG, "ransac: null argument");
     if (n_hyp < 1 || n_hyp > kMaxHyp) return set_error(MVOSR_ERR_ARG, "ransac: n_hyp must be in 1..%d", kMaxHyp);
     if (n_frames <= 0) return MVOSR_OK;
-    int rc = ctx_activate(ctx);
-    if (rc) return rc;
     RansacArgs a;
     a.n_frames = n_frames; a.pts_off = pts_off; a.pts_cnt = pts_cnt; a.px = px; a.py = py; a.pz = pz; a.triples = samples;
     a.n_hyp = n_hyp; a.threshold = threshold; a.goal_fraction = goal_fraction; a.counts = counts; a.model = model;
     a.best_ic = best_ic; a.used = used; a.line = line;
-    const size_t lds = 36u * (size_t)n_hyp + 16;
-    hipLaunchKernelGGL(ransac_plane_kernel, dim3((unsigned)n_frames), dim3(kRsBlock), lds, ctx_stream(ctx), a);
-    return check_launch("ransac_plane_kernel");
+    // (kMaxHyp hypotheses are 18 KB: no limit to raise)
+    return rs_launch(ctx, ransac_plane_kernel, "ransac_plane_kernel", n_frames, kRsBlock, ransac_plan<size_t>(n_hyp).total, a, false);
 }
 
 int mvosr_ransac_plane_batch(mvosr_ctx *ctx, int64_t n_frames, const int64_t *pts_off, const int32_t *pts_cnt,
@@ -1457,18 +1379,12 @@ int mvosr_triangle_batch(mvosr_ctx *ctx, const mvosr_batch *b, double focus, dou
     if (!b->feat_off || !b->feat_cnt || !b->x || !b->v || !b->z || !b->tri1_off || !b->tri1)
         return set_error(MVOSR_ERR_ARG, "triangle_batch: missing u (x) / v / depth (z) / tri1");
     if (b->n_frames <= 0) return MVOSR_OK;
-    int rc = ctx_activate(ctx);
-    if (rc) return rc;
-    g_rs_max_lds = ctx->max_lds_per_block;
     TriBatchArgs a;
     a.n_frames = b->n_frames; a.feat_off = b->feat_off; a.feat_cnt = b->feat_cnt; a.u = b->x; a.v = b->v; a.depth = b->z;
     a.tri_off = b->tri1_off; a.tri = b->tri1; a.focus = focus; a.cx = cx; a.cy = cy; a.s_min = s_min; a.n_sigma = n_sigma;
     a.max_feat = b->max_feat;
     a.height = height; a.counts = counts; a.status = status;
-    const size_t lds = 24u * (size_t)((b->max_feat + 1) & ~1) + 8u * 3 * 2 * kRsWaves + 32;
-    if ((rc = rs_prepare(triangle_batch_kernel, lds))) return rc;
-    hipLaunchKernelGGL(triangle_batch_kernel, dim3((unsigned)b->n_frames), dim3(kRsBlock), lds, ctx_stream(ctx), a);
-    return check_launch("triangle_batch_kernel");
+    return rs_launch(ctx, triangle_batch_kernel, "triangle_batch_kernel", b->n_frames, kRsBlock, tribatch_plan<size_t>(b->max_feat).total, a);
 }
 
 int mvosr_plane_inliers(mvosr_ctx *ctx, int64_t n, const double *px, const double *py, const double *pz, const double *model4,

@@ -487,7 +487,8 @@ class ScaleEstimator(stream.StreamKnobs):
 
     def _max_points(self):
         """Largest frame the device-resident kernels take (flat_selection + RANSAC hold a frame's survivors, rows'
-        heights and flags in one workgroup's LDS: 42 B per feature + 12 KB)."""
+        heights and flags in one workgroup's LDS).  The LDS term bounds ``flat_plan(dev, n, 2 n, N_HYP).total`` of
+        csrc/mvosr_rescale_plan.hpp from above (tests/test_rescale_plan.py)."""
         return min(packing.delaunay_gpu_max_points(), int(self.ctx.lib.mvosr_delaunay_lds_points()),
                    (self.ctx.lds_per_block - 14000 - 36 * self.N_HYP) // 43)
 
