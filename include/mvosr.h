@@ -391,6 +391,33 @@ int mvosr_outlier_vote_batch(mvosr_ctx *ctx, const mvosr_params *p, const mvosr_
                              const mvosr_outputs *o, int waves_per_frame);
 
 /*
+ * The reference's other vote: find_reliability_by_graph (scale_calculator.py:127-149, with triangle2graph :86-99 and
+ * check_depth :121-125) for every frame, one workgroup each (reliability_kernel).  Reads what mvosr_outlier_vote_batch reads:
+ * b->feat_*, y, z, v, tri1* (z is remapped at load with p's cos/sin, as the vote does).
+ *   Every feature starts at 0.8.  Each row is sorted to (s0, s1, s2) and offers the edges (s0,s1), (s0,s2), (s1,s2); an edge
+ *   joins its LOWER end's list when first seen.  The edges are applied once, over i ascending and graph[i] in list order —
+ *   i.e. sorted by (i, first row that names both ends, j).  Edge (i, j), i < j, with ri, rj read first:
+ *     a = ri*rj, b = (1-ri)*rj, c = (1-rj)*ri, d = (1-ri)*(1-rj);
+ *     abnormal — the fp64 product (v[i]-v[j]) * (z[i]-z[j]) > 0 (an underflow to 0 or a NaN is normal) —:
+ *       ri' = (0.25*c) / (0.25*(b+c) + 0.5*d),  rj' = (0.25*b) / (0.25*(b+c) + 0.5*d);
+ *     normal:  ri' = (a + 0.25*c) / (a + 0.25*(b+c) + 0.5*d),  rj' = (a + 0.25*b) / (a + 0.25*(b+c) + 0.5*d);
+ *   every operation an IEEE binary64 operation of its own, in this association; 0/0 = NaN is kept.  The device applies, round
+ *   after round, the edges that are next at both their ends: the same values bit for bit.
+ * reliability_out: double per feature, laid out like z.  keep_out: int32 per feature, 0 where reliability > 0.8 (:145), else -1
+ * (a feature no row names stays at exactly 0.8: rejected; NaN: rejected).  status_out [F]: 0, or MVOSR_ST_ERR_MASK.
+ * A frame without rows: every reliability 0.8, every keep -1, status 0 (what the reference returns there).
+ * Refused with MVOSR_ST_ERR_MASK and an all -1 keep slice, reliabilities not written: a row that names a vertex twice or an id
+ * outside [0, feat_cnt[f]).  b->max_feat sizes the launch's LDS, for max_tri = 2 * b->max_feat rows (at least 1): a frame with
+ * feat_cnt[f] > b->max_feat or more rows than max_tri is refused before LDS is touched — MVOSR_ST_ERR_MASK, keep all -1,
+ * reliabilities not written.
+ * LDS, with N = b->max_feat, T = max_tri: 16 (N rounded up to even) + 16 + 4 (N + 2) + 24 T + 8 ceil(3 T / 32) + 64 bytes —
+ * 136 KB for 2 000 features; a launch beyond the device's limit returns MVOSR_ERR_TOO_LARGE, as does b->max_feat > 65535 or
+ * 3 * max_tri > 65535 (16-bit ids in LDS).
+ */
+int mvosr_reliability_batch(mvosr_ctx *ctx, const mvosr_params *p, const mvosr_batch *b, double *reliability_out,
+                            int32_t *keep_out, int32_t *status_out);
+
+/*
  * Stage K3 alone: road_model_calculation_static (scale_calculator.py:324-354) on packed
  * lists of already-remapped y values (feat_off/feat_cnt/y of `b`; nothing else is read);
  * `height_level_in` [F] supplies the fallback level (:335).  Writes height, status and the

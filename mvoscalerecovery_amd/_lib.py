@@ -164,6 +164,7 @@ SYMBOLS = {
                                     C.c_int64, C.c_int64]),
     "mvosr_batch_size_hint": (C.c_int, [_P, C.c_int64, C.POINTER(Batch)]),
     "mvosr_outlier_vote_batch": (C.c_int, [_P, C.POINTER(Params), C.POINTER(Batch), C.POINTER(Outputs), C.c_int]),
+    "mvosr_reliability_batch": (C.c_int, [_P, C.POINTER(Params), C.POINTER(Batch), _P, _P, _P]),
     "mvosr_road_model_batch": (C.c_int, [_P, C.POINTER(Params), C.POINTER(Batch), _P, C.POINTER(Outputs), C.c_int]),
     "mvosr_window_median": (C.c_int, [_P, _P, C.c_int64, C.c_int, _P, C.c_int, _P]),
     "mvosr_window_median_blocked": (C.c_int, [_P, _P, C.c_int64, C.c_int, C.c_int64, C.c_int, _P, C.c_int, _P]),

@@ -442,6 +442,32 @@ class DeviceOutputs:
         self.bufs = {}
 
 
+class ReliabilityOutputs:
+    """Output arrays of ``ScaleEngine.reliability_batch`` in one device block: ``reliability`` (double) and ``keep`` (int32, 0 =
+    survives, -1 = not) per feature, laid out like the feature planes; ``status`` per frame."""
+
+    def __init__(self, ctx, batch: DeviceBatch):
+        F = max(batch.n_frames, 1)
+        self.ctx = ctx
+        self.block = ctx.block([("reliability", batch.total_padded, np.float64), ("keep", batch.total_padded, np.int32),
+                                ("status", F, np.int32)])
+        self.bufs = dict(self.block.views)
+        self.block.zero()
+
+    def invalidate(self):
+        self.block.invalidate()
+        self.block.mark(False)
+
+    def get(self, name):
+        return self.bufs[name].download()
+
+    def free(self):
+        if self.block is not None:
+            self.block.free()
+            self.block = None
+        self.bufs = {}
+
+
 class ScaleEngine:
     """Launches the hot-path kernels.  One engine = one context (device + stream) + parameters."""
 
@@ -468,6 +494,14 @@ class ScaleEngine:
         out.invalidate()
         _lib.check(self.lib.mvosr_outlier_vote_batch(self.ctx.handle, C.byref(self.params), C.byref(b), C.byref(o),
                                                      int(waves)), "mvosr_outlier_vote_batch")
+
+    def reliability_batch(self, batch: DeviceBatch, out: ReliabilityOutputs):
+        """find_reliability_by_graph (/root/reference/src/scale_calculator.py:127-149) for every frame of the batch, on its first
+        triangulation: one launch of mvosr_reliability_batch."""
+        b = batch.struct()
+        out.invalidate()
+        _lib.check(self.lib.mvosr_reliability_batch(self.ctx.handle, C.byref(self.params), C.byref(b), out.bufs["reliability"].ptr,
+                                                    out.bufs["keep"].ptr, out.bufs["status"].ptr), "mvosr_reliability_batch")
 
     def road_model_batch(self, batch: DeviceBatch, out: DeviceOutputs, height_level=None, waves=0):
         b, o = batch.struct(), out.struct()

@@ -536,14 +536,27 @@ def _metric_survivors(estimator, feature3ds, feature2ds, cam, scales):
     for f, err in sorted(pf.extra["tri1_errors"].items()):
         raise err
     db = DeviceBatch(ctx, pf, with_tri2=False)
-    vote_out = DeviceOutputs(ctx, db, counts=True, stage=True)
-    try:
-        eng.outlier_vote_batch(db, vote_out)
-        counters = vote_out.get("vote_counters")
-    finally:
-        vote_out.free()
-        db.free()
-    masks = [counters[pf.frame_slice(f)] >= 0 for f in range(len(f3s))]                                  # :166
+    if getattr(estimator, "vote", "outliers") == "reliability":
+        from .engine import ReliabilityOutputs
+        vote_out = ReliabilityOutputs(ctx, db)
+        try:
+            eng.reliability_batch(db, vote_out)
+            keep, refused = vote_out.get("keep"), vote_out.get("status")
+        finally:
+            vote_out.free()
+            db.free()
+        if np.any(refused[:len(f3s)] != 0):
+            raise _lib.MvosrLibraryError("the reliability vote refused the rows of frame %d" % int(np.argmax(refused[:len(f3s)] != 0)))
+        masks = [keep[pf.frame_slice(f)] == 0 for f in range(len(f3s))]                                  # :145
+    else:
+        vote_out = DeviceOutputs(ctx, db, counts=True, stage=True)
+        try:
+            eng.outlier_vote_batch(db, vote_out)
+            counters = vote_out.get("vote_counters")
+        finally:
+            vote_out.free()
+            db.free()
+        masks = [counters[pf.frame_slice(f)] >= 0 for f in range(len(f3s))]                              # :166
     rec = Reconstruct(cam, ctx=ctx, delaunay_workers=estimator.delaunay_workers)
     rows = rec._rows_for(f2s, masks, "scipy")
     if estimator.check_triangle == "fixed":

@@ -30,7 +30,7 @@ from . import _lib
 from . import constants as K
 from . import packing
 from . import stream
-from .engine import DeviceBatch, DeviceOutputs, ScaleEngine
+from .engine import DeviceBatch, DeviceOutputs, ReliabilityOutputs, ScaleEngine
 
 
 def raise_for_status(status, frame=None):
@@ -46,6 +46,19 @@ def raise_for_status(status, frame=None):
         raise _lib.MvosrLibraryError("second triangulation inconsistent with the vote computed on the GPU" + where)
     if status == K.ST_ERR_EMPTY:
         raise ValueError("frame without features below the vanishing row / without triangles" + where)
+
+
+class _HostOutputs:
+    """Stage outputs that were assembled on the host, behind ``DeviceOutputs``' reading interface (``get`` / ``free``)."""
+
+    def __init__(self, arrays):
+        self.bufs = dict(arrays)
+
+    def get(self, name):
+        return self.bufs[name]
+
+    def free(self):
+        self.bufs = {}
 
 
 class ScaleEstimator(stream.StreamKnobs):
@@ -70,7 +83,7 @@ class ScaleEstimator(stream.StreamKnobs):
     GPU_REDO_DEFER = True           # ... and finished after the call's last chunk (its SciPy calls start on the worker pool at once)
 
     def __init__(self, absolute_reference, window_size=6, vanish=K.VANISH, focus=K.FOCUS, device=0,
-                 delaunay_workers=None, verbose=False, mutate_inputs=True, triangulation=None, check_triangle=None):
+                 delaunay_workers=None, verbose=False, mutate_inputs=True, triangulation=None, check_triangle=None, vote="outliers"):
         # reference attributes (scale_calculator.py:23-40)
         self.absolute_reference = absolute_reference
         self.camera_pitch = K.CAMERA_PITCH
@@ -116,6 +129,15 @@ class ScaleEstimator(stream.StreamKnobs):
             check_triangle = "fixed" if triangulation == "gpu" else "reference"
         if check_triangle not in ("reference", "fixed"):
             raise ValueError("check_triangle must be 'reference' or 'fixed'")
+        # vote = "outliers": find_outliers decides which features have a wrong depth (:260, the reference's live line).
+        # "reliability": find_reliability_by_graph in its place (:259, the reference's commented alternative) — on the staged
+        # host-triangulation path only: the fused device-resident kernels recompute find_outliers themselves.
+        if vote not in ("outliers", "reliability"):
+            raise ValueError("vote must be 'outliers' or 'reliability'")
+        if vote == "reliability" and triangulation != "scipy":
+            raise ValueError("vote='reliability' runs on the staged host-triangulation path: it needs triangulation='scipy'")
+        self.vote = vote
+        self.last_reliability = None
         self.triangulation = triangulation
         self.check_triangle = check_triangle
         if delaunay_workers is None or delaunay_workers > 1:
@@ -253,6 +275,31 @@ class ScaleEstimator(stream.StreamKnobs):
             print('feature left     ', int(np.sum(counters >= 0)))
         return counters >= 0
 
+    def find_reliability_by_graph(self, feature3d, feature2d, triangle_ids):
+        """scale_calculator.py:127-149: boolean mask of the features whose reliability ends above 0.8; the values themselves
+        stay in ``self.last_reliability``."""
+        eng, ctx = self._plain_engine(), self.engine.ctx
+        pf = self._pack_plain(feature3d, np.asarray(feature2d)[:, 1])
+        packing.attach_tri1(pf, [np.asarray(triangle_ids)])
+        db = DeviceBatch(ctx, pf, with_tri2=False)
+        out = ReliabilityOutputs(ctx, db)
+        try:
+            eng.reliability_batch(db, out)
+            sl = pf.frame_slice(0)
+            reliability, keep, st = out.get("reliability")[sl], out.get("keep")[sl], int(out.get("status")[0])
+        finally:
+            out.free()
+            db.free()
+        if st != 0:
+            raise ValueError("triangle_ids name a vertex twice in a row, or a vertex outside the features")
+        self.last_reliability = reliability
+        valid_id = keep == 0                                                  # :145
+        if self.verbose and len(reliability):
+            print('reliability', np.min(reliability), np.median(reliability), np.max(reliability))
+            print('feature rejected ', int(np.sum(~valid_id)))
+            print('feature left     ', int(np.sum(valid_id)))
+        return valid_id
+
     def feature_selection_by_tri(self, feature3d, triangle_ids):
         """scale_calculator.py:225-248: sorted unique vertex ids of the flat, low triangles; sets
         ``self.height_level``."""
@@ -280,7 +327,8 @@ class ScaleEstimator(stream.StreamKnobs):
         feature3d, feature2d = np.asarray(feature3d, dtype=np.float64), np.asarray(feature2d, dtype=np.float64)
         low = feature2d[:, 1] > self.vanish                                   # :252-254
         feature2d, feature3d = feature2d[low, :], feature3d[low, :]
-        valid = self.find_outliers(feature3d, feature2d, delaunay_simplices(feature2d))     # :257-260
+        vote = self.find_reliability_by_graph if self.vote == "reliability" else self.find_outliers          # :259 / :260
+        valid = vote(feature3d, feature2d, delaunay_simplices(feature2d))     # :257-260
         if not valid.shape[0] > 3:                                            # :263 (length of the mask)
             if self.verbose:
                 print('no enough feature for triangulation')
@@ -379,7 +427,9 @@ class ScaleEstimator(stream.StreamKnobs):
                 self.triangulation == "gpu" and self.check_triangle == "fixed":
             fast = self._single_exact_fast(feature3ds, feature2ds, fixed=True)
         lazy_level = None
-        if fast is not None:
+        if self.vote == "reliability":
+            raw, status, level, counts, host_errors, last = self._stream_reliability(feature3ds, feature2ds, tri1s, tri2s, stage)
+        elif fast is not None:
             raw, status, level, counts, host_errors, last, lazy_level = fast
         elif self.triangulation == "gpu" and tri1s is None and tri2s is None and not few_exact:
             lazy_last = bool(self.GPU_EXACT_LAZY_LEVEL and self.check_triangle == "reference" and not stage)
@@ -569,6 +619,112 @@ class ScaleEstimator(stream.StreamKnobs):
         level = np.array(level, copy=True)
         level[mask != 0] = new[mask != 0]
         return level
+
+    # -- vote="reliability": the staged path with find_reliability_by_graph in find_outliers' place (:259 for :260)
+    def _chunk_reliability(self, f3s, f2s, tri1s=None, stage=False, _remapped=False):
+        """One chunk of frames: vanishing-row filter, packing and Delaunay #1 on the host (SciPy's rows verbatim: the vote reads
+        their ORDER, :91-98), the vote on the device (mvosr_reliability_batch), the survivors compacted and Delaunay #2 on the host
+        (:263-267), then the survivors as frames of their own — no first triangulation, so every one of them passes the scale
+        kernel's own vote, the arrangement of ``feature_selection_by_tri`` — through mvosr_scale_batch (:225-248, :324-354, :419),
+        every frame in the exact mode.  Returns ``(raw, status, level, counts, host_errors, state)``."""
+        F = len(f3s)
+        eng = self._plain_engine() if _remapped else self.engine
+        ctx = eng.ctx
+        pf = packing.pack_features(f3s, f2s, self.vanish)             # raw values, packed BEFORE the in-place remap below
+        if self.mutate_inputs and not _remapped:
+            for f3 in f3s:
+                if isinstance(f3, np.ndarray) and f3.size:
+                    self.feature_remap(f3)                             # :414
+        pf.extra["canonical"] = False
+        packing.attach_tri1(pf, tri1s if tri1s is not None else packing.submit_tri1(pf, self.delaunay_workers, slot=stream.SLOT_CHUNK),
+                            self.delaunay_workers)
+        host_errors = dict(pf.extra["tri1_errors"])                    # QhullError at :257
+        db = DeviceBatch(ctx, pf, with_tri2=False)
+        rout = ReliabilityOutputs(ctx, db)
+        try:
+            eng.reliability_batch(db, rout)
+            rel, keep, vote_status = rout.get("reliability"), rout.get("keep"), rout.get("status")
+        finally:
+            rout.free()
+            db.free()
+        masks = [keep[pf.frame_slice(f)] == 0 for f in range(F)]      # :145
+        self.last_reliability = [rel[pf.frame_slice(f)] for f in range(F)]        # (of the call's last chunk)
+        if self.verbose:
+            for f, m in enumerate(masks):
+                if len(m) and f not in host_errors:
+                    r = self.last_reliability[f]
+                    print('reliability', np.min(r), np.median(r), np.max(r))
+                    print('feature rejected ', int(np.sum(~m)))
+                    print('feature left     ', int(np.sum(m)))
+        raw, level = np.full(F, np.nan), np.full(F, np.nan)
+        status = np.full(F, K.ST_ERR_EMPTY, dtype=np.int32)
+        counts = np.zeros((F, _lib.N_COUNTS), dtype=np.int32)
+        cnt = np.asarray(pf.feat_cnt)
+        status[cnt == 3] = K.ST_TOO_FEW                                 # :263-270 (the LENGTH of the mask)
+        counts[cnt == 3, K.CNT_VALID] = 3
+        status[np.asarray(vote_status[:F]) != 0] = K.ST_ERR_MASK        # (rows the vote refused: precomputed tri1s only)
+        todo = [f for f in range(F) if cnt[f] > 3 and f not in host_errors and vote_status[f] == 0]
+        pts = packing.survivor_points(pf, masks)
+        fixed = self.check_triangle == "fixed"
+        rows = packing.delaunay_submit([pts[f] for f in todo], self.delaunay_workers, slot=stream.SLOT_CHUNK_TRI2, canonical=fixed).get()   # :266
+        go = []
+        for f, t in zip(todo, rows):
+            if isinstance(t, Exception):
+                host_errors[f] = t                                       # QhullError at :266
+            else:
+                go.append((f, np.ascontiguousarray(t, dtype=np.int32)))
+        selected = np.zeros(max(pf.total_padded, 1), dtype=np.uint8)
+        if go:
+            kept = np.array([int(np.count_nonzero(masks[f])) for f, _ in go], dtype=np.int32)
+            # (exactly three survivors are one triangle to the reference, :266, but "too few features" to the scale kernel, which reads
+            # a frame's size as the LENGTH of the mask, :263: such a frame carries its first survivor once more, named by no row)
+            cnt2 = np.maximum(kept, 4).astype(np.int32)
+            off2, total2 = packing.pack_layout(cnt2)
+            planes = {k: np.zeros(total2) for k in "xyzvu"}
+            for g, (f, _) in enumerate(go):
+                sl, m = pf.frame_slice(f), masks[f]
+                for k in "xyzvu":
+                    planes[k][off2[g]:off2[g] + kept[g]] = getattr(pf, k)[sl][m]      # :264-265
+                    planes[k][off2[g] + kept[g]:off2[g] + cnt2[g]] = planes[k][off2[g]]
+            pf2 = packing.PackedFrames(len(go), off2, cnt2, planes["x"], planes["y"], planes["z"], planes["v"], planes["u"],
+                                       [None] * len(go), max_feat=int(cnt2.max()))
+            pf2.extra["canonical"] = fixed
+            pf2.extra["tri1_is_canonical"] = True                         # (no rows: nothing to bring into canonical form)
+            packing.attach_tri1(pf2, [np.zeros((0, 3), dtype=np.int32)] * len(go))          # no vote: every survivor stays
+            packing.attach_tri2(pf2, [t for _, t in go], [np.ones(int(c), dtype=bool) for c in cnt2])
+            db2 = DeviceBatch(ctx, pf2, exact_all=True)
+            out2 = DeviceOutputs(ctx, db2, counts=True, stage=stage)
+            try:
+                eng.scale_batch(db2, out2, exact=True)
+                r2, s2, l2, c2 = out2.get("raw_scale"), out2.get("status"), out2.get("height_level"), out2.get("counts")
+                sel2 = out2.get("selected") if stage else None
+            finally:
+                out2.free()
+                db2.free()
+            for g, (f, _) in enumerate(go):
+                raw[f], status[f], level[f], counts[f] = r2[g], s2[g], l2[g], c2[g]
+                counts[f, K.CNT_VALID] = kept[g]
+                if sel2 is not None:
+                    o = int(pf.feat_off[f])
+                    selected[o:o + kept[g]] = sel2[pf2.frame_slice(g)][:kept[g]]      # over the survivors, as the fused path lays it out
+        st = {"pf": pf, "n": F, "masks": masks, "dbatch": None, "out": _HostOutputs({"selected": selected})}
+        return raw, status, level, counts, host_errors, st
+
+    def _stream_reliability(self, feature3ds, feature2ds, tri1s, tri2s, stage):
+        """A call's frames through ``_chunk_reliability`` in chunks of ``PIPELINE_CHUNK``."""
+        if tri2s is not None:
+            raise ValueError("vote='reliability': precomputed tri2s would have to be built on ITS survivors; pass tri1s only")
+        F, C = len(feature3ds), self.PIPELINE_CHUNK
+        res, last = [], None
+        for a in range(0, F, C):
+            b = min(F, a + C)
+            r = self._chunk_reliability(feature3ds[a:b], feature2ds[a:b], None if tri1s is None else tri1s[a:b], stage)
+            res.append(r[:5])
+            last = r[5]
+        host_errors = {}
+        for k, r in enumerate(res):
+            host_errors.update({k * C + f: e for f, e in r[4].items()})
+        return tuple(np.concatenate([r[k] for r in res]) for k in range(4)) + (host_errors, last)
 
     def _stream_chunks(self, feature3ds, feature2ds, depth=2):
         F, C = len(feature3ds), self.PIPELINE_CHUNK
@@ -1086,6 +1242,12 @@ class ScaleEstimator(stream.StreamKnobs):
         mutate = keep_mutate if mutate is None else mutate             # (were the frame's values remapped in place when it was processed?)
         self.mutate_inputs = False
         try:
+            if self.vote == "reliability":
+                _, status, _, _, _, one = self._chunk_reliability([f3], [f2], None, True, _remapped=mutate)
+                if mutate:
+                    self.mutate_inputs = True          # (_store_flat_feature then takes f3 as already remapped)
+                self._store_flat_feature(one["pf"], one["out"], [f3], [f2], one["masks"], 0, status[0])
+                return
             if self.triangulation == "gpu" and not mutate and self.check_triangle == "fixed":
                 # (the device's triangulations for this one frame as well: two host Delaunay calls are 5 ms, the whole
                 # per-frame device path 1.5)
