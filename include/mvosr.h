@@ -636,6 +636,66 @@ typedef struct mvosr_grow_outputs {
 int mvosr_region_grow_batch(mvosr_ctx *ctx, const mvosr_batch *b, const double *tri_height_in, const double *tri_angle_in,
                             const mvosr_grow_params *gp, const mvosr_grow_outputs *o, int64_t max_tri);
 
+/* ---- the triangle-graph road selection (/root/reference/src/scale_calculator.py:177-222) ------------------------------- */
+
+/* outputs of mvosr_tri_graph_batch (device pointers; every one except status, selected and height_level may be NULL).
+ * "rows": laid out like tri2. */
+typedef struct mvosr_trigraph_outputs {
+    double  *p_road;             /* [rows] the probability a row ends with (:213; a row that is not flat keeps its initial one) */
+    double  *p_initial;          /* [rows] max((-70 - pitch_deg) / 20 - 0.2, 0) (:188-189) */
+    uint8_t *valid;              /* [rows] p_road > 0.5 (:219) */
+    int32_t *neighbors;          /* [rows][3] graph[row] of triangle2region_graph (:56-81) in ITS list order, -1 padded */
+    double  *tri_height;         /* [rows] from-points form: mean y' of the three vertices (:186) */
+    double  *tri_pitch_deg;      /* [rows] from-points form: asin(-n_y/|n|) * 180/pi (:185) */
+    uint8_t *selected;           /* [features, laid out like x] 1 where the feature is a vertex of a valid row (:221) */
+    double  *height_level;       /* [F] np.mean(heights[pitch_deg >= -80]) in NumPy's summation order (:216); NaN: no such row */
+    int32_t *n_flat, *n_valid;   /* [F] rows with pitch_deg < -80 (:190); valid rows */
+    int32_t *n_rounds;           /* [F] rounds the sweep took (the depth of the flat rows' dependency order) */
+    int32_t *status;             /* [F] 0, MVOSR_ST_ERR_SINGULAR, _MASK or _EMPTY */
+} mvosr_trigraph_outputs;
+
+/*
+ * feature_selection_by_tri_graph (scale_calculator.py:177-222, with triangle2region_graph :56-81 and compare :169-175) for every
+ * frame, one workgroup each (tri_graph_kernel).  Rows: b->tri2 at b->tri2_off[f], b->tri2_cnt[f] of them when tri2_cnt is
+ * given, else tri2_off[f+1] - tri2_off[f]; ids in [0, feat_cnt[f]).
+ *   graph[i]: rows are visited ascending; row i = (a, b, c) looks for an EARLIER row that shares the edge ab, then ac, then bc,
+ *   and each hit appends the earlier row to graph[i] and i to graph[earlier].  So graph[i] holds first its lower-index
+ *   neighbours in the order of row i's own edge slots (ab, ac, bc) — the row as given, not sorted —, then its higher-index
+ *   neighbours ascending; at most 3 entries.
+ *   p = (-70 - pitch_deg) / 20 - 0.2, set to 0 where p < 0 (a NaN stays).  flat: pitch_deg < p->pitch_threshold_deg (-80).
+ *   For v over the flat rows, ascending: ha = heights[v], pa = p[v]; for u in graph[v], in list order:
+ *     d = heights[u] - ha;  column c = 0 where d < -0.1, 2 where d > 0.1, else 1 (both strict; a NaN gives 1);
+ *     pc = p[u]  — the FINAL value where u < v and u is flat, else the initial one (a higher flat row is read before its turn);
+ *     m0 = (1-pa)*(1-pc), m1 = (1-pa)*pc, m2 = pa*(1-pc), m3 = pa*pc;
+ *     o = column c of [[0.33,0.33,0.33],[0.03,0.07,0.90],[0.90,0.07,0.03],[0.05,0.9,0.05]];
+ *     pa = num / den  with  num = fma(o3, m3, o2*m2),  den = fma(o0, m0, o2*m2) + fma(o1, m1, o3*m3)
+ *   then p[v] = pa.  The two dot products are NumPy's `@` (:210), i.e. the installed BLAS's strided ddot; the form above is the
+ *   DECLARED RULE: it reproduces OpenBLAS 0.3.29's Haswell kernel bit for bit on every operand tried, where a left-to-right
+ *   sum does not; another BLAS build may give the reference itself other last bits.  Every other operation is one IEEE
+ *   binary64 operation; 0/0 = NaN is kept.  The device finishes, round after round, the flat rows whose flat lower-index
+ *   neighbours are final: the same values bit for bit, with no cap on the rounds.
+ *   valid = p > 0.5 over all rows; selected marks the vertices of the valid rows; height_level = np.mean(heights[pitch_deg >=
+ *   thr]) in NumPy's pairwise order (NaN when no row is steep).
+ * Two forms: tri_height_in and tri_pitch_in both given ([rows]: mean height and pitch in degrees per row; x/y/z are not read and
+ * everything after them is bit-exact; a NaN flows through as IEEE: never flat, never steep, never valid, "equal" in compare), or
+ * both NULL: they are computed from the frame's x/y/z, remapped at load with p's cos/sin, by the scale kernel's reference
+ * formulation (n = A^-1 . 1 by LU with partial pivoting, normalise, asin, degrees; h = ((y0 + y1) + y2) / 3) and written to
+ * tri_height / tri_pitch_deg when asked for; a zero pivot gives MVOSR_ST_ERR_SINGULAR (:181 raises).  Exactly one of the two
+ * given: MVOSR_ERR_ARG.
+ * Refused with MVOSR_ST_ERR_MASK (what :68's list(intersect)[0] would pick arbitrarily): an edge named by more than two rows, a
+ * row that names a vertex twice, an id outside [0, feat_cnt[f]).  A refused frame (MASK or SINGULAR) gets all-zero valid and
+ * selected slices, height_level NaN and counts 0; p_road, p_initial and neighbors are not written (tri_height / tri_pitch_deg
+ * are, once the ids have passed).  A frame with no rows: MVOSR_ST_ERR_EMPTY, an all-zero selected slice, the same per-frame values.
+ * b->max_feat sizes the launch's LDS, for max_tri = 2 * b->max_feat rows (at least 1): a frame with feat_cnt[f] > b->max_feat
+ * or more rows than max_tri is refused before LDS is touched — MVOSR_ST_ERR_MASK, height_level NaN, counts 0, none of its
+ * per-row or per-feature outputs written.
+ * LDS, with N = b->max_feat, T = max_tri:  max(4 (N + 2) + 12 T, 8 T + 1712, from-points ? 24 (N rounded up to even) : 0)
+ * + 25 T + 4 ceil(N / 32) + 80 bytes, each term rounded up to 8 — 153 KB for 2 000 features, 2 095 features within 160 KB; a launch
+ * beyond the device's limit returns MVOSR_ERR_TOO_LARGE, as does b->max_feat > 65535 or max_tri > 65535 (16-bit ids in LDS).
+ */
+int mvosr_tri_graph_batch(mvosr_ctx *ctx, const mvosr_params *p, const mvosr_batch *b, const double *tri_height_in,
+                          const double *tri_pitch_in, const mvosr_trigraph_outputs *o);
+
 /*
  * The cross-frame tail of scale_calculation_ransac (rescale.py:169-178) over a run of frames, on the device: the slew
  * limiter — a frame with apply[i] != 0 moves the running scale towards raw[i] by at most `slew` (0.3), any other frame

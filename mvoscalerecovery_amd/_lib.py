@@ -92,6 +92,13 @@ class GrowOutputs(C.Structure):
                 ("tri_angle", C.c_void_p)]
 
 
+class TriGraphOutputs(C.Structure):
+    """mvosr_trigraph_outputs"""
+    _fields_ = [("p_road", C.c_void_p), ("p_initial", C.c_void_p), ("valid", C.c_void_p), ("neighbors", C.c_void_p),
+                ("tri_height", C.c_void_p), ("tri_pitch_deg", C.c_void_p), ("selected", C.c_void_p), ("height_level", C.c_void_p),
+                ("n_flat", C.c_void_p), ("n_valid", C.c_void_p), ("n_rounds", C.c_void_p), ("status", C.c_void_p)]
+
+
 class Camera(C.Structure):
     """mvosr_camera"""
     _fields_ = [("width", C.c_int32), ("height", C.c_int32), ("fx", C.c_double), ("fy", C.c_double), ("cx", C.c_double), ("cy", C.c_double)]
@@ -175,6 +182,7 @@ SYMBOLS = {
     "mvosr_flat_ransac_batch": (C.c_int, [_P, C.POINTER(Batch), _P, C.POINTER(RescaleParams), _P, _P, _P, C.POINTER(RescaleOutputs),
                                           C.c_int64]),
     "mvosr_region_grow_batch": (C.c_int, [_P, C.POINTER(Batch), _P, _P, C.POINTER(GrowParams), C.POINTER(GrowOutputs), C.c_int64]),
+    "mvosr_tri_graph_batch": (C.c_int, [_P, C.POINTER(Params), C.POINTER(Batch), _P, _P, C.POINTER(TriGraphOutputs)]),
     "mvosr_slew_median": (C.c_int, [_P, _P, _P, C.c_int64, C.c_double, C.c_double, C.c_int, _P, C.c_int, _P, _P]),
     "mvosr_slew_median_host": (C.c_int, [_P, _P, C.c_int64, C.c_double, C.c_double, C.c_int, _P, C.c_int, _P, _P, _P]),
     "mvosr_ransac_plane_batch": (C.c_int, [_P, C.c_int64, _P, _P, _P, _P, _P, _P, C.c_int, C.c_double, C.c_double,

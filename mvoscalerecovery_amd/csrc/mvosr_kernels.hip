@@ -28,6 +28,7 @@
 #include "../../include/mvosr.h"
 #include "mvosr_device.hpp"
 #include "mvosr_host.hpp"
+#include "mvosr_npsum.hpp"
 
 namespace mvosr {
 
@@ -294,40 +295,9 @@ __device__ __forceinline__ int phase_vote(const Smem &s, int n, const double *gx
     return total;
 }
 
-// np.add.reduce's summation order for a 1-D float64 array (numpy/core/src/umath/loops_utils.h.src,
-// @TYPE@_pairwise_sum: below 8 values a plain loop; up to 128 eight strided accumulators combined as
-// ((r0+r1)+(r2+r3))+((r4+r5)+(r6+r7)) and the remainder added one by one; above that the halves —
-// the first rounded down to a multiple of 8 — summed recursively).  With sq the terms are
-// (a[i]-shift)^2, as in np.std's  x = arr - mean; x = x*x; sum(x).  Every lane of the wavefront runs it
-// redundantly on the same packed list; it is the cold path behind the skewness decision (road_wave).
-__device__ __forceinline__ double np_term(const double *a, int i, double shift, bool sq) {
-    const double v = a[i];
-    if (!sq) return v;
-    const double d = v - shift;
-    return d * d;
-}
-__device__ double np_leaf_sum(const double *a, int n, double shift, bool sq) {
-    if (n < 8) {
-        double res = 0.0;
-        for (int i = 0; i < n; ++i) res += np_term(a, i, shift, sq);
-        return res;
-    }
-    double r[8];
-#pragma unroll
-    for (int j = 0; j < 8; ++j) r[j] = np_term(a, j, shift, sq);
-    int i = 8;
-    for (; i < n - (n % 8); i += 8) {
-#pragma unroll
-        for (int j = 0; j < 8; ++j) r[j] += np_term(a, i + j, shift, sq);
-    }
-    double res = ((r[0] + r[1]) + (r[2] + r[3])) + ((r[4] + r[5]) + (r[6] + r[7]));
-    for (; i < n; ++i) res += np_term(a, i, shift, sq);
-    return res;
-}
 // The recursion's stack lives in LDS (kNpStackInts ints per wavefront, 8-byte aligned; every lane of the wavefront walks
 // the same list and writes the same values): as private arrays it was 688 B of scratch memory per lane of every wavefront
 // of road_model_kernel, for a branch one list in thousands takes.
-constexpr int kNpDepth = 8;                                  // a chunk has <= 8192 elements, a leaf <= 128: at most 7 levels
 constexpr int kNpStackInts = 3 * kNpDepth + 2 * kNpDepth;
 __device__ __attribute__((noinline)) double np_pairwise_chunk_cold(const double *a, int n, double shift, int sq, int *stk) {
     int *lo_s = stk, *n_s = stk + kNpDepth, *stage_s = stk + 2 * kNpDepth;
@@ -346,10 +316,6 @@ __device__ __attribute__((noinline)) double np_pairwise_chunk_cold(const double 
     return val[0];
 }
 
-// np.add.reduce hands its inner loop at most `bufsize` (8192, np.getbufsize()) elements at a time and adds the
-// chunks' pairwise sums up from left to right (checked against NumPy 2.2 for lists of 10^4 - 2*10^5 elements: a single
-// pairwise recursion over the whole list differs in the last bits from 10291 elements on).
-constexpr int kNpBufSize = 8192;
 __device__ __forceinline__ double np_pairwise_sum_cold(const double *a, int n, double shift, int sq, int *stk) {
     double res = np_pairwise_chunk_cold(a, min(n, kNpBufSize), shift, sq, stk);
     for (int lo = kNpBufSize; lo < n; lo += kNpBufSize) res += np_pairwise_chunk_cold(a + lo, min(kNpBufSize, n - lo), shift, sq, stk);

@@ -468,6 +468,42 @@ class ReliabilityOutputs:
         self.bufs = {}
 
 
+class TriGraphOutputs:
+    """Output arrays of ``ScaleEngine.tri_graph_batch`` in one device block.  Per row of the second triangulation: ``p_road``,
+    ``p_initial``, ``valid``, ``neighbors`` (3 per row, -1 padded, the reference's list order) and, with ``values``, the
+    ``tri_height`` / ``tri_pitch_deg`` the from-points form computed; per feature ``selected``; per frame ``height_level``,
+    ``n_flat``, ``n_valid``, ``n_rounds``, ``status``."""
+
+    def __init__(self, ctx, batch: DeviceBatch, values=False):
+        F, T = max(batch.n_frames, 1), max(batch.n_tri2, 1)
+        self.ctx = ctx
+        spec = [("p_road", T, np.float64), ("p_initial", T, np.float64), ("height_level", F, np.float64), ("neighbors", (T, 3), np.int32),
+                ("n_flat", F, np.int32), ("n_valid", F, np.int32), ("n_rounds", F, np.int32), ("status", F, np.int32),
+                ("valid", T, np.uint8), ("selected", batch.total_padded, np.uint8)]
+        if values:
+            spec = [("tri_height", T, np.float64), ("tri_pitch_deg", T, np.float64)] + spec
+        self.block = ctx.block(spec)
+        self.bufs = dict(self.block.views)
+        self.block.zero()
+
+    def struct(self):
+        p = lambda k: (self.bufs[k].ptr if k in self.bufs else None)
+        return _lib.TriGraphOutputs(**{k: p(k) for k, _ in _lib.TriGraphOutputs._fields_})
+
+    def invalidate(self):
+        self.block.invalidate()
+        self.block.mark(False)
+
+    def get(self, name):
+        return self.bufs[name].download()
+
+    def free(self):
+        if self.block is not None:
+            self.block.free()
+            self.block = None
+        self.bufs = {}
+
+
 class ScaleEngine:
     """Launches the hot-path kernels.  One engine = one context (device + stream) + parameters."""
 
@@ -502,6 +538,17 @@ class ScaleEngine:
         out.invalidate()
         _lib.check(self.lib.mvosr_reliability_batch(self.ctx.handle, C.byref(self.params), C.byref(b), out.bufs["reliability"].ptr,
                                                     out.bufs["keep"].ptr, out.bufs["status"].ptr), "mvosr_reliability_batch")
+
+    def tri_graph_batch(self, batch: DeviceBatch, out: TriGraphOutputs, tri_height=None, tri_pitch_deg=None):
+        """feature_selection_by_tri_graph (/root/reference/src/scale_calculator.py:177-222) for every frame of the batch, on its
+        second triangulation: one launch of mvosr_tri_graph_batch.  ``tri_height`` / ``tri_pitch_deg`` (device buffers, one value
+        per row): the given form; both None: from the batch's points."""
+        b, o = batch.struct(), out.struct()
+        out.invalidate()
+        _lib.check(self.lib.mvosr_tri_graph_batch(self.ctx.handle, C.byref(self.params), C.byref(b),
+                                                  tri_height.ptr if tri_height is not None else None,
+                                                  tri_pitch_deg.ptr if tri_pitch_deg is not None else None, C.byref(o)),
+                   "mvosr_tri_graph_batch")
 
     def road_model_batch(self, batch: DeviceBatch, out: DeviceOutputs, height_level=None, waves=0):
         b, o = batch.struct(), out.struct()

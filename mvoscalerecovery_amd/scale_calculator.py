@@ -30,7 +30,7 @@ from . import _lib
 from . import constants as K
 from . import packing
 from . import stream
-from .engine import DeviceBatch, DeviceOutputs, ReliabilityOutputs, ScaleEngine
+from .engine import DeviceBatch, DeviceOutputs, ReliabilityOutputs, ScaleEngine, TriGraphOutputs
 
 
 def raise_for_status(status, frame=None):
@@ -83,7 +83,7 @@ class ScaleEstimator(stream.StreamKnobs):
     GPU_REDO_DEFER = True           # ... and finished after the call's last chunk (its SciPy calls start on the worker pool at once)
 
     def __init__(self, absolute_reference, window_size=6, vanish=K.VANISH, focus=K.FOCUS, device=0,
-                 delaunay_workers=None, verbose=False, mutate_inputs=True, triangulation=None, check_triangle=None, vote="outliers"):
+                 delaunay_workers=None, verbose=False, mutate_inputs=True, triangulation=None, check_triangle=None, vote="outliers", selection="tri"):
         # reference attributes (scale_calculator.py:23-40)
         self.absolute_reference = absolute_reference
         self.camera_pitch = K.CAMERA_PITCH
@@ -138,6 +138,15 @@ class ScaleEstimator(stream.StreamKnobs):
             raise ValueError("vote='reliability' runs on the staged host-triangulation path: it needs triangulation='scipy'")
         self.vote = vote
         self.last_reliability = None
+        # selection = "tri": feature_selection_by_tri picks the road's features (:273, the reference's live line).  "tri_graph":
+        # feature_selection_by_tri_graph in its place (:589, the reference's commented alternative) — on the staged
+        # host-triangulation path only, with either vote.
+        if selection not in ("tri", "tri_graph"):
+            raise ValueError("selection must be 'tri' or 'tri_graph'")
+        if selection == "tri_graph" and triangulation != "scipy":
+            raise ValueError("selection='tri_graph' runs on the staged host-triangulation path: it needs triangulation='scipy'")
+        self.selection = selection
+        self.last_tri_graph = None
         self.triangulation = triangulation
         self.check_triangle = check_triangle
         if delaunay_workers is None or delaunay_workers > 1:
@@ -321,6 +330,61 @@ class ScaleEstimator(stream.StreamKnobs):
             raise_for_status(st)
         return np.nonzero(sel)[0]                                             # :247
 
+    def _tri_graph_launch(self, feature3d, triangle_ids, given=None):
+        """One frame through mvosr_tri_graph_batch on the identity-remap engine -> dict of host arrays.  ``given``: (heights,
+        pitch_deg) per row for the given form; None: from ``feature3d``."""
+        eng, ctx = self._plain_engine(), self.engine.ctx
+        f3 = np.asarray(feature3d, dtype=np.float64)
+        tri = np.ascontiguousarray(triangle_ids, dtype=np.int32).reshape(-1, 3)
+        pf = self._pack_plain(f3, np.zeros(f3.shape[0]))
+        packing.attach_tri1(pf, [np.zeros((0, 3), dtype=np.int32)])
+        packing.attach_tri2(pf, [tri], [np.ones(f3.shape[0], dtype=bool)])
+        db = DeviceBatch(ctx, pf)
+        out = TriGraphOutputs(ctx, db)
+        bufs = [ctx.to_device(np.ascontiguousarray(a, dtype=np.float64)) for a in given] if given is not None else [None, None]
+        try:
+            eng.tri_graph_batch(db, out, bufs[0], bufs[1])
+            ctx.sync()
+            T = len(tri)
+            r = {k: out.get(k)[:T] for k in ("p_road", "p_initial", "valid", "neighbors")}
+            r.update({k: out.get(k)[0] for k in ("height_level", "n_flat", "n_valid", "n_rounds", "status")})
+            r["selected"] = out.get("selected")[pf.frame_slice(0)]
+        finally:
+            for b in bufs:
+                if b is not None:
+                    b.free()
+            out.free()
+            db.free()
+        return r
+
+    def triangle2region_graph(self, triangle_ids):
+        """scale_calculator.py:56-81: per row the rows that share an edge with it, in the reference's list order (first the
+        lower-index neighbours in the order of the row's own edges ab, ac, bc, then the higher-index ones ascending)."""
+        tri = np.asarray(triangle_ids).reshape(-1, 3)
+        if len(tri) == 0:
+            return []
+        n = max(int(tri.max()) + 1, 3)                                        # :59
+        zeros = np.zeros(len(tri))
+        r = self._tri_graph_launch(np.zeros((n, 3)), tri, given=(zeros, zeros))
+        if int(r["status"]) != 0:
+            raise ValueError("triangle_ids name a vertex twice in a row, a vertex below 0, or an edge on more than two rows")
+        return [[int(u) for u in row if u >= 0] for row in r["neighbors"]]
+
+    def feature_selection_by_tri_graph(self, feature3d, triangle_ids):
+        """scale_calculator.py:177-222: sorted unique vertex ids of the rows whose road probability ends above 0.5; sets
+        ``self.height_level``; the probabilities stay in ``self.last_tri_graph``."""
+        r = self._tri_graph_launch(feature3d, triangle_ids)
+        st = int(r["status"])
+        if st in (K.ST_ERR_SINGULAR, K.ST_ERR_MASK, K.ST_ERR_EMPTY):
+            raise_for_status(st)
+        self.height_level = r["height_level"]                                 # :217
+        self.last_tri_graph = {"p_road": r["p_road"], "p_initial": r["p_initial"], "n_rounds": int(r["n_rounds"])}
+        if self.verbose:
+            print('triangle left ', int(r["n_flat"]), 'from', len(r["valid"]))                     # :215
+            print('height level', self.height_level)                                                # :218
+            print('triangle left final', int(r["n_valid"]), 'from', len(r["valid"]))               # :220
+        return np.nonzero(r["selected"])[0]                                   # :221
+
     def feature_selection(self, feature3d, feature2d):
         """scale_calculator.py:250-279 on remapped input: the selected road points, or None."""
         from .packing import delaunay_simplices
@@ -334,7 +398,8 @@ class ScaleEstimator(stream.StreamKnobs):
                 print('no enough feature for triangulation')
             return None                                                       # :268-270
         feature2d, feature3d = feature2d[valid, :], feature3d[valid, :]       # :264-265
-        selected = self.feature_selection_by_tri(feature3d, delaunay_simplices(feature2d))  # :266-273
+        select = self.feature_selection_by_tri_graph if self.selection == "tri_graph" else self.feature_selection_by_tri   # :589 / :273
+        selected = select(feature3d, delaunay_simplices(feature2d))           # :266-273
         if len(selected) > 0:
             self.flat_feature_2d = feature2d[selected]                        # :275
             return feature3d[selected]
@@ -427,8 +492,8 @@ class ScaleEstimator(stream.StreamKnobs):
                 self.triangulation == "gpu" and self.check_triangle == "fixed":
             fast = self._single_exact_fast(feature3ds, feature2ds, fixed=True)
         lazy_level = None
-        if self.vote == "reliability":
-            raw, status, level, counts, host_errors, last = self._stream_reliability(feature3ds, feature2ds, tri1s, tri2s, stage)
+        if self.vote == "reliability" or self.selection == "tri_graph":
+            raw, status, level, counts, host_errors, last = self._stream_staged(feature3ds, feature2ds, tri1s, tri2s, stage)
         elif fast is not None:
             raw, status, level, counts, host_errors, last, lazy_level = fast
         elif self.triangulation == "gpu" and tri1s is None and tri2s is None and not few_exact:
@@ -620,13 +685,15 @@ class ScaleEstimator(stream.StreamKnobs):
         level[mask != 0] = new[mask != 0]
         return level
 
-    # -- vote="reliability": the staged path with find_reliability_by_graph in find_outliers' place (:259 for :260)
-    def _chunk_reliability(self, f3s, f2s, tri1s=None, stage=False, _remapped=False):
-        """One chunk of frames: vanishing-row filter, packing and Delaunay #1 on the host (SciPy's rows verbatim: the vote reads
-        their ORDER, :91-98), the vote on the device (mvosr_reliability_batch), the survivors compacted and Delaunay #2 on the host
-        (:263-267), then the survivors as frames of their own — no first triangulation, so every one of them passes the scale
-        kernel's own vote, the arrangement of ``feature_selection_by_tri`` — through mvosr_scale_batch (:225-248, :324-354, :419),
-        every frame in the exact mode.  Returns ``(raw, status, level, counts, host_errors, state)``."""
+    # -- vote="reliability" / selection="tri_graph": the staged path with the reference's commented alternatives in place of its
+    # live lines (:259 for :260, :589 at :273)
+    def _chunk_staged(self, f3s, f2s, tri1s=None, stage=False, _remapped=False):
+        """One chunk of frames: vanishing-row filter, packing and Delaunay #1 on the host (SciPy's rows verbatim: the reliability
+        vote reads their ORDER, :91-98), the configured vote on the device (mvosr_reliability_batch or mvosr_outlier_vote_batch),
+        the survivors compacted and Delaunay #2 on the host (:263-267), then the survivors as frames of their own.
+        selection="tri": no first triangulation, so every one of them passes the scale kernel's own vote, the arrangement of
+        ``feature_selection_by_tri`` — through mvosr_scale_batch (:225-248, :324-354, :419), every frame in the exact mode.
+        selection="tri_graph": ``_select_tri_graph``.  Returns ``(raw, status, level, counts, host_errors, state)``."""
         F = len(f3s)
         eng = self._plain_engine() if _remapped else self.engine
         ctx = eng.ctx
@@ -635,25 +702,33 @@ class ScaleEstimator(stream.StreamKnobs):
             for f3 in f3s:
                 if isinstance(f3, np.ndarray) and f3.size:
                     self.feature_remap(f3)                             # :414
-        pf.extra["canonical"] = False
+        reliability = self.vote == "reliability"
+        pf.extra["canonical"] = (not reliability) and self.check_triangle == "fixed"
         packing.attach_tri1(pf, tri1s if tri1s is not None else packing.submit_tri1(pf, self.delaunay_workers, slot=stream.SLOT_CHUNK),
                             self.delaunay_workers)
         host_errors = dict(pf.extra["tri1_errors"])                    # QhullError at :257
         db = DeviceBatch(ctx, pf, with_tri2=False)
-        rout = ReliabilityOutputs(ctx, db)
+        rout = ReliabilityOutputs(ctx, db) if reliability else DeviceOutputs(ctx, db, counts=True, stage=True)
         try:
-            eng.reliability_batch(db, rout)
-            rel, keep, vote_status = rout.get("reliability"), rout.get("keep"), rout.get("status")
+            if reliability:
+                eng.reliability_batch(db, rout)
+                rel, keep, vote_status = rout.get("reliability"), rout.get("keep"), rout.get("status")
+            else:
+                eng.outlier_vote_batch(db, rout)
+                ctx.sync()
+                keep, vote_status = np.where(rout.get("vote_counters") >= 0, 0, -1), np.zeros(F, dtype=np.int32)      # :166
         finally:
             rout.free()
             db.free()
         masks = [keep[pf.frame_slice(f)] == 0 for f in range(F)]      # :145
-        self.last_reliability = [rel[pf.frame_slice(f)] for f in range(F)]        # (of the call's last chunk)
+        if reliability:
+            self.last_reliability = [rel[pf.frame_slice(f)] for f in range(F)]    # (of the call's last chunk)
         if self.verbose:
             for f, m in enumerate(masks):
                 if len(m) and f not in host_errors:
-                    r = self.last_reliability[f]
-                    print('reliability', np.min(r), np.median(r), np.max(r))
+                    if reliability:
+                        r = self.last_reliability[f]
+                        print('reliability', np.min(r), np.median(r), np.max(r))
                     print('feature rejected ', int(np.sum(~m)))
                     print('feature left     ', int(np.sum(m)))
         raw, level = np.full(F, np.nan), np.full(F, np.nan)
@@ -674,7 +749,9 @@ class ScaleEstimator(stream.StreamKnobs):
             else:
                 go.append((f, np.ascontiguousarray(t, dtype=np.int32)))
         selected = np.zeros(max(pf.total_padded, 1), dtype=np.uint8)
-        if go:
+        if go and self.selection == "tri_graph":
+            self._select_tri_graph(eng, pf, masks, go, raw, status, level, counts, selected)
+        elif go:
             kept = np.array([int(np.count_nonzero(masks[f])) for f, _ in go], dtype=np.int32)
             # (exactly three survivors are one triangle to the reference, :266, but "too few features" to the scale kernel, which reads
             # a frame's size as the LENGTH of the mask, :263: such a frame carries its first survivor once more, named by no row)
@@ -710,15 +787,88 @@ class ScaleEstimator(stream.StreamKnobs):
         st = {"pf": pf, "n": F, "masks": masks, "dbatch": None, "out": _HostOutputs({"selected": selected})}
         return raw, status, level, counts, host_errors, st
 
-    def _stream_reliability(self, feature3ds, feature2ds, tri1s, tri2s, stage):
-        """A call's frames through ``_chunk_reliability`` in chunks of ``PIPELINE_CHUNK``."""
+    def _select_tri_graph(self, eng, pf, masks, go, raw, status, level, counts, selected):
+        """selection="tri_graph" for the frames ``go`` = [(frame, SciPy's second triangulation)] of a staged chunk: ONE
+        mvosr_tri_graph_batch launch over the survivors' frames (from-points form: :177-222), the selected y' lists packed on the
+        host, mvosr_road_model_batch with the launch's height_level as the fallback level (:324-354, :419); an empty selection
+        takes its no-flat branch (:277-279, :420-422).  Fills the chunk's per-frame arrays in place."""
+        ctx = eng.ctx
+        kept = np.array([int(np.count_nonzero(masks[f])) for f, _ in go], dtype=np.int32)
+        off2, total2 = packing.pack_layout(kept)
+        planes = {k: np.zeros(total2) for k in "xyzvu"}
+        for g, (f, _) in enumerate(go):
+            sl, m = pf.frame_slice(f), masks[f]
+            for k in "xyzvu":
+                planes[k][off2[g]:off2[g] + kept[g]] = getattr(pf, k)[sl][m]          # :264-265
+        pf2 = packing.PackedFrames(len(go), off2, kept, planes["x"], planes["y"], planes["z"], planes["v"], planes["u"],
+                                   [None] * len(go), max_feat=int(kept.max()))
+        pf2.extra["canonical"] = False
+        pf2.extra["tri1_is_canonical"] = True
+        packing.attach_tri1(pf2, [np.zeros((0, 3), dtype=np.int32)] * len(go))
+        packing.attach_tri2(pf2, [t for _, t in go], [np.ones(int(c), dtype=bool) for c in kept])
+        db2 = DeviceBatch(ctx, pf2)
+        tout = TriGraphOutputs(ctx, db2)
+        try:
+            eng.tri_graph_batch(db2, tout)
+            ctx.sync()
+            st2, lvl2, sel2 = tout.get("status"), tout.get("height_level"), tout.get("selected")
+            p_road, p_initial, n_rounds, n_flat, n_valid = (tout.get(k) for k in ("p_road", "p_initial", "n_rounds", "n_flat", "n_valid"))
+        finally:
+            tout.free()
+            db2.free()
+        toff = pf2.tri2_off
+        self.last_tri_graph = [{"p_road": p_road[toff[g]:toff[g + 1]], "p_initial": p_initial[toff[g]:toff[g + 1]], "n_rounds": int(n_rounds[g])}
+                               for g in range(len(go))]                       # (of the call's last chunk, one per frame that reached :273)
+        cp, sp = float(eng.params.cos_pitch), float(eng.params.sin_pitch)
+        ys, good = [], []
+        for g, (f, _) in enumerate(go):
+            counts[f, K.CNT_VALID] = kept[g]
+            if self.verbose and st2[g] == 0:
+                print('triangle left ', int(n_flat[g]), 'from', int(toff[g + 1] - toff[g]))
+                print('triangle left final', int(n_valid[g]), 'from', int(toff[g + 1] - toff[g]))
+            if st2[g] != 0:
+                status[f] = st2[g]                                            # :181 raises; rows the kernel refuses
+                continue
+            sl2 = pf2.frame_slice(g)
+            pick = sel2[sl2] != 0
+            ys.append(pf2.y[sl2][pick] * cp - pf2.z[sl2][pick] * sp)          # :391 with the engine's doubles, as the kernels remap at load
+            good.append(g)
+            o = int(pf.feat_off[f])
+            selected[o:o + kept[g]] = sel2[sl2]                               # over the survivors, as the fused path lays it out
+        if not good:
+            return
+        cnt3 = np.array([len(y) for y in ys], dtype=np.int32)
+        off3, total3 = packing.pack_layout(cnt3)
+        yplane = np.zeros(total3)
+        for y, o in zip(ys, off3):
+            yplane[o:o + len(y)] = y
+        zero = np.zeros(total3)
+        pf3 = packing.PackedFrames(len(good), off3, cnt3, zero, yplane, zero, zero, zero, [None] * len(good), max_feat=max(int(cnt3.max()), 1))
+        db3 = DeviceBatch(ctx, pf3, with_tri2=False)
+        out3 = DeviceOutputs(ctx, db3, counts=True)
+        try:
+            eng.road_model_batch(db3, out3, np.ascontiguousarray(lvl2[good], dtype=np.float64))
+            r3, s3, c3 = out3.get("raw_scale"), out3.get("status"), out3.get("counts")
+        finally:
+            out3.free()
+            db3.free()
+        for k, g in enumerate(good):
+            f = go[g][0]
+            raw[f], status[f], level[f] = r3[k], s3[k], lvl2[g]
+            keep_valid = counts[f, K.CNT_VALID]
+            counts[f] = c3[k]
+            counts[f, K.CNT_VALID], counts[f, K.CNT_TRI_PITCH], counts[f, K.CNT_TRI_VALID] = keep_valid, n_flat[g], n_valid[g]
+
+    def _stream_staged(self, feature3ds, feature2ds, tri1s, tri2s, stage):
+        """A call's frames through ``_chunk_staged`` in chunks of ``PIPELINE_CHUNK``."""
         if tri2s is not None:
-            raise ValueError("vote='reliability': precomputed tri2s would have to be built on ITS survivors; pass tri1s only")
+            raise ValueError("vote='reliability' / selection='tri_graph': precomputed tri2s would have to be built on the configured "
+                             "vote's survivors; pass tri1s only")
         F, C = len(feature3ds), self.PIPELINE_CHUNK
         res, last = [], None
         for a in range(0, F, C):
             b = min(F, a + C)
-            r = self._chunk_reliability(feature3ds[a:b], feature2ds[a:b], None if tri1s is None else tri1s[a:b], stage)
+            r = self._chunk_staged(feature3ds[a:b], feature2ds[a:b], None if tri1s is None else tri1s[a:b], stage)
             res.append(r[:5])
             last = r[5]
         host_errors = {}
@@ -1242,8 +1392,8 @@ class ScaleEstimator(stream.StreamKnobs):
         mutate = keep_mutate if mutate is None else mutate             # (were the frame's values remapped in place when it was processed?)
         self.mutate_inputs = False
         try:
-            if self.vote == "reliability":
-                _, status, _, _, _, one = self._chunk_reliability([f3], [f2], None, True, _remapped=mutate)
+            if self.vote == "reliability" or self.selection == "tri_graph":
+                _, status, _, _, _, one = self._chunk_staged([f3], [f2], None, True, _remapped=mutate)
                 if mutate:
                     self.mutate_inputs = True          # (_store_flat_feature then takes f3 as already remapped)
                 self._store_flat_feature(one["pf"], one["out"], [f3], [f2], one["masks"], 0, status[0])
