@@ -684,9 +684,9 @@ def test_singular_triangle_status(gpu):
     f3 = f3.copy()
     f3[b] = f3[a]
     r2 = so.frame_raw_scale(f3, f2, 1.75, r.tri1, r.tri2)
-    if r2.status == so.ST_ERR_SINGULAR and np.array_equal(r2.valid, r.valid):
-        pf, res = _run_fused(gpu, [(f3, f2)], [r2], stage=False, hist=False)
-        assert res["status"][0] == K.ST_ERR_SINGULAR
+    assert r2.status == so.ST_ERR_SINGULAR and np.array_equal(r2.valid, r.valid)      # (the precondition: the oracle raises, same mask)
+    pf, res = _run_fused(gpu, [(f3, f2)], [r2], stage=False, hist=False)
+    assert res["status"][0] == K.ST_ERR_SINGULAR
 
 
 def test_triangle_batch_golden(gpu):
