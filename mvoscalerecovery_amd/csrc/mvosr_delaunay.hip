@@ -63,6 +63,12 @@ constexpr int kDtHardCap = 256;          // points left to the group pass
 constexpr int kDtArenaSlack = 64;
 constexpr double kDtTieTol = 1e-9;       // relative guard band on cot differences
 constexpr double kDtColTol = 1e-12;      // relative guard band on collinearity (|cross| <= tol |a| |b|)
+// Beside the relative band an ABSOLUTE one: Qhull decides on distances to the planes of the lifted, 'Qbb'-scaled sites and merges
+// facets within DISTround of each other — inside that band SciPy's rows are not the Delaunay triangulation, whatever the relative
+// difference of two cots (a ring of 0.05 px radius: eps up to 1e-5).  kDtQhullGuard DISTround is the band of the two replays
+// (mvosr_qhull_host.c, mvosr_qhull.hip: guard); see dt_qhull_band.
+constexpr double kDtEps = 2.220446049250313e-16;
+constexpr double kDtQhullGuard = 64.0;
 constexpr double kDtColSeg = (1.0 + 1e-9) / (kDtColTol * kDtColTol);      // a2col * kDtColSeg = |a|^2 (1 + 1e-9): a collinear candidate with a larger dot lies beyond q
 
 // why a frame was declined (status bits 8..)
@@ -196,6 +202,8 @@ enum { DW_CNT = 0, DW_SUM = 16, DW_SUM2 = 32, DW_SUM3 = 48 };        // wsl[]: 1
 
 struct DtGrid {
     double lo_u, lo_v, ix, iy, sx, sy;
+    double pw;                     // the frame's absolute tie band, as a power (px^2): dt_qhull_band
+    double kf;                     // the lane pass's flag: pw + kDtTieTol * (a bound on |num| + cr in this frame)
     int gx, gy;
     const uint32_t *cs;
     __device__ __forceinline__ int cellx(double x) const { return (int)fmin(fmax((x - lo_u) * ix, 0.0), (double)(gx - 1)); }
@@ -226,6 +234,37 @@ struct DtEdge {
         i = i_; iq = -1; side = 0;
     }
 };
+
+// Qhull's guard band of a frame in the units of the tie test.  For the edge p -> q and the best apex w (t1 = n1 / c1), num - t1 cr is a
+// quadratic in the candidate c with |c|^2's coefficient 1 that vanishes on the circle through p, q and w: the POWER of c with respect
+// to that circle, (num c1 - n1 cr) / c1.  Qhull's distance of the lifted c to the facet of p, q, w is scale * power / |(2 scale O, -1)|
+// (O the circumcentre, scale = maxabs / (zhigh - zlow) from 'Qbb').  So "within 64 DISTround" means power <= 64 DISTround
+// sqrt(1 / scale^2 + 4 |O|^2), and |num c1 - n1 cr| <= pw c1 with pw = 64 DISTround sqrt(((zhigh - zlow) / maxabs)^2 + 4 (mx^2 + my^2))
+// covers it for every triangle whose circumcentre lies within the sites' range (|O|^2 <= mx^2 + my^2, mx = max |x|, my = max |y|):
+// DISTround as Qhull forms it (qh_detroundoff: mvosr_qhull_host.c, "roundoff constants") from the bounding box, the lifted range
+// bounded by [0, 1.1 (mx^2 + my^2)] (the point at infinity sits at 1.1 times the largest height).  For those triangles the band is
+// no narrower than the replays'; 3.2e-7 px^2 on a 1241 x 376 image.  (A circumcentre far outside the range belongs to a sliver beside
+// the hull: the collinearity band's matter, kDtColTol.)
+// A statement about the triangle p, q, w and the site c, whichever of the triangle's edges a star found it from.  The lane pass's FLAG
+// takes the power of either candidate with respect to the other's circle, |num c1 - n1 cr| <= pw max(cr, c1): a candidate c within the
+// band of the final best sets it at some arrival — at its own, against a best that was no worse than c is (the cot difference is no
+// larger, the cross product is c's), or, where c was the best of its time, at the arrival of the next one (the cross product is c's again,
+// now as c1).  The flag's relative part is the frame's bound, kDtTieTol (|n1| + c1) <= kDtTieTol 2 (W^2 + H^2), not the best's own: one
+// constant, two instructions per candidate instead of three, a few calls of dt_confirm_tie per frame that find nothing.
+// dt_confirm_tie then decides with the one-sided test.
+// The group and wavefront picks (dt_group_pick, dt_wave_pick) test each lane's best and its runner-up BY COT.  For the relative term
+// that is every candidate that can tie; for the absolute one it is not: a third candidate of a lane with a larger cot and a much
+// smaller cross product can lie within pw of the circle while the runner-up does not, and is not seen.  It takes three candidates of
+// one lane near one circle, and the other edges of those sites are tested as well (a frame declines on ANY of them) — the picks have
+// no completeness argument of the lane pass's kind.
+__device__ __forceinline__ double dt_qhull_band(double lo_u, double hi_u, double lo_v, double hi_v) {
+    const double mx = fmax(hi_u, -lo_u), my = fmax(hi_v, -lo_v), maxabs = fmax(mx, my);
+    const double maxsum = mx + my + maxabs;
+    const double maxdistsum = fmin(sqrt(3.0) * maxabs, maxsum);
+    const double distround = kDtEps * (3 * maxdistsum * 1.01 + maxabs);
+    const double d2 = mx * mx + my * my, inv_scale = 1.1 * d2 / maxabs;
+    return kDtQhullGuard * distround * sqrt(inv_scale * inv_scale + 4.0 * d2);
+}
 
 // The best apex seen so far as a fraction num / cr (cr > 0): t = cot of the angle under which the candidate sees the
 // edge.  Lane pass: `tie` = a candidate came within the guard band of the best OF ITS TIME — which covers every
@@ -292,7 +331,7 @@ __device__ __forceinline__ void dt_step(DtAcc &A, const DtEdge &E, int j, double
 
 // one candidate of the lane pass (as dt_step; best + `tie` only).  m1 = the lane is wrapping its star; otherwise it is
 // looking for its point's nearest neighbour, which the edge's set_nn() turns into the same arithmetic.
-__device__ __forceinline__ void dt_step_lane(DtAcc &A, const DtEdge &E, bool m1, int j, double2 c) {
+__device__ __forceinline__ void dt_step_lane(DtAcc &A, const DtEdge &E, bool m1, int j, double2 c, double kf) {
     const double bx = c.x - E.px, by = c.y - E.py;
     const double cr = __builtin_fma(E.sax, by, __builtin_fma(-E.say, bx, E.cr_add));
     const double b2 = __builtin_fma(bx, bx, by * by);
@@ -304,7 +343,7 @@ __device__ __forceinline__ void dt_step_lane(DtAcc &A, const DtEdge &E, bool m1,
     const bool ok = !skip & !col & (cr > 0.0);
     const double d = __builtin_fma(num, A.c1, -(A.n1 * cr));
     const bool better = ok & (d < 0.0);
-    A.tie |= (m1 & ok & (fabs(d) <= (kDtTieTol * (fabs(A.n1) + A.c1)) * cr)) ? 1 : 0;
+    A.tie |= (m1 & ok & (fabs(d) <= kf * fmax(cr, A.c1))) ? 1 : 0;
     A.n1 = better ? num : A.n1; A.c1 = better ? cr : A.c1; A.b1 = better ? j : A.b1;
 }
 
@@ -341,8 +380,8 @@ __device__ __forceinline__ void dt_row_range_lane(const DtGrid &G, const DtEdge 
 // loop around the call kept the edge, the box and the grid up to date there — a dozen scratch stores per scan step.)
 __device__ __attribute__((noinline)) bool dt_confirm_tie(const double2 *S, const uint32_t *cs, int gx, int xa, int xb, int ya, int yb,
                                                          double px, double py, double ax, double ay, double sgn, double a2col,
-                                                         int ei, int eiq, int b1, double n1, double c1) {
-    const double s1 = kDtTieTol * (fabs(n1) + c1);
+                                                         int ei, int eiq, int b1, double n1, double c1, double pw) {
+    const double s1 = kDtTieTol * (fabs(n1) + c1), s0 = pw * c1;
     bool tie = false;
     for (int y = ya; y <= yb; ++y) {
         const int j1 = (int)cs[y * gx + xb];
@@ -354,7 +393,7 @@ __device__ __attribute__((noinline)) bool dt_confirm_tie(const double2 *S, const
             const double b2 = __builtin_fma(bx, bx, by * by);
             if (cr * cr <= a2col * b2 || !(cr > 0.0)) continue;
             const double num = b2 - __builtin_fma(bx, ax, by * ay);
-            if (fabs(__builtin_fma(num, c1, -(n1 * cr))) <= s1 * cr) tie = true;
+            if (fabs(__builtin_fma(num, c1, -(n1 * cr))) <= __builtin_fma(s1, cr, s0)) tie = true;
         }
     }
     return tie;
@@ -392,7 +431,7 @@ __device__ __forceinline__ double dt_wave_min(double x) {
 
 struct DtPick { int id, tie, flag; };
 // the group's answer from its lanes' accumulators
-__device__ __forceinline__ DtPick dt_group_pick(const DtAcc &A) {
+__device__ __forceinline__ DtPick dt_group_pick(const DtAcc &A, double pw) {
     const double t1 = A.b1 >= 0 ? A.n1 / A.c1 : INFINITY;
     const double m = dt_group_min(t1);
     DtPick r;
@@ -400,21 +439,21 @@ __device__ __forceinline__ DtPick dt_group_pick(const DtAcc &A) {
     r.id = dt_group_shfl(A.b1, who ? (int)__ffs((int)who) - 1 : 0);
     if (!who) r.id = -1;
     const double band = kDtTieTol * (fabs(m) + 1.0);
-    const bool close = (A.b1 >= 0 && A.b1 != r.id && t1 - m <= band) || (A.n2 / A.c2 - m <= band);
+    const bool close = (A.b1 >= 0 && A.b1 != r.id && (t1 - m - band) * A.c1 <= pw) || ((A.n2 / A.c2 - m - band) * A.c2 <= pw);     // ((t - m) cr = the power)
     r.tie = (r.id >= 0) && dt_group_ballot(close) != 0u;
     r.flag = (dt_group_ballot((A.flag & 1) != 0) != 0u ? 1 : 0) | (dt_group_ballot((A.flag & 2) != 0) != 0u ? 2 : 0);
     return r;
 }
 
 // the wavefront's answer (a wide search that all 64 lanes scan together)
-__device__ __forceinline__ DtPick dt_wave_pick(const DtAcc &A) {
+__device__ __forceinline__ DtPick dt_wave_pick(const DtAcc &A, double pw) {
     const double t1 = A.b1 >= 0 ? A.n1 / A.c1 : INFINITY;
     const double m = dt_wave_min(t1);
     DtPick r;
     const unsigned long long who = __ballot(A.b1 >= 0 && t1 == m);
     r.id = who ? __builtin_amdgcn_readlane(A.b1, (int)__ffsll((long long)who) - 1) : -1;
     const double band = kDtTieTol * (fabs(m) + 1.0);
-    const bool close = (A.b1 >= 0 && A.b1 != r.id && t1 - m <= band) || (A.n2 / A.c2 - m <= band);
+    const bool close = (A.b1 >= 0 && A.b1 != r.id && (t1 - m - band) * A.c1 <= pw) || ((A.n2 / A.c2 - m - band) * A.c2 <= pw);     // ((t - m) cr = the power)
     r.tie = (r.id >= 0) && __ballot(close) != 0ull;
     r.flag = __ballot(A.flag != 0) != 0ull;
     return r;
@@ -592,6 +631,8 @@ __global__ __launch_bounds__(WAVES *kWave, PARTS ? 1 : ((ARENA_OUT && WAVES == 4
         }
         G.gx = (int)fx; G.gy = (int)fy;
         G.lo_u = lo_u; G.lo_v = lo_v; G.ix = fx / W; G.iy = fy / H; G.sx = W / fx; G.sy = H / fy; G.cs = cs;
+        G.pw = readlane_d(dt_qhull_band(lo_u, hi_u, lo_v, hi_v), 0);             // (the same in every lane: a scalar)
+        G.kf = readlane_d(__builtin_fma(kDtTieTol, 2.02 * (W * W + H * H), G.pw), 0);    // (|num|, cr <= the bounding box's diagonal squared)
     }
     const int ncell = G.gx * G.gy;
     // PARTS: the part a cell's stars belong to — a strip of cell columns, so that every part has its share of the long top and
@@ -966,7 +1007,7 @@ __global__ __launch_bounds__(WAVES *kWave, PARTS ? 1 : ((ARENA_OUT && WAVES == 4
 #ifdef MVOSR_STAMPS
                 if (lane == 0) { atomicAdd(&misc[41], my_trips); atomicAdd(&misc[42], 1); atomicAdd(&misc[43], (bb.yb - bb.ya + 1 + kDtServeRows - 1) / kDtServeRows); }
 #endif
-                const DtPick pk = dt_wave_pick(A2);
+                const DtPick pk = dt_wave_pick(A2, G.pw);
                 if (pk.tie) degenerate |= DT_WHY_TIE;
                 any = true;
                 // (a collinear candidate ahead of p: the lane's completion hands its point to the group pass, which tells the kinds apart)
@@ -1049,7 +1090,7 @@ __global__ __launch_bounds__(WAVES *kWave, PARTS ? 1 : ((ARENA_OUT && WAVES == 4
                         sg[kDtRows - 1] = 0u;
                         j = (int)(nx & 0xFFFFu); je = (int)(nx >> 16);
                     }
-                    dt_step_lane(A, E, m1, jc, c);
+                    dt_step_lane(A, E, m1, jc, c, G.kf);
                 }
                 DT_MARK(scan_done);
 #ifdef MVOSR_STAMPS
@@ -1122,7 +1163,7 @@ __global__ __launch_bounds__(WAVES *kWave, PARTS ? 1 : ((ARENA_OUT && WAVES == 4
                 DT_SEC(4);
                 DT_MARK(c_accept);
                 if (accept >= 0) {
-                    if (A.tie && dt_confirm_tie(S, cs, G.gx, box.xa, box.xb, box.ya, box.yb, E.px, E.py, E.ax, E.ay, E.sgn, E.a2col, E.i, E.iq, A.b1, A.n1, A.c1))
+                    if (A.tie && dt_confirm_tie(S, cs, G.gx, box.xa, box.xb, box.ya, box.yb, E.px, E.py, E.ax, E.ay, E.sgn, E.a2col, E.i, E.iq, A.b1, A.n1, A.c1, G.pw))
                         degenerate |= DT_WHY_TIE;
                     if (hints) {
                         // counter-clockwise walk: (p, iq, accept) is the triangle; clockwise: (p, accept, iq)
@@ -1285,7 +1326,7 @@ __global__ __launch_bounds__(WAVES *kWave, PARTS ? 1 : ((ARENA_OUT && WAVES == 4
                     DtAcc A;
                     A.reset();
                     dt_scan_box<kDtGroup, true>(A, S, G, blk, E, q);
-                    DtPick pk = dt_group_pick(A);
+                    DtPick pk = dt_group_pick(A, G.pw);
                     if (pk.id < 0 || !dt_inside(dt_circle_box(G, p.x, p.y, q, S[max(pk.id, 0)]), blk)) {
                         // nothing on that side within the block, or a circumcircle that leaves it: search the circle's
                         // cell box, or the whole frame (row by row, each row cut down to the wanted side of the edge)
@@ -1293,7 +1334,7 @@ __global__ __launch_bounds__(WAVES *kWave, PARTS ? 1 : ((ARENA_OUT && WAVES == 4
                         const int seg_seen = pk.flag & 1;           // (a candidate on the segment p..q stays one in whatever box)
                         A.reset();
                         dt_scan_box<kDtGroup, true>(A, S, G, B, E, q);
-                        pk = dt_group_pick(A);
+                        pk = dt_group_pick(A, G.pw);
                         pk.flag |= seg_seen;
                     }
                     if (dt_col_declines(pk.flag, pk.id)) degenerate |= DT_WHY_COLLINEAR;
