@@ -697,6 +697,38 @@ int mvosr_tri_graph_batch(mvosr_ctx *ctx, const mvosr_params *p, const mvosr_bat
                           const double *tri_pitch_in, const mvosr_trigraph_outputs *o);
 
 /*
+ * road_model_calculation_static_tri (/root/reference/src/scale_calculator.py:294-310 with check_mode :446-483; what follows the
+ * return at :310 is dead, the result of :305 unused) for n_lists lists of triangle heights, one wavefront per list
+ * (static_tri_kernel): the road model that rescale.py:194 leaves commented out, fed by flat_selection's heights[pitch < loose]
+ * (rescale.py:102).  Every output is a function of the list's counted values alone and is compared for bit equality.
+ * List f is the entries i in [off[f], off[f] + cnt[f]) of `height` — cnt == NULL: off has n_lists + 1 entries and the lengths
+ * are their differences —; an entry counts where flags == NULL (packed lists) or flags[i] & 1 (the row form: tri_height and
+ * tri_flags as mvosr_flat_selection_batch / mvosr_flat_ransac_batch write them, off / cnt the batch's tri2_off / tri2_cnt).
+ * The height of an entry that does not count is never read.  With n the number of counted entries:
+ *   hi = 1.0 / h, the IEEE quotient (:296).
+ *   dis[k], k = 0..18: how many hi satisfy e[k] <= hi < e[k+1] with e[k] = (double)k * 0.1, bin 18 also hi == e[19] (:297,
+ *   np.histogram over an explicit edge array counts by comparison); a value outside [0, e[19]] is in no bin.
+ *   dis[k] == 1 becomes 0 (:299); max is taken after that.
+ *   max <= 2 (:451-452, :302-303): scale_norm = np.median(hi) over ALL n values — the middle order statistic, or (a + b) / 2.0 of
+ *   the two middle ones —, status MVOSR_ST_MEDIAN.
+ *   Else bin 0 and bin 18 are flagged where they equal max, bin k in 1..17 where dis[k] >= dis[k-1], dis[k] >= dis[k+1],
+ *   (double)dis[k] >= 0.33 * (double)max and dis[k] >= 2 (:454-463); with i..j the FIRST run of consecutive flagged bins
+ *   (modes[0], :473-481, :306-307 — not the run that holds the maximum), scale_norm = (double)((i + 1) + (j + 1)) / 2.0 / 10.0
+ *   (:308-310; int(e[k] * 10) == k for every k), status MVOSR_ST_MODE.
+ * raw_scale = scale_norm * absolute_reference (rescale.py:183).  n_used = n.  hist (optional, [n_lists][19]): dis after the ones
+ * are zeroed.
+ * n <= min_count (rescale.py:181 asks for more than 12; 0 for the bare function) or n == 0: MVOSR_ST_RS_FEW, scale_norm and
+ * raw_scale NaN, hist zero.  A counted height that is not finite or not > 0 is outside the contract (flat_selection produces
+ * none): the list gets MVOSR_ST_ERR_MASK, NaN and a zero hist, as does a list with a negative offset or length or more than
+ * 2^31 - 1 entries, of which nothing is read.
+ * No LDS.  n_lists <= 0: MVOSR_OK, nothing launched.  MVOSR_ERR_ARG: a null ctx / off / height / scale_norm / raw_scale / n_used /
+ * status, or min_count < 0.
+ */
+int mvosr_static_tri_batch(mvosr_ctx *ctx, int64_t n_lists, const int64_t *off, const int32_t *cnt, const double *height,
+                           const uint8_t *flags, int32_t min_count, double absolute_reference, double *scale_norm,
+                           double *raw_scale, int32_t *n_used, int32_t *hist, int32_t *status);
+
+/*
  * The cross-frame tail of scale_calculation_ransac (rescale.py:169-178) over a run of frames, on the device: the slew
  * limiter — a frame with apply[i] != 0 moves the running scale towards raw[i] by at most `slew` (0.3), any other frame
  * leaves it — followed by the window median of the pushed values (np.median(self.scale_queue)).  raw/apply/pushed/

@@ -183,6 +183,7 @@ SYMBOLS = {
                                           C.c_int64]),
     "mvosr_region_grow_batch": (C.c_int, [_P, C.POINTER(Batch), _P, _P, C.POINTER(GrowParams), C.POINTER(GrowOutputs), C.c_int64]),
     "mvosr_tri_graph_batch": (C.c_int, [_P, C.POINTER(Params), C.POINTER(Batch), _P, _P, C.POINTER(TriGraphOutputs)]),
+    "mvosr_static_tri_batch": (C.c_int, [_P, C.c_int64, _P, _P, _P, _P, C.c_int32, C.c_double, _P, _P, _P, _P, _P]),
     "mvosr_slew_median": (C.c_int, [_P, _P, _P, C.c_int64, C.c_double, C.c_double, C.c_int, _P, C.c_int, _P, _P]),
     "mvosr_slew_median_host": (C.c_int, [_P, _P, C.c_int64, C.c_double, C.c_double, C.c_int, _P, C.c_int, _P, _P, _P]),
     "mvosr_ransac_plane_batch": (C.c_int, [_P, C.c_int64, _P, _P, _P, _P, _P, _P, C.c_int, C.c_double, C.c_double,

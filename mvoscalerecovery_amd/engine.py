@@ -550,6 +550,27 @@ class ScaleEngine:
                                                   tri_pitch_deg.ptr if tri_pitch_deg is not None else None, C.byref(o)),
                    "mvosr_tri_graph_batch")
 
+    def static_tri_batch(self, n_lists, off, height, flags=None, cnt=None, min_count=0, absolute_reference=None, hist=False):
+        """road_model_calculation_static_tri (/root/reference/src/scale_calculator.py:294-310) for ``n_lists`` lists of triangle
+        heights: one launch of mvosr_static_tri_batch.  ``off`` / ``height`` / ``flags`` / ``cnt`` are DEVICE buffers: packed lists
+        (``flags`` None) or the row form flat_selection writes (``flags``: its tri_flags; ``cnt`` None: ``off`` has one more
+        entry).  Only the per-list results come back: {"scale_norm", "raw_scale", "n_used", "status"[, "hist"]}."""
+        F = int(n_lists)
+        spec = [("scale_norm", max(F, 1), np.float64), ("raw_scale", max(F, 1), np.float64), ("n_used", max(F, 1), np.int32),
+                ("status", max(F, 1), np.int32)]
+        if hist:
+            spec.append(("hist", (max(F, 1), 19), np.int32))
+        out = self.ctx.block(spec)
+        ref = self.params.absolute_reference if absolute_reference is None else absolute_reference
+        try:
+            _lib.check(self.lib.mvosr_static_tri_batch(self.ctx.handle, F, off.ptr, cnt.ptr if cnt is not None else None, height.ptr,
+                                                       flags.ptr if flags is not None else None, int(min_count), float(ref),
+                                                       out["scale_norm"].ptr, out["raw_scale"].ptr, out["n_used"].ptr,
+                                                       out["hist"].ptr if hist else None, out["status"].ptr), "mvosr_static_tri_batch")
+            return {name: out[name].download()[:F] for name, _, _ in spec}
+        finally:
+            out.free()
+
     def road_model_batch(self, batch: DeviceBatch, out: DeviceOutputs, height_level=None, waves=0):
         b, o = batch.struct(), out.struct()
         out.invalidate()

@@ -35,6 +35,11 @@ reference's SVD of such a rank-2 sample returns a plane picked by rounding noise
 real hypothesis (tests/golden/rescale.npz frame 26); rounds 4-5 drew such a sample again (a declared deviation: gone).  The scale
 distribution is compared with the unseeded reference's in tests/test_gpu_rescale.py.  ``triangulation="scipy", sampling="device"`` runs the
 same kernels on SciPy's triangulations brought to the same row form, with bit-identical results.
+
+``model="static_tri"`` and ``model="static"`` are the two road models rescale.py:194-195 leave commented out behind the RANSAC plane,
+on the staged path: the mode of the flat triangles' inverse heights (mvosr_static_tri_batch, launched on flat_selection's device
+buffers; :179-187) and scale_calculator's road model on the selected points through the inner estimator ``self.sc`` (:31).  Both are
+deterministic: tests/golden/statictri.npz holds the reference's own sequences, reproduced bit for bit.
 """
 from __future__ import annotations
 
@@ -60,6 +65,7 @@ RANSAC_THRESHOLD = 0.005                              # rescale.py:155
 RANSAC_GOAL = 0.8                                     # estimate_road_norm.py:68
 RANSAC_MIN_POINTS = 12                                # rescale.py:152
 MIN_VALID_FOR_RETRI = 10                              # rescale.py:133
+STATIC_TRI_MIN_COUNT = 12                             # rescale.py:181 (more than 12 heights)
 SLEW = 0.3                                            # rescale.py:169-172
 _FIELDS = ("raw_scale", "height_level", "model", "best_ic", "used", "n_kept", "status")     # a chunk's results, per frame
 
@@ -92,7 +98,7 @@ class ScaleEstimator(stream.StreamKnobs):
     N_HYP = RANSAC_ITERATIONS
 
     def __init__(self, absolute_reference, window_size=6, device=0, ransac_seed=None, sampler=None,
-                 delaunay_workers=None, verbose=False, triangulation=None, sampling=None, region="threshold"):
+                 delaunay_workers=None, verbose=False, triangulation=None, sampling=None, region="threshold", model="ransac"):
         # region "threshold": the road rows are the reference's two thresholds (rescale.py:94-96); "grow": GraphGrow's region over
         # the rows' adjacency (graph.py:85-107, the call rescale.py:99 leaves commented out) — on the staged path only, which it
         # selects (checked first: no device is needed to refuse a combination).
@@ -104,6 +110,18 @@ class ScaleEstimator(stream.StreamKnobs):
                                  "device-resident kernel keeps the threshold selection)")
             triangulation, sampling = "scipy", "host"
         self.region = region
+        # model "ransac": the road model is the RANSAC plane (rescale.py:193, the reference's live line).  "static_tri": the mode of
+        # the flat triangles' inverse heights (:194, scale_calculation_static_tri :179-187).  "static": scale_calculator's road
+        # model on the selected points, through an inner estimator with its own queue and camera pitch (:195, self.sc :31).  The two
+        # commented-out choices run on the staged path only, which they select.
+        if model not in ("ransac", "static_tri", "static"):
+            raise ValueError("model must be 'ransac', 'static_tri' or 'static'")
+        if model != "ransac":
+            if triangulation not in (None, "scipy") or sampling not in (None, "host"):
+                raise ValueError("model=%r runs on the staged path: triangulation='scipy', sampling='host' (the fused "
+                                 "device-resident kernel ends in the RANSAC plane)" % model)
+            triangulation, sampling = "scipy", "host"
+        self.model = model
         # reference attributes (rescale.py:24-35)
         self.absolute_reference = absolute_reference
         self.camera_pitch = 0
@@ -151,6 +169,10 @@ class ScaleEstimator(stream.StreamKnobs):
         self.grow_threshold_angle = 8               # graph.py:40 (rescale.py:33 builds GraphGrow with its default)
         self.stage_outputs = False                  # device path, per-frame calls: keep masks / rows / flags in self.last
         self.last_declined = 0
+        if model == "static":                       # rescale.py:31: its own scale_queue, its own camera_pitch = -0.5 deg
+            from . import scale_calculator
+            self.sc = scale_calculator.ScaleEstimator(absolute_reference, window_size, device=device, delaunay_workers=delaunay_workers,
+                                                      verbose=verbose, triangulation="scipy")
 
     def initial_estimation(self, motion_matrix):
         return 0                                                   # rescale.py:36-38
@@ -180,7 +202,10 @@ class ScaleEstimator(stream.StreamKnobs):
         db.free()
         return t, g, st
 
-    def _flat_selection(self, pf2):
+    def _flat_selection(self, pf2, static_tri=False):
+        """flat_selection (rescale.py:75-102) over the batch: ``(tri_height, tri_flags, height_level, status)``.  ``static_tri``:
+        mvosr_static_tri_batch right behind it, in row form on its tri_height / tri_flags and the batch's tri2_off — the heights do
+        not visit the host: ``(None, None, height_level, status, results)``."""
         ctx, lib = self.ctx, self.ctx.lib
         db = DeviceBatch(ctx, pf2, with_tri2=True)
         nt = max(int(pf2.tri2_off[-1]), 1)
@@ -193,6 +218,15 @@ class ScaleEstimator(stream.StreamKnobs):
         b = db.struct()
         _lib.check(lib.mvosr_flat_selection_batch(ctx.handle, C.byref(b), -80.0, -85.0, 0.9, tri_h.ptr, tri_f.ptr, level.ptr,
                                                   nkept.ptr, status.ptr, max_tri), "mvosr_flat_selection_batch")
+        if static_tri:                                                                      # rescale.py:194
+            try:
+                res = self.engine.static_tri_batch(pf2.n_frames, db.bufs["tri2_off"], tri_h, flags=tri_f, min_count=STATIC_TRI_MIN_COUNT,
+                                                   absolute_reference=self.absolute_reference)
+                return None, None, level.download(), status.download(), res
+            finally:
+                for buf in (tri_h, tri_f, level, nkept, status):
+                    buf.free()
+                db.free()
         ctx.sync()
         out = tri_h.download(), tri_f.download(), level.download(), status.download()
         for buf in (tri_h, tri_f, level, nkept, status):
@@ -230,8 +264,9 @@ class ScaleEstimator(stream.StreamKnobs):
         return out
 
     # ---- reference surface ---------------------------------------------------------------------------
-    def feature_selection_batch(self, feature3ds, feature2ds):
-        """rescale.py:113-148 for a list of frames: returns a list of (point_selected, heights_loose)."""
+    def _second_triangulations(self, feature3ds, feature2ds):
+        """rescale.py:115-137 for a list of frames — the vanishing-row filter, the first triangulation, the vote, the second
+        triangulation where more than 10 survive: ``(pf2, low3, tris, valids)``."""
         f3s = [np.asarray(a, dtype=np.float64) for a in feature3ds]
         f2s = [np.asarray(a, dtype=np.float64) for a in feature2ds]
         pf = packing.pack_features(f3s, f2s, self.vanish)                                   # :115-117
@@ -267,6 +302,11 @@ class ScaleEstimator(stream.StreamKnobs):
                     raise t
                 tris[f] = t
         packing.attach_tri2(pf2, tris, None)
+        return pf2, low3, tris, valids
+
+    def feature_selection_batch(self, feature3ds, feature2ds):
+        """rescale.py:113-148 for a list of frames: returns a list of (point_selected, heights_loose)."""
+        pf2, low3, tris, valids = self._second_triangulations(feature3ds, feature2ds)
         tri_h, tri_f, level, st2 = self._flat_selection(pf2)
         out = []
         for f in range(pf2.n_frames):
@@ -336,10 +376,66 @@ class ScaleEstimator(stream.StreamKnobs):
         s, e = self.scale_calculation_ransac_batch([np.asarray(point_selected, dtype=np.float64)])
         return s[0], 1
 
+    # ---- the two road models rescale.py:194-195 leave commented out --------------------------------------------
+    def _static_tri_carry(self, raw, status, n_frames=None):
+        """rescale.py:181-187 over a run of lists, in order: a list with more than 12 heights sets ``self.scale``, any other
+        returns it as it stands.  No slew limiter, no window; ``scale_queue`` is not touched."""
+        n = len(raw) if n_frames is None else n_frames
+        scales = np.empty(n, dtype=np.float64)
+        for f in range(n):
+            if status[f] == K.ST_ERR_MASK:
+                raise ValueError("scale_calculation_static_tri: heights must be finite and positive (list %d)" % f)
+            if status[f] != K.ST_RS_FEW:
+                self.scale = raw[f]                                                         # :183-184
+            scales[f] = self.scale
+        return scales
+
+    def scale_calculation_static_tri_batch(self, heights_lists):
+        """``scale_calculation_static_tri`` once per list, in order: the packed lists uploaded together, ONE launch of
+        mvosr_static_tri_batch, ``self.scale`` carried across the lists of 12 or fewer heights.  Returns ``(scales[F], zeros[F])``."""
+        lists = [np.asarray(h, dtype=np.float64).reshape(-1) for h in heights_lists]
+        F = len(lists)
+        if F == 0:
+            return np.zeros(0), np.zeros(0)
+        off = np.zeros(F + 1, dtype=np.int64)
+        np.cumsum([h.size for h in lists], out=off[1:])
+        ctx = self.ctx
+        blk = ctx.block([("off", F + 1, np.int64), ("height", max(int(off[-1]), 1), np.float64)])
+        try:
+            blk.upload({"off": off, "height": np.concatenate(lists) if off[-1] else np.ones(1)})
+            r = self.engine.static_tri_batch(F, blk["off"], blk["height"], min_count=STATIC_TRI_MIN_COUNT,
+                                             absolute_reference=self.absolute_reference)
+        finally:
+            blk.free()
+        return self._static_tri_carry(r["raw_scale"], r["status"]), np.zeros(F)
+
+    def scale_calculation_static_tri(self, heights):
+        """rescale.py:179-187."""
+        s, _ = self.scale_calculation_static_tri_batch([heights])
+        return s[0], 0
+
+    def _static_tri_frames(self, feature3ds, feature2ds):
+        """model="static_tri" (rescale.py:192,194) for a list of frames: the stages of ``feature_selection_batch`` up to
+        flat_selection, the road model on its device-resident heights, the carry on the host.  No triples are drawn and no RANSAC
+        launch is made; the region (:94-99) does not enter the heights (:102)."""
+        pf2, low3, tris, valids = self._second_triangulations(feature3ds, feature2ds)
+        _, _, level, st2, r = self._flat_selection(pf2, static_tri=True)
+        F = pf2.n_frames
+        self.last = {"valid": valids, "tris2": tris, "height_level": level, "pf2": pf2, "scale_norm": r["scale_norm"],
+                     "raw_scale": r["raw_scale"], "n_used": r["n_used"], "status": r["status"]}
+        singular = np.nonzero(st2 == 7)[0]
+        n_ok = int(singular[0]) if len(singular) else F
+        scales = self._static_tri_carry(r["raw_scale"], r["status"], n_ok)
+        if n_ok:
+            self.height_level = level[n_ok - 1]                                             # :92
+        if n_ok < F:
+            raise np.linalg.LinAlgError("Singular matrix")                                  # :79
+        return scales, np.zeros(F)
+
     def scale_calculation(self, feature3d, feature2d, img=None):
-        """rescale.py:191-193."""
+        """rescale.py:191-195."""
         s, e = self.scale_calculation_batch([feature3d], [feature2d], stage=self.stage_outputs)
-        return s[0], 1
+        return s[0], (0 if self.model == "static_tri" else 1)
 
     def scale_calculation_batch(self, feature3ds, feature2ds, id_triples=None, stage=False):
         """Equivalent to scale_calculation per frame, in order.  sampling="host": one launch per GPU stage with host
@@ -350,7 +446,11 @@ class ScaleEstimator(stream.StreamKnobs):
             return self._stream_device(feature3ds, feature2ds, id_triples, stage)
         if id_triples is not None:
             raise ValueError("id_triples belong to sampling='device'")
+        if self.model == "static_tri":                                                      # rescale.py:194
+            return self._static_tri_frames(feature3ds, feature2ds)
         sel = self.feature_selection_batch(feature3ds, feature2ds)
+        if self.model == "static":                                                          # rescale.py:195
+            return self.sc.scale_calculation_static_batch([s[0] for s in sel])
         return self.scale_calculation_ransac_batch([s[0] for s in sel])
 
     # ---- the device-resident path ------------------------------------------------------------------------------

@@ -427,6 +427,26 @@ class ScaleEstimator(stream.StreamKnobs):
     def road_model_calculation(self, feature3d):
         return self.road_model_calculation_static(feature3d)                  # :281-282
 
+    def road_model_calculation_static_tri(self, heights):
+        """scale_calculator.py:294-310 (what follows the return at :310 is dead): ``(scale_norm, 0, 1)`` from a list of triangle
+        heights — the first run of modes of the histogram of 1/h over 19 bins of 0.1, or the median of 1/h when there is none.
+        One packed list uploaded, one launch of mvosr_static_tri_batch.  Like the reference's function it asks for no minimum
+        count (rescale.py:181 does); an empty list gives NaN, as ``np.median([])`` does.  A height that is not finite or not
+        positive raises ValueError (flat_selection produces none)."""
+        h = np.ascontiguousarray(np.asarray(heights, dtype=np.float64).reshape(-1))
+        if self.verbose:
+            print('flat features', h.size)                                    # :295
+        ctx = self.engine.ctx
+        blk = ctx.block([("off", 2, np.int64), ("height", max(h.size, 1), np.float64)])
+        try:
+            blk.upload({"off": np.array([0, h.size], dtype=np.int64), "height": h if h.size else np.ones(1)})
+            r = self.engine.static_tri_batch(1, blk["off"], blk["height"], min_count=0, absolute_reference=self.absolute_reference)
+        finally:
+            blk.free()
+        if int(r["status"][0]) == K.ST_ERR_MASK:
+            raise ValueError("road_model_calculation_static_tri: heights must be finite and positive")
+        return float(r["scale_norm"][0]), 0, 1
+
     def road_model_calculation_ransac(self, feature3d, seed=None, triples=None):
         """scale_calculator.py:366-384 (not on the path of :281; kept for callers that use it): RANSAC plane through the
         selected points (30 hypotheses, threshold 0.005; :369), its inliers at 0.01 (:370-371), camera height
@@ -450,6 +470,50 @@ class ScaleEstimator(stream.StreamKnobs):
         height, pitch, std = self.road_model_calculation(point_selected)
         scale = self.absolute_reference / height
         return self.scale_filtering(scale), std
+
+    def scale_calculation_static_batch(self, point_lists):
+        """``scale_calculation_static`` (:401-409) once per list, in order, on this estimator: every list remapped in place
+        (:402), ONE mvosr_road_model_batch over all of them (:324-354), scale = reference / height (:405) and the window median
+        (:396-400).  Returns ``(filtered[F], ones[F])``.  A list at which the reference raises (IndexError :343-344; AttributeError
+        where an empty list finds no ``height_level``, :335) raises here after the lists before it have been pushed."""
+        for p in point_lists:
+            self.feature_remap(p)                                             # :402
+        F = len(point_lists)
+        if F == 0:
+            return np.zeros(0), np.ones(0)
+        eng, ctx = self._plain_engine(), self.engine.ctx
+        f3s = [np.asarray(p, dtype=np.float64).reshape(-1, 3) for p in point_lists]
+        pf = packing.pack_features(f3s, [np.zeros((a.shape[0], 2)) for a in f3s], -np.inf)
+        db = DeviceBatch(ctx, pf, with_tri2=False)
+        out = DeviceOutputs(ctx, db, counts=True)
+        try:
+            eng.road_model_batch(db, out, np.full(F, np.nan))
+            status, height = out.get("status")[:F], out.get("height")[:F]
+        finally:
+            out.free()
+            db.free()
+        pushed, error = [], None
+        for f in range(F):
+            try:
+                h = height[f]
+                if int(status[f]) in (K.ST_NO_FLAT, K.ST_LEVEL):              # no modes and no points left (:334-335): the level —
+                    h = np.float64(self.height_level)                         # AttributeError where it was never set, as in the reference
+                else:
+                    raise_for_status(int(status[f]), f if F > 1 else None)
+            except (IndexError, AttributeError, np.linalg.LinAlgError, _lib.MvosrLibraryError, ValueError) as exc:
+                error = exc
+                break
+            with np.errstate(all="ignore"):
+                pushed.append(self.absolute_reference / h)                    # :405
+        filtered = np.zeros(0)
+        if pushed:
+            filtered = self.engine.window_median_host(np.array(pushed, dtype=np.float64), self.window_size, list(self.scale_queue))
+            self.scale_queue.extend(pushed)                                   # :397-399
+            while len(self.scale_queue) > self.window_size:
+                self.scale_queue.popleft()
+        if error is not None:
+            raise error
+        return filtered, np.ones(F)
 
     # dead-but-referenced methods of the reference (main.py:117-123 under ``if(False)``)
     def check_full_distribution(self, *a, **k):
