@@ -242,7 +242,11 @@ int mvosr_device_numa_node(int device);
 int mvosr_ctx_create(int device, mvosr_ctx **out);
 int mvosr_ctx_destroy(mvosr_ctx *ctx);
 /* Adopt an external stream (e.g. torch.cuda.current_stream().cuda_stream); NULL restores the
- * context's own stream. */
+ * context's own stream.  Either way the incoming stream is ordered behind everything the context has queued on the
+ * outgoing one (an event recorded there and waited for by the incoming stream; no host wait when the outgoing stream is
+ * the caller's), so work queued before the call and work queued after it keep their order, and a block released after the
+ * call still waits for its readers on the old stream.  The outgoing stream must therefore still exist when this is called:
+ * hand the context another stream (or NULL) BEFORE destroying the one it has adopted. */
 int mvosr_ctx_set_stream(mvosr_ctx *ctx, void *hip_stream);
 void *mvosr_ctx_stream(mvosr_ctx *ctx);
 int mvosr_ctx_sync(mvosr_ctx *ctx);

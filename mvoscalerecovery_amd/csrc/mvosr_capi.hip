@@ -442,15 +442,31 @@ int mvosr_ctx_destroy(mvosr_ctx *ctx) {
     return MVOSR_OK;
 }
 
+// Work queued on `from` so far comes before whatever is queued on `to` from now on (no host wait): a block released after a
+// change of streams gets its event on the new stream, and that event must not complete before the old stream's readers have.
+static hipError_t order_behind(hipStream_t from, hipStream_t to) {
+    hipEvent_t ev;
+    hipError_t e = hipEventCreateWithFlags(&ev, hipEventDisableTiming);
+    if (e != hipSuccess) return e;
+    e = hipEventRecord(ev, from);
+    if (e == hipSuccess) e = hipStreamWaitEvent(to, ev, 0);
+    (void)hipEventDestroy(ev);                                       // (released by the runtime once the wait has been served)
+    return e;
+}
+
 int mvosr_ctx_set_stream(mvosr_ctx *ctx, void *hip_stream) {
     if (!ctx) return set_error(MVOSR_ERR_ARG, "null context");
     HIP_TRY(hipSetDevice(ctx->device));
     if (hip_stream) {
+        hipStream_t in = reinterpret_cast<hipStream_t>(hip_stream);
+        const bool was_own = ctx->own_stream && ctx->stream == ctx->own_stream;
         // the context's own stream is given back while the caller's is in use (one hardware queue less, see above)
         if (ctx->own_stream) { HIP_TRY(hipStreamSynchronize(ctx->own_stream)); HIP_TRY(hipStreamDestroy(ctx->own_stream)); ctx->own_stream = nullptr; }
-        ctx->stream = reinterpret_cast<hipStream_t>(hip_stream);
+        if (!was_own && ctx->stream != in) HIP_TRY(order_behind(ctx->stream, in));       // (one adopted stream to another)
+        ctx->stream = in;
     } else {
         if (!ctx->own_stream) HIP_TRY(hipStreamCreateWithFlags(&ctx->own_stream, hipStreamNonBlocking));
+        if (ctx->stream != ctx->own_stream) HIP_TRY(order_behind(ctx->stream, ctx->own_stream));
         ctx->stream = ctx->own_stream;
     }
     return MVOSR_OK;

@@ -307,6 +307,25 @@ def test_batch_size_hint_is_host_only():
     assert lib.mvosr_batch_size_hint(bad.ctypes.data, 2, C.byref(b)) != 0
 
 
+def test_runtime_calls_refuse_a_null_context():
+    """The context runtime's entry points need no device to refuse a null context: MVOSR_ERR_ARG and an error text of their own."""
+    import ctypes as C
+    from mvoscalerecovery_amd import _lib
+    lib = _lib.load()
+    p, word = C.c_void_p(), (C.c_char * 64)()
+    here = C.addressof(word)
+    calls = {"mvosr_malloc": (None, 64, C.byref(p)), "mvosr_free": (None, here), "mvosr_host_alloc": (None, 64, C.byref(p)),
+             "mvosr_block_mark": (None, here, _lib.MARK_NOW), "mvosr_memcpy_d2h_kernel": (None, here, here, 16),
+             "mvosr_upload_fence": (None,), "mvosr_ctx_set_stream": (None, None)}
+    for name, args in calls.items():
+        assert lib.mvosr_batch_size_hint(None, 3, C.byref(_lib.Batch())) != 0          # (another call's text is in place)
+        before = lib.mvosr_last_error()
+        assert getattr(lib, name)(*args) == -2, name
+        text = lib.mvosr_last_error()
+        assert text and text != before and b"null" in text, (name, text)
+    assert p.value is None and bytes(word) == bytes(64)
+
+
 def test_tile_layout_far_table_is_a_copy_of_the_planes():
     """packing.apply_tile_order + attach_tri2(feature_ids=True): the far rows' vertex table holds, per far row, the
     planes' own values of its three vertices — (y, z, v) for tri1, (x, y, z) for tri2 — and every frame starts on a
