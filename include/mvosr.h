@@ -37,7 +37,8 @@ extern "C" {
 #define MVOSR_ABI_VERSION 13
 /* (mvosr_point_cloud_batch and its three structs were added WITHOUT raising this number: the change is purely additive —
  * no existing struct or signature moved — and a binding resolves every symbol it declares when it loads the library, so a
- * library older than its binding fails loudly at load time anyway.) */
+ * library older than its binding fails loudly at load time anyway.  mvosr_height_pitch_batch, its two structs and
+ * mvosr_height_pitch_lds_bytes were added the same way.) */
 
 /* error codes (function return values) */
 enum mvosr_err {
@@ -767,6 +768,74 @@ int mvosr_triangle_batch(mvosr_ctx *ctx, const mvosr_batch *b, double focus, dou
  * plane model4 = (n, d) given on the HOST; px/py/pz/mask are device arrays of n elements. */
 int mvosr_plane_inliers(mvosr_ctx *ctx, int64_t n, const double *px, const double *py, const double *pz, const double *model4,
                         double threshold, uint8_t *mask);
+
+/* ---- the per-frame camera-height and road-pitch estimator (/root/reference/src/calculate_height_pitch.py) ---------- */
+
+typedef struct mvosr_height_pitch_params {
+    double focus, cx, cy;        /* 718.856, 607.1928, 185.2157 (calculate_height_pitch.py:15-17) */
+    int32_t min_points;          /* 12: fewer list points and the frame is not fitted (:140); >= 3 */
+    int32_t n_hyp;               /* 500 (:145); <= 512 */
+    double threshold;            /* 0.005: a hypothesis' inliers among the list (:145) */
+    double goal_fraction;        /* 0.8 (/root/reference/src/estimate_road_norm.py:68) */
+    double inlier_threshold;     /* 0.01: the best plane's inliers among ALL points (:149) */
+    uint64_t seed;               /* key of the sample sequence when `triples` is NULL */
+    int64_t frame_base;          /* counter of frame 0 of the batch in the sample sequence (frame f: frame_base + f) */
+} mvosr_height_pitch_params;
+
+/* per-frame outputs of mvosr_height_pitch_batch (device pointers; the optional ones may be NULL) */
+typedef struct mvosr_height_pitch_outputs {
+    double *ransac_height;       /* [F] 1 / (|n| / h_bar) of the best plane (:154-166) */
+    double *model;               /* [F][4] unit (n, d) of the best plane, n_y >= 0 (:157-159) */
+    int32_t *best_ic, *used;     /* [F] inlier count of the best hypothesis, hypotheses consumed (ransac.py:9-22) */
+    int32_t *n_selected;         /* [F] length of the point list, 3 per kept row: the script's "suitable point" (:135) */
+    int32_t *n_inliers;          /* [F] points within inlier_threshold of the best plane (:172) */
+    double *refined_normal;      /* [F][3] unit normal of the plane through the first three inliers, n_y >= 0 (:178-186) */
+    double *refined_pitch;       /* [F] asin(n_y) of it (:188) */
+    double *refined_mean, *refined_std;   /* [F] mean and (population) std of inliers . normal (:192-195) */
+    double *height_t_mean;       /* [F] mean of z sin + y cos over the inliers, with the PRIOR's angle (:202-203) */
+    int32_t *status;             /* [F] 0, MVOSR_ST_RS_FEW, MVOSR_ST_ERR_SINGULAR, _MASK, _EMPTY */
+    uint8_t *mask;               /* optional [laid out like z] 1 = inlier (:149); written for frames with status 0 only */
+    int32_t *point_list;         /* optional: frame f's list at point_list + 3 * tri1_off[f], n_selected[f] vertex ids (:114-116) */
+    int32_t *hyp_counts;         /* optional [F][n_hyp] inlier count of every hypothesis; written for fitted frames only */
+} mvosr_height_pitch_outputs;
+
+/*
+ * The body of calculate_height_pitch.py's frame loop (:62-204) for every frame, one workgroup each, ONE launch
+ * (height_pitch_kernel): the frame's points, list, hypotheses and inlier mask never leave LDS.
+ * b: x = u, v = v, z = depth (the [u, v, depth] rows of the script's dumps), tri1 = Delaunay(u, v).simplices with tri1_off, or
+ * tri1_off + tri1_cnt, as mvosr_triangle_batch reads them.  frame_prior [F][4] (device): est_deg - 95, est_deg - 85 — the window's
+ * edges in degrees as the script forms them, est_deg = estimated_pitch * 180 / 3.1415926 (:63, :111) —, then math.sin and math.cos
+ * of estimated_pitch (:202): the host's doubles, so that no device sin or cos enters a result.
+ *   Points: (depth * (u - cx) / focus, depth * (v - cy) / focus, depth) (:67-68).  Per row: n = A^-1 . 1 (LU with partial pivoting, as
+ *   mvosr_triangle_batch), height = 1 / |n|, both negated when n_y < 0, pitch_deg = asin(-n_y / |n|) * 180 / 3.1415926 (:83-91); a
+ *   row is kept when low < pitch_deg < high and height > 0 (:111-112).  The comparison is made on -n_y / |n| against the edges'
+ *   sines; within 1e-12 of one the script's own expression decides.  A NaN edge keeps nothing.
+ *   The list: the kept rows' three ids in row order, repeats included (:114-116); fewer than min_points entries: MVOSR_ST_RS_FEW.
+ *   RANSAC over the list's points (:145): hypothesis h is the plane through the list entries at positions triples[f][h][0..2], as
+ *   the unit 4-vector (n, d); its count is the number of list entries with |m . [p, 1]| < threshold; the replay rule is
+ *   mvosr_ransac_plane_batch's (first best, stop at the first best above goal_fraction * list length).  A sample that names a
+ *   position outside the list, or one VERTEX twice, is spent: NaN plane, count 0 (mvosr_flat_ransac_batch's rule; the script's SVD
+ *   returns an arbitrary plane of the pencil there).  triples == NULL: the positions are mvosr_flat_ransac_batch's counter-based
+ *   draw from (seed, frame_base + f, h).  No hypothesis with an inlier: MVOSR_ST_RS_FEW (the script has no model either).
+ *   Inliers: every point of the frame with |n . p + d| < inlier_threshold, in feature order (:149-150).
+ *   ransac_height = 1 / (sqrt(n . n) / -d) with n_y >= 0 (:154-166).
+ *   Refinement: n^ = the unit normal of the plane through the first three inliers, (p1 - p0) x (p2 - p0) normalised, n^_y >= 0 — the
+ *   null vector the script's SVD of [p, 1] yields, up to rounding (:178-186) —; refined_pitch = asin(n^_y); refined_mean / _std over
+ *   ((x n^_x + y n^_y) + z n^_z) of the inliers; height_t_mean = mean(z sin + y cos).  Fewer than three inliers: these are NaN.
+ *   Sums: per thread over its points ascending, then lanes, then wavefronts, in a fixed order — a frame's results are bit-identical
+ *   from run to run, alone or in a batch.
+ * A frame that is not fitted (any status but 0) has NaN in every double output, 0 in best_ic / n_inliers (and in used, except
+ * where every hypothesis was spent), and n_selected = the list's length for MVOSR_ST_RS_FEW, else 0.
+ * b->max_feat sizes the launch's LDS, for max_tri = 2 * b->max_feat rows (at least 1): a frame with feat_cnt[f] > b->max_feat or
+ * more rows is refused before LDS is touched (MVOSR_ST_ERR_MASK); a vertex id outside [0, feat_cnt[f]) gives MVOSR_ST_ERR_MASK,
+ * a zero pivot MVOSR_ST_ERR_SINGULAR (the script raises LinAlgError, :83), no features or no rows MVOSR_ST_ERR_EMPTY.
+ * LDS: mvosr_height_pitch_lds_bytes(max_feat, n_hyp) = 24 N + 12 N + 36 n_hyp + N / 8 + ~500 bytes (91 KB for 2 000 features
+ * and 500 hypotheses: one workgroup of 8 wavefronts per CU); beyond the device's limit, or with max_feat > 10 922 (16-bit list
+ * positions), MVOSR_ERR_TOO_LARGE.
+ */
+int mvosr_height_pitch_batch(mvosr_ctx *ctx, const mvosr_batch *b, const mvosr_height_pitch_params *p, const double *frame_prior,
+                             const int32_t *triples, const mvosr_height_pitch_outputs *o);
+size_t mvosr_height_pitch_lds_bytes(int max_feat, int n_hyp);
 
 /* ---- dense depth maps from the triangle planes (/root/reference/src/reconstruct.py) ------------------ */
 

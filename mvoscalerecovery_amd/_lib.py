@@ -109,6 +109,21 @@ class DepthOutputs(C.Structure):
     _fields_ = [("depth", C.c_void_p), ("tri_id", C.c_void_p), ("tri_model", C.c_void_p), ("covered", C.c_void_p), ("status", C.c_void_p)]
 
 
+class HeightPitchParams(C.Structure):
+    """mvosr_height_pitch_params"""
+    _fields_ = [("focus", C.c_double), ("cx", C.c_double), ("cy", C.c_double), ("min_points", C.c_int32), ("n_hyp", C.c_int32),
+                ("threshold", C.c_double), ("goal_fraction", C.c_double), ("inlier_threshold", C.c_double), ("seed", C.c_uint64),
+                ("frame_base", C.c_int64)]
+
+
+class HeightPitchOutputs(C.Structure):
+    """mvosr_height_pitch_outputs"""
+    _fields_ = [("ransac_height", C.c_void_p), ("model", C.c_void_p), ("best_ic", C.c_void_p), ("used", C.c_void_p),
+                ("n_selected", C.c_void_p), ("n_inliers", C.c_void_p), ("refined_normal", C.c_void_p), ("refined_pitch", C.c_void_p),
+                ("refined_mean", C.c_void_p), ("refined_std", C.c_void_p), ("height_t_mean", C.c_void_p), ("status", C.c_void_p),
+                ("mask", C.c_void_p), ("point_list", C.c_void_p), ("hyp_counts", C.c_void_p)]
+
+
 CLOUD_RANGE, CLOUD_F32 = 1, 2             # enum mvosr_cloud_flags
 
 
@@ -193,6 +208,8 @@ SYMBOLS = {
     "mvosr_triangle_batch": (C.c_int, [_P, C.POINTER(Batch), C.c_double, C.c_double, C.c_double, C.c_double, C.c_double,
                                        _P, _P, _P]),
     "mvosr_plane_inliers": (C.c_int, [_P, C.c_int64, _P, _P, _P, _P, C.c_double, _P]),
+    "mvosr_height_pitch_batch": (C.c_int, [_P, C.POINTER(Batch), C.POINTER(HeightPitchParams), _P, _P, C.POINTER(HeightPitchOutputs)]),
+    "mvosr_height_pitch_lds_bytes": (C.c_size_t, [C.c_int, C.c_int]),
     "mvosr_triangle_model_batch": (C.c_int, [_P, C.POINTER(Batch), C.c_int, _P, _P, _P]),
     "mvosr_dense_depth_batch": (C.c_int, [_P, C.POINTER(Batch), C.c_int, _P, _P, C.POINTER(Camera), C.POINTER(DepthOutputs), C.c_int64, C.c_int64]),
     "mvosr_point_cloud_batch": (C.c_int, [_P, C.POINTER(CloudInputs), C.POINTER(Camera), C.POINTER(CloudParams), C.POINTER(CloudOutputs)]),
