@@ -837,6 +837,74 @@ int mvosr_height_pitch_batch(mvosr_ctx *ctx, const mvosr_batch *b, const mvosr_h
                              const int32_t *triples, const mvosr_height_pitch_outputs *o);
 size_t mvosr_height_pitch_lds_bytes(int max_feat, int n_hyp);
 
+/* ---- the RANSAC evaluation runs (/root/reference/src/calculate_height_pitch_eval.py, calculate_height_pitch_eval_line.py) ---- */
+
+enum mvosr_hp_model {
+    MVOSR_HP_MODEL_PLANE = 0,    /* _eval.py: get_pitch_ransac over the list's (x, y, z), estimate for the refinement       */
+    MVOSR_HP_MODEL_LINE = 1      /* _eval_line.py: get_pitch_line_ransac over the list's (y, z), estimate_line              */
+};
+
+/* status of a fitted (frame, case) whose refinement sample — the first three (plane) or two (line) list inliers — names fewer
+ * vertices than it has entries: the script's SVD returns rounding noise there.  Additive: no other status has this bit. */
+#define MVOSR_ST_HP_REFINE_DEGENERATE 0x100
+
+typedef struct mvosr_height_pitch_eval_params {
+    double focus, cx, cy;        /* as mvosr_height_pitch_params */
+    int32_t min_points;          /* 12 (_eval.py:159); >= 3 */
+    int32_t n_hyp;               /* the scripts' iter_number (argv[4]); <= 4096, processed in tiles of 512 */
+    double threshold;            /* 0.005 (:164) */
+    double goal_fraction;        /* 0.8 */
+    double inlier_threshold;     /* 0.01: the best model's inliers among the LIST (:167) */
+    uint64_t seed;               /* key of the sample sequence when `samples` is NULL */
+    int64_t frame_base;          /* counter of frame 0 of the batch in the sample sequence */
+    int32_t model;               /* enum mvosr_hp_model */
+    int32_t n_cases;             /* the scripts' ten (`for case_i in range(0,10)`); 1..1024 */
+    int32_t cases_per_group;     /* cases one workgroup runs with its frame resident; 0: the library's default (1, as measured) */
+} mvosr_height_pitch_eval_params;
+
+/* outputs of mvosr_height_pitch_eval_batch (device pointers; C = n_cases; the optional ones may be NULL) */
+typedef struct mvosr_height_pitch_eval_outputs {
+    double *ransac_height;       /* [F][C] 1 / (|n| / h_bar) of the best model (:175-187); the line's may be negative */
+    double *model;               /* [F][C][4] plane: unit (n, d), n_y >= 0; line: unit (a, b, 0, c) of a y + b z + c = 0, b >= 0 */
+    int32_t *best_ic, *used;     /* [F][C] */
+    int32_t *n_selected;         /* [F] length of the point list (the same for every case) */
+    int32_t *n_inliers;          /* [F][C] LIST entries within inlier_threshold of the best model, repeats counted (:193) */
+    double *refined_normal;      /* [F][C][3] plane: as mvosr_height_pitch_outputs; line: (0, n_y, n_z), n_z >= 0 */
+    double *refined_pitch;       /* [F][C] asin(n_y) */
+    double *refined_mean, *refined_std;   /* [F][C] over the list inliers, with multiplicity */
+    double *height_t_mean;       /* [F][C] */
+    double *sum_y, *sum_z;       /* [F][C] sums of y and z over the list inliers: a carried frame's height_t_mean under a new prior */
+    int32_t *status;             /* [F][C] 0, MVOSR_ST_HP_REFINE_DEGENERATE, MVOSR_ST_RS_FEW, MVOSR_ST_ERR_SINGULAR, _MASK, _EMPTY */
+    uint8_t *list_mask;          /* optional: 1 = list inlier; case c of frame f at c * list_stride + 3 * tri1_off[f], n_selected[f] bytes */
+    int64_t list_stride;         /* bytes per case of list_mask: at least 3 * tri1_off[F] */
+    int32_t *point_list;         /* optional: as mvosr_height_pitch_outputs */
+    int32_t *hyp_counts;         /* optional [F][C][n_hyp]; written for fitted frames only */
+} mvosr_height_pitch_eval_outputs;
+
+/*
+ * The bodies of both evaluation scripts' frame loops for every frame and every case in ONE launch
+ * (height_pitch_eval_kernel<model>): grid = frames x ceil(n_cases / cases_per_group) workgroups; a workgroup runs steps (1)-(2)
+ * of mvosr_height_pitch_batch once — the same statuses and refusals, written to every case — and then, for each of its cases,
+ *   hypotheses: samples[f][c][h][0..2] (the line reads two) are list positions; NULL: a counter-based draw from
+ *   (seed, frame_base + f, c, h) — key = mix(mix(seed ^ (frame_base + f) * 0xD1B54A32D192ED03) ^ (c + 1) * 0xA0761D6478BD642F),
+ *   then mvosr_height_pitch_batch's triple, or its first two positions for the line — which depends neither on the batch nor on
+ *   cases_per_group.  A position outside the list or a vertex named twice: spent.  The plane is mvosr_height_pitch_batch's; the
+ *   line is mvosr_ransac_line_batch's through (y, z) of the two vertices, its residual (y a + z b) + c.  Counts over the list at
+ *   `threshold`; the replay rule carried over tiles of 512 hypotheses.  No hypothesis with an inlier: MVOSR_ST_RS_FEW for the case.
+ *   Inliers: the LIST entries within inlier_threshold of the best model, in list order, repeats included (:167-169).
+ *   ransac_height: plane — flipped on n_y < 0, -d / |n|; line — (a, b) and h_bar = -c flipped on b < 0, h_bar / sqrt(a^2 + b^2).
+ *   Refinement: plane — as mvosr_height_pitch_batch over the first three list inliers; line — the normal (z1 - z0, -(y1 - y0)) of the
+ *   line through the first two, flipped when its z component is < 0, normalised; refined_pitch = asin of its y component; distances
+ *   y n_y + z n_z.  Sums per thread over its list positions ascending, then lanes, then wavefronts.  A sample that names a vertex
+ *   twice (or has too few entries): MVOSR_ST_HP_REFINE_DEGENERATE, refined_normal / _pitch / _mean / _std and height_t_mean NaN;
+ *   everything else is written.
+ * LDS: mvosr_height_pitch_eval_lds_bytes(max_feat, n_hyp, model) = 24 N + 12 N + 36 min(n_hyp, 512) + 3 N / 4 + ~700 bytes: it
+ * does not grow with n_cases.  Limits as mvosr_height_pitch_batch; frames x groups < 2^31.
+ */
+int mvosr_height_pitch_eval_batch(mvosr_ctx *ctx, const mvosr_batch *b, const mvosr_height_pitch_eval_params *p, const double *frame_prior,
+                                  const int32_t *samples, const mvosr_height_pitch_eval_outputs *o);
+size_t mvosr_height_pitch_eval_lds_bytes(int max_feat, int n_hyp, int model);
+
 /* ---- dense depth maps from the triangle planes (/root/reference/src/reconstruct.py) ------------------ */
 
 /* The pinhole camera of the reference's PinholeCamera (/root/reference/src/reconstruct.py:21-36 reads these six). */

@@ -124,6 +124,23 @@ class HeightPitchOutputs(C.Structure):
                 ("mask", C.c_void_p), ("point_list", C.c_void_p), ("hyp_counts", C.c_void_p)]
 
 
+class HeightPitchEvalParams(C.Structure):
+    """mvosr_height_pitch_eval_params"""
+    _fields_ = HeightPitchParams._fields_ + [("model", C.c_int32), ("n_cases", C.c_int32), ("cases_per_group", C.c_int32)]
+
+
+class HeightPitchEvalOutputs(C.Structure):
+    """mvosr_height_pitch_eval_outputs"""
+    _fields_ = [("ransac_height", C.c_void_p), ("model", C.c_void_p), ("best_ic", C.c_void_p), ("used", C.c_void_p),
+                ("n_selected", C.c_void_p), ("n_inliers", C.c_void_p), ("refined_normal", C.c_void_p), ("refined_pitch", C.c_void_p),
+                ("refined_mean", C.c_void_p), ("refined_std", C.c_void_p), ("height_t_mean", C.c_void_p), ("sum_y", C.c_void_p),
+                ("sum_z", C.c_void_p), ("status", C.c_void_p), ("list_mask", C.c_void_p), ("list_stride", C.c_int64),
+                ("point_list", C.c_void_p), ("hyp_counts", C.c_void_p)]
+
+
+HP_MODEL_PLANE, HP_MODEL_LINE = 0, 1      # enum mvosr_hp_model
+ST_HP_REFINE_DEGENERATE = 0x100           # MVOSR_ST_HP_REFINE_DEGENERATE
+
 CLOUD_RANGE, CLOUD_F32 = 1, 2             # enum mvosr_cloud_flags
 
 
@@ -210,6 +227,9 @@ SYMBOLS = {
     "mvosr_plane_inliers": (C.c_int, [_P, C.c_int64, _P, _P, _P, _P, C.c_double, _P]),
     "mvosr_height_pitch_batch": (C.c_int, [_P, C.POINTER(Batch), C.POINTER(HeightPitchParams), _P, _P, C.POINTER(HeightPitchOutputs)]),
     "mvosr_height_pitch_lds_bytes": (C.c_size_t, [C.c_int, C.c_int]),
+    "mvosr_height_pitch_eval_batch": (C.c_int, [_P, C.POINTER(Batch), C.POINTER(HeightPitchEvalParams), _P, _P,
+                                                C.POINTER(HeightPitchEvalOutputs)]),
+    "mvosr_height_pitch_eval_lds_bytes": (C.c_size_t, [C.c_int, C.c_int, C.c_int]),
     "mvosr_triangle_model_batch": (C.c_int, [_P, C.POINTER(Batch), C.c_int, _P, _P, _P]),
     "mvosr_dense_depth_batch": (C.c_int, [_P, C.POINTER(Batch), C.c_int, _P, _P, C.POINTER(Camera), C.POINTER(DepthOutputs), C.c_int64, C.c_int64]),
     "mvosr_point_cloud_batch": (C.c_int, [_P, C.POINTER(CloudInputs), C.POINTER(Camera), C.POINTER(CloudParams), C.POINTER(CloudOutputs)]),

@@ -18,13 +18,9 @@
 #include "mvosr_device.hpp"
 #include "mvosr_host.hpp"
 #include "mvosr_heightpitch_plan.hpp"
+#include "mvosr_heightpitch_pass.hpp"
 
 namespace mvosr {
-
-constexpr int kHpBlock = kHpWaves * kWave;
-constexpr int kHpPPT = 8;               // list points a thread holds in registers per chunk (chunks of 4096 entries)
-constexpr double kHpPi = 3.1415926;     // the script's constant (:63, :91)
-constexpr double kHpBand = 1e-12;       // |n_y/|n| - edge| within this: the script's own expression decides
 
 struct HpArgs {
     int64_t n_frames;
@@ -45,33 +41,6 @@ struct HpArgs {
     int32_t *point_list;           // optional, at 3 * tri_off[f]
     int32_t *hyp_counts;           // optional [F][H]
 };
-
-// mvosr_flat_ransac_batch's counter-based sample sequence (include/mvosr.h), as list POSITIONS
-__device__ __forceinline__ uint64_t hp_mix64(uint64_t x) {
-    x += 0x9E3779B97F4A7C15ull;
-    x = (x ^ (x >> 30)) * 0xBF58476D1CE4E5B9ull;
-    x = (x ^ (x >> 27)) * 0x94D049BB133111EBull;
-    return x ^ (x >> 31);
-}
-__device__ __forceinline__ void hp_draw3(uint64_t key, int h, int M, int &i0, int &i1, int &i2) {
-    const uint64_t hk = hp_mix64(key + (uint64_t)h);
-    const uint64_t r0 = hp_mix64(hk), r1 = hp_mix64(hk + 1ull), r2 = hp_mix64(hk + 2ull);
-    i0 = (int)__umul64hi(r0, (uint64_t)M);
-    i1 = (int)__umul64hi(r1, (uint64_t)(M - 1)); if (i1 >= i0) ++i1;
-    i2 = (int)__umul64hi(r2, (uint64_t)(M - 2));
-    const int lo = min(i0, i1), hi = max(i0, i1);
-    if (i2 >= lo) ++i2;
-    if (i2 >= hi) ++i2;
-}
-
-// The value of n_y/|n| at which asin(.) * 180 / 3.1415926 crosses `deg`; -2 / 2 where every / no value lies above it.  Only
-// compared against from further than kHpBand away (the device sin never decides).
-__device__ __forceinline__ double hp_edge(double deg) {
-    const double t = deg * kHpPi / 180.0;
-    if (t <= -1.58) return -2.0;
-    if (t >= 1.58) return 2.0;
-    return sin(fmin(fmax(t, -1.5707963267948966), 1.5707963267948966));
-}
 
 __device__ __forceinline__ void hp_refuse(const HpArgs &a, int64_t f, int status, int n_selected) {
     const double q = nan("");
@@ -105,77 +74,11 @@ __global__ __launch_bounds__(kHpBlock) void height_pitch_kernel(const HpArgs a) 
     int *misc = reinterpret_cast<int *>(smem + lds.misc);
     double *red = reinterpret_cast<double *>(smem + lds.red);
 
-    if (tid < HM_N) misc[tid] = 0;
-    for (int i = tid; i < n; i += kHpBlock) {
-        const double d = a.depth[off + i];
-        X[i] = d * (a.u[off + i] - a.cx) / a.focus;                                  // :67
-        Y[i] = d * (a.v[off + i] - a.cy) / a.focus;                                  // :68
-        Z[i] = d;
-    }
-    const double *pr = a.prior + 4 * f;
-    const double lo_deg = pr[0], hi_deg = pr[1], sin_est = pr[2], cos_est = pr[3];
-    const bool prior_ok = lo_deg == lo_deg && hi_deg == hi_deg;                      // (a NaN prior keeps no row, as the script's comparisons)
-    const double s_lo = hp_edge(lo_deg), s_hi = hp_edge(hi_deg);
-    __syncthreads();
-
-    // ---- the rows (:77-116), wavefront by wavefront over contiguous row segments so that the list comes out in row order
-    const int seg = ((tn + kHpBlock - 1) / kHpBlock) * kWave;                        // (tn <= 21845: at most 43 trips, one bit each)
-    const int s0 = wave * seg, s1 = min(tn, s0 + seg);
-    unsigned long long mine = 0ull;
-    int c = 0;
-    {
-        int j = 0;
-        for (int t0 = s0; t0 < s1; t0 += kWave, ++j) {
-            const int t = t0 + lane;
-            bool kp = false;
-            if (t < s1) {
-                const TriIds q = load_tri(a.tri + 3 * tb, t);
-                if (!ids_in_range(q.a, q.b, q.c, n)) misc[HM_BADID] = 1;
-                else {
-                    double nx, ny, nz;
-                    if (!plane_normal(X[q.a], Y[q.a], Z[q.a], X[q.b], Y[q.b], Z[q.b], X[q.c], Y[q.c], Z[q.c], nx, ny, nz)) misc[HM_SINGULAR] = 1;   // :83-84
-                    const double len = sqrt((nx * nx + ny * ny) + nz * nz);          // :85-86
-                    double height = 1.0 / len;
-                    if (ny < 0.0) { ny = -ny; height = -height; }                    // :87-89
-                    const double mu = -ny / len;                                     // :90, the sine of the pitch
-                    bool in;
-                    if (fabs(mu - s_lo) > kHpBand && fabs(mu - s_hi) > kHpBand) in = mu > s_lo && mu < s_hi;
-                    else {
-                        const double pitch_deg = asin(mu) * 180.0 / kHpPi;           // :90-91
-                        in = pitch_deg > lo_deg && pitch_deg < hi_deg;               // :111
-                    }
-                    kp = prior_ok && in && height > 0.0;                             // :112
-                }
-            }
-            const unsigned long long m = __ballot(kp);
-            if (kp) mine |= 1ull << j;
-            c += __popcll(m);
-        }
-    }
-    if (lane == 0) misc[HM_CW + wave] = c;
-    __syncthreads();
-    int base = 0, K = 0;
-#pragma unroll
-    for (int w = 0; w < kHpWaves; ++w) { const int cw = misc[HM_CW + w]; K += cw; if (w < wave) base += cw; }
-    const int M = 3 * K;                                                             // point_selected.shape[0], :135
-    if (misc[HM_BADID] || misc[HM_SINGULAR]) {
+    double sin_est, cos_est;
+    const int M = hp_frame_pass(a, f, n, tn, off, tb, true, X, Y, Z, L, misc, sin_est, cos_est);   // steps (1)-(2), :62-116
+    if (M < 0) {
         if (tid == 0) hp_refuse(a, f, misc[HM_BADID] ? MVOSR_ST_ERR_MASK : MVOSR_ST_ERR_SINGULAR, 0);
         return;
-    }
-    {
-        int j = 0;
-        for (int t0 = s0; t0 < s1; t0 += kWave, ++j) {
-            const int t = t0 + lane;
-            const bool kp = (mine >> j) & 1ull;
-            const unsigned long long m = __ballot(kp);
-            if (kp) {
-                const TriIds q = load_tri(a.tri + 3 * tb, t);
-                const int pos = 3 * (base + __popcll(m & ((1ull << lane) - 1ull)));
-                L[pos] = (uint16_t)q.a; L[pos + 1] = (uint16_t)q.b; L[pos + 2] = (uint16_t)q.c;   // :114-116
-                if (a.point_list) { int32_t *pl = a.point_list + 3 * tb + pos; pl[0] = q.a; pl[1] = q.b; pl[2] = q.c; }
-            }
-            base += __popcll(m);
-        }
     }
     if (M < a.min_points) {                                                          // :140: the host carries the previous frame
         if (tid == 0) hp_refuse(a, f, MVOSR_ST_RS_FEW, M);

@@ -1,13 +1,20 @@
-"""GPU mirror of the per-frame camera-height and road-pitch estimator /root/reference/src/calculate_height_pitch.py
-(its ``_eval`` / ``_eval_line`` copies share the frame loop): per frame of ``[u, v, depth]`` features and a pitch prior from
-the camera motion, the RANSAC road plane over the triangles the prior admits, its inliers among all points, and from them
-the camera height, a refined pitch, and the height under the prior's pitch.
+"""GPU mirror of the per-frame camera-height and road-pitch estimator /root/reference/src/calculate_height_pitch.py: per
+frame of ``[u, v, depth]`` features and a pitch prior from the camera motion, the RANSAC road plane over the triangles the
+prior admits, its inliers among all points, and from them the camera height, a refined pitch, and the height under the
+prior's pitch — :class:`HeightPitchEstimator`.
+
+Its two siblings ``calculate_height_pitch_eval.py`` and ``calculate_height_pitch_eval_line.py`` share the rows and the point
+list with it and nothing after: they run the whole sequence ten times at an iteration budget from the command line, take the
+inliers among the LIST points (repeats included), refine over those, and — the line script — fit the 2-D line model in
+(y, z), the one place in the reference where the line RANSAC decides a result.  :class:`RansacEvaluation` is both of them
+(``mvosr_height_pitch_eval_batch``).
 
 The reference is a Python-2 script over text dumps that writes six result files at its end; here the frame loop's body is
 ONE kernel launch for a batch of frames (``mvosr_height_pitch_batch``) and the script's cross-frame state —
 a frame with fewer than 12 list points repeats the previous frame's plane and inliers (:163-165) — is kept by
 :class:`HeightPitchEstimator`.  The triangulation's rows are built on the host (SciPy) or on the device and visit the
-host either way in this version.  The line RANSAC of :146 is printed by the script and never used: it is not computed."""
+host either way in this version.  The line RANSAC of :146 is printed by the base script and never used there: the estimator
+does not compute it (the evaluation's line model does)."""
 from __future__ import annotations
 
 import collections
@@ -60,6 +67,52 @@ def back_project(points3d, focus=FOCUS, cx=CX, cy=CY):
     return p
 
 
+def _pack_frames(pts, rows, priors):
+    """The batch both launches upload: feature planes at even segment starts, the rows back to back, the priors.
+    -> (spec_in, arrays, feat_off, tri_off, planes, total rows (at least 1))"""
+    F = len(pts)
+    cnt = np.array([len(p) for p in pts], dtype=np.int32)
+    off = np.zeros(F, dtype=np.int64)
+    off[1:] = np.cumsum((cnt[:-1].astype(np.int64) + 1) & ~1)                       # even segment starts
+    total = int(off[-1]) + ((int(cnt[-1]) + 1) & ~1)
+    planes = np.zeros((3, max(total, 2)), dtype=np.float64)
+    for f, p in enumerate(pts):
+        planes[:, off[f]:off[f] + len(p)] = p.T
+    tcnt = np.array([len(t) for t in rows], dtype=np.int64)
+    toff = np.concatenate([[0], np.cumsum(tcnt)]).astype(np.int64)
+    T = max(int(toff[-1]), 1)
+    tri = np.concatenate(rows + [np.zeros((0, 3), np.int32)]).astype(np.int32).reshape(-1)
+    tri = tri if tri.size else np.zeros(3, dtype=np.int32)
+    spec_in = [("feat_off", F, np.int64), ("feat_cnt", F, np.int32), ("u", planes.shape[1], np.float64), ("v", planes.shape[1], np.float64),
+               ("z", planes.shape[1], np.float64), ("tri1_off", F + 1, np.int64), ("tri1", tri.size, np.int32), ("prior", (F, 4), np.float64)]
+    arrays = {"feat_off": off, "feat_cnt": cnt, "u": planes[0], "v": planes[1], "z": planes[2], "tri1_off": toff, "tri1": tri,
+              "prior": np.ascontiguousarray(np.asarray(priors, dtype=np.float64).reshape(F, 4))}
+    return spec_in, arrays, off, toff, planes, T
+
+
+def _delaunay_rows(ctx, pts2d, triangulation, workers):
+    todo = [f for f, p in enumerate(pts2d) if len(p) >= 3]
+    rows = [np.zeros((0, 3), dtype=np.int32)] * len(pts2d)
+    if triangulation == "gpu":
+        got = packing.delaunay_gpu_or_host(ctx, [pts2d[f] for f in todo], workers, canonical=True)
+    else:
+        got = packing.delaunay_many([pts2d[f] for f in todo], workers)
+    for f, t in zip(todo, got):
+        if isinstance(t, Exception):
+            raise t
+        rows[f] = np.ascontiguousarray(t, dtype=np.int32)
+    return rows
+
+
+def _batch_header(din, F, max_feat, total_feat):
+    b = _lib.Batch()
+    b.n_frames, b.feat_off, b.feat_cnt = F, din["feat_off"].ptr, din["feat_cnt"].ptr
+    b.x, b.v, b.z = din["u"].ptr, din["v"].ptr, din["z"].ptr
+    b.tri1_off, b.tri1 = din["tri1_off"].ptr, din["tri1"].ptr
+    b.max_feat, b.total_feat = max_feat, total_feat
+    return b
+
+
 class HeightPitchEstimator:
     """The script's frame loop as an object: ``process`` / ``process_batch`` take frames in sequence order and keep what the
     script carries from one frame to the next; the six result lists grow as the script's do."""
@@ -82,17 +135,7 @@ class HeightPitchEstimator:
 
     # ---- rows
     def _rows_for(self, pts2d):
-        todo = [f for f, p in enumerate(pts2d) if len(p) >= 3]
-        rows = [np.zeros((0, 3), dtype=np.int32)] * len(pts2d)
-        if self.triangulation == "gpu":
-            got = packing.delaunay_gpu_or_host(self.ctx, [pts2d[f] for f in todo], self.delaunay_workers, canonical=True)
-        else:
-            got = packing.delaunay_many([pts2d[f] for f in todo], self.delaunay_workers)
-        for f, t in zip(todo, got):
-            if isinstance(t, Exception):
-                raise t
-            rows[f] = np.ascontiguousarray(t, dtype=np.int32)
-        return rows
+        return _delaunay_rows(self.ctx, pts2d, self.triangulation, self.delaunay_workers)
 
     # ---- one launch
     def launch(self, points3d_list, priors, triples=None, tris=None, frame_base=None, stage=False, max_feat=None, timing=0):
@@ -113,21 +156,7 @@ class HeightPitchEstimator:
         need = int(lib.mvosr_height_pitch_lds_bytes(max_feat, H))
         if need > ctx.lds_per_block:
             raise ValueError("a frame of %d features needs %d bytes of LDS, the device has %d" % (max_feat, need, ctx.lds_per_block))
-        off = np.zeros(F, dtype=np.int64)
-        off[1:] = np.cumsum((cnt[:-1].astype(np.int64) + 1) & ~1)                   # even segment starts
-        total = int(off[-1]) + ((int(cnt[-1]) + 1) & ~1)
-        planes = np.zeros((3, max(total, 2)), dtype=np.float64)
-        for f, p in enumerate(pts):
-            planes[:, off[f]:off[f] + len(p)] = p.T
-        tcnt = np.array([len(t) for t in rows], dtype=np.int64)
-        toff = np.concatenate([[0], np.cumsum(tcnt)]).astype(np.int64)
-        T = max(int(toff[-1]), 1)
-        tri = np.concatenate(rows + [np.zeros((0, 3), np.int32)]).astype(np.int32).reshape(-1)
-        tri = tri if tri.size else np.zeros(3, dtype=np.int32)
-        spec_in = [("feat_off", F, np.int64), ("feat_cnt", F, np.int32), ("u", planes.shape[1], np.float64), ("v", planes.shape[1], np.float64),
-                   ("z", planes.shape[1], np.float64), ("tri1_off", F + 1, np.int64), ("tri1", tri.size, np.int32), ("prior", (F, 4), np.float64)]
-        arrays = {"feat_off": off, "feat_cnt": cnt, "u": planes[0], "v": planes[1], "z": planes[2], "tri1_off": toff, "tri1": tri,
-                  "prior": np.ascontiguousarray(np.asarray(priors, dtype=np.float64).reshape(F, 4))}
+        spec_in, arrays, off, toff, planes, T = _pack_frames(pts, rows, priors)
         if triples is not None:
             tr = np.full((F, H, 3), -1, dtype=np.int32)                             # (-1: outside every list, the sample is spent)
             for f, t in enumerate(triples):
@@ -146,11 +175,7 @@ class HeightPitchEstimator:
         try:
             din.upload(arrays)
             dout.zero()
-            b = _lib.Batch()
-            b.n_frames, b.feat_off, b.feat_cnt = F, din["feat_off"].ptr, din["feat_cnt"].ptr
-            b.x, b.v, b.z = din["u"].ptr, din["v"].ptr, din["z"].ptr
-            b.tri1_off, b.tri1 = din["tri1_off"].ptr, din["tri1"].ptr
-            b.max_feat, b.total_feat = max_feat, planes.shape[1]
+            b = _batch_header(din, F, max_feat, planes.shape[1])
             p = _lib.HeightPitchParams(self.focus, self.cx, self.cy, MIN_POINTS, H, self.threshold, GOAL_FRACTION, self.inlier_threshold,
                                        self.seed, int(self.frame_count if frame_base is None else frame_base))
             o = _lib.HeightPitchOutputs(*[(dout[k].ptr if k in dout else None) for k, _ in _lib.HeightPitchOutputs._fields_])
@@ -236,3 +261,209 @@ class HeightPitchEstimator:
         """The six files under the script's names, as its ``np.savetxt`` calls write them (:228-244)."""
         for name, arr in zip(RESULT_FILES, self.result_arrays()):
             np.savetxt(os.path.join(directory, name), arr)
+
+
+# ---- the evaluation runs ---------------------------------------------------------------------------------------------------
+EVAL_MODELS = {"plane": _lib.HP_MODEL_PLANE, "line": _lib.HP_MODEL_LINE}
+EVAL_DIRS = {"plane": "eval_ransac", "line": "eval_ransac_line"}                     # _eval.py:250, _eval_line.py:251
+# the scripts' six files per case (_eval.py:250-265): the first name ends in '_', the others run straight into input_id, and
+# only the first lacks the doubled extension — for both models ("plane" in the line script's name too)
+EVAL_FILES = (("result_heights_plane_ransac_", ".txt"), ("refined_camera_height_means", ".txt.txt"), ("refined_camera_height_stds", ".txt.txt"),
+              ("refined_camera_height_t_means", ".txt.txt"), ("refined_pitch", ".txt.txt"), ("inlier_numbers", ".txt.txt"))
+ST_HP_REFINE_DEGENERATE = _lib.ST_HP_REFINE_DEGENERATE
+MAX_EVAL_ITERATIONS = 4096
+
+
+def eval_file_names(model, input_id, input_date, iterations, cases=10):
+    """The sixty relative paths the scripts write, case-major, in RESULT_FIELDS' order within a case."""
+    return [os.path.join(EVAL_DIRS[model], "%s%s_%s_%d_%d%s" % (stem, input_id, input_date, iterations, c, ext))
+            for c in range(cases) for stem, ext in EVAL_FILES]
+
+
+class RansacEvaluation:
+    """``calculate_height_pitch_eval.py`` (model "plane") and ``calculate_height_pitch_eval_line.py`` ("line"): the sequence run
+    ``cases`` times with ``iterations`` hypotheses per frame, every case with a sample sequence of its own.  One launch per batch of
+    frames covers all cases; the scripts' cross-frame rules are applied per case on the host."""
+
+    def __init__(self, model, iterations, cases=10, focus=FOCUS, cx=CX, cy=CY, threshold=0.005, inlier_threshold=0.01, seed=None,
+                 device=0, triangulation="scipy", cases_per_group=None, delaunay_workers=0):
+        if model not in EVAL_MODELS:
+            raise ValueError("model must be 'plane' or 'line'")
+        if triangulation not in ("scipy", "gpu"):
+            raise ValueError("triangulation must be 'scipy' or 'gpu'")
+        if not 1 <= int(iterations) <= MAX_EVAL_ITERATIONS:
+            raise ValueError("iterations must be in 1..%d" % MAX_EVAL_ITERATIONS)
+        if int(cases) < 1:
+            raise ValueError("cases must be at least 1")
+        self.ctx = _lib.default_context(device)
+        self.model, self.iterations, self.cases = model, int(iterations), int(cases)
+        self.focus, self.cx, self.cy = float(focus), float(cx), float(cy)
+        self.threshold, self.inlier_threshold = float(threshold), float(inlier_threshold)
+        self.seed = int.from_bytes(os.urandom(8), "little") if seed is None else int(seed) & (2 ** 64 - 1)
+        self.triangulation, self.delaunay_workers = triangulation, delaunay_workers
+        self.cases_per_group = 0 if cases_per_group is None else int(cases_per_group)  # (0: the library's default, one case per workgroup)
+        self.results = None                            # field -> (cases, frames) after run()
+        self.carried = None                            # (frames,) bool
+        self.degenerate = None                         # (cases, frames) bool: the refinement's sample named a vertex twice
+        self.last = None
+
+    # ---- one launch
+    def launch(self, points3d_list, priors, samples=None, tris=None, frame_base=0, stage=False, max_feat=None, timing=0, cases_per_group=None):
+        """``mvosr_height_pitch_eval_batch`` over the frames -> dict of host arrays, (F, C) per quantity (``model`` (F, C, 4),
+        ``n_selected`` (F,)).  ``samples``: None (the device draws), or per frame an array of list positions shaped (C, h, 2 or 3),
+        h <= iterations (None / shorter: the missing samples are spent).  ``stage``: also ``hyp_counts`` (F, C, H), ``list_mask``
+        (per frame (C, n_selected) bool) and ``point_list``."""
+        ctx, lib = self.ctx, self.ctx.lib
+        pts = [np.ascontiguousarray(np.asarray(p, dtype=np.float64).reshape(-1, 3)) for p in points3d_list]
+        F, H, Cn = len(pts), self.iterations, self.cases
+        if F == 0:
+            return None
+        rows = [np.ascontiguousarray(np.asarray(t, dtype=np.int32).reshape(-1, 3)) for t in tris] if tris is not None \
+            else _delaunay_rows(ctx, [np.ascontiguousarray(p[:, 0:2]) for p in pts], self.triangulation, self.delaunay_workers)
+        cnt = np.array([len(p) for p in pts], dtype=np.int32)
+        max_feat = int(cnt.max()) if max_feat is None else int(max_feat)
+        need = int(lib.mvosr_height_pitch_eval_lds_bytes(max_feat, H, EVAL_MODELS[self.model]))
+        if need > ctx.lds_per_block:
+            raise ValueError("a frame of %d features needs %d bytes of LDS, the device has %d" % (max_feat, need, ctx.lds_per_block))
+        spec_in, arrays, off, toff, planes, T = _pack_frames(pts, rows, priors)
+        if samples is not None:
+            sm = np.full((F, Cn, H, 3), -1, dtype=np.int32)                         # (-1: outside every list, the sample is spent)
+            for f, t in enumerate(samples):
+                if t is None:
+                    continue
+                t = np.asarray(t, dtype=np.int32)
+                if t.ndim != 3 or t.shape[0] != Cn or t.shape[2] not in (2, 3):
+                    raise ValueError("samples[%d] must be shaped (cases, h, 2 or 3)" % f)
+                h = min(H, t.shape[1])
+                sm[f, :, :h, :t.shape[2]] = t[:, :h]
+            spec_in.append(("samples", (F, Cn, H, 3), np.int32))
+            arrays["samples"] = sm
+        FC = (F, Cn)
+        spec_out = [("ransac_height", FC, np.float64), ("model", (F, Cn, 4), np.float64), ("best_ic", FC, np.int32), ("used", FC, np.int32),
+                    ("n_selected", F, np.int32), ("n_inliers", FC, np.int32), ("refined_normal", (F, Cn, 3), np.float64),
+                    ("refined_pitch", FC, np.float64), ("refined_mean", FC, np.float64), ("refined_std", FC, np.float64),
+                    ("height_t_mean", FC, np.float64), ("sum_y", FC, np.float64), ("sum_z", FC, np.float64), ("status", FC, np.int32)]
+        if stage:
+            spec_out += [("list_mask", (Cn, 3 * T), np.uint8), ("point_list", 3 * T, np.int32), ("hyp_counts", (F, Cn, H), np.int32)]
+        din, dout = ctx.block(spec_in), ctx.block(spec_out)
+        try:
+            din.upload(arrays)
+            dout.zero()
+            b = _batch_header(din, F, max_feat, planes.shape[1])
+            G = self.cases_per_group if cases_per_group is None else int(cases_per_group)
+            p = _lib.HeightPitchEvalParams(self.focus, self.cx, self.cy, MIN_POINTS, H, self.threshold, GOAL_FRACTION, self.inlier_threshold,
+                                           self.seed, int(frame_base), EVAL_MODELS[self.model], Cn, G)
+            o = _lib.HeightPitchEvalOutputs()
+            for k, tp in _lib.HeightPitchEvalOutputs._fields_:
+                if k == "list_stride":
+                    o.list_stride = 3 * T
+                elif k in dout:
+                    setattr(o, k, dout[k].ptr)
+            def call():
+                _lib.check(lib.mvosr_height_pitch_eval_batch(ctx.handle, C.byref(b), C.byref(p), din["prior"].ptr,
+                                                             din["samples"].ptr if samples is not None else None, C.byref(o)),
+                           "mvosr_height_pitch_eval_batch")
+            call()
+            kernel_ms = None
+            if timing > 0:
+                ev = ctx.event(), ctx.event()
+                ctx.record(ev[0])
+                for _ in range(int(timing)):
+                    call()
+                ctx.record(ev[1])
+                kernel_ms = ctx.elapsed_ms(*ev) / int(timing)
+                for e in ev:
+                    lib.mvosr_event_destroy(ctx.handle, e)
+            res = {k: dout[k].download() for k, _, _ in spec_out}
+            if kernel_ms is not None:
+                res["kernel_ms"] = kernel_ms
+        finally:
+            din.free()
+            dout.free()
+        if stage:
+            nsel = [max(int(m), 0) for m in res["n_selected"]]
+            res["list_mask"] = [res["list_mask"][:, 3 * toff[f]:3 * toff[f] + nsel[f]].astype(bool) for f in range(F)]
+            res["point_list"] = [res["point_list"][3 * toff[f]:3 * toff[f] + nsel[f]] for f in range(F)]
+        res["rows"] = rows
+        return res
+
+    # ---- the scripts' run
+    def run(self, frames, motion_ts, samples=None, tris=None, batch=512):
+        """``frames[i]`` is dump ``i + 1`` and its prior ``get_pitch(motion_ts[0:i + 2])`` (_eval.py:70, :80).  Returns a dict of the
+        six (cases, frames) arrays under RESULT_FIELDS' names.  An empty dump gives six zeros and leaves what is carried untouched
+        (:71-79); a frame with fewer than 12 list points repeats the previous frame's outputs of its case, ``height_t_mean`` under
+        the new prior (:184-186, :223); a first fitted frame with too few points raises ``IndexError`` (:188), a singular row
+        ``np.linalg.LinAlgError`` (:101).  Where the refinement's sample names a vertex twice, the refined values are NaN
+        (``self.degenerate``); the RANSAC height and the inlier number are not affected."""
+        n, Cn = len(frames), self.cases
+        ests = estimated_pitches(motion_ts, 1, n) if n else np.zeros(0)
+        out = {k: np.zeros((Cn, n), dtype=np.float64) for k in RESULT_FIELDS}
+        self.carried, self.degenerate = np.zeros(n, dtype=bool), np.zeros((Cn, n), dtype=bool)
+        # contiguous runs of non-empty dumps, at most `batch` frames each: the sample sequence's frame counter is the dump's
+        # index, so a split run draws what the whole run draws
+        runs = []
+        for i in range(n):
+            if not np.asarray(frames[i]).size:
+                continue
+            if runs and runs[-1][-1] == i - 1 and len(runs[-1]) < int(batch):
+                runs[-1].append(i)
+            else:
+                runs.append([i])
+        prev = None                                    # per case: the six values, sum_y, sum_z, degenerate — of the last fitted frame
+        for idx in runs:
+            r = self.launch([frames[i] for i in idx], [frame_prior(ests[i]) for i in idx], None if samples is None else [samples[i] for i in idx],
+                            None if tris is None else [tris[i] for i in idx], frame_base=idx[0])
+            self.last = r
+            for j, i in enumerate(idx):
+                st, n_sel = r["status"][j], int(r["n_selected"][j])
+                if np.any(st == ST_ERR_SINGULAR):
+                    raise np.linalg.LinAlgError("Singular matrix")                   # :101
+                if np.any((st == ST_ERR_MASK) | (st == ST_ERR_EMPTY)):
+                    raise ValueError("frame %d: %s" % (i, "no features or no triangles" if np.any(st == ST_ERR_EMPTY) else
+                                                       "a triangle names a vertex outside the frame"))
+                if np.any(st == ST_RS_FEW) and n_sel >= MIN_POINTS:
+                    raise ValueError("frame %d: no sample of the RANSAC had an inlier" % i)
+                if n_sel < MIN_POINTS:
+                    if prev is None:                                                 # :188 indexes the 1-D norm_prev of :55 with two indices
+                        raise IndexError("too many indices for array: array is 1-dimensional, but 2 were indexed")
+                    self.carried[i] = True
+                    cur = dict(prev)
+                    # :184-186 and the surviving `inliers`: everything repeats, but :223-224 see the new prior
+                    cur["height_t_mean"] = np.where(prev["degenerate"], np.nan,
+                                                    (prev["sum_z"] * math.sin(ests[i]) + prev["sum_y"] * math.cos(ests[i])) / prev["n_inliers"])
+                else:
+                    cur = {k2: np.array(r[k2][j], dtype=np.float64) for k2 in RESULT_FIELDS + ("sum_y", "sum_z")}
+                    cur["degenerate"] = (st & ST_HP_REFINE_DEGENERATE) != 0
+                prev = cur
+                for k2 in RESULT_FIELDS:
+                    out[k2][:, i] = cur[k2]
+                self.degenerate[:, i] = cur["degenerate"]
+        self.results = out
+        return out
+
+    def spread(self):
+        """Per frame the mean and the (population) std over the cases of each of the six quantities — what the runs exist for:
+        dict field -> (mean (frames,), std (frames,)).  Refined values of degenerate pairs are left out of their frame's figures."""
+        if self.results is None:
+            raise RuntimeError("run() first")
+        out = {}
+        with np.errstate(all="ignore"):
+            import warnings
+            with warnings.catch_warnings():
+                warnings.simplefilter("ignore", RuntimeWarning)
+                for k, v in self.results.items():
+                    out[k] = (np.nanmean(v, axis=0), np.nanstd(v, axis=0))
+        return out
+
+    def write_results(self, directory, input_id, input_date):
+        """The scripts' sixty files under the scripts' own names (_eval.py:250-265), in ``directory``/eval_ransac or
+        ``directory``/eval_ransac_line (created if missing).  Returns the paths."""
+        if self.results is None:
+            raise RuntimeError("run() first")
+        names = eval_file_names(self.model, input_id, input_date, self.iterations, self.cases)
+        os.makedirs(os.path.join(directory, EVAL_DIRS[self.model]), exist_ok=True)
+        for c in range(self.cases):
+            for k, field in enumerate(RESULT_FIELDS):
+                np.savetxt(os.path.join(directory, names[c * len(RESULT_FIELDS) + k]), self.results[field][c])
+        return [os.path.join(directory, x) for x in names]
+

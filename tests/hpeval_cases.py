@@ -1,0 +1,533 @@
+"""Frames and references for height_pitch_eval_kernel (csrc/mvosr_hpeval.hip) — shared by tests/test_hpeval_cases.py (CPU),
+tests/test_gpu_hpeval.py (the device) and tests/golden/make_golden_hpeval.py (the reference's own runs).  Test infrastructure.
+
+The two evaluation scripts, /root/reference/src/calculate_height_pitch_eval.py ("plane") and calculate_height_pitch_eval_line.py
+("line"), share rows and point list with calculate_height_pitch.py (tests/heightpitch_cases.py: `select`, `keep_bounds`) and
+differ from it after: the inliers are taken among the LIST entries, repeats included, the refinement runs over those, and the line
+script fits a y + b z + c = 0 over the list's (y, z).
+
+* `restate`: one (frame, case) of either script in NumPy float64, the sample positions as an input.  The refinement takes the plane
+  through the first three / the line through the first two list inliers in closed form (the kernel's form; the scripts ask an SVD
+  for the same null vector): the gap between the two on the scripts' own frames is what the golden stores as gap_*.
+* `reference`: the same in np.longdouble with error bounds, and the assertion that every integer is DECIDED.
+* `check_margins`: the generator's bands — no decision of a recorded run inside a rounding band.
+* crafted scenes: points of two parallel tilted planes 0.3 apart, rows as triples of them (vertices are shared: the list repeats).
+
+A model is a 4-vector in both cases: the plane's unit (n, d), the line's unit (a, b, 0, c); the sign rule reads slot 1 either way
+(n_y, _eval.py:178; b, _eval_line.py:178)."""
+import math
+
+import numpy as np
+
+import flat_cases as fc
+import heightpitch_cases as hc
+from flat_cases import U53
+from heightpitch_cases import GOAL, INLIER_THRESHOLD, MIN_POINTS, THRESHOLD, L, ST_EMPTY, ST_MASK, ST_RS_FEW, ST_SINGULAR  # noqa: F401
+
+MODELS = ("plane", "line")
+ST_DEGENERATE = 0x100                   # MVOSR_ST_HP_REFINE_DEGENERATE
+TILE = 512                              # kHpMaxHyp
+FIELDS = ("ransac_height", "refined_mean", "refined_std", "height_t_mean", "refined_pitch", "n_inliers")
+REFINED = ("refined_mean", "refined_std", "height_t_mean", "refined_pitch")
+
+
+def K_of(model):
+    return 2 if model == "line" else 3
+
+
+def coords(model, P):
+    """What the model is fitted to: (x, y, z), or the line's (y, z) (_eval_line.py:165: a_array[:,1:])."""
+    return P[:, 1:3] if model == "line" else P
+
+
+def vertex_samples(model, ids, positions):
+    """List positions (H, >= K) -> vertex samples (H, K); a position outside the list gives a repeated vertex: the spent sample."""
+    K = K_of(model)
+    pos = np.asarray(positions, dtype=np.int64).reshape(len(positions), -1)[:, :K]
+    ok = np.all((pos >= 0) & (pos < len(ids)), 1)
+    v = np.zeros_like(pos)
+    if len(ids):
+        v[ok] = np.asarray(ids, dtype=np.int64)[pos[ok]]
+    return v
+
+
+def spent(v):
+    return (v[:, 0] == v[:, 1]) if v.shape[1] == 2 else ((v[:, 0] == v[:, 1]) | (v[:, 0] == v[:, 2]) | (v[:, 1] == v[:, 2]))
+
+
+# ---- float64 ----------------------------------------------------------------------------------------------------------------
+def models_from(model, P, v):
+    """Unit 4-vectors of the hypotheses through the vertex samples v, as the kernels build them; a repeated vertex gives NaN."""
+    if model == "plane":
+        return hc.planes_from(P, v)
+    y0, z0, y1, z1 = P[v[:, 0], 1], P[v[:, 0], 2], P[v[:, 1], 1], P[v[:, 1], 2]
+    a, b = z1 - z0, -(y1 - y0)                                                       # estimate_road_norm.py:44-46, in closed form
+    c = -(a * y0 + b * z0)
+    with np.errstate(all="ignore"):
+        inv = 1.0 / np.sqrt(((a * a + b * b) + 0.0) + c * c)
+        m = np.stack([a * inv, b * inv, 0.0 * inv, c * inv], 1)
+    m[spent(v)] = np.nan
+    return m
+
+
+def residuals(model, P, m):
+    if model == "plane":
+        return hc.residuals(P, m)
+    return np.abs((P[:, 1] * m[0] + P[:, 2] * m[1]) + m[3])                          # estimate_road_norm.py:49, :74-75
+
+
+def refined_normal(model, S):
+    """Closed form of estimate / estimate_line on the sample S (K points), sign and length as the scripts fix them -> (3,)."""
+    if model == "plane":
+        e1, e2 = S[1] - S[0], S[2] - S[0]
+        n = np.array([e1[1] * e2[2] - e1[2] * e2[1], e1[2] * e2[0] - e1[0] * e2[2], e1[0] * e2[1] - e1[1] * e2[0]])
+        if n[1] < 0:                                                                 # _eval.py:200-201
+            n = -n
+        return n / np.sqrt((n[0] * n[0] + n[1] * n[1]) + n[2] * n[2])                # :203-205
+    ny, nz = S[1][2] - S[0][2], -(S[1][1] - S[0][1])
+    if nz < 0:                                                                       # _eval_line.py:201-202
+        ny, nz = -ny, -nz
+    ln = np.sqrt(ny * ny + nz * nz)
+    return np.array([0.0, ny / ln, nz / ln])
+
+
+def degenerate(model, inlier_ids):
+    """The flag's predicate: the first K set list positions name fewer than K vertices."""
+    K = K_of(model)
+    return len(set(int(i) for i in inlier_ids[:K])) < K
+
+
+def restate(model, pts, rows, est, positions, prev=None):
+    """One (frame, case) of the script's loop body (_eval.py:80-225).  positions: (H, K or 3) list positions (the script's
+    random.sample, recorded).  prev: the previous fitted frame's dict of this case.  -> dict; raises IndexError on a first frame
+    with too few points."""
+    P = hc.back_project(pts)
+    rows = np.asarray(rows, dtype=np.int64).reshape(-1, 3)
+    keep, ids, _, _ = hc.select(P, rows, est)
+    r = {"n_selected": len(ids), "ids": ids.astype(np.int32), "carried": len(ids) < MIN_POINTS}
+    if not r["carried"]:                                                             # :159
+        v = vertex_samples(model, ids, positions)
+        m = models_from(model, P, v)
+        Q = P[ids]
+        with np.errstate(invalid="ignore"):
+            counts = np.array([int(np.sum(residuals(model, Q, mm) < THRESHOLD)) for mm in m])
+        best, best_ic, used = fc.replay(counts, len(ids), GOAL)
+        mod = m[best] if m[best][1] >= 0 else -m[best]                               # :178-180
+        mask = residuals(model, Q, mod) < INLIER_THRESHOLD                           # :167: over the LIST
+        r.update(hyp_counts=counts.astype(np.int32), best=best, best_ic=best_ic, used=used, model=mod, list_mask=mask,
+                 ransac_height=1 / (math.sqrt((mod[0] * mod[0] + mod[1] * mod[1]) + mod[2] * mod[2]) / -mod[3]),   # :176-187
+                 inliers=Q[mask], inlier_ids=ids[mask])
+    else:
+        if prev is None:
+            raise IndexError("too many indices for array")                           # :188 on the 1-D norm_prev of :55
+        r.update(ransac_height=prev["ransac_height"], inliers=prev["inliers"], inlier_ids=prev["inlier_ids"], list_mask=None)
+    inl = r["inliers"]
+    r["degenerate"] = degenerate(model, r["inlier_ids"])
+    r["n_inliers"] = len(inl)                                                        # :193
+    if r["degenerate"]:
+        r.update(refined_normal=np.full(3, np.nan), refined_pitch=np.nan, refined_mean=np.nan, refined_std=np.nan, height_t_mean=np.nan)
+    else:
+        nh = refined_normal(model, inl)
+        hs = (inl[:, 0] * nh[0] + inl[:, 1] * nh[1]) + inl[:, 2] * nh[2] if model == "plane" else inl[:, 1] * nh[1] + inl[:, 2] * nh[2]
+        r.update(refined_normal=nh, refined_pitch=math.asin(nh[1]), refined_mean=np.mean(hs), refined_std=np.std(hs),
+                 height_t_mean=np.mean(inl[:, 2] * math.sin(est) + inl[:, 1] * math.cos(est)))    # :208-224
+    # (the scripts' height_t_mean does not read the refined normal: it is what they write for a degenerate pair too)
+    r["height_t_mean_script"] = float(np.mean(inl[:, 2] * math.sin(est) + inl[:, 1] * math.cos(est))) if len(inl) else np.nan
+    r.update(sum_y=float(np.sum(inl[:, 1])), sum_z=float(np.sum(inl[:, 2])))
+    return r
+
+
+# ---- np.longdouble, with bounds -----------------------------------------------------------------------------------------------
+def _terms(model, P, v):
+    """Unnormalised hypotheses in np.longdouble and the bounds on a float64 evaluation of the same expressions:
+    n (H, dims), d, dn, dd, N — flat_cases._plane_terms, and its analogue for the line (one subtraction per component)."""
+    if model == "plane":
+        return fc._plane_terms(P, v)
+    p0, p1 = P[v[:, 0], 1:3].astype(L), P[v[:, 1], 1:3].astype(L)
+    n = np.stack([p1[:, 1] - p0[:, 1], -(p1[:, 0] - p0[:, 0])], 1)
+    dn = L(1.1 * U53) * np.abs(n)
+    d = -np.sum(n * p0, 1)
+    dd = np.sum(dn * np.abs(p0), 1) + L(2.1 * U53) * np.sum(np.abs(n * p0), 1)
+    N = np.sqrt(np.sum(n * n, 1) + d * d)
+    return n, d, dn, dd, N
+
+
+def count_bounds(model, P, ids, v, threshold=THRESHOLD, chunk=64):
+    """flat_cases.count_bounds for either model: per hypothesis the list entries (repeats counted) surely / possibly within threshold."""
+    uniq, mult = np.unique(np.asarray(ids), return_counts=True)
+    Q = coords(model, P)[uniq].astype(L)
+    lo, hi = np.zeros(len(v), np.int64), np.zeros(len(v), np.int64)
+    for s in range(0, len(v), chunk):
+        tr = v[s:s + chunk]
+        n, d, dn, dd, N = _terms(model, P, tr)
+        with np.errstate(all="ignore"):
+            r = np.abs(Q @ n.T + d[None, :]) / N[None, :]
+            eps = (np.abs(Q) @ dn.T + dd[None, :]) / N[None, :] + r * (np.sqrt(np.sum(dn * dn, 1) + dd * dd) / N + 8 * U53)[None, :] \
+                + L(4.1 * U53) * (np.abs(Q) @ np.abs(n).T + np.abs(d)[None, :]) / N[None, :]
+            eps = 2 * eps
+            a = np.where(r < threshold - eps, mult[:, None], 0).sum(0)
+            b = np.where(~(r >= threshold + eps), mult[:, None], 0).sum(0)
+        rep = spent(tr)
+        lo[s:s + chunk], hi[s:s + chunk] = np.where(rep, 0, a), np.where(rep, 0, b)
+    return lo, hi
+
+
+def model_ld(model, P, sample):
+    """The unit model through one vertex sample in np.longdouble, slot 1 >= 0, the bound on a float64 model's components, and
+    whether the sign of slot 1 is decided -> (m (dims + 1,), tol, sign_decided)."""
+    n, d, dn, dd, N = _terms(model, P, np.asarray(sample).reshape(1, -1))
+    m = np.concatenate([n[0], d]) / N[0]
+    err = np.sqrt(np.sum(dn[0] ** 2) + dd[0] ** 2) / N[0]
+    tol = 2.0 * float(2 * err + 8 * U53)
+    return (m if m[1] >= 0 else -m), tol, bool(abs(m[1]) > tol)
+
+
+def four(model, m):
+    m = np.asarray(m, dtype=np.float64)
+    return m if model == "plane" else np.array([m[0], m[1], 0.0, m[2]])
+
+
+def reference(model, pts, rows, est, positions):
+    """One (frame, case) in np.longdouble -> dict of expected values and bounds; `decided`: every integer output, every sign and
+    the degenerate flag are fixed by the bounds."""
+    P = hc.back_project(pts)
+    rows = np.asarray(rows, dtype=np.int64).reshape(-1, 3)
+    sure, maybe, q = hc.keep_bounds(P, rows, est)
+    r = {"decided": bool(np.array_equal(sure, maybe)), "keep": sure}
+    ids = rows[sure].reshape(-1)
+    r.update(n_selected=len(ids), ids=ids.astype(np.int32))
+    if not r["decided"] or len(ids) < MIN_POINTS:
+        r["status"] = ST_RS_FEW
+        return r
+    K = K_of(model)
+    v = vertex_samples(model, ids, positions)
+    lo, hi = count_bounds(model, P, ids, v)
+    r["decided"] &= bool(np.array_equal(lo, hi))
+    best, best_ic, used = fc.replay(lo, len(ids), GOAL)
+    r.update(hyp_counts=lo.astype(np.int32), best=best, best_ic=best_ic, used=used, status=0 if best >= 0 else ST_RS_FEW)
+    if best < 0 or not r["decided"]:
+        return r
+    m, tol, sign_ok = model_ld(model, P, v[best])
+    r["decided"] &= sign_ok
+    Cm = coords(model, P)
+    QL = Cm[ids].astype(L)
+    res = np.abs(QL @ m[:-1] + m[-1])
+    eps = 2 * L(4.1 * U53) * (np.abs(QL) @ np.abs(m[:-1]) + abs(m[-1])) + L(tol) * (np.sum(np.abs(QL), 1) + 1)
+    r["decided"] &= bool(np.all(np.abs(res - L(INLIER_THRESHOLD)) > eps))
+    mask = np.asarray(res < INLIER_THRESHOLD)
+    nn = np.sqrt(np.sum(m[:-1] * m[:-1]))
+    k = int(mask.sum())
+    inl_ids = ids[mask]
+    r.update(model=four(model, m), model_tol=tol, list_mask=mask, n_inliers=k, inlier_ids=inl_ids,
+             ransac_height=float(-m[-1] / nn), ransac_height_tol=2 * float(tol * (1 / abs(m[-1]) + 1 / nn) + 8 * U53),
+             degenerate=degenerate(model, inl_ids))
+    if r["degenerate"]:
+        r["status"] = ST_DEGENERATE
+    inl = QL[mask]
+    yz = Cm[ids][mask][:, -2:].astype(L)                                              # (y, z) of the list inliers
+    r.update(sum_y=float(np.sum(yz[:, 0])), sum_y_tol=float((k + 4) * U53 * np.sum(np.abs(yz[:, 0]))),
+             sum_z=float(np.sum(yz[:, 1])), sum_z_tol=float((k + 4) * U53 * np.sum(np.abs(yz[:, 1]))))
+    if r["degenerate"]:
+        return r
+    first = inl_ids[:K].astype(np.int64)
+    if model == "plane":
+        n, _, dn, _, _ = fc._plane_terms(P, first.reshape(1, 3))
+        n, dn, sl = n[0], dn[0], 1                                                    # the sign rule reads n_y
+    else:
+        n, _, dn, _, _ = _terms("line", P, first.reshape(1, 2))
+        n, dn, sl = n[0], dn[0], 1                                                    # ... the z component of (n_y, n_z)
+    r["decided"] &= bool(abs(n[sl]) > 2 * dn[sl])
+    ln = np.sqrt(np.sum(n * n))
+    nh = (n if n[sl] >= 0 else -n) / ln
+    e_n = 2 * float(2 * np.sqrt(np.sum(dn * dn)) / ln + 8 * U53)                      # every component of n^, absolute
+    hs = inl @ nh
+    d_h = e_n * np.sum(np.abs(inl), 1) + L(4.1 * U53) * (np.abs(inl) @ np.abs(nh))     # every inlier's distance, absolute
+    mean = np.mean(hs)
+    ts = yz[:, 1] * L(math.sin(est)) + yz[:, 0] * L(math.cos(est))
+    py = nh[1] if model == "plane" else nh[0]                                         # the y component: what asin reads
+    r.update(refined_normal=(nh if model == "plane" else np.concatenate([[0], nh])).astype(np.float64), refined_normal_tol=e_n,
+             refined_pitch=float(np.arcsin(py)), refined_pitch_tol=hc.asin_bound(py, e_n) + 4 * U53,
+             refined_mean=float(mean), refined_mean_tol=float(np.mean(d_h) + (k + 4) * U53 * np.mean(np.abs(hs))),
+             refined_std=float(np.sqrt(np.mean((hs - mean) ** 2))),
+             refined_std_tol=2 * float(np.max(d_h) + (k + 8) * U53 * np.max(np.abs(hs))),
+             height_t_mean=float(np.mean(ts)),
+             height_t_mean_tol=float((k + 6) * U53 * np.mean(np.abs(yz[:, 1] * L(math.sin(est))) + np.abs(yz[:, 0] * L(math.cos(est))))))
+    return r
+
+
+def within(r, ref, name=""):
+    """A float64 result `r` (restate's dict, or the device's values under the same keys) against the reference and its bounds."""
+    assert r["n_selected"] == ref["n_selected"] and np.array_equal(r["ids"], ref["ids"]), name
+    if ref["status"] == ST_RS_FEW:
+        return
+    assert np.array_equal(r["hyp_counts"], ref["hyp_counts"]), (name, np.nonzero(np.asarray(r["hyp_counts"]) != ref["hyp_counts"])[0][:8])
+    assert (int(r["best_ic"]), int(r["used"])) == (ref["best_ic"], ref["used"]), (name, r["best_ic"], r["used"], ref["best_ic"], ref["used"])
+    assert np.array_equal(r["list_mask"], ref["list_mask"]) and int(r["n_inliers"]) == ref["n_inliers"], name
+    assert bool(r["degenerate"]) == ref["degenerate"], name
+    assert np.all(np.abs(r["model"] - ref["model"]) <= ref["model_tol"]), (name, r["model"], ref["model"])
+    assert abs(r["ransac_height"] - ref["ransac_height"]) <= ref["ransac_height_tol"] * abs(ref["ransac_height"]), name
+    for k in ("sum_y", "sum_z"):
+        assert abs(r[k] - ref[k]) <= ref[k + "_tol"], (name, k, r[k], ref[k])
+    if ref["degenerate"]:
+        assert all(np.isnan(r[k]) for k in REFINED) and np.isnan(r["refined_normal"]).all(), name
+        return
+    for k in REFINED:
+        assert abs(r[k] - ref[k]) <= ref[k + "_tol"], (name, k, r[k], ref[k], ref[k + "_tol"])
+    assert np.all(np.abs(r["refined_normal"] - ref["refined_normal"]) <= ref["refined_normal_tol"]), name
+
+
+# ---- the generator's bands ----------------------------------------------------------------------------------------------------
+def check_margins(model, pts, rows, est, positions):
+    """True when no decision of this (frame, case) lies inside a rounding band: every row's pitch further than
+    flat_cases.pitch_margin_deg from both window edges; every list residual further than 2 . 4.1 . 2^-53 . (sum |p_i| |m_i| + |m_last|)
+    from its threshold — for the line (|y||a| + |z||b| + |c|) —, under every hypothesis at 0.005 and under the best model at 0.01."""
+    P = hc.back_project(pts)
+    sure, maybe, q = hc.keep_bounds(P, rows, est)
+    if not np.array_equal(sure, maybe):
+        return False
+    ids = np.asarray(rows)[sure].reshape(-1)
+    if len(ids) < MIN_POINTS:
+        return True
+    m = models_from(model, P, vertex_samples(model, ids, positions))
+    Q = P[ids]
+    A = np.abs(Q) if model == "plane" else np.abs(np.stack([Q[:, 1], Q[:, 2], 0 * Q[:, 0]], 1))
+    for mm in m:
+        if np.isnan(mm[0]):
+            continue
+        band = 2 * 4.1 * U53 * (A @ np.abs(mm[:3]) + abs(mm[3]))
+        if np.any(np.abs(residuals(model, Q, mm) - THRESHOLD) <= band):
+            return False
+    cnt = np.array([np.sum(residuals(model, Q, mm) < THRESHOLD) for mm in np.nan_to_num(m, nan=1e300)])
+    best = fc.replay(cnt, len(ids), GOAL)[0]
+    band = 2 * 4.1 * U53 * (A @ np.abs(m[best][:3]) + abs(m[best][3]))
+    return not np.any(np.abs(residuals(model, Q, m[best]) - INLIER_THRESHOLD) <= band)
+
+
+# ---- the device draw (include/mvosr.h, mvosr_height_pitch_eval_batch), restated -------------------------------------------------
+_M64 = (1 << 64) - 1
+
+
+def draw_positions(model, seed, frame_counter, case, n_hyp, M):
+    """(n_hyp, 3) list positions of (seed, frame, case): heightpitch_cases.draw_positions under the case's key; the line's pair is
+    the triple's first two draws (column 2 is -1)."""
+    fkey = hc._mix64((seed ^ ((frame_counter * 0xD1B54A32D192ED03) & _M64)) & _M64)
+    key = hc._mix64(fkey ^ (((case + 1) * 0xA0761D6478BD642F) & _M64))
+    out = np.full((n_hyp, 3), -1, dtype=np.int32)
+    for h in range(n_hyp):
+        hk = hc._mix64((key + h) & _M64)
+        r0, r1, r2 = hc._mix64(hk), hc._mix64((hk + 1) & _M64), hc._mix64((hk + 2) & _M64)
+        i0 = (r0 * M) >> 64
+        i1 = (r1 * (M - 1)) >> 64
+        i1 += i1 >= i0
+        if model == "line":
+            out[h, :2] = (i0, i1)
+            continue
+        i2 = (r2 * (M - 2)) >> 64
+        lo, hi = min(i0, i1), max(i0, i1)
+        i2 += i2 >= lo
+        i2 += i2 >= hi
+        out[h] = (i0, i1, i2)
+    return out
+
+
+# ---- crafted scenes -------------------------------------------------------------------------------------------------------------
+class Scene:
+    """pts (N, 3) [u, v, depth]; rows (T, 3); est; positions (C, H, 3) list positions (the line reads two)."""
+
+    def __init__(self, name, pts, rows, est, positions, max_feat=None):
+        self.name, self.est, self.max_feat = name, float(est), max_feat
+        self.pts = np.ascontiguousarray(pts, dtype=np.float64).reshape(-1, 3)
+        self.rows = np.ascontiguousarray(rows, dtype=np.int32).reshape(-1, 3)
+        self.positions = np.ascontiguousarray(positions, dtype=np.int32)
+        self.ids = hc.select(hc.back_project(self.pts), self.rows.astype(np.int64), self.est)[1] if len(self.rows) else np.zeros(0, np.int64)
+        self.M = len(self.ids)
+
+
+NA, NB, NO = 40, 16, 8                  # vertices of plane A (0 ..), of plane B (NA ..), A's first NO lifted by 0.03 (NA + NB ..)
+A0, B0, O0 = 0, NA, NA + NB
+
+
+def _on_plane(rng, k, h, tilt_deg):
+    t = np.deg2rad(tilt_deg)
+    x, z = rng.uniform(-8.0, 8.0, k), rng.uniform(6.0, 30.0, k)
+    return np.stack([x, (h - z * np.sin(t)) / np.cos(t), z], 1)                      # y cos t + z sin t = h
+
+
+def _triple(rng, xyz, lo, n, min_area=12.0):
+    """Three vertices of [lo, lo + n) that span at least min_area in (x, z): a well-conditioned row."""
+    while True:
+        t = lo + rng.choice(n, 3, replace=False)
+        a, b, c = xyz[t][:, [0, 2]]
+        if abs((b[0] - a[0]) * (c[1] - a[1]) - (b[1] - a[1]) * (c[0] - a[0])) >= 2 * min_area:
+            return t
+
+
+def build(name, seed, rows, tilt=1.0, H=64, C=1, first=None, max_feat=None, draw=True):
+    """rows: a list of "A" / "B" (a random triple of that plane's vertices), "W" (a wall triangle with vertices of its own, never
+    kept) or explicit vertex triples.  Plane A: y cos t + z sin t = 1.7, plane B: 2.0, the lifted copies of A's first NO vertices
+    0.03 below A (not inliers of A at 0.01, their rows still inside the window).  tilt < 0: the line model's b < 0, its height
+    negative.  first: (C?, h, 3) list positions for the first hypotheses of every case; the others are seeded draws over the list,
+    which repeat vertices now and then: spent samples."""
+    rng = np.random.default_rng(seed)
+    A, B = _on_plane(rng, NA, 1.7, tilt), _on_plane(rng, NB, 2.0, tilt)
+    O = A[:NO] + np.array([0.4, 0.03, 0.0])
+    xyz = [A, B, O]
+    n = NA + NB + NO
+    base = np.concatenate(xyz)
+    out = []
+    for r in rows:
+        if isinstance(r, str) and r == "W":
+            xyz.append(hc.wall_tri(rng))
+            out.append([n, n + 1, n + 2])
+            n += 3
+        elif isinstance(r, str):
+            out.append(_triple(rng, base, A0 if r == "A" else B0, NA if r == "A" else NB))
+        else:
+            out.append(list(r))
+    pts = hc.project(np.concatenate(xyz))
+    s = Scene(name, pts, np.array(out), 0.0, np.zeros((C, H, 3), np.int32), max_feat)
+    pos = rng.integers(0, max(s.M, 1), (C, H, 3)).astype(np.int32) if draw else np.full((C, H, 3), -1, np.int32)
+    if first is not None:
+        first = np.asarray(first, dtype=np.int32)
+        first = np.broadcast_to(first, (C,) + first.shape[-2:])
+        pos[:, :first.shape[1]] = first
+    s.positions = pos
+    return s
+
+
+_CRAFTED = {}
+MIX = ["A"] * 7 + ["B"] * 3 + ["W"] * 2                                               # 70 % of the kept entries on A: no stop at 0.8
+
+
+def crafted():
+    """name -> Scene.  Every scene's integers are decided by `reference` for both models (test_hpeval_cases.py asserts it)."""
+    if _CRAFTED:
+        return _CRAFTED
+    c = _CRAFTED
+    rng = np.random.default_rng(5)
+
+    def mix(k):
+        return [MIX[i] for i in rng.integers(0, len(MIX), k)]
+    c["min12"] = build("min12", 1, ["A", "W", "A", "B", "A"], H=16, C=3)                                  # M = 12: the minimum (:159)
+    c["few9"] = build("few9", 2, ["A", "W", "A", "B"], H=16, C=3)                                         # M = 9: carried
+    c["mix60"] = build("mix60", 3, mix(24), H=65, C=3)
+    c["neg"] = build("neg", 4, mix(24), tilt=-1.0, H=64, C=3)                                             # the line's b < 0: a negative height
+    c["cases10"] = build("cases10", 5, mix(30), H=63, C=10)
+    # H = 513 crosses a tile.  best_late: hypotheses 0 .. 511 are spent but for an A sample of count ~ 0.7 M at 3, the 513th names
+    # three B vertices and changes nothing; goal_late: 90 % A entries, every sample of the first tile mixes planes or is spent, the
+    # stop comes at hypothesis 512
+    rowsA = ["A"] * 18 + ["B"] * 2
+    g = build("goal_late", 6, rowsA, H=513, C=2, draw=False)
+    g.positions[:, 7] = [54, 57, 1]                                                                      # two B entries and one of A: a few inliers
+    g.positions[:, 512] = _first_kind(g, "A")
+    c["goal_late"] = g
+    b = build("best_first_tile", 7, mix(24), H=513, C=2, draw=False)
+    b.positions[:, 3] = _first_kind(b, "A")
+    b.positions[:, 512] = _first_kind(b, "B")
+    c["best_first_tile"] = b
+    b = build("best_second_tile", 8, mix(24), H=513, C=2, draw=False)
+    b.positions[:, 3] = _first_kind(b, "B")
+    b.positions[:, 512] = _first_kind(b, "A")
+    c["best_second_tile"] = b
+    c["tile512"] = build("tile512", 9, mix(24), H=512, C=1)
+    h1 = build("h1", 10, mix(24), H=1, C=2, draw=False)
+    h1.positions[:, 0] = _first_kind(h1, "A")
+    c["h1"] = h1
+    # the list mask's words: M = 189, 192 (three words exactly), 195
+    for k in (63, 64, 65):
+        c["words%d" % (3 * k)] = build("words%d" % (3 * k), 20 + k, ["A" if i % 3 else "B" for i in range(k)] + ["W"] * 3, H=32, C=2)
+    # the register chunk of 512 x 8 = 4096 entries: M = 4092, 4095, 4098 (M is a multiple of 3), rows far beyond 2 N: max_feat states them
+    for k in (1364, 1365, 1366):
+        c["chunk%d" % (3 * k)] = build("chunk%d" % (3 * k), 30 + k, ["A" if i % 4 else "B" for i in range(k)], H=8, C=2, max_feat=700)
+    # the best model fits the LAST kept row only (parallel planes elsewhere): inliers at M - 3 .. M - 1; and the first row only
+    lastrow = ["B"] * 21 + [[O0, O0 + 1, O0 + 2]]
+    c["inliers_last"] = build("inliers_last", 11, lastrow, H=2, C=1, first=[[63, 64, 65], [63, 64, 65]], draw=False)
+    c["inliers_first"] = build("inliers_first", 12, [[O0, O0 + 1, O0 + 2]] + ["B"] * 21, H=2, C=1, first=[[0, 1, 2], [0, 1, 2]], draw=False)
+    # the refinement's sample over two wavefronts' row segments: 70 rows, wavefront 0 has rows 0 .. 63; row 63 holds one inlier
+    strad = ["B"] * 63 + [[O0, O0 + 1, A0 + 1], [A0 + 2, A0 + 3, A0 + 4]] + ["A"] * 5
+    c["straddle"] = build("straddle", 13, strad, H=4, C=2, first=[[3 * 64, 3 * 64 + 1, 3 * 64 + 2]], draw=False)
+    # a degenerate refinement sample: the first inliers are A1, A1 (line) / A1, A1, A2 (plane)
+    deg = ["B"] * 4 + [[O0, O0 + 1, A0 + 1], [A0 + 1, A0 + 2, A0 + 3]] + ["A"] * 6
+    c["degenerate"] = build("degenerate", 16, deg, H=4, C=2, first=[[3 * 5, 3 * 5 + 1, 3 * 5 + 2]], draw=False)
+    # spent samples: outside the list, a vertex twice through two list positions, a position twice
+    sp = build("spent", 15, [[A0, A0 + 1, A0 + 2], [A0, A0 + 3, A0 + 4]] + ["A"] * 4 + ["B"] * 2, H=12, C=2, draw=False)
+    sp.positions[:, :7] = [[0, 3, 5], [3, 0, 7], [-1, 0, 1], [2, 1 << 20, 1], [0, 0, 1], [sp.M, 1, 2], [1, 2, 4]]
+    c["spent"] = sp
+    # refusals
+    s = build("singular", 18, ["A"] * 5 + [[A0, A0 + 1, A0 + 2]], H=8, C=2)
+    s.pts[[A0, A0 + 1, A0 + 2], 0] = hc.CX                                             # x = depth * 0 / focus = 0 for the row's three vertices: a zero first pivot, exactly
+    c["singular"] = s
+    b = build("badid", 17, ["A"] * 5 + ["B"], H=8, C=2)
+    b.rows[2, 1] = len(b.pts)
+    c["badid"] = b
+    c["empty"] = Scene("empty", np.zeros((0, 3)), np.zeros((0, 3)), 0.0, np.full((2, 8, 3), -1))
+    return c
+
+
+def _first_kind(scene, kind):
+    """List positions of three entries of the first kept row whose vertices all lie on plane `kind`."""
+    lo, hi = (A0, A0 + NA) if kind == "A" else (B0, B0 + NB)
+    ids = scene.ids.reshape(-1, 3)
+    for r, t in enumerate(ids):
+        if np.all((t >= lo) & (t < hi)):
+            return [3 * r, 3 * r + 1, 3 * r + 2]
+    raise AssertionError("no row of plane " + kind)
+
+
+NO_REF = ("empty", "singular", "badid")
+
+
+_REFS = {}
+
+
+def ref_for(model, s, c, positions=None):
+    """The reference of scene s, case c (computed once, shared by the tests)."""
+    key = (model, s.name, c, None if positions is None else np.asarray(positions).tobytes())
+    if key not in _REFS:
+        _REFS[key] = reference(model, s.pts, s.rows, s.est, s.positions[c] if positions is None else positions)
+    return _REFS[key]
+
+
+# ---- the fixture ----------------------------------------------------------------------------------------------------------------
+def dump_of(spec):
+    """A fixture frame from its spec: ("synth", frame, n, seed) / ("wall", seed, n) / ("empty",)."""
+    from mvoscalerecovery_amd import synth
+    if spec[0] == "synth":
+        f3, f2 = synth.synth_frame(spec[1], spec[2], base_seed=spec[3])
+        return np.stack([f2[:, 0], f2[:, 1], f3[:, 2]], 1)
+    if spec[0] == "wall":
+        return hc.wall_frame(spec[1], spec[2])
+    return np.zeros((0, 3))
+
+
+def load_golden():
+    """tests/golden/hpeval.npz -> {model: {case: dict}}; the inputs are regenerated from the stored seeds and checked against the
+    stored checksums."""
+    import json
+    import os
+    import sys
+    here = os.path.dirname(os.path.abspath(__file__))
+    if os.path.dirname(here) not in sys.path:
+        sys.path.insert(0, os.path.dirname(here))
+    z = np.load(os.path.join(here, "golden", "hpeval.npz"), allow_pickle=False)
+    meta = json.loads(str(z["meta"]))
+    out = {m: {} for m in MODELS}
+    for case, cm in meta["cases"].items():
+        frames = [dump_of(fr["spec"]) for fr in cm["frames"]]
+        for fr, d in zip(cm["frames"], frames):
+            assert hc.crc(d) == fr["crc"], "synthetic generator drifted from the fixture"
+        mot = hc.motions(cm["motion_seed"], len(frames) + 2)
+        assert hc.crc(mot) == cm["motion_crc"]
+        rows = [z["%s_rows%d" % (case, i)].astype(np.int32) if "%s_rows%d" % (case, i) in z.files else np.zeros((0, 3), np.int32)
+                for i in range(len(frames))]
+        for model in MODELS:
+            pre = "%s_%s_" % (model, case)
+            g = {"frames": frames, "rows": rows, "motion": mot, "meta": cm, "run": cm[model], "priors": z[case + "_priors"]}
+            for k in FIELDS + ("suitable",):
+                if pre + k in z.files:
+                    g[k] = z[pre + k]
+            for k in ("positions", "model", "best_ic", "mask"):
+                g[k] = [(z[pre + k + str(i)] if pre + k + str(i) in z.files else None) for i in range(len(frames))]
+            out[model][case] = g
+    out["meta"] = meta
+    return out
