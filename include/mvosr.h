@@ -590,6 +590,52 @@ int mvosr_flat_ransac_batch(mvosr_ctx *ctx, const mvosr_batch *b, const int32_t 
                             const int32_t *id_triples, const int64_t *frame_ids, const int32_t *dt_status,
                             const mvosr_rescale_outputs *o, int64_t max_tri);
 
+/* ---- C runs of a sequence at once (/root/reference/test_off_line.sh:4-16 runs main_offline.py ten times on one saved dict) ---- */
+
+/* which form of the point list a frame's inlier counts were taken over (count_form; the counts do not depend on it) */
+enum mvosr_cases_form {
+    MVOSR_CASES_FORM_NONE = 0,   /* the frame was not fitted                                                              */
+    MVOSR_CASES_FORM_GATHER = 1, /* distinct vertices with multiplicities, coordinates gathered by id                     */
+    MVOSR_CASES_FORM_PACKED = 2  /* at most 1024 distinct vertices: coordinates and multiplicities side by side in LDS    */
+};
+
+/* outputs of mvosr_flat_ransac_cases_batch (device pointers; C = n_cases; the optional ones may be NULL) */
+typedef struct mvosr_rescale_cases_outputs {
+    double *raw_scale;           /* [F][C] as mvosr_rescale_outputs.raw_scale, per case; NaN where the case's status != 0 */
+    double *model;               /* [F][C][4] */
+    int32_t *best_ic, *used;     /* [F][C] */
+    int32_t *status;             /* [F][C] 0, MVOSR_ST_RS_FEW, MVOSR_ST_ERR_MASK, MVOSR_ST_ERR_EMPTY */
+    int32_t *hyp_counts;         /* optional [F][C][n_hyp] */
+    int32_t *count_form;         /* optional [F] enum mvosr_cases_form */
+} mvosr_rescale_cases_outputs;
+
+/*
+ * The plane fit of mvosr_flat_ransac_batch for n_cases sample sequences of every frame in ONE launch, the deterministic stages
+ * not repeated.  It runs behind a launch of mvosr_flat_ransac_batch over the same batch, keep, dt_status and max_tri that was asked
+ * for tri_flags, and reads per frame: the features with keep[i] >= 0 compacted in order (the numbering of b->tri2's ids), b->tri2
+ * with its counts, and tri_flags (laid out like tri2), whose bit 2 marks a kept row.  The point list is rebuilt in that kernel's
+ * order — kept rows in row order, three vertex ids each, repeats included (/root/reference/src/rescale.py:101) —; the draw indexes
+ * list positions.  Hypothesis h of case c of frame f takes mvosr_flat_ransac_batch's draw with
+ *     key = mix(case_seeds[c] ^ (frame counter) * 0xD1B54A32D192ED03),   frame counter = frame_ids ? frame_ids[f] : rp->frame_base + f
+ * so case c is, bit for bit, what mvosr_flat_ransac_batch returns with rp->seed = case_seeds[c] (rp->seed itself is not read; nor
+ * are good_bits, min_valid, loose_deg, tight_deg and height_factor).  id_triples (optional, [F][C][n_hyp][3] survivor-numbered
+ * vertex ids) replaces the draw as in that call.  Counts, replay rule, sign rule and raw scale are that call's.
+ * Grid: frames x ceil(n_cases / cases_per_group) workgroups; a workgroup loads the frame and builds the list once and loops over its
+ * cases (cases_per_group 0: the measured default; the results do not depend on it).  case_seeds: [n_cases] device array.
+ * Statuses per (frame, case): MVOSR_ST_RS_FEW — a list shorter than ransac_min_points, or no hypothesis with an inlier —;
+ * MVOSR_ST_ERR_MASK — feat_cnt[f] > b->max_feat or more rows than max_tri (refused before LDS is touched), or a kept row that names
+ * a vertex outside the survivors —; MVOSR_ST_ERR_EMPTY — no features, no rows, or dt_status[f] != 0 (skipped like a declined frame).
+ * A case that is not fitted has NaN raw_scale and model, best_ic = used = 0; its hyp_counts are not written.  The heights are not
+ * recomputed here: what mvosr_flat_ransac_batch says of the FRAME — MVOSR_ST_ERR_SINGULAR, or MVOSR_ST_ERR_MASK for a row that is
+ * not kept — is that launch's status to read (rescale.ScaleEstimator.raw_scale_cases_batch merges the two).
+ */
+int mvosr_flat_ransac_cases_batch(mvosr_ctx *ctx, const mvosr_batch *b, const int32_t *keep, const mvosr_rescale_params *rp,
+                                  const uint64_t *case_seeds, int32_t n_cases, int32_t cases_per_group, const int32_t *id_triples,
+                                  const int64_t *frame_ids, const int32_t *dt_status, const uint8_t *tri_flags,
+                                  const mvosr_rescale_cases_outputs *o, int64_t max_tri);
+/* dynamic LDS a launch asks for at (b->max_feat, max_tri (<= 0: 2 * max_feat), n_hyp) */
+size_t mvosr_flat_ransac_cases_lds_bytes(int max_feat, int64_t max_tri, int n_hyp);
+
 /* ---- GraphGrow: the road region grown over triangle adjacency (/root/reference/src/graph.py:39-107) ---------------- */
 
 typedef struct mvosr_grow_params {

@@ -80,6 +80,15 @@ class RescaleOutputs(C.Structure):
                 ("tri_flags", C.c_void_p), ("hyp_counts", C.c_void_p)]
 
 
+class RescaleCasesOutputs(C.Structure):
+    """mvosr_rescale_cases_outputs"""
+    _fields_ = [("raw_scale", C.c_void_p), ("model", C.c_void_p), ("best_ic", C.c_void_p), ("used", C.c_void_p),
+                ("status", C.c_void_p), ("hyp_counts", C.c_void_p), ("count_form", C.c_void_p)]
+
+
+CASES_FORM_NONE, CASES_FORM_GATHER, CASES_FORM_PACKED = 0, 1, 2      # enum mvosr_cases_form
+
+
 class GrowParams(C.Structure):
     """mvosr_grow_params"""
     _fields_ = [("threshold_angle", C.c_double), ("seed_deg", C.c_double), ("level_deg", C.c_double), ("height_factor", C.c_double)]
@@ -213,6 +222,9 @@ SYMBOLS = {
     "mvosr_graph_keep_batch": (C.c_int, [_P, C.POINTER(Batch), C.c_uint32, C.c_int32, _P, _P, _P, _P]),
     "mvosr_flat_ransac_batch": (C.c_int, [_P, C.POINTER(Batch), _P, C.POINTER(RescaleParams), _P, _P, _P, C.POINTER(RescaleOutputs),
                                           C.c_int64]),
+    "mvosr_flat_ransac_cases_batch": (C.c_int, [_P, C.POINTER(Batch), _P, C.POINTER(RescaleParams), _P, C.c_int32, C.c_int32, _P, _P, _P, _P,
+                                                C.POINTER(RescaleCasesOutputs), C.c_int64]),
+    "mvosr_flat_ransac_cases_lds_bytes": (C.c_size_t, [C.c_int, C.c_int64, C.c_int]),
     "mvosr_region_grow_batch": (C.c_int, [_P, C.POINTER(Batch), _P, _P, C.POINTER(GrowParams), C.POINTER(GrowOutputs), C.c_int64]),
     "mvosr_tri_graph_batch": (C.c_int, [_P, C.POINTER(Params), C.POINTER(Batch), _P, _P, C.POINTER(TriGraphOutputs)]),
     "mvosr_static_tri_batch": (C.c_int, [_P, C.c_int64, _P, _P, _P, _P, C.c_int32, C.c_double, _P, _P, _P, _P, _P]),

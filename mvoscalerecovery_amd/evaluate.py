@@ -90,3 +90,36 @@ def pose2motion(poses):
     for i in range(poses.shape[0] - 1):
         out[i] = (np.linalg.inv(_mat(poses[i])) @ _mat(poses[i + 1]))[:3].reshape(-1)
     return out
+
+
+# ---- the repeated runs' score (/root/reference/test_off_line.sh:11-23) ------------------------------------------------------------
+def trimmed_mean(values):
+    """/root/reference/script/score_calculation.py:21-22: sort, drop the best and the worst, take the mean."""
+    v = np.sort(np.asarray(values, dtype=np.float64).reshape(-1))
+    if v.size < 3:
+        raise ValueError("trimmed_mean: at least three values (the best and the worst are dropped), got %d" % v.size)
+    return float(np.mean(v[1:-1]))
+
+
+def repeat_scores(poses_gt, paths):
+    """What evaluate_vo.py:104-107 prints for every path of a repeated run — the per-length translation and rotation errors (eight
+    each on a sequence long enough for every length) and their two means — and, over the cases, the trimmed mean of each
+    (score_calculation.py:17-22, calculate_mean.py).
+
+    The reference picks ONE field of evaluate_vo's printed log by its position in a comma split (score_calculation.py:3-7) and its
+    scale branch raises NameError (:13 returns a name that is not defined there); neither is mirrored: every figure is returned by
+    name.  Returns ``{"tra": (C, L), "rot": (C, L), "tra_mean": (C,), "rot_mean": (C,), "trimmed": {...the same four keys...}}``."""
+    tra, rot = [], []
+    for p in paths:
+        r, t, _ = calculate_ave_errors(calculate_sequence_error(poses_gt, p))
+        tra.append(np.asarray(t, dtype=np.float64))
+        rot.append(np.asarray(r, dtype=np.float64))
+    tra, rot = np.array(tra), np.array(rot)
+    import warnings
+    with warnings.catch_warnings():
+        warnings.simplefilter("ignore")
+        out = {"tra": tra, "rot": rot, "tra_mean": tra.mean(axis=1), "rot_mean": rot.mean(axis=1)}      # evaluate_vo.py:107
+    out["trimmed"] = {"tra": np.array([trimmed_mean(tra[:, k]) for k in range(tra.shape[1])]),
+                      "rot": np.array([trimmed_mean(rot[:, k]) for k in range(rot.shape[1])]),
+                      "tra_mean": trimmed_mean(out["tra_mean"]), "rot_mean": trimmed_mean(out["rot_mean"])}
+    return out

@@ -856,6 +856,178 @@ class ScaleEstimator(stream.StreamKnobs):
         finally:
             self._frame_counter = keep
 
+    # ---- C runs of a sequence at once: the per-frame half (mvosr_flat_ransac_cases_batch; RepeatedRuns carries the tails) ----
+    _CASE_FIELDS = ("raw_scale", "model", "best_ic", "used", "status")
+
+    def _launch_cases(self, db, keep_ptr, dt2_ptr, flags_ptr, seeds, frame_base, frame_ids, id_triples, max_tri, opts, ctx=None):
+        """mvosr_flat_ransac_cases_batch behind the chunk's mvosr_flat_ransac_batch, on the same resident batch, keep words and
+        flags; returns the outputs' block (download queued) and the side blocks."""
+        ctx, F, H, Cn = ctx or self.ctx, db.n_frames, self.N_HYP, len(seeds)
+        spec = [("raw_scale", (F, Cn), np.float64), ("model", (F, Cn, 4), np.float64), ("best_ic", (F, Cn), np.int32),
+                ("used", (F, Cn), np.int32), ("status", (F, Cn), np.int32), ("count_form", F, np.int32)]
+        if opts.get("hyp_counts"):
+            spec.append(("hyp_counts", (F, Cn, H), np.int32))
+        out = ctx.block(spec)
+        side = ctx.block([("seeds", Cn, np.uint64)] + ([("frame_ids", F, np.int64)] if frame_ids is not None else []) +
+                         ([("id_triples", (F, Cn, H, 3), np.int32)] if id_triples is not None else []))
+        up = {"seeds": np.asarray(seeds, dtype=np.uint64)}
+        if frame_ids is not None:
+            up["frame_ids"] = np.asarray(frame_ids, dtype=np.int64)
+        if id_triples is not None:
+            up["id_triples"] = np.ascontiguousarray(np.asarray(id_triples, dtype=np.int32).reshape(F, Cn, H, 3))
+        side.upload(up)
+        o = _lib.RescaleCasesOutputs(out["raw_scale"].ptr, out["model"].ptr, out["best_ic"].ptr, out["used"].ptr, out["status"].ptr,
+                                     out["hyp_counts"].ptr if "hyp_counts" in out else None, out["count_form"].ptr)
+        rp = self._rescale_params(frame_base)
+        b = db.struct()
+        _lib.check(ctx.lib.mvosr_flat_ransac_cases_batch(ctx.handle, C.byref(b), keep_ptr, C.byref(rp), side["seeds"].ptr, Cn,
+                                                         int(opts.get("cases_per_group", 0)),
+                                                         side["id_triples"].ptr if id_triples is not None else None,
+                                                         side["frame_ids"].ptr if frame_ids is not None else None, dt2_ptr, flags_ptr,
+                                                         C.byref(o), int(max_tri)), "mvosr_flat_ransac_cases_batch")
+        out.prefetch()
+        return out, side
+
+    @staticmethod
+    def _collect_cases(res, out):
+        """A chunk's case outputs next to its per-frame results.  The cases kernel does not recompute the heights: a frame the
+        flat selection refuses as a whole (singular row, bad vertex id, no rows) is refused for every case here."""
+        for k in out.views:
+            res["case_" + k] = out[k].download()
+        bad = np.isin(res["status"], (K.ST_ERR_SINGULAR, K.ST_ERR_MASK, K.ST_ERR_EMPTY))
+        if bad.any():
+            res["case_status"][bad] = res["status"][bad][:, None]
+            res["case_raw_scale"][bad] = np.nan
+            res["case_model"][bad] = np.nan
+            res["case_best_ic"][bad] = 0
+            res["case_used"][bad] = 0
+            res["case_count_form"][bad] = 0
+        return res
+
+    def _cases_host(self, f3s, f2s, seeds, frame_base, frame_ids, id_triples, opts):
+        """One chunk of the cases path on the host's triangulations: triangulation="scipy" with sampling="device", and the frames
+        both device triangulations declined (``frame_ids``: their own sample counters)."""
+        rec = self._host_begin(f3s, f2s, frame_base)
+        cases = None
+        try:
+            self._host_keep_start(rec)
+            self._host_tri2_start(rec)
+            self._host_flat_start(rec, frame_base, frame_ids, None, True)
+            pf = rec["pf"]
+            max_tri = max(int(np.max(np.diff(pf.tri2_off))) if pf.n_frames else 0, 1)
+            cases, side = self._launch_cases(rec["db"], rec["aux"]["keep"].ptr, None, rec["flags"]["tri_flags"].ptr, seeds, frame_base,
+                                             frame_ids, id_triples, max_tri, opts, ctx=rec["ctx"])
+            rec["side"] = rec["side"] + [side]
+            host_errors = dict(pf.extra["tri2_errors"])
+            host_errors.update(pf.extra["tri1_errors"])
+            res = self._collect_cases(self._collect(rec["out"], pf.n_frames), cases)
+            res["host_errors"] = host_errors
+            return res
+        finally:
+            if cases is not None:
+                cases.free()
+            stream.free_blocks(rec)
+
+    def _cases_gpu_start(self, f3s, f2s, seeds, frame_base, id_triples, opts):
+        st = self._chunk_dev_gpu(f3s, f2s, frame_base, None, True)
+        if st["gpu"]:
+            db = st["db"]
+            try:
+                db.mark(False)
+                st["cases"], side = self._launch_cases(db, db.bufs["vote_counters"].ptr, db.bufs["dt2_status"].ptr, st["flags"]["tri_flags"].ptr,
+                                                       seeds, frame_base, None, id_triples, 2 * int(db.max_feat), opts)
+                st["side"] = st["side"] + [side]
+                db.mark()
+            except Exception:
+                stream.free_blocks(st)
+                raise
+        return st
+
+    def _cases_gpu_finish(self, st, f3s, f2s, seeds, frame_base, id_triples, opts):
+        if not st["gpu"]:
+            return self._cases_host(f3s, f2s, seeds, frame_base, None, id_triples, opts)
+        try:
+            res = self._collect_cases(self._collect(st["out"], len(f3s)), st["cases"])
+            s1, s2 = st["db"].triangulation_status()
+        finally:
+            if st.get("cases") is not None:
+                st.pop("cases").free()
+            stream.free_blocks(st)
+        res["host_errors"] = {}
+        redo = np.nonzero((s1 != 0) | (s2 != 0))[0]
+        self.last_declined += len(redo)
+        if len(redo):                                # both device triangulations declined: the host's, with the frames' own counters
+            sub = self._cases_host([f3s[f] for f in redo], [f2s[f] for f in redo], seeds, 0, frame_base + redo,
+                                   None if id_triples is None else [id_triples[f] for f in redo], opts)
+            for k, v in sub.items():
+                if k != "host_errors":
+                    res[k][redo] = v
+            for j, e in sub["host_errors"].items():
+                res["host_errors"][int(redo[j])] = e
+        return res
+
+    def raw_scale_cases_batch(self, feature3ds, feature2ds, seeds, frame_base=0, id_triples=None, cases_per_group=0, hyp_counts=False):
+        """The per-frame half for ``C = len(seeds)`` sample sequences of the same frames at once (no cross-frame state touched): both
+        triangulations, the vote and the flat selection run ONCE per frame, chunk by chunk through the device-resident stages, and
+        behind each chunk's mvosr_flat_ransac_batch one launch of mvosr_flat_ransac_cases_batch fits all cases on the same resident
+        batch.  Case ``c`` is, bit for bit, what an estimator built with ``ransac_seed=seeds[c]`` computes for these frames.
+
+        ``id_triples``: per frame a ``(C, H, 3)`` array of survivor-numbered vertex ids replacing the draws.  ``frame_base`` as in
+        ``raw_scale_batch``.  Returns a dict: ``raw_scale``, ``best_ic``, ``used``, ``status`` ``(C, F)``, ``model`` ``(C, F, 4)``, the
+        per-frame ``height_level``, ``n_kept``, ``frame_status`` and ``count_form`` ``(F,)``, ``host_errors`` (frame -> exception),
+        and ``hyp_counts`` ``(C, F, H)`` when asked for.  Chunks are started one ahead of the one being collected; frames that both
+        device triangulations decline are re-run on the host's at once.  An oversized frame is refused up front."""
+        if self.sampling != "device":
+            raise ValueError("the repeated runs need the device sample sequence: ScaleEstimator(..., triangulation='gpu') or "
+                             "(..., sampling='device')")
+        seeds = [int(s) & ((1 << 64) - 1) for s in seeds]
+        Cn, F, H = len(seeds), len(feature3ds), self.N_HYP
+        if Cn < 1:
+            raise ValueError("raw_scale_cases_batch: at least one seed")
+        opts = {"cases_per_group": int(cases_per_group), "hyp_counts": bool(hyp_counts)}
+        empty = {"raw_scale": np.zeros((Cn, 0)), "model": np.zeros((Cn, 0, 4)), "best_ic": np.zeros((Cn, 0), np.int32),
+                 "used": np.zeros((Cn, 0), np.int32), "status": np.zeros((Cn, 0), np.int32), "height_level": np.zeros(0),
+                 "n_kept": np.zeros(0, np.int32), "frame_status": np.zeros(0, np.int32), "count_form": np.zeros(0, np.int32), "host_errors": {}}
+        if F == 0:
+            return empty
+        over = self._first_oversized(feature2ds, [len(x) for x in feature2ds], 0)
+        if over is not None:
+            raise self._oversized_error(*over)
+        base = self._frame_counter + int(frame_base)
+        self.last_declined = 0
+        triples = (lambda a, b: None) if id_triples is None else (lambda a, b: id_triples[a:b])
+        gpu = self.triangulation == "gpu"
+        step = stream.chunk_size(F, self.GPU_CHUNK, self.GPU_MIN_CHUNK, self.GPU_CHUNK_POINTS, [len(x) for x in feature3ds[:64]])[0] if gpu else 2048
+        bounds = [(a, min(F, a + step)) for a in range(0, F, step)]
+        results, pending = [], None
+        try:
+            for a, b in bounds:
+                if gpu:
+                    st = self._cases_gpu_start(feature3ds[a:b], feature2ds[a:b], seeds, base + a, triples(a, b), opts)
+                    if pending is not None:
+                        pa, pb, pst = pending
+                        pending = None
+                        results.append(self._cases_gpu_finish(pst, feature3ds[pa:pb], feature2ds[pa:pb], seeds, base + pa, triples(pa, pb), opts))
+                    pending = (a, b, st)
+                else:
+                    results.append(self._cases_host(feature3ds[a:b], feature2ds[a:b], seeds, base + a, None, triples(a, b), opts))
+            if pending is not None:
+                pa, pb, pst = pending
+                pending = None
+                results.append(self._cases_gpu_finish(pst, feature3ds[pa:pb], feature2ds[pa:pb], seeds, base + pa, triples(pa, pb), opts))
+        finally:
+            if pending is not None:
+                if pending[2].get("cases") is not None:
+                    pending[2].pop("cases").free()
+                stream.free_blocks(pending[2])
+        cat = lambda k: np.concatenate([r[k] for r in results])
+        out = {k: np.ascontiguousarray(np.moveaxis(cat("case_" + k), 1, 0)) for k in self._CASE_FIELDS}
+        if hyp_counts:
+            out["hyp_counts"] = np.ascontiguousarray(np.moveaxis(cat("case_hyp_counts"), 1, 0))
+        out.update(height_level=cat("height_level"), n_kept=cat("n_kept"), frame_status=cat("status"), count_form=cat("case_count_form"))
+        out["host_errors"] = {a + int(f): e for (a, b), r in zip(bounds, results) for f, e in r["host_errors"].items()}
+        return out
+
     def push_raw_scales(self, raw, status, level=None, host_errors=None):
         """Cross-frame half (slew limiter, window median, raise sites) for raw scales computed elsewhere (other ranks):
         returns ``(scales, stds)`` like ``scale_calculation_batch``."""
@@ -920,3 +1092,152 @@ class ScaleEstimator(stream.StreamKnobs):
                 raise _lib.MvosrLibraryError("triangulation with an out-of-range vertex id (frame %d of the batch)" % n_ok)
             raise ValueError("frame %d of the batch has no triangles below the vanishing row" % n_ok)
         return filtered, np.ones(F)
+
+
+# ---- the repeated offline runs (/root/reference/test_off_line.sh:4-16) ------------------------------------------------------
+_MASK64 = (1 << 64) - 1
+CASE_SEED_STEP = 0xA0761D6478BD642F
+
+
+def _mix64(x):
+    """splitmix64's finaliser, as mvosr_flat_ransac_batch's sample sequence uses it (include/mvosr.h)."""
+    x = (x + 0x9E3779B97F4A7C15) & _MASK64
+    x = ((x ^ (x >> 30)) * 0xBF58476D1CE4E5B9) & _MASK64
+    x = ((x ^ (x >> 27)) * 0x94D049BB133111EB) & _MASK64
+    return x ^ (x >> 31)
+
+
+def case_seeds(seed, cases):
+    """The case seeds ``RepeatedRuns(seed=...)`` derives: ``seed_c = mix64((seed + c * 0xA0761D6478BD642F) mod 2^64)``,
+    ``c = 0 .. cases - 1`` — counter-based, so case c does not depend on how many cases run beside it."""
+    return [_mix64((int(seed) + c * CASE_SEED_STEP) & _MASK64) for c in range(int(cases))]
+
+
+class _CaseTail:
+    """One case's cross-frame state — the running scale and the scale queue of rescale.py:24-35 — behind the estimator's own tail
+    (``ScaleEstimator._push_device``: mvosr_slew_median_host once per call, the raise sites)."""
+    push = ScaleEstimator._push_device
+
+    def __init__(self, ctx, window_size):
+        self.ctx, self.window_size = ctx, window_size
+        self.scale, self.scale_queue = 1, deque()                                           # rescale.py:28,30
+        self.height_level, self._frame_counter = None, 0
+        self.prev = (0, 100)                                                                # main_offline.py:46-47
+
+
+class RepeatedRuns:
+    """``cases`` runs of a sequence at once: what /root/reference/test_off_line.sh:4-16 gets from ten processes of main_offline.py
+    on one saved dict (its RANSAC is unseeded, ransac.py:6, so the runs differ).  One inner ``ScaleEstimator`` in a device-sampling
+    mode does the deterministic stages once per frame and the RANSAC of every case in one launch per chunk
+    (``raw_scale_cases_batch``); every case has its own tail — running scale and scale queue from the reference's initial state.
+
+    ``seeds``: the case seeds; else ``case_seeds(seed, cases)``; else drawn from the OS.  Row c of ``run`` equals
+    ``offline.run_sequence_batched`` with ``ScaleEstimator(ransac_seed=seeds[c])``.  A second ``run`` continues the sequence: the
+    frame counter, every tail and the "previous scale" of the too-few-features rule carry over."""
+
+    def __init__(self, absolute_reference, window_size=5, cases=10, seeds=None, seed=None, **estimator_kw):
+        if seeds is not None:
+            self.seeds = [int(s) & _MASK64 for s in seeds]
+        elif seed is not None:
+            self.seeds = case_seeds(seed, cases)
+        else:
+            self.seeds = [int.from_bytes(os.urandom(8), "little") for _ in range(int(cases))]
+        if not self.seeds:
+            raise ValueError("RepeatedRuns: at least one case")
+        self.cases = len(self.seeds)
+        self.estimator = self._make_estimator(absolute_reference, window_size, estimator_kw)
+        if self.estimator.sampling != "device":
+            raise ValueError("RepeatedRuns needs a device-sampling mode: triangulation='gpu', or triangulation='scipy' with sampling='device'")
+        self.tails = [_CaseTail(self.estimator.ctx, window_size) for _ in range(self.cases)]
+        self._scales, self._motions, self._raw, self.last = [], [], [], {}
+
+    @staticmethod
+    def _make_estimator(absolute_reference, window_size, kw):
+        return ScaleEstimator(absolute_reference, window_size, ransac_seed=0, **kw)
+
+    def run(self, data, id_triples=None, minimum_feature_for_scale=None):
+        """``main_offline``'s loop over the dict for every case: the not-moving skip, the ``N > 100`` gate and repeat-previous
+        (offline.plan_sequence / assemble_outputs).  ``id_triples``: ``(C, processed frames, H, 3)`` vertex ids replacing the draws.
+        Returns ``scales`` ``(C, n)`` — each row shaped like main_offline's scales file —, ``error`` ``(C, n + 1)``, ``kinds`` and the
+        per-case ``raw_scale`` / ``status`` of the processed frames."""
+        from . import offline
+        kinds = offline.plan_sequence(data, offline.MINIMUM_FEATURE_FOR_SCALE if minimum_feature_for_scale is None else minimum_feature_for_scale)
+        idx = [i for i, k in enumerate(kinds) if k == 1]
+        f3 = [np.asarray(data["feature3ds"][i], dtype=np.float64) for i in idx]
+        f2 = [np.asarray(data["feature2ds"][i], dtype=np.float64) for i in idx]
+        per_frame = None
+        if id_triples is not None:
+            t = np.asarray(id_triples, dtype=np.int32)
+            per_frame = [np.ascontiguousarray(t[:, f]) for f in range(len(idx))]
+        est = self.estimator
+        r = est.raw_scale_cases_batch(f3, f2, self.seeds, id_triples=per_frame)
+        Fp = len(idx)
+        scales, errors, first_exc = [], [], None
+        for c, tail in enumerate(self.tails):
+            try:
+                filt, std = tail.push(r["raw_scale"][c], r["status"][c], r["height_level"], r["host_errors"]) if Fp else (np.zeros(0), np.zeros(0))
+            except Exception as exc:                     # (a frame at which the reference raises: every tail has pushed the frames before it)
+                first_exc = first_exc or exc
+                continue
+            s, e = self._assemble(kinds, list(filt), list(std), tail.prev)
+            tail.prev = (s[-1], e[-1])
+            scales.append(s[1:])
+            errors.append(e)
+        est._frame_counter = self.tails[0]._frame_counter if Fp else est._frame_counter
+        if first_exc is not None:
+            raise first_exc
+        out = {"scales": np.array(scales, dtype=np.float64).reshape(self.cases, len(kinds)), "error": np.array(errors, dtype=np.float64),
+               "kinds": kinds, "raw_scale": r["raw_scale"], "status": r["status"]}
+        self._scales.append(out["scales"])
+        self._raw.append(r["raw_scale"])
+        self._motions.append(np.array(data["motions"], dtype=np.float64).reshape(len(kinds), -1))
+        self.last = dict(r, **out)
+        return out
+
+    @staticmethod
+    def _assemble(kinds, est_scales, est_stds, prev):
+        """offline.assemble_outputs, with a leading run of too-few-features frames repeating what the previous ``run`` left (the
+        initial entries 0 / 100 in the first)."""
+        from . import offline
+        scales, error = offline.assemble_outputs(kinds, est_scales, est_stds)
+        scales[0], error[0] = prev
+        for i, k in enumerate(kinds):
+            if k != 2:
+                break
+            scales[i + 1], error[i + 1] = prev
+        return scales, error
+
+    def scales(self):
+        """``(C, n)`` over every frame run so far."""
+        return np.concatenate(self._scales, axis=1) if self._scales else np.zeros((self.cases, 0))
+
+    def paths(self, data=None):
+        """The C integrated trajectories (offline.get_path, main_offline.py:92): of ``data`` — run first when given —, else of
+        everything run so far."""
+        from . import offline
+        if data is not None:
+            scales, motions = self.run(data)["scales"], np.array(data["motions"], dtype=np.float64).reshape(len(data["move_flags"]), -1)
+        else:
+            scales, motions = self.scales(), (np.concatenate(self._motions) if self._motions else np.zeros((0, 12)))
+        return [offline.get_path(motions, scales[c]) for c in range(self.cases)]
+
+    def write_results(self, res_addr, tag):
+        """``<res_addr>scales.txt<tag><num>`` and ``<res_addr>path.txt<tag><num>``, num = 0 .. C - 1: the files main_offline.py:90-93
+        leaves under test_off_line.sh's tags ``$1$num``.  Returns the file names."""
+        from . import offline
+        scales, motions = self.scales(), (np.concatenate(self._motions) if self._motions else np.zeros((0, 12)))
+        names = []
+        for c in range(self.cases):
+            offline.save_outputs(res_addr, "%s%d" % (tag, c), scales[c], motions)
+            names += [res_addr + "scales.txt%s%d" % (tag, c), res_addr + "path.txt%s%d" % (tag, c)]
+        return names
+
+    def spread(self):
+        """Per-frame mean and standard deviation over the cases: of the filtered scale over every frame run so far (``scale_mean``,
+        ``scale_std``) and of the raw scale over the processed frames (``raw_mean``, ``raw_std``; a case without a fit is left out)."""
+        s = self.scales()
+        raw = np.concatenate(self._raw, axis=1) if self._raw else np.zeros((self.cases, 0))
+        import warnings
+        with warnings.catch_warnings(), np.errstate(all="ignore"):
+            warnings.simplefilter("ignore")
+            return {"scale_mean": s.mean(axis=0), "scale_std": s.std(axis=0), "raw_mean": np.nanmean(raw, axis=0), "raw_std": np.nanstd(raw, axis=0)}
