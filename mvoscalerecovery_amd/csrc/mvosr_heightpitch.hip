@@ -16,6 +16,7 @@
 
 #include "../../include/mvosr.h"
 #include "mvosr_device.hpp"
+#include "mvosr_ransac.hpp"
 #include "mvosr_host.hpp"
 #include "mvosr_heightpitch_plan.hpp"
 #include "mvosr_heightpitch_pass.hpp"
@@ -88,25 +89,17 @@ __global__ __launch_bounds__(kHpBlock) void height_pitch_kernel(const HpArgs a) 
 
     // ---- the hypotheses' planes, one thread each (ransac.py:10-11, estimate_road_norm.py:13-15)
     {
-        const uint64_t key = hp_mix64(a.seed ^ ((uint64_t)(a.frame_base + f) * 0xD1B54A32D192ED03ull));
+        const uint64_t key = ransac_frame_key(a.seed, (uint64_t)(a.frame_base + f));
         for (int h = tid; h < H; h += kHpBlock) {
             int p0, p1, p2;
             if (a.triples) { const int32_t *t = a.triples + ((int64_t)f * H + h) * 3; p0 = t[0]; p1 = t[1]; p2 = t[2]; }
-            else hp_draw3(key, h, M, p0, p1, p2);
+            else ransac_draw3(key, h, M, p0, p1, p2);
             // a sample that names a position outside the list, or one vertex twice, is spent: NaN plane, no inlier
             bool ok = ids_in_range(p0, p1, p2, M);
             int v0 = 0, v1 = 0, v2 = 0;
             if (ok) { v0 = L[p0]; v1 = L[p1]; v2 = L[p2]; ok = v0 != v1 && v0 != v2 && v1 != v2; }
             double4 m; m.x = m.y = m.z = m.w = nan("");
-            if (ok) {
-                const double x0 = X[v0], y0 = Y[v0], z0 = Z[v0];
-                const double e1x = X[v1] - x0, e1y = Y[v1] - y0, e1z = Z[v1] - z0;
-                const double e2x = X[v2] - x0, e2y = Y[v2] - y0, e2z = Z[v2] - z0;
-                const double nx = e1y * e2z - e1z * e2y, ny = e1z * e2x - e1x * e2z, nz = e1x * e2y - e1y * e2x;
-                const double d = -((nx * x0 + ny * y0) + nz * z0);
-                const double inv = 1.0 / sqrt(((nx * nx + ny * ny) + nz * nz) + d * d);
-                m.x = nx * inv; m.y = ny * inv; m.z = nz * inv; m.w = d * inv;
-            }
+            if (ok) m = ransac_unit_plane(X, Y, Z, v0, v1, v2);
             mods[h] = m;
             cnts[h] = 0;
         }
@@ -114,51 +107,19 @@ __global__ __launch_bounds__(kHpBlock) void height_pitch_kernel(const HpArgs a) 
     __syncthreads();
     // ---- inlier counts over the list, repeats included (estimate_road_norm.py:17-18): the list's points in registers, the
     // hypotheses streamed from LDS (wave-uniform reads), ballot + popcount, one integer LDS add per wavefront
-    for (int c0 = 0; c0 < M; c0 += kHpBlock * kHpPPT) {
-        double qx[kHpPPT], qy[kHpPPT], qz[kHpPPT];
-#pragma unroll
-        for (int k = 0; k < kHpPPT; ++k) {
-            const int j = c0 + k * kHpBlock + tid;
-            const int id = L[min(j, M - 1)];
-            qx[k] = X[id]; qy[k] = Y[id]; qz[k] = Z[id];
-            if (j >= M) qx[k] = nan("");                                             // never an inlier
-        }
-        const int rows = min(kHpPPT, (M - c0 + kHpBlock - 1) / kHpBlock);            // workgroup-uniform
-#pragma unroll 2
-        for (int h = 0; h < H; ++h) {
-            const double4 m = mods[h];
-            int ic = 0;
-#pragma unroll
-            for (int k = 0; k < kHpPPT; ++k)
-                if (k < rows) ic += __popcll(__ballot(fabs(((qx[k] * m.x + qy[k] * m.y) + qz[k] * m.z) + m.w) < a.threshold));
-            if (lane == 0 && ic) atomicAdd(&cnts[h], ic);
-        }
-    }
+    ransac_count_resident<false, kHpPPT, 2, kHpBlock>(M, mods, cnts, H, a.threshold,
+        [&](int j, double &x, double &y, double &z) { const int id = L[j]; x = X[id]; y = Y[id]; z = Z[id]; });
     __syncthreads();
     if (a.hyp_counts) for (int h = tid; h < H; h += kHpBlock) a.hyp_counts[(int64_t)f * H + h] = cnts[h];
     // ---- ransac.py:9-22 by wavefront 0, 64 hypotheses at a time: the first best, the stop at the first count above the goal
     if (wave == 0) {
-        const double goal = (double)M * a.goal_fraction;                             // estimate_road_norm.py:68
-        int best = -1, best_ic = 0, used = H;
-        for (int h0 = 0; h0 < H; h0 += kWave) {
-            const int h = h0 + lane;
-            const int cc = h < H ? cnts[h] : -1;
-            const unsigned long long over = __ballot(h < H && (double)cc > goal);
-            const int limit = over ? (int)__ffsll((long long)over) - 1 : kWave - 1;
-            const bool in = h < H && lane <= limit;
-            const int mx = wave_max(in ? cc : -1);
-            if (mx > best_ic) {
-                const unsigned long long who = __ballot(in && cc == mx);
-                best = h0 + (int)__ffsll((long long)who) - 1; best_ic = mx;
-            }
-            if (over) { used = h0 + limit + 1; break; }
-        }
+        RansacReplay rp = {-1, 0, H, 0};
+        ransac_replay(rp, cnts, 0, H, (double)M * a.goal_fraction);                  // the goal: estimate_road_norm.py:68
         if (lane == 0) {
-            misc[HM_BEST] = best; misc[HM_BESTIC] = best_ic; misc[HM_USED] = used;
-            if (best >= 0) {
-                const double4 bm = mods[best];
-                const double sgn = (bm.y < 0.0) ? -1.0 : 1.0;                        // :157-159
-                red[HR_MODEL] = sgn * bm.x; red[HR_MODEL + 1] = sgn * bm.y; red[HR_MODEL + 2] = sgn * bm.z; red[HR_MODEL + 3] = sgn * bm.w;
+            misc[HM_BEST] = rp.best; misc[HM_BESTIC] = rp.best_ic; misc[HM_USED] = rp.used;
+            if (rp.best >= 0) {
+                const double4 bm = ransac_sign_rule(mods[rp.best]);                  // :157-159
+                red[HR_MODEL] = bm.x; red[HR_MODEL + 1] = bm.y; red[HR_MODEL + 2] = bm.z; red[HR_MODEL + 3] = bm.w;
             }
         }
     }
@@ -198,10 +159,8 @@ __global__ __launch_bounds__(kHpBlock) void height_pitch_kernel(const HpArgs a) 
     double nhx = nan(""), nhy = nan(""), nhz = nan("");
     if (n_in >= 3) {
         const int i0 = misc[HM_I0], i1 = misc[HM_I0 + 1], i2 = misc[HM_I0 + 2];
-        const double x0 = X[i0], y0 = Y[i0], z0 = Z[i0];
-        const double e1x = X[i1] - x0, e1y = Y[i1] - y0, e1z = Z[i1] - z0;
-        const double e2x = X[i2] - x0, e2y = Y[i2] - y0, e2z = Z[i2] - z0;
-        double nx = e1y * e2z - e1z * e2y, ny = e1z * e2x - e1x * e2z, nz = e1x * e2y - e1y * e2x;
+        double nx, ny, nz;
+        ransac_edge_cross(X[i0], Y[i0], Z[i0], X[i1], Y[i1], Z[i1], X[i2], Y[i2], Z[i2], nx, ny, nz);
         if (ny < 0.0) { nx = -nx; ny = -ny; nz = -nz; }                              // :180-181
         const double len = sqrt((nx * nx + ny * ny) + nz * nz);                      // :183-185
         nhx = nx / len; nhy = ny / len; nhz = nz / len;
@@ -219,9 +178,7 @@ __global__ __launch_bounds__(kHpBlock) void height_pitch_kernel(const HpArgs a) 
         if ((words[i >> 6] >> (i & 63)) & 1ull) { const double d = ((X[i] * nhx + Y[i] * nhy) + Z[i] * nhz) - mean; ss += d * d; }
     block_sum2<kHpWaves>(ss, dummy, red + HR_DEV);
     if (tid == 0) {
-        const double h_bar = -m3;                                                    // :156
-        const double norm_norm = sqrt((m0 * m0 + m1 * m1) + m2 * m2) / h_bar;        // :160-161
-        a.ransac_height[f] = 1.0 / norm_norm;                                        // :166
+        a.ransac_height[f] = ransac_camera_height(make_double4(m0, m1, m2, m3));     // :156-166
         a.model[4 * f] = m0; a.model[4 * f + 1] = m1; a.model[4 * f + 2] = m2; a.model[4 * f + 3] = m3;
         a.best_ic[f] = misc[HM_BESTIC]; a.used[f] = misc[HM_USED]; a.n_selected[f] = M; a.n_inliers[f] = n_in;
         a.refined_normal[3 * f] = nhx; a.refined_normal[3 * f + 1] = nhy; a.refined_normal[3 * f + 2] = nhz;

@@ -1,8 +1,7 @@
 // mvosr_heightpitch_pass.hpp — what height_pitch_kernel (mvosr_heightpitch.hip) and height_pitch_eval_kernel (mvosr_hpeval.hip)
 // do once per frame, /root/reference/src/calculate_height_pitch.py:62-116 (its _eval copies: the same lines, 19 further down):
 // back-projection, the rows' normals, the prior's window and height > 0, and the point list as 16-bit vertex ids in row order.
-// Also the counter-based sample draw both kernels share.  Device code only; included after mvosr_device.hpp and a plan header
-// that defines kHpWaves and the HM_* slots.
+// Device code only; included after mvosr_device.hpp, mvosr_ransac.hpp and a plan header that defines kHpWaves and the HM_* slots.
 #pragma once
 
 #include <hip/hip_runtime.h>
@@ -15,31 +14,6 @@ constexpr int kHpBlock = kHpWaves * kWave;
 constexpr int kHpPPT = 8;               // list points a thread holds in registers per chunk (chunks of 4096 entries)
 constexpr double kHpPi = 3.1415926;     // the script's constant (:63, :91)
 constexpr double kHpBand = 1e-12;       // |n_y/|n| - edge| within this: the script's own expression decides
-
-// mvosr_flat_ransac_batch's counter-based sample sequence (include/mvosr.h), as list POSITIONS
-__device__ __forceinline__ uint64_t hp_mix64(uint64_t x) {
-    x += 0x9E3779B97F4A7C15ull;
-    x = (x ^ (x >> 30)) * 0xBF58476D1CE4E5B9ull;
-    x = (x ^ (x >> 27)) * 0x94D049BB133111EBull;
-    return x ^ (x >> 31);
-}
-__device__ __forceinline__ void hp_draw3(uint64_t key, int h, int M, int &i0, int &i1, int &i2) {
-    const uint64_t hk = hp_mix64(key + (uint64_t)h);
-    const uint64_t r0 = hp_mix64(hk), r1 = hp_mix64(hk + 1ull), r2 = hp_mix64(hk + 2ull);
-    i0 = (int)__umul64hi(r0, (uint64_t)M);
-    i1 = (int)__umul64hi(r1, (uint64_t)(M - 1)); if (i1 >= i0) ++i1;
-    i2 = (int)__umul64hi(r2, (uint64_t)(M - 2));
-    const int lo = min(i0, i1), hi = max(i0, i1);
-    if (i2 >= lo) ++i2;
-    if (i2 >= hi) ++i2;
-}
-// the first two positions of hp_draw3: a pair of distinct positions
-__device__ __forceinline__ void hp_draw2(uint64_t key, int h, int M, int &i0, int &i1) {
-    const uint64_t hk = hp_mix64(key + (uint64_t)h);
-    const uint64_t r0 = hp_mix64(hk), r1 = hp_mix64(hk + 1ull);
-    i0 = (int)__umul64hi(r0, (uint64_t)M);
-    i1 = (int)__umul64hi(r1, (uint64_t)(M - 1)); if (i1 >= i0) ++i1;
-}
 
 // The value of n_y/|n| at which asin(.) * 180 / 3.1415926 crosses `deg`; -2 / 2 where every / no value lies above it.  Only
 // compared against from further than kHpBand away (the device sin never decides).
@@ -57,7 +31,7 @@ __device__ __forceinline__ double hp_edge(double deg) {
 template <typename Args>
 __device__ __forceinline__ int hp_frame_pass(const Args &a, int64_t f, int n, int tn, int64_t off, int64_t tb, bool write_list,
                                              double *X, double *Y, double *Z, uint16_t *L, int *misc, double &sin_est, double &cos_est) {
-    const int tid = threadIdx.x, lane = lane_id(), wave = wave_id();
+    const int tid = threadIdx.x, lane = lane_id();
     if (tid < HM_N) misc[tid] = 0;
     for (int i = tid; i < n; i += kHpBlock) {
         const double d = a.depth[off + i];
@@ -73,8 +47,8 @@ __device__ __forceinline__ int hp_frame_pass(const Args &a, int64_t f, int n, in
     __syncthreads();
 
     // ---- the rows (:77-116), wavefront by wavefront over contiguous row segments so that the list comes out in row order
-    const int seg = ((tn + kHpBlock - 1) / kHpBlock) * kWave;                        // (tn <= 21845: at most 43 trips, one bit each)
-    const int s0 = wave * seg, s1 = min(tn, s0 + seg);
+    int s0, s1;
+    ordered_segment(tn, kHpBlock, s0, s1);                                           // (tn <= 21845: at most 43 trips, one bit each)
     unsigned long long mine = 0ull;
     int c = 0;
     {
@@ -106,25 +80,20 @@ __device__ __forceinline__ int hp_frame_pass(const Args &a, int64_t f, int n, in
             c += __popcll(m);
         }
     }
-    if (lane == 0) misc[HM_CW + wave] = c;
-    __syncthreads();
-    int base = 0, K = 0;
-#pragma unroll
-    for (int w = 0; w < kHpWaves; ++w) { const int cw = misc[HM_CW + w]; K += cw; if (w < wave) base += cw; }
+    int base, K;
+    ordered_prefix<kHpWaves>(misc + HM_CW, c, base, K);
     if (misc[HM_BADID] || misc[HM_SINGULAR]) return -1;
     {
         int j = 0;
         for (int t0 = s0; t0 < s1; t0 += kWave, ++j) {
             const int t = t0 + lane;
             const bool kp = (mine >> j) & 1ull;
-            const unsigned long long m = __ballot(kp);
+            const int pos = 3 * ordered_rank(kp, base);
             if (kp) {
                 const TriIds q = load_tri(a.tri + 3 * tb, t);
-                const int pos = 3 * (base + __popcll(m & ((1ull << lane) - 1ull)));
                 L[pos] = (uint16_t)q.a; L[pos + 1] = (uint16_t)q.b; L[pos + 2] = (uint16_t)q.c;   // :114-116
                 if (write_list && a.point_list) { int32_t *pl = a.point_list + 3 * tb + pos; pl[0] = q.a; pl[1] = q.b; pl[2] = q.c; }
             }
-            base += __popcll(m);
         }
     }
     return 3 * K;                                                                    // point_selected.shape[0], :135

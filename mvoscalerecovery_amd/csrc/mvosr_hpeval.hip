@@ -16,6 +16,7 @@
 
 #include "../../include/mvosr.h"
 #include "mvosr_device.hpp"
+#include "mvosr_ransac.hpp"
 #include "mvosr_host.hpp"
 #include "mvosr_hpeval_plan.hpp"
 #include "mvosr_heightpitch_pass.hpp"
@@ -103,13 +104,13 @@ __global__ __launch_bounds__(kHpBlock) void height_pitch_eval_kernel(const HpeAr
     }
     if (tid == 0 && g == 0) a.n_selected[f] = M;
     __syncthreads();
-    const uint64_t fkey = hp_mix64(a.seed ^ ((uint64_t)(a.frame_base + f) * 0xD1B54A32D192ED03ull));
+    const uint64_t fkey = ransac_frame_key(a.seed, (uint64_t)(a.frame_base + f));
     const double goal = (double)M * a.goal_fraction;                                 // estimate_road_norm.py:62, :68
     const int nw = (M + kWave - 1) / kWave;
 
     for (int c = c_lo; c < c_hi; ++c) {
         const int64_t fc = f * C + c;
-        const uint64_t key = hp_mix64(fkey ^ ((uint64_t)(c + 1) * 0xA0761D6478BD642Full));
+        const uint64_t key = ransac_mix64(fkey ^ ((uint64_t)(c + 1) * 0xA0761D6478BD642Full));
         if (tid == 0) { misc[HM_BEST] = -1; misc[HM_BESTIC] = 0; misc[HM_USED] = H; misc[HE_DONE] = 0; }
         for (int h0 = 0; h0 < H; h0 += kHpMaxHyp) {
             const int T = min(kHpMaxHyp, H - h0);
@@ -118,79 +119,33 @@ __global__ __launch_bounds__(kHpBlock) void height_pitch_eval_kernel(const HpeAr
                 const int h = h0 + ht;
                 int p0, p1, p2 = 0;
                 if (a.samples) { const int32_t *t = a.samples + (fc * H + h) * 3; p0 = t[0]; p1 = t[1]; if (!LINE) p2 = t[2]; }
-                else if (LINE) hp_draw2(key, h, M, p0, p1);
-                else hp_draw3(key, h, M, p0, p1, p2);
+                else if (LINE) ransac_draw2(key, h, M, p0, p1);
+                else ransac_draw3(key, h, M, p0, p1, p2);
                 // a sample that names a position outside the list, or one vertex twice, is spent: NaN model, no inlier
                 bool ok = ids_in_range(p0, p1, p2, M);
                 int v0 = 0, v1 = 0, v2 = 0;
                 if (ok) { v0 = L[p0]; v1 = L[p1]; v2 = L[p2]; ok = LINE ? v0 != v1 : (v0 != v1 && v0 != v2 && v1 != v2); }
                 double4 m; m.x = m.y = m.z = m.w = nan("");
-                if (ok) {
-                    double nx, ny, nz, d;
-                    if (LINE) {                                                      // a y + b z + c = 0 through two points, as ransac_plane_kernel's line mode
-                        const double y0 = Y[v0], z0 = Z[v0];
-                        nx = Z[v1] - z0; ny = -(Y[v1] - y0); nz = 0.0;
-                        d = -(nx * y0 + ny * z0);
-                    } else {
-                        const double x0 = X[v0], y0 = Y[v0], z0 = Z[v0];
-                        const double e1x = X[v1] - x0, e1y = Y[v1] - y0, e1z = Z[v1] - z0;
-                        const double e2x = X[v2] - x0, e2y = Y[v2] - y0, e2z = Z[v2] - z0;
-                        nx = e1y * e2z - e1z * e2y; ny = e1z * e2x - e1x * e2z; nz = e1x * e2y - e1y * e2x;
-                        d = -((nx * x0 + ny * y0) + nz * z0);
-                    }
-                    const double inv = 1.0 / sqrt(((nx * nx + ny * ny) + nz * nz) + d * d);
-                    m.x = nx * inv; m.y = ny * inv; m.z = nz * inv; m.w = d * inv;
-                }
+                if (ok) m = LINE ? ransac_unit_line(Y, Z, v0, v1) : ransac_unit_plane(X, Y, Z, v0, v1, v2);   // the line: a y + b z + c = 0
                 mods[ht] = m;
                 cnts[ht] = 0;
             }
             __syncthreads();
             // ---- inlier counts over the list, repeats included: the list's points in registers, the hypotheses streamed from LDS
             // (wave-uniform reads), ballot + popcount, one integer LDS add per wavefront and hypothesis
-            for (int c0 = 0; c0 < M; c0 += kHpBlock * kHpPPT) {
-                double qx[kHpPPT], qy[kHpPPT], qz[kHpPPT];
-#pragma unroll
-                for (int k = 0; k < kHpPPT; ++k) {
-                    const int j = c0 + k * kHpBlock + tid;
-                    const int id = L[min(j, M - 1)];
-                    qx[k] = LINE ? 0.0 : X[id]; qy[k] = Y[id]; qz[k] = Z[id];
-                    if (j >= M) qy[k] = nan("");                                     // never an inlier
-                }
-                const int rows = min(kHpPPT, (M - c0 + kHpBlock - 1) / kHpBlock);    // workgroup-uniform
-#pragma unroll 2
-                for (int ht = 0; ht < T; ++ht) {
-                    const double4 m = mods[ht];
-                    int ic = 0;
-#pragma unroll
-                    for (int k = 0; k < kHpPPT; ++k)
-                        if (k < rows) {
-                            const double r = LINE ? (qy[k] * m.x + qz[k] * m.y) + m.w : ((qx[k] * m.x + qy[k] * m.y) + qz[k] * m.z) + m.w;
-                            ic += __popcll(__ballot(fabs(r) < a.threshold));
-                        }
-                    if (lane == 0 && ic) atomicAdd(&cnts[ht], ic);
-                }
-            }
+            ransac_count_resident<LINE, kHpPPT, 2, kHpBlock>(M, mods, cnts, T, a.threshold, [&](int j, double &q0, double &q1, double &q2) {
+                const int id = L[j];
+                if (LINE) { q0 = Y[id]; q1 = Z[id]; q2 = 0.0; } else { q0 = X[id]; q1 = Y[id]; q2 = Z[id]; }
+            });
             __syncthreads();
             if (a.hyp_counts) for (int ht = tid; ht < T; ht += kHpBlock) a.hyp_counts[fc * H + h0 + ht] = cnts[ht];
             // ---- ransac.py:9-22 by wavefront 0, 64 hypotheses at a time, its state carried from tile to tile
             if (wave == 0 && !misc[HE_DONE]) {
-                int best = misc[HM_BEST], best_ic = misc[HM_BESTIC], used = misc[HM_USED], done = 0, local = -1;
-                for (int t0 = 0; t0 < T; t0 += kWave) {
-                    const int ht = t0 + lane;
-                    const int cc = ht < T ? cnts[ht] : -1;
-                    const unsigned long long over = __ballot(ht < T && (double)cc > goal);
-                    const int limit = over ? (int)__ffsll((long long)over) - 1 : kWave - 1;
-                    const bool in = ht < T && lane <= limit;
-                    const int mx = wave_max(in ? cc : -1);
-                    if (mx > best_ic) {
-                        const unsigned long long who = __ballot(in && cc == mx);
-                        local = t0 + (int)__ffsll((long long)who) - 1; best = h0 + local; best_ic = mx;
-                    }
-                    if (over) { used = h0 + t0 + limit + 1; done = 1; break; }
-                }
+                RansacReplay rp = {misc[HM_BEST], misc[HM_BESTIC], misc[HM_USED], 0};
+                ransac_replay(rp, cnts, h0, T, goal);
                 if (lane == 0) {
-                    misc[HM_BEST] = best; misc[HM_BESTIC] = best_ic; misc[HM_USED] = used; misc[HE_DONE] = done;
-                    if (local >= 0) { const double4 bm = mods[local]; red[HER_MODEL] = bm.x; red[HER_MODEL + 1] = bm.y; red[HER_MODEL + 2] = bm.z; red[HER_MODEL + 3] = bm.w; }
+                    misc[HM_BEST] = rp.best; misc[HM_BESTIC] = rp.best_ic; misc[HM_USED] = rp.used; misc[HE_DONE] = rp.done;
+                    if (rp.best >= h0) { const double4 bm = mods[rp.best - h0]; red[HER_MODEL] = bm.x; red[HER_MODEL + 1] = bm.y; red[HER_MODEL + 2] = bm.z; red[HER_MODEL + 3] = bm.w; }   // (a best of this tile)
                 }
             }
             __syncthreads();
@@ -202,8 +157,8 @@ __global__ __launch_bounds__(kHpBlock) void height_pitch_eval_kernel(const HpeAr
             continue;
         }
         // :175-180: plane — flipped on n_y < 0; line — (a, b) and h_bar flipped on b < 0: the model's second slot either way
-        const double sgn = (red[HER_MODEL + 1] < 0.0) ? -1.0 : 1.0;
-        const double m0 = sgn * red[HER_MODEL], m1 = sgn * red[HER_MODEL + 1], m2 = sgn * red[HER_MODEL + 2], m3 = sgn * red[HER_MODEL + 3];
+        const double4 bm = ransac_sign_rule(make_double4(red[HER_MODEL], red[HER_MODEL + 1], red[HER_MODEL + 2], red[HER_MODEL + 3]));
+        const double m0 = bm.x, m1 = bm.y, m2 = bm.z, m3 = bm.w;
         // ---- get_inliers over the LIST (:167-169, estimate_road_norm.py:71-78): one ballot per 64 list positions
         for (int w = wave; w < nw; w += kHpWaves) {
             const int j = w * kWave + lane;
@@ -246,10 +201,8 @@ __global__ __launch_bounds__(kHpBlock) void height_pitch_eval_kernel(const HpeAr
                 nhy = ny / len; nhz = nz / len;
             } else {
                 const int i2 = misc[HM_I0 + 2];
-                const double x0 = X[i0], y0 = Y[i0], z0 = Z[i0];
-                const double e1x = X[i1] - x0, e1y = Y[i1] - y0, e1z = Z[i1] - z0;
-                const double e2x = X[i2] - x0, e2y = Y[i2] - y0, e2z = Z[i2] - z0;
-                double nx = e1y * e2z - e1z * e2y, ny = e1z * e2x - e1x * e2z, nz = e1x * e2y - e1y * e2x;
+                double nx, ny, nz;
+                ransac_edge_cross(X[i0], Y[i0], Z[i0], X[i1], Y[i1], Z[i1], X[i2], Y[i2], Z[i2], nx, ny, nz);
                 if (ny < 0.0) { nx = -nx; ny = -ny; nz = -nz; }                      // _eval.py:200-201
                 const double len = sqrt((nx * nx + ny * ny) + nz * nz);              // :203-205
                 nhx = nx / len; nhy = ny / len; nhz = nz / len;
@@ -275,9 +228,7 @@ __global__ __launch_bounds__(kHpBlock) void height_pitch_eval_kernel(const HpeAr
             }
         block_sum2<kHpWaves>(ss, dummy, red + HER_DEV);
         if (tid == 0) {
-            const double h_bar = -m3;                                                // :176
-            const double norm_norm = sqrt((m0 * m0 + m1 * m1) + m2 * m2) / h_bar;    // :180-181
-            a.ransac_height[fc] = 1.0 / norm_norm;                                   // :186
+            a.ransac_height[fc] = ransac_camera_height(bm);                          // :176-186
             a.model[4 * fc] = m0; a.model[4 * fc + 1] = m1; a.model[4 * fc + 2] = m2; a.model[4 * fc + 3] = m3;
             a.best_ic[fc] = best_ic; a.used[fc] = used; a.n_inliers[fc] = n_in;
             a.refined_normal[3 * fc] = degen ? nan("") : nhx; a.refined_normal[3 * fc + 1] = nhy; a.refined_normal[3 * fc + 2] = nhz;

@@ -15,6 +15,7 @@
 
 #include "../../include/mvosr.h"
 #include "mvosr_device.hpp"
+#include "mvosr_ransac.hpp"
 #include "mvosr_host.hpp"
 #include "mvosr_rescale_plan.hpp"
 
@@ -167,33 +168,6 @@ constexpr int kFlatDirect = 64;         // that few candidates left: wavefront 0
 constexpr int kMaxHyp = 512;
 constexpr int kRansacPPT = 8;           // points per thread per chunk (chunks of 4096 points)
 
-// The sample sequence of the device-resident RANSAC (include/mvosr.h, mvosr_flat_ransac_batch): splitmix64's finaliser as a
-// counter-based generator.  oracle/rescale_oracle.py restates it.
-__host__ __device__ __forceinline__ uint64_t rs_mix64(uint64_t x) {
-    x += 0x9E3779B97F4A7C15ull;
-    x = (x ^ (x >> 30)) * 0xBF58476D1CE4E5B9ull;
-    x = (x ^ (x >> 27)) * 0x94D049BB133111EBull;
-    return x ^ (x >> 31);
-}
-// Hypothesis h of a frame: three distinct list positions, uniform (ransac.py:10, random.sample over the list).  The list repeats
-// every vertex once per kept triangle (rescale.py:101), so 0.5-2 % of the samples name one VERTEX twice.  The reference spends
-// the iteration on such a sample (ransac.py:8-21): its SVD of the rank-2 matrix returns a plane that rounding noise picks from
-// the pencil through two points.  Here the iteration is spent as well — the sample is NOT drawn again (rounds 4-5 did, a
-// declared deviation that inflated the iteration budget) —: the cross product of a repeated vertex is exactly zero, the model
-// NaN, the hypothesis counts zero inliers and can never be the best — what the id_triples path has always done with such a
-// triple (pinned against the reference's own run on such triples: tests/golden/rescale.npz frame 26).
-__device__ __forceinline__ void rs_draw3(uint64_t key, int h, int M, const uint16_t *L, int &v0, int &v1, int &v2) {
-    const uint64_t hk = rs_mix64(key + (uint64_t)h);
-    const uint64_t r0 = rs_mix64(hk), r1 = rs_mix64(hk + 1ull), r2 = rs_mix64(hk + 2ull);
-    const int i0 = (int)__umul64hi(r0, (uint64_t)M);                          // uniform on [0, M) up to M / 2^64
-    int i1 = (int)__umul64hi(r1, (uint64_t)(M - 1)); if (i1 >= i0) ++i1;       // ... on the M - 1 other positions
-    int i2 = (int)__umul64hi(r2, (uint64_t)(M - 2));
-    const int lo = min(i0, i1), hi = max(i0, i1);
-    if (i2 >= lo) ++i2;
-    if (i2 >= hi) ++i2;
-    v0 = L[i0]; v1 = L[i1]; v2 = L[i2];
-}
-
 constexpr int kFlatDevWaves = 16;   // the device-resident form holds 96 KB of LDS — one workgroup per CU —, so it brings its own occupancy: 16 wavefronts
 
 template <bool DEV, int WAVES = kRsWaves>
@@ -252,12 +226,12 @@ __global__ __launch_bounds__(WAVES *kWave) void flat_selection_kernel(const Flat
     if (DEV && a.keep) {
         // ordered compaction at load (rescale.py:134-135: feature3d[valid_id]): every wavefront owns a contiguous segment of
         // the frame, counts its survivors, and after one barrier knows where its segment starts in LDS
-        const int seg = ((n_all + BLK - 1) / BLK) * kWave;
-        const int s0 = wave * seg, s1 = min(n_all, s0 + seg);
+        int s0, s1;
+        ordered_segment(n_all, BLK, s0, s1);
         // (a lane's features — up to four: 4 096 per frame on sixteen wavefronts — with their keep flags in one batch of loads,
         // before the count: flag, wait, coordinates, wait, twice over, was a tenth of this kernel's time with nothing else on the CU)
         constexpr int kOwn = 4;
-        const bool own = seg <= kOwn * kWave;
+        const bool own = n_all <= kOwn * BLK;
         double ox[kOwn], oy[kOwn], oz[kOwn];
         unsigned okeep = 0u;
         int c = 0;
@@ -277,33 +251,21 @@ __global__ __launch_bounds__(WAVES *kWave) void flat_selection_kernel(const Flat
             const int i = i0 + lane;
             c += __popcll(__ballot(i < s1 && a.keep[off + i] >= 0));
         }
-        if (lane == 0) misc[FM_CW + wave] = c;
-        __syncthreads();
-        int base = 0, total = 0;
-#pragma unroll
-        for (int w = 0; w < WAVES; ++w) { const int cw = misc[FM_CW + w]; total += cw; if (w < wave) base += cw; }
-        n = total;
+        int base;
+        ordered_prefix<WAVES>(misc + FM_CW, c, base, n);
         if (own) {
 #pragma unroll
             for (int r = 0; r < kOwn; ++r) {
                 const bool k = (okeep >> r) & 1u;
-                const unsigned long long m = __ballot(k);
-                if (k) {
-                    const int pos = base + __popcll(m & ((1ull << lane) - 1ull));
-                    X[pos] = ox[r]; Y[pos] = oy[r]; Z[pos] = oz[r];
-                }
-                base += __popcll(m);
+                const int pos = ordered_rank(k, base);
+                if (k) { X[pos] = ox[r]; Y[pos] = oy[r]; Z[pos] = oz[r]; }
             }
         } else
         for (int i0 = s0; i0 < s1; i0 += kWave) {
             const int i = i0 + lane;
             const bool k = i < s1 && a.keep[off + i] >= 0;
-            const unsigned long long m = __ballot(k);
-            if (k) {
-                const int pos = base + __popcll(m & ((1ull << lane) - 1ull));
-                X[pos] = a.x[off + i]; Y[pos] = a.y[off + i]; Z[pos] = a.z[off + i];
-            }
-            base += __popcll(m);
+            const int pos = ordered_rank(k, base);
+            if (k) { X[pos] = a.x[off + i]; Y[pos] = a.y[off + i]; Z[pos] = a.z[off + i]; }
         }
     } else {
 #pragma unroll 4
@@ -462,8 +424,8 @@ __global__ __launch_bounds__(WAVES *kWave) void flat_selection_kernel(const Flat
     } else {
         // ---- the kept rows (:94-96), wavefront by wavefront over contiguous row segments so that the point list —
         // triangle_ids[valid_id].reshape(-1), :101 — comes out in row order without a sort
-        const int seg = ((tn + BLK - 1) / BLK) * kWave;
-        const int s0 = wave * seg, s1 = min(tn, s0 + seg);
+        int s0, s1;
+        ordered_segment(tn, BLK, s0, s1);
         int c = 0;
         for (int t0 = s0; t0 < s1; t0 += kWave) {
             const int t = t0 + lane;
@@ -476,11 +438,8 @@ __global__ __launch_bounds__(WAVES *kWave) void flat_selection_kernel(const Flat
             }
             c += __popcll(__ballot(kp));
         }
-        if (lane == 0) misc[FM_CW + wave] = c;
-        __syncthreads();                                         // (every height has been compared: their room is the list's now)
-        int base = 0, K = 0;
-#pragma unroll
-        for (int w = 0; w < WAVES; ++w) { const int cw = misc[FM_CW + w]; K += cw; if (w < wave) base += cw; }
+        int base, K;
+        ordered_prefix<WAVES>(misc + FM_CW, c, base, K);         // (its barrier: every height has been compared, their room is the list's now)
         const int M = 3 * K;                                     // len(point_selected), :140
         uint16_t *L = reinterpret_cast<uint16_t *>(smem + lds.list);   // the point list as vertex ids
         const int H = a.n_hyp;
@@ -492,35 +451,27 @@ __global__ __launch_bounds__(WAVES *kWave) void flat_selection_kernel(const Flat
             for (int t0 = s0; t0 < s1; t0 += kWave) {
                 const int t = t0 + lane;
                 const bool kp = t < s1 && (Fl[t] & 4);
-                const unsigned long long m = __ballot(kp);
+                const int pos = 3 * ordered_rank(kp, base);
                 if (kp) {
                     const TriIds q = load_tri(a.tri + 3 * tb, t);
-                    const int pos = 3 * (base + __popcll(m & ((1ull << lane) - 1ull)));
                     L[pos] = (uint16_t)q.a; L[pos + 1] = (uint16_t)q.b; L[pos + 2] = (uint16_t)q.c;
                 }
-                base += __popcll(m);
             }
             __syncthreads();
             FS_STAMP(4);
             // the hypotheses' planes, one thread each (ransac.py:10-11, estimate_road_norm.py:13-15)
-            const uint64_t fc = (uint64_t)(a.frame_ids ? a.frame_ids[f] : a.frame_base + f);
-            const uint64_t key = rs_mix64(a.seed ^ (fc * 0xD1B54A32D192ED03ull));
+            const uint64_t key = ransac_frame_key(a.seed, (uint64_t)(a.frame_ids ? a.frame_ids[f] : a.frame_base + f));
             for (int h = tid; h < H; h += BLK) {
                 int v0, v1, v2;
                 if (a.id_triples) {
                     const int32_t *t = a.id_triples + ((int64_t)f * H + h) * 3;
                     v0 = min(max(t[0], 0), n - 1); v1 = min(max(t[1], 0), n - 1); v2 = min(max(t[2], 0), n - 1);
                 } else {
-                    rs_draw3(key, h, M, L, v0, v1, v2);
+                    ransac_draw3(key, h, M, v0, v1, v2);         // (list positions: mvosr_ransac.hpp on a vertex drawn twice)
+                    v0 = L[v0]; v1 = L[v1]; v2 = L[v2];
                 }
-                const double x0 = X[v0], y0 = Y[v0], z0 = Z[v0];
-                const double e1x = X[v1] - x0, e1y = Y[v1] - y0, e1z = Z[v1] - z0;
-                const double e2x = X[v2] - x0, e2y = Y[v2] - y0, e2z = Z[v2] - z0;
-                const double nx = e1y * e2z - e1z * e2y, ny = e1z * e2x - e1x * e2z, nz = e1x * e2y - e1y * e2x;
-                const double d = -((nx * x0 + ny * y0) + nz * z0);
-                const double inv = 1.0 / sqrt(((nx * nx + ny * ny) + nz * nz) + d * d);
-                double2 m0, m1; m0.x = nx * inv; m0.y = ny * inv; m1.x = nz * inv; m1.y = d * inv;
-                mods[2 * h] = m0; mods[2 * h + 1] = m1;
+                const double4 m = ransac_unit_plane(X, Y, Z, v0, v1, v2);
+                mods[2 * h] = make_double2(m.x, m.y); mods[2 * h + 1] = make_double2(m.z, m.w);
                 cnts[h] = 0;
             }
             __syncthreads();
@@ -574,43 +525,14 @@ __global__ __launch_bounds__(WAVES *kWave) void flat_selection_kernel(const Flat
             }
             FS_STAMP(6);
             const uint16_t *items = dedup ? Dv : L;
-            // a wavefront's hypotheses seven at a time (all of them, with 100 hypotheses on 16 wavefronts), their planes in registers: a vertex is gathered (id -> multiplicity, x, y,
-            // z: four LDS gathers with bank conflicts) once per pass and tested against all four (one hypothesis per pass spent
-            // 41 % of the kernel's time on those gathers)
-            constexpr int kHypPass = 7;
-            for (int k0 = 0; wave + WAVES * k0 < H; k0 += kHypPass) {
-                double2 ma[kHypPass], mb[kHypPass];
-                int acc[kHypPass];
-#pragma unroll
-                for (int q = 0; q < kHypPass; ++q) {
-                    const int h = min(wave + WAVES * (k0 + q), H - 1);
-                    ma[q] = mods[2 * h]; mb[q] = mods[2 * h + 1]; acc[q] = 0;
-                }
-                if (packed) {
-                    for (int j = lane; j < n_items; j += kWave) {
-                        const double px = PX[j], py = PY[j], pz = PZ[j];
-                        const int wgt = PW[j];
-#pragma unroll
-                        for (int q = 0; q < kHypPass; ++q)
-                            acc[q] += (fabs(((px * ma[q].x + py * ma[q].y) + pz * mb[q].x) + mb[q].y) < a.threshold) ? wgt : 0;   // estimate_road_norm.py:18
-                    }
-                } else {
-                    for (int j = lane; j < n_items; j += kWave) {
-                        const uint32_t id = items[j];
-                        const int wgt = dedup ? (int)((W2[id >> 1] >> (16u * (id & 1u))) & 0xFFFFu) : 1;
-                        const double px = X[id], py = Y[id], pz = Z[id];
-#pragma unroll
-                        for (int q = 0; q < kHypPass; ++q)
-                            acc[q] += (fabs(((px * ma[q].x + py * ma[q].y) + pz * mb[q].x) + mb[q].y) < a.threshold) ? wgt : 0;
-                    }
-                }
-#pragma unroll
-                for (int q = 0; q < kHypPass; ++q) {
-                    const int h = wave + WAVES * (k0 + q);
-                    const int sum = wave_sum(acc[q]);
-                    if (lane == 0 && h < H) cnts[h] = sum;
-                }
-            }
+            // (mvosr_ransac.hpp: a wavefront's hypotheses seven at a time — all of them, with 100 hypotheses on 16 wavefronts)
+            ransac_count_weighted<WAVES>(mods, cnts, H, n_items, a.threshold, packed,
+                [&](int j, double &px, double &py, double &pz, int &wgt) { px = PX[j]; py = PY[j]; pz = PZ[j]; wgt = PW[j]; },
+                [&](int j, double &px, double &py, double &pz, int &wgt) {
+                    const uint32_t id = items[j];
+                    wgt = dedup ? (int)((W2[id >> 1] >> (16u * (id & 1u))) & 0xFFFFu) : 1;
+                    px = X[id]; py = Y[id]; pz = Z[id];
+                });
             __syncthreads();
             FS_STAMP(7);
             if (a.hyp_counts) for (int h = tid; h < H; h += BLK) a.hyp_counts[(int64_t)f * H + h] = cnts[h];
@@ -621,33 +543,14 @@ __global__ __launch_bounds__(WAVES *kWave) void flat_selection_kernel(const Flat
             double m[4] = {nan(""), nan(""), nan(""), nan("")};
             double raw = nan("");
             if (fit) {
-                // ransac.py:9-22 — a hypothesis is the new best when it counts MORE than the best so far, and the loop stops
-                // at a new best above the goal — by the wavefront, 64 hypotheses at a time: the loop stops at the first count
-                // above the goal (the best before it was not, so it is a new best), and the best is the first occurrence of
-                // the largest count up to there.  (One thread walking the hundred counts was 16 % of the kernel's time.)
-                const double goal = (double)M * a.goal_fraction;                  // estimate_road_norm.py:68
-                used = H;
-                for (int h0 = 0; h0 < H; h0 += kWave) {
-                    const int h = h0 + lane;
-                    const int c = h < H ? cnts[h] : -1;
-                    const unsigned long long over = __ballot(h < H && (double)c > goal);
-                    const int limit = over ? (int)__ffsll((long long)over) - 1 : kWave - 1;
-                    const bool in = h < H && lane <= limit;
-                    const int mx = wave_max(in ? c : -1);
-                    if (mx > best_ic) {
-                        const unsigned long long who = __ballot(in && c == mx);
-                        best = h0 + (int)__ffsll((long long)who) - 1; best_ic = mx;
-                    }
-                    if (over) { used = h0 + limit + 1; break; }
-                }
+                RansacReplay rp = {-1, 0, H, 0};
+                ransac_replay(rp, cnts, 0, H, (double)M * a.goal_fraction);       // ransac.py:9-22; the goal: estimate_road_norm.py:68
+                best = rp.best; best_ic = rp.best_ic; used = rp.used;
                 if (best >= 0) {
                     const double2 b0 = mods[2 * best], b1 = mods[2 * best + 1];
-                    const double sgn = (b0.y < 0.0) ? -1.0 : 1.0;                 // rescale.py:159-161
-                    m[0] = sgn * b0.x; m[1] = sgn * b0.y; m[2] = sgn * b1.x; m[3] = sgn * b1.y;
-                    const double h_bar = -m[3];                                    // :158
-                    const double norm_norm = sqrt((m[0] * m[0] + m[1] * m[1]) + m[2] * m[2]) / h_bar;   // :162-163
-                    const double cam_h = 1.0 / norm_norm;                          // :165
-                    raw = a.absolute_reference / cam_h;                            // :167
+                    const double4 bm = ransac_sign_rule(make_double4(b0.x, b0.y, b1.x, b1.y));   // rescale.py:159-161
+                    m[0] = bm.x; m[1] = bm.y; m[2] = bm.z; m[3] = bm.w;
+                    raw = a.absolute_reference / ransac_camera_height(bm);         // :158-167
                 } else status = MVOSR_ST_RS_FEW;                                   // (no hypothesis with an inlier: NaN planes only)
             }
             if (lane == 0) {
@@ -676,7 +579,7 @@ __global__ __launch_bounds__(WAVES *kWave) void flat_selection_kernel(const Flat
 // hypothesis is the plane through its three sample points as the unit 4-vector (n, d)/|(n, d)| — the
 // null vector the reference gets from the SVD of [x y z 1] (estimate_road_norm.py:13-15), up to sign
 // — and |m.[p,1]| < threshold is counted over the frame's points (estimate_road_norm.py:17-18), the
-// points held in registers, the hypotheses streamed from LDS.  One lane then replays the reference's sequential
+// points held in registers, the hypotheses streamed from LDS.  Wavefront 0 then replays the reference's sequential
 // rule: a hypothesis replaces the best when its count is strictly larger, and the loop stops at
 // the first such improvement that exceeds the goal.
 // ---------------------------------------------------------------------------------------------
@@ -720,68 +623,24 @@ __global__ __launch_bounds__(kRsBlock) void ransac_plane_kernel(const RansacArgs
             cnts[h] = 0;
             continue;
         }
-        double nx, ny, nz, d;
-        if (a.line) {
-            // the line a x + b y + c = 0 through two points: the null vector of [x y 1] (estimate_road_norm.py:44-46)
-            const double x0 = px[i0], y0 = py[i0];
-            nx = py[i1] - y0; ny = -(px[i1] - x0); nz = 0.0;
-            d = -(nx * x0 + ny * y0);
-        } else {
-            const double x0 = px[i0], y0 = py[i0], z0 = pz[i0];
-            const double e1x = px[i1] - x0, e1y = py[i1] - y0, e1z = pz[i1] - z0;
-            const double e2x = px[i2] - x0, e2y = py[i2] - y0, e2z = pz[i2] - z0;
-            nx = e1y * e2z - e1z * e2y; ny = e1z * e2x - e1x * e2z; nz = e1x * e2y - e1y * e2x;
-            d = -((nx * x0 + ny * y0) + nz * z0);
-        }
-        const double inv = 1.0 / sqrt(((nx * nx + ny * ny) + nz * nz) + d * d);
-        double4 m; m.x = nx * inv; m.y = ny * inv; m.z = nz * inv; m.w = d * inv;
-        mods[h] = m;
+        mods[h] = a.line ? ransac_unit_line(px, py, i0, i1) : ransac_unit_plane(px, py, pz, i0, i1, i2);
         cnts[h] = 0;
     }
     __syncthreads();
-    // Every thread keeps up to kRansacPPT points in registers (read from HBM once, coalesced) and the
-    // hypotheses stream past them from LDS (wave-uniform reads); a hypothesis' inliers among a
-    // wavefront's points are counted on the scalar unit (ballot + popcount), one LDS add per wave.
-    for (int c0 = 0; c0 < M; c0 += kRsBlock * kRansacPPT) {
-        double qx[kRansacPPT], qy[kRansacPPT], qz[kRansacPPT];
-#pragma unroll
-        for (int k = 0; k < kRansacPPT; ++k) {
-            const int j = c0 + k * kRsBlock + tid;
-            const int jc = min(j, M - 1);
-            qx[k] = px[jc]; qy[k] = py[jc]; qz[k] = a.line ? 0.0 : pz[jc];
-            if (j >= M) qx[k] = nan("");                         // never an inlier: no masks or branches in the loop below
-        }
-        const int rows = min(kRansacPPT, (M - c0 + kRsBlock - 1) / kRsBlock);      // workgroup-uniform: rows that hold any point
-#pragma unroll 4
-        for (int h = 0; h < H; ++h) {
-            const double4 m = mods[h];
-            int ic = 0;
-#pragma unroll
-            for (int k = 0; k < kRansacPPT; ++k)
-                if (k < rows) ic += __popcll(__ballot(fabs(((qx[k] * m.x + qy[k] * m.y) + qz[k] * m.z) + m.w) < a.threshold));   // estimate_road_norm.py:18
-            if (lane == 0 && ic) atomicAdd(&cnts[h], ic);
-        }
-    }
+    // the points in registers (read from HBM once, coalesced), the hypotheses streamed past them (mvosr_ransac.hpp)
+    ransac_count_resident<false, kRansacPPT, 4, kRsBlock>(M, mods, cnts, H, a.threshold,
+        [&](int j, double &x, double &y, double &z) { x = px[j]; y = py[j]; z = a.line ? 0.0 : pz[j]; });
     __syncthreads();
     if (a.counts) for (int h = tid; h < H; h += kRsBlock) a.counts[(int64_t)f * H + h] = cnts[h];
-    if (tid == 0) {
-        const double goal = (double)M * a.goal_fraction;                  // estimate_road_norm.py:68
-        int best = -1, best_ic = 0, used = 0;
-        for (int h = 0; h < H; ++h) {                                     // ransac.py:9-22
-            used = h + 1;
-            if (cnts[h] > best_ic) {
-                best_ic = cnts[h]; best = h;
-                if ((double)best_ic > goal) break;
-            }
+    if (wave_id() == 0) {
+        RansacReplay rp = {-1, 0, H, 0};
+        ransac_replay(rp, cnts, 0, H, (double)M * a.goal_fraction);       // ransac.py:9-22; the goal: estimate_road_norm.py:68
+        if (lane == 0) {
+            a.best_ic[f] = rp.best_ic; a.used[f] = rp.used;
+            double4 bm; bm.x = bm.y = bm.z = bm.w = nan("");
+            if (rp.best >= 0) bm = ransac_sign_rule(mods[rp.best]);       // rescale.py:159-161
+            a.model[4 * f] = bm.x; a.model[4 * f + 1] = bm.y; a.model[4 * f + 2] = bm.z; a.model[4 * f + 3] = bm.w;
         }
-        a.best_ic[f] = best_ic; a.used[f] = used;
-        double m[4] = {nan(""), nan(""), nan(""), nan("")};
-        if (best >= 0) {
-            const double4 bm = mods[best];
-            const double sgn = (bm.y < 0.0) ? -1.0 : 1.0;                 // rescale.py:159-161
-            m[0] = sgn * bm.x; m[1] = sgn * bm.y; m[2] = sgn * bm.z; m[3] = sgn * bm.w;
-        }
-        for (int k = 0; k < 4; ++k) a.model[4 * f + k] = m[k];
     }
 }
 

@@ -9,9 +9,9 @@
 //   once per workgroup: the survivors' x / y / z compacted by keep >= 0 in order — as flat_selection_kernel<true> numbers them —,
 //   the point list from the rows whose flag has bit 2 (kept), in row order, three ids each, repeats included (rescale.py:101),
 //   and the counting form: the list's distinct vertices with their multiplicities;
-//   per case: the hypotheses from rs_draw3 keyed by the CASE's seed, their counts, the replay rule, the sign rule and the raw
-//   scale (rescale.py:156-167) — the code of flat_selection_kernel<true>'s tail, so that case c equals, bit for bit, what
-//   mvosr_flat_ransac_batch returns with rp->seed = case_seeds[c].
+//   per case: the hypotheses from ransac_draw3 keyed by the CASE's seed, their counts, the replay rule, the sign rule and the raw
+//   scale (rescale.py:156-167) — the functions flat_selection_kernel<true>'s tail calls (mvosr_ransac.hpp), so that case c equals,
+//   bit for bit, what mvosr_flat_ransac_batch returns with rp->seed = case_seeds[c].
 //
 // fp64, compiled with -ffp-contract=off.  The counts are integer sums: they depend neither on the counting form nor on the order
 // in which the distinct vertices were appended.
@@ -21,6 +21,7 @@
 
 #include "../../include/mvosr.h"
 #include "mvosr_device.hpp"
+#include "mvosr_ransac.hpp"
 #include "mvosr_host.hpp"
 #include "mvosr_rescale_cases_plan.hpp"
 
@@ -51,27 +52,6 @@ struct CasesArgs {
     int32_t *hyp_counts;           // optional [F][C][H]
     int32_t *count_form;           // optional [F]
 };
-
-// The sample sequence of mvosr_flat_ransac_batch, restated (mvosr_rescale.hip keeps its own copy: that file's code object does not
-// change with this one).  oracle/rescale_oracle.py restates it too.
-__device__ __forceinline__ uint64_t rc_mix64(uint64_t x) {
-    x += 0x9E3779B97F4A7C15ull;
-    x = (x ^ (x >> 30)) * 0xBF58476D1CE4E5B9ull;
-    x = (x ^ (x >> 27)) * 0x94D049BB133111EBull;
-    return x ^ (x >> 31);
-}
-// three distinct list positions, uniform; a draw that names one VERTEX twice spends its iteration (include/mvosr.h)
-__device__ __forceinline__ void rc_draw3(uint64_t key, int h, int M, const uint16_t *L, int &v0, int &v1, int &v2) {
-    const uint64_t hk = rc_mix64(key + (uint64_t)h);
-    const uint64_t r0 = rc_mix64(hk), r1 = rc_mix64(hk + 1ull), r2 = rc_mix64(hk + 2ull);
-    const int i0 = (int)__umul64hi(r0, (uint64_t)M);
-    int i1 = (int)__umul64hi(r1, (uint64_t)(M - 1)); if (i1 >= i0) ++i1;
-    int i2 = (int)__umul64hi(r2, (uint64_t)(M - 2));
-    const int lo = min(i0, i1), hi = max(i0, i1);
-    if (i2 >= lo) ++i2;
-    if (i2 >= hi) ++i2;
-    v0 = L[i0]; v1 = L[i1]; v2 = L[i2];
-}
 
 // every case of this workgroup's group is not fitted: NaN doubles, zero counts
 __device__ __forceinline__ void cases_refuse(const CasesArgs &a, int64_t f, int g, int c_lo, int c_hi, int status) {
@@ -120,60 +100,47 @@ __global__ __launch_bounds__(WAVES *kWave) void flat_ransac_cases_kernel(const C
     // ---- the survivors, compacted in order (rescale.py:134-135): every wavefront owns a contiguous segment of the frame
     int n;
     {
-        const int seg = ((n_all + BLK - 1) / BLK) * kWave;
-        const int s0 = wave * seg, s1 = min(n_all, s0 + seg);
+        int s0, s1;
+        ordered_segment(n_all, BLK, s0, s1);
         int c = 0;
         for (int i0 = s0; i0 < s1; i0 += kWave) {
             const int i = i0 + lane;
             c += __popcll(__ballot(i < s1 && (!a.keep || a.keep[off + i] >= 0)));
         }
-        if (lane == 0) misc[CM_CW + wave] = c;
-        __syncthreads();
-        int base = 0, total = 0;
-#pragma unroll
-        for (int w = 0; w < WAVES; ++w) { const int cw = misc[CM_CW + w]; total += cw; if (w < wave) base += cw; }
-        n = total;
+        int base;
+        ordered_prefix<WAVES>(misc + CM_CW, c, base, n);
         for (int i0 = s0; i0 < s1; i0 += kWave) {
             const int i = i0 + lane;
             const bool k = i < s1 && (!a.keep || a.keep[off + i] >= 0);
-            const unsigned long long m = __ballot(k);
-            if (k) {
-                const int pos = base + __popcll(m & ((1ull << lane) - 1ull));
-                X[pos] = a.x[off + i]; Y[pos] = a.y[off + i]; Z[pos] = a.z[off + i];
-            }
-            base += __popcll(m);
+            const int pos = ordered_rank(k, base);
+            if (k) { X[pos] = a.x[off + i]; Y[pos] = a.y[off + i]; Z[pos] = a.z[off + i]; }
         }
     }
     // ---- the kept rows, in row order (rescale.py:94-96, :101): the same segmented compaction over the flags
-    const int segt = ((tn + BLK - 1) / BLK) * kWave;
-    const int t0w = wave * segt, t1w = min(tn, t0w + segt);
+    for (int v = tid; v < n_all; v += BLK) W[v] = 0;
+    int t0w, t1w;
+    ordered_segment(tn, BLK, t0w, t1w);
+    int base, K;
     {
         int c = 0;
         for (int t0 = t0w; t0 < t1w; t0 += kWave) {
             const int t = t0 + lane;
             c += __popcll(__ballot(t < t1w && (a.tri_flags[tb + t] & 4)));
         }
-        if (lane == 0) misc[CM_CW2 + wave] = c;
+        ordered_prefix<WAVES>(misc + CM_CW2, c, base, K);
     }
-    for (int v = tid; v < n_all; v += BLK) W[v] = 0;
-    __syncthreads();
-    int base = 0, K = 0;
-#pragma unroll
-    for (int w = 0; w < WAVES; ++w) { const int cw = misc[CM_CW2 + w]; K += cw; if (w < wave) base += cw; }
     const int M = 3 * K;                                             // len(point_selected), rescale.py:140
     {
         int bad = 0;
         for (int t0 = t0w; t0 < t1w; t0 += kWave) {
             const int t = t0 + lane;
             const bool kp = t < t1w && (a.tri_flags[tb + t] & 4);
-            const unsigned long long m = __ballot(kp);
+            const int pos = 3 * ordered_rank(kp, base);
             if (kp) {
                 TriIds q = load_tri(a.tri + 3 * tb, t);
                 if (!ids_in_range(q.a, q.b, q.c, n)) { bad = 1; q.a = q.b = q.c = 0; }
-                const int pos = 3 * (base + __popcll(m & ((1ull << lane) - 1ull)));
                 L[pos] = (uint16_t)q.a; L[pos + 1] = (uint16_t)q.b; L[pos + 2] = (uint16_t)q.c;
             }
-            base += __popcll(m);
         }
         if (bad) misc[CM_BAD] = 1;
     }
@@ -218,93 +185,40 @@ __global__ __launch_bounds__(WAVES *kWave) void flat_ransac_cases_kernel(const C
     for (int c = c_lo; c < c_hi; ++c) {
         const int64_t fc = f * C + c;
         // the hypotheses' planes, one thread each (ransac.py:10-11, estimate_road_norm.py:13-15)
-        const uint64_t key = rc_mix64(a.case_seeds[c] ^ (fcnt * 0xD1B54A32D192ED03ull));
+        const uint64_t key = ransac_frame_key(a.case_seeds[c], fcnt);
         for (int h = tid; h < H; h += BLK) {
             int v0, v1, v2;
             if (a.id_triples) {
                 const int32_t *t = a.id_triples + (fc * H + h) * 3;
                 v0 = min(max(t[0], 0), n - 1); v1 = min(max(t[1], 0), n - 1); v2 = min(max(t[2], 0), n - 1);
             } else {
-                rc_draw3(key, h, M, L, v0, v1, v2);
+                ransac_draw3(key, h, M, v0, v1, v2);
+                v0 = L[v0]; v1 = L[v1]; v2 = L[v2];
             }
-            const double x0 = X[v0], y0 = Y[v0], z0 = Z[v0];
-            const double e1x = X[v1] - x0, e1y = Y[v1] - y0, e1z = Z[v1] - z0;
-            const double e2x = X[v2] - x0, e2y = Y[v2] - y0, e2z = Z[v2] - z0;
-            const double nx = e1y * e2z - e1z * e2y, ny = e1z * e2x - e1x * e2z, nz = e1x * e2y - e1y * e2x;
-            const double d = -((nx * x0 + ny * y0) + nz * z0);
-            const double inv = 1.0 / sqrt(((nx * nx + ny * ny) + nz * nz) + d * d);
-            double2 m0, m1; m0.x = nx * inv; m0.y = ny * inv; m1.x = nz * inv; m1.y = d * inv;
-            mods[2 * h] = m0; mods[2 * h + 1] = m1;
+            const double4 m = ransac_unit_plane(X, Y, Z, v0, v1, v2);
+            mods[2 * h] = make_double2(m.x, m.y); mods[2 * h + 1] = make_double2(m.z, m.w);
             cnts[h] = 0;
         }
         __syncthreads();
-        // a wavefront's hypotheses seven at a time (all of them, with 100 hypotheses on 16 wavefronts), their planes in registers
-        constexpr int kHypPass = 7;
-        for (int k0 = 0; wave + WAVES * k0 < H; k0 += kHypPass) {
-            double2 ma[kHypPass], mb[kHypPass];
-            int acc[kHypPass];
-#pragma unroll
-            for (int q = 0; q < kHypPass; ++q) {
-                const int h = min(wave + WAVES * (k0 + q), H - 1);
-                ma[q] = mods[2 * h]; mb[q] = mods[2 * h + 1]; acc[q] = 0;
-            }
-            if (packed) {
-                for (int j = lane; j < n_items; j += kWave) {
-                    const double px = PX[j], py = PY[j], pz = PZ[j];
-                    const int wgt = PW[j];
-#pragma unroll
-                    for (int q = 0; q < kHypPass; ++q)
-                        acc[q] += (fabs(((px * ma[q].x + py * ma[q].y) + pz * mb[q].x) + mb[q].y) < a.threshold) ? wgt : 0;   // estimate_road_norm.py:18
-                }
-            } else {
-                for (int j = lane; j < n_items; j += kWave) {
-                    const int id = Dv[j];
-                    const int wgt = W[id];
-                    const double px = X[id], py = Y[id], pz = Z[id];
-#pragma unroll
-                    for (int q = 0; q < kHypPass; ++q)
-                        acc[q] += (fabs(((px * ma[q].x + py * ma[q].y) + pz * mb[q].x) + mb[q].y) < a.threshold) ? wgt : 0;
-                }
-            }
-#pragma unroll
-            for (int q = 0; q < kHypPass; ++q) {
-                const int h = wave + WAVES * (k0 + q);
-                const int sum = wave_sum(acc[q]);
-                if (lane == 0 && h < H) cnts[h] = sum;
-            }
-        }
+        ransac_count_weighted<WAVES>(mods, cnts, H, n_items, a.threshold, packed,
+            [&](int j, double &px, double &py, double &pz, int &wgt) { px = PX[j]; py = PY[j]; pz = PZ[j]; wgt = PW[j]; },
+            [&](int j, double &px, double &py, double &pz, int &wgt) { const int id = Dv[j]; wgt = W[id]; px = X[id]; py = Y[id]; pz = Z[id]; });
         __syncthreads();
         if (a.hyp_counts) for (int h = tid; h < H; h += BLK) a.hyp_counts[fc * H + h] = cnts[h];
         if (wave == 0) {
-            // ransac.py:9-22 by the wavefront, 64 hypotheses at a time: the loop stops at the first count above the goal, and the
-            // best is the first occurrence of the largest count up to there
-            int status = 0, best = -1, best_ic = 0, used = H;
+            int status = 0;
             double m[4] = {nan(""), nan(""), nan(""), nan("")};
             double raw = nan("");
-            for (int h0 = 0; h0 < H; h0 += kWave) {
-                const int h = h0 + lane;
-                const int cc = h < H ? cnts[h] : -1;
-                const unsigned long long over = __ballot(h < H && (double)cc > goal);
-                const int limit = over ? (int)__ffsll((long long)over) - 1 : kWave - 1;
-                const bool in = h < H && lane <= limit;
-                const int mx = wave_max(in ? cc : -1);
-                if (mx > best_ic) {
-                    const unsigned long long who = __ballot(in && cc == mx);
-                    best = h0 + (int)__ffsll((long long)who) - 1; best_ic = mx;
-                }
-                if (over) { used = h0 + limit + 1; break; }
-            }
-            if (best >= 0) {
-                const double2 b0 = mods[2 * best], b1 = mods[2 * best + 1];
-                const double sgn = (b0.y < 0.0) ? -1.0 : 1.0;                     // rescale.py:159-161
-                m[0] = sgn * b0.x; m[1] = sgn * b0.y; m[2] = sgn * b1.x; m[3] = sgn * b1.y;
-                const double h_bar = -m[3];                                        // :158
-                const double norm_norm = sqrt((m[0] * m[0] + m[1] * m[1]) + m[2] * m[2]) / h_bar;   // :162-163
-                const double cam_h = 1.0 / norm_norm;                              // :165
-                raw = a.absolute_reference / cam_h;                                // :167
+            RansacReplay rp = {-1, 0, H, 0};
+            ransac_replay(rp, cnts, 0, H, goal);                                   // ransac.py:9-22
+            if (rp.best >= 0) {
+                const double2 b0 = mods[2 * rp.best], b1 = mods[2 * rp.best + 1];
+                const double4 bm = ransac_sign_rule(make_double4(b0.x, b0.y, b1.x, b1.y));   // rescale.py:159-161
+                m[0] = bm.x; m[1] = bm.y; m[2] = bm.z; m[3] = bm.w;
+                raw = a.absolute_reference / ransac_camera_height(bm);             // :158-167
             } else status = MVOSR_ST_RS_FEW;                                       // (no hypothesis with an inlier: NaN planes only)
             if (lane == 0) {
-                a.status[fc] = status; a.raw_scale[fc] = raw; a.best_ic[fc] = best_ic; a.used[fc] = used;
+                a.status[fc] = status; a.raw_scale[fc] = raw; a.best_ic[fc] = rp.best_ic; a.used[fc] = rp.used;
                 for (int kk = 0; kk < 4; ++kk) a.model[4 * fc + kk] = m[kk];
             }
         }

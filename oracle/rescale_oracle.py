@@ -204,24 +204,30 @@ def mix64(x):
     return x ^ (x >> 31)
 
 
-def device_triples(seed, frame_counter, ids, n_hyp=RANSAC_ITERATIONS):
-    """The list positions hypothesis h = 0..n_hyp-1 of frame `frame_counter` draws under key `seed` from the point list whose
-    vertex ids are `ids` (an int m: a list of m distinct points): three distinct positions, uniform — the reference draws
-    them with random.sample from OS entropy, /root/reference/src/thirdparty/Ransac/ransac.py:6,10.  ONE draw per hypothesis:
-    a sample that names one vertex twice (the list repeats vertices, /root/reference/src/rescale.py:101) spends its
-    iteration, as in the reference (ransac.py:8-21)."""
-    ids = np.arange(ids) if np.isscalar(ids) else np.asarray(ids)
-    m = len(ids)
-    key = mix64((seed ^ ((frame_counter * 0xD1B54A32D192ED03) & _M64)) & _M64)
-    out = np.zeros((n_hyp, 3), dtype=np.int64)
+def frame_key(seed, frame_counter):
+    """The key of a frame's hypotheses: its sample-sequence counter under the run's seed."""
+    return mix64((seed ^ ((frame_counter * 0xD1B54A32D192ED03) & _M64)) & _M64)
+
+
+def eval_case_key(seed, frame_counter, case):
+    """The key of case `case` of a frame in the evaluation runs (include/mvosr.h, mvosr_height_pitch_eval_batch)."""
+    return mix64(frame_key(seed, frame_counter) ^ (((case + 1) * 0xA0761D6478BD642F) & _M64))
+
+
+def key_draws(key, m, n_hyp, size=3):
+    """(n_hyp, size) distinct positions in a list of m that hypothesis h = 0..n_hyp-1 draws under `key`, uniform; size 2 — the
+    pair draw of the line model — is the triple's first two."""
+    out = np.zeros((n_hyp, size), dtype=np.int64)
     for h in range(n_hyp):
         hk = mix64((key + h) & _M64)
-        r = [mix64((hk + k) & _M64) for k in range(3)]
-        i0 = (r[0] * m) >> 64
-        i1 = (r[1] * (m - 1)) >> 64
+        i0 = (mix64(hk) * m) >> 64
+        i1 = (mix64((hk + 1) & _M64) * (m - 1)) >> 64
         if i1 >= i0:
             i1 += 1
-        i2 = (r[2] * (m - 2)) >> 64
+        if size == 2:
+            out[h] = (i0, i1)
+            continue
+        i2 = (mix64((hk + 2) & _M64) * (m - 2)) >> 64
         lo, hi = min(i0, i1), max(i0, i1)
         if i2 >= lo:
             i2 += 1
@@ -229,6 +235,16 @@ def device_triples(seed, frame_counter, ids, n_hyp=RANSAC_ITERATIONS):
             i2 += 1
         out[h] = (i0, i1, i2)
     return out
+
+
+def device_triples(seed, frame_counter, ids, n_hyp=RANSAC_ITERATIONS):
+    """The list positions hypothesis h = 0..n_hyp-1 of frame `frame_counter` draws under key `seed` from the point list whose
+    vertex ids are `ids` (an int m: a list of m distinct points): three distinct positions, uniform — the reference draws
+    them with random.sample from OS entropy, /root/reference/src/thirdparty/Ransac/ransac.py:6,10.  ONE draw per hypothesis:
+    a sample that names one vertex twice (the list repeats vertices, /root/reference/src/rescale.py:101) spends its
+    iteration, as in the reference (ransac.py:8-21)."""
+    m = ids if np.isscalar(ids) else len(ids)
+    return key_draws(frame_key(seed, frame_counter), m, n_hyp)
 
 
 def canonical_rows(tri):

@@ -15,6 +15,7 @@ import numpy as np
 
 import flat_cases as fc
 from flat_cases import U53
+from oracle import rescale_oracle as ro
 
 L = np.longdouble
 FOCUS, CX, CY = 718.856, 607.1928, 185.2157        # calculate_height_pitch.py:15-17
@@ -241,32 +242,9 @@ def reference(pts, rows, est, positions, n_hyp=None):
     return r
 
 
-# ---- the device draw (include/mvosr.h, mvosr_flat_ransac_batch), restated ---------------------------------------------------
-_M64 = (1 << 64) - 1
-
-
-def _mix64(x):
-    x = (x + 0x9E3779B97F4A7C15) & _M64
-    x = ((x ^ (x >> 30)) * 0xBF58476D1CE4E5B9) & _M64
-    x = ((x ^ (x >> 27)) * 0x94D049BB133111EB) & _M64
-    return x ^ (x >> 31)
-
-
+# ---- the device draw (include/mvosr.h, mvosr_flat_ransac_batch): the oracle's restatement ---------------------------------------
 def draw_positions(seed, frame_counter, n_hyp, M):
-    key = _mix64((seed ^ ((frame_counter * 0xD1B54A32D192ED03) & _M64)) & _M64)
-    out = np.zeros((n_hyp, 3), dtype=np.int32)
-    for h in range(n_hyp):
-        hk = _mix64((key + h) & _M64)
-        r0, r1, r2 = _mix64(hk), _mix64((hk + 1) & _M64), _mix64((hk + 2) & _M64)
-        i0 = (r0 * M) >> 64
-        i1 = (r1 * (M - 1)) >> 64
-        i1 += i1 >= i0
-        i2 = (r2 * (M - 2)) >> 64
-        lo, hi = min(i0, i1), max(i0, i1)
-        i2 += i2 >= lo
-        i2 += i2 >= hi
-        out[h] = (i0, i1, i2)
-    return out
+    return ro.device_triples(seed, frame_counter, M, n_hyp).astype(np.int32)
 
 
 # ---- crafted frames ---------------------------------------------------------------------------------------------------------

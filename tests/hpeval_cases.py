@@ -22,6 +22,7 @@ import numpy as np
 import flat_cases as fc
 import heightpitch_cases as hc
 from flat_cases import U53
+from oracle import rescale_oracle as ro
 from heightpitch_cases import GOAL, INLIER_THRESHOLD, MIN_POINTS, THRESHOLD, L, ST_EMPTY, ST_MASK, ST_RS_FEW, ST_SINGULAR  # noqa: F401
 
 MODELS = ("plane", "line")
@@ -303,30 +304,13 @@ def check_margins(model, pts, rows, est, positions):
     return not np.any(np.abs(residuals(model, Q, m[best]) - INLIER_THRESHOLD) <= band)
 
 
-# ---- the device draw (include/mvosr.h, mvosr_height_pitch_eval_batch), restated -------------------------------------------------
-_M64 = (1 << 64) - 1
-
-
+# ---- the device draw (include/mvosr.h, mvosr_height_pitch_eval_batch): the oracle's restatement ----------------------------------
 def draw_positions(model, seed, frame_counter, case, n_hyp, M):
     """(n_hyp, 3) list positions of (seed, frame, case): heightpitch_cases.draw_positions under the case's key; the line's pair is
     the triple's first two draws (column 2 is -1)."""
-    fkey = hc._mix64((seed ^ ((frame_counter * 0xD1B54A32D192ED03) & _M64)) & _M64)
-    key = hc._mix64(fkey ^ (((case + 1) * 0xA0761D6478BD642F) & _M64))
     out = np.full((n_hyp, 3), -1, dtype=np.int32)
-    for h in range(n_hyp):
-        hk = hc._mix64((key + h) & _M64)
-        r0, r1, r2 = hc._mix64(hk), hc._mix64((hk + 1) & _M64), hc._mix64((hk + 2) & _M64)
-        i0 = (r0 * M) >> 64
-        i1 = (r1 * (M - 1)) >> 64
-        i1 += i1 >= i0
-        if model == "line":
-            out[h, :2] = (i0, i1)
-            continue
-        i2 = (r2 * (M - 2)) >> 64
-        lo, hi = min(i0, i1), max(i0, i1)
-        i2 += i2 >= lo
-        i2 += i2 >= hi
-        out[h] = (i0, i1, i2)
+    size = 2 if model == "line" else 3
+    out[:, :size] = ro.key_draws(ro.eval_case_key(seed, frame_counter, case), M, n_hyp, size)
     return out
 
 

@@ -30,6 +30,8 @@ H_OF = {1: 63, 2: 64, 3: 65, 63: 100, 64: 129, 65: 1, 511: 512, 512: 63, 513: 64
 GOAL_M = (5, 10, 65, 100, 5120)                # M * 0.8 is an integer in float64 (64 * 0.8 and 4096 * 0.8 are not)
 BATCH_H = 65                                   # the hypothesis count of the one ragged batch (every table resized to it)
 MODEL_SHARE_MEASURED = {"plane": 0.04, "line": 0.07}
+WIDE_H = 130                                   # the replay runs 64 hypotheses at a time: two full blocks and a ragged one of 2
+WIDE_M = 65                                    # the smallest SIZES entry with all five levels
 
 
 class Case:
@@ -153,12 +155,12 @@ def replay_cases():
         ids = [np.nonzero(pts[:, 1] == y)[0] for y in LEVELS]
         cnt = level_counts(sizes)
 
-        def table(name, spec, goal=GOAL, note=""):
+        def table(name, spec, goal=GOAL, note="", spent=lambda i, j: [i, j, j]):
             rows, expect = [], []
             for k in spec:
                 if k < 0:
                     i, j = rng.choice(M, 2, replace=False)
-                    rows.append([i, j, j]); expect.append(0)
+                    rows.append(spent(i, j)); expect.append(0)
                 else:
                     rows.append(_pick3(rng, ids[k])); expect.append(cnt[k])
             out.append(Case("%s_%d" % (name, M), pts, rows, goal=goal, pinned=True, expect=expect, note=note))
@@ -173,7 +175,36 @@ def replay_cases():
             table("goal_stop", (3, 2, 0, 1, 1, 0, -1), note="L1 is the first count above the goal: used == 4")
             table("later_larger", (3, 2, 0, 1, -1), goal=0.25, note="goal 0.25 M: L2 stops the loop at index 1; the larger L0, L1 after it are ignored")
             table("never", (-1, 3, 2, 4, 2), note="the goal is never reached: used == H")
+        if M == WIDE_M:
+            # WIDE_H hypotheses, for the replay 64 at a time.  `at`: index -> level; the other rows cycle through `before` up to the
+            # last index of `at` and through `after` behind it; a spent row repeats its FIRST index (spent for the line's pair too).
+            def wide(name, at, before=(-1,), after=(-1,), goal=GOAL, note=""):
+                last = max(at)
+                spec = [at.get(h, before[h % len(before)] if h < last else after[h % len(after)]) for h in range(WIDE_H)]
+                table("wide_" + name, spec, goal, note, spent=lambda i, j: [i, i, j])
+
+            for i in WIDE_STOPS:
+                wide("stop%d" % i, {i: 1}, before=(0, 2, 3, -1, 4), after=(1, 0),
+                     note="L1 at %d is the first count above the goal (L0 before it counts exactly the goal): best %d, used %d" % (i, i, i + 1))
+            wide("tie_adjacent", {63: 3, 64: 4}, note="F1 at 63 and F2 at 64 tie across the blocks' edge, the rest is spent: 63 wins, used == H")
+            wide("tie_apart", {64: 3, 128: 4}, note="F1 at 64 and F2 at 128 tie two blocks apart: 64 wins, used == H")
+            wide("stop_then_larger", {62: 2}, before=(3, -1, 4), after=(0, 1), goal=0.25,
+                 note="goal 0.25 M: L2 at 62 stops the loop; the larger L0, L1 from 63 on (the rest of its block and blocks 1, 2) are ignored")
+            wide("goal_exact", {0: 0}, note="L0 at 0 counts exactly the goal, the rest is spent: best 0, used == H")
     return out
+
+
+WIDE_STOPS = (63, 64, 65, 129)                 # the last lane of block 0, the first two of block 1, the last of the ragged block
+
+
+def wide_expected(case):
+    """(best, best_ic, used) the notes of the wide tables promise, from the construction alone."""
+    kind = case.name[len("wide_"):].rsplit("_", 1)[0]
+    cnt = level_counts(SIZES[WIDE_M])
+    if kind.startswith("stop") and kind[4:].isdigit():
+        return int(kind[4:]), cnt[1], int(kind[4:]) + 1
+    return {"tie_adjacent": (63, cnt[3], WIDE_H), "tie_apart": (64, cnt[3], WIDE_H), "stop_then_larger": (62, cnt[2], 63),
+            "goal_exact": (0, cnt[0], WIDE_H)}[kind]
 
 
 def edge_cases():

@@ -10,6 +10,7 @@ import ctypes as C
 import numpy as np
 
 import flat_cases as fc
+from oracle.rescale_oracle import mix64
 
 MASK64 = (1 << 64) - 1
 FORM_NONE, FORM_GATHER, FORM_PACKED = 0, 1, 2
@@ -17,15 +18,7 @@ PACK_MAX = 1024                                         # kCasesPackMax (csrc/mv
 SINGLE_KEYS = ("raw_scale", "model", "best_ic", "used", "status", "hyp_counts")
 
 
-# ---- the seed rule of rescale.RepeatedRuns(seed=...), restated ------------------------------------------------------------------
-def mix64(x):
-    """splitmix64's finaliser as include/mvosr.h states it for mvosr_flat_ransac_batch."""
-    x = (x + 0x9E3779B97F4A7C15) & MASK64
-    x = ((x ^ (x >> 30)) * 0xBF58476D1CE4E5B9) & MASK64
-    x = ((x ^ (x >> 27)) * 0x94D049BB133111EB) & MASK64
-    return x ^ (x >> 31)
-
-
+# ---- the seed rule of rescale.RepeatedRuns(seed=...), restated (mix64: the oracle's) ---------------------------------------------
 def case_seeds(seed, cases):
     """seed_c = mix64(seed + c * 0xA0761D6478BD642F), c = 0 .. cases - 1 (rescale.RepeatedRuns' documented rule)."""
     return [mix64((int(seed) + c * 0xA0761D6478BD642F) & MASK64) for c in range(cases)]

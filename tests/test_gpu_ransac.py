@@ -98,6 +98,25 @@ def test_replay_rule_at_its_edges(runs, cases):
     assert len(seen) == 5
 
 
+def test_replay_rule_across_blocks_of_64(runs, cases):
+    """The tables of 130 hypotheses (ransac_cases.replay_cases, `wide_*`), plane and line: the kernel replays 64 counts at a time, so
+    the first count above the goal is placed at the last lane of a block, the first two of the next and the last lane of the ragged
+    block, ties straddle an edge and lie two blocks apart, larger counts follow a stop, and a count equal to the goal stands alone.
+    Counts as constructed, best_ic / used as the sequential restatement of ransac.py:9-22 gives them, the model the best row's level."""
+    seen = 0
+    for (name, line), o in runs.items():
+        if not name.startswith("wide_"):
+            continue
+        seen += 1
+        c = cases[name]
+        assert np.array_equal(o["counts"].astype(np.int64), c.expect), (name, line)
+        best, best_ic, used = rc.replay(c.expect, c.M, c.goal)
+        assert (best, best_ic, used) == rc.wide_expected(c)
+        assert (o["best_ic"], o["used"]) == (best_ic, used), (name, line, o["best_ic"], o["used"], best_ic, used)
+        assert abs(-o["model"][3] / o["model"][1] - c.pts[c.samples[best, 0], 1]) < 1e-9, (name, line, o["model"])
+    assert seen == 2 * (len(rc.WIDE_STOPS) + 4)
+
+
 def test_degenerate_and_guarded_samples(runs, cases):
     """Every hypothesis spent: best_ic 0, NaN model, used == H (M = 1, M = 2 in 3-D, the all-degenerate table); indices M, -1 and
     2^31 - 1 among valid samples count nothing and the valid ones around them count as usual (checked against the bounds in

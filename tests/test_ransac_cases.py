@@ -88,6 +88,39 @@ def test_replay_tables_are_what_their_notes_say(cases):
     assert seen == set(want)
 
 
+def test_wide_replay_tables_are_what_their_notes_say(cases):
+    """The tables of 130 hypotheses (the replay runs 64 at a time): the module's sequential restatement of ransac.py:9-22 gives what
+    the construction promises, the promised counts are what both bounds give for the plane AND the line (a spent row is spent for
+    both), and the designs hold: where the first count above the goal lies, which rows tie, what lies behind a stop."""
+    wide = {n: c for n, c in cases.items() if n.startswith("wide_")}
+    assert len(wide) == len(rc.WIDE_STOPS) + 4 and rc.SIZES[rc.WIDE_M] == min((s for s in rc.SIZES.items() if all(s[1])), key=lambda s: s[0])[1]
+    for name, c in wide.items():
+        assert c.H == rc.WIDE_H == 2 * 64 + 2 and c.M == rc.WIDE_M and c.pinned
+        want = rc.wide_expected(c)
+        assert rc.replay(c.expect, c.M, c.goal) == want, (name, rc.replay(c.expect, c.M, c.goal), want)
+        for line in (False, True):
+            lo, hi = rc.bounds(c, line)
+            assert np.array_equal(lo, c.expect) and np.array_equal(hi, c.expect), (name, line)
+            assert np.array_equal(rc._spent(c, line)[0], c.expect == 0), (name, line)
+        goal = float(c.M) * c.goal
+        over = np.nonzero(c.expect > goal)[0]
+        kind = name[len("wide_"):].rsplit("_", 1)[0]
+        if kind.startswith("stop"):
+            assert over[0] == want[0] and c.expect[:want[0]].max() < c.expect[want[0]]
+        else:
+            assert len(over) == 0
+        if kind.startswith("stop") and kind != "stop_then_larger":
+            assert c.expect[0] == goal and want[0] in rc.WIDE_STOPS                 # (a count equal to the goal before it: no stop there)
+        if kind == "stop_then_larger":
+            assert c.expect[63] > c.expect[62] and c.expect[64:128].max() > c.expect[62] and c.expect[128:].max() > c.expect[62]
+        if kind in ("tie_adjacent", "tie_apart"):
+            i, j = np.nonzero(c.expect)[0]
+            assert (i, j) == ((63, 64) if kind == "tie_adjacent" else (64, 128)) and c.expect[i] == c.expect[j]
+            assert c.pts[c.samples[i, 0], 1] != c.pts[c.samples[j, 0], 1]         # two levels: the model tells which one won
+        if kind == "goal_exact":
+            assert c.expect[0] == goal and not c.expect[1:].any()
+
+
 def test_float64_restatement_within_the_bounds(cases):
     """The kernel's expressions in float64 NumPy: counts between lo and hi, the model of every hypothesis that can have one within
     the derived tolerance of the np.longdouble one (and NaN for the spent ones); prints the share of the tolerance it uses."""

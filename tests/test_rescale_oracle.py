@@ -93,6 +93,19 @@ def test_rescale_row_form_invariance_golden():
         assert np.array_equal(ro.canonical_rows(est.last["tri2"]), est.last["tri2"])
 
 
+def test_sample_sequence_pinned_values():
+    """The values every restatement of the sample sequence is held to (csrc/mvosr_ransac.hpp asserts the first two at compile time),
+    and the pair draw and the evaluation runs' case key beside the triple draw."""
+    assert ro.mix64(0) == 0xe220a8397b1dcdaf
+    assert ro.mix64(1) == 0x910a2dec89025cc1
+    assert ro.device_triples(7, 3, 12, 4).tolist() == [[6, 3, 11], [7, 9, 5], [10, 11, 1], [2, 11, 6]]
+    assert np.array_equal(ro.key_draws(ro.frame_key(7, 3), 12, 4), ro.device_triples(7, 3, 12, 4))
+    k = ro.eval_case_key(7, 3, 0)
+    assert k != ro.frame_key(7, 3) and k != ro.eval_case_key(7, 3, 1)
+    assert np.array_equal(ro.key_draws(k, 12, 50, 2), ro.key_draws(k, 12, 50)[:, :2])        # the pair: the triple's first two
+    assert ro.device_triples(5, 0, 3, 20).min() == 0 and all(sorted(r) == [0, 1, 2] for r in ro.device_triples(5, 0, 3, 20).tolist())
+
+
 def test_device_sample_sequence():
     """The counter-based sample sequence: three distinct positions below m, a function of (seed, frame counter,
     hypothesis) only, and close to uniform over positions."""
