@@ -780,6 +780,44 @@ int mvosr_static_tri_batch(mvosr_ctx *ctx, int64_t n_lists, const int64_t *off, 
                            double *raw_scale, int32_t *n_used, int32_t *hist, int32_t *status);
 
 /*
+ * The feature-distribution analysis (/root/reference/src/scale_calculator.py:486-599: check_full_distribution, check_skewness,
+ * skewness_analysis, mode_analysis, plot_distribution — what they compute, not what they draw) for n_frames frames, one workgroup
+ * per frame and one wavefront per population (featdist_kernel).  Every output is a function of the frame's values alone and is
+ * compared for bit equality.
+ * Frame f is the entries i in [off[f], off[f] + cnt[f]) of `y` and `level` — cnt == NULL: off has n_frames + 1 entries and the
+ * lengths are their differences.  y: the features' raw y (no remap, :563).  level: 0 = a feature below the vanishing row (:564),
+ * 1 = also kept by the vote (:575-578), 2 = also selected (:588-591).  Population p = 0, 1, 2 is the entries with level >= p in
+ * packed order (the order of the reference's mask and np.unique indexing).  scale[f]: the frame's true scale (:569).
+ * Per frame and population, row = f * MVOSR_FD_POPULATIONS + p:
+ *   n_out[row]: the population's size.
+ *   hist[row][0..168]: how many y satisfy e[k] <= y < e[k+1] with e[k] = (double)k * 0.1, bin 168 also y == e[169] (:492;
+ *   np.histogram over an explicit edge array counts by comparison; NaN and values outside [0, e[169]] are in no bin).
+ *   hist[row][169..171]: how many y are exactly e[29], e[49], e[99].  np.histogram over np.array(range(0, m + 1)) * 0.1 (m = 29: :514;
+ *   49: :528-536; 99: :506) is hist[row][0..m-1] with that count added to bin m - 1: its last bin is closed.
+ *   hist_scaled[row]: the same 172 words of y * scale[f] (one IEEE multiply).  A product that is not finite is in no bin.
+ *   stats[row][0..2]: np.mean(y), np.std(y), np.median(y) to the last bit — the sums in np.add.reduce's pairwise order (below 8
+ *   values a plain loop from 0.0, up to 128 eight strided accumulators, above that halves split at a multiple of 8), std =
+ *   sqrt(sum((y - mean)^2) / n), the median (0.0 + a) / 1.0 or ((0.0 + a) + b) / 2.0 of the middle order statistics, NaN where the
+ *   population holds a NaN.
+ *   An empty population: n_out 0, stats NaN, zero histograms; that is no error.
+ * status[f]: 0, or MVOSR_ST_ERR_MASK — a level above 2 (with one level per feature "selected" implies "kept": no other sequence
+ * is invalid), a negative offset or length, or more entries than max_feat; of such a frame nothing past the levels is used:
+ * n_out 0, stats NaN, zero histograms, nothing added to the tables.
+ * seq_tables (optional): int64 [MVOSR_FD_POPULATIONS][MVOSR_FD_HIST_WORDS] in device memory, owned by the caller and kept across
+ * launches: every frame's hist_scaled is ADDED to it (64-bit atomic adds of integers from the frame's finished LDS histogram:
+ * the order of arrival changes nothing).  The caller zeroes it.
+ * LDS is carved at max_feat (mvosr_featdist_plan.hpp): above mvosr_featdist_max_features() — the largest frame whose three lists
+ * fit 160 KiB — the launch returns MVOSR_ERR_TOO_LARGE.  n_frames <= 0: MVOSR_OK, nothing launched.  MVOSR_ERR_ARG: a null
+ * argument other than cnt / seq_tables, or max_feat < 0.
+ */
+#define MVOSR_FD_POPULATIONS 3
+#define MVOSR_FD_HIST_WORDS 172  /* MVOSR_HIST_BINS + the three closing-edge counts */
+int mvosr_feature_distribution_batch(mvosr_ctx *ctx, int64_t n_frames, const int64_t *off, const int32_t *cnt, const double *y,
+                                     const uint8_t *level, const double *scale, int32_t max_feat, int32_t *n_out, int32_t *hist,
+                                     int32_t *hist_scaled, double *stats, int32_t *status, int64_t *seq_tables);
+int mvosr_featdist_max_features(void);
+
+/*
  * The cross-frame tail of scale_calculation_ransac (rescale.py:169-178) over a run of frames, on the device: the slew
  * limiter — a frame with apply[i] != 0 moves the running scale towards raw[i] by at most `slew` (0.3), any other frame
  * leaves it — followed by the window median of the pushed values (np.median(self.scale_queue)).  raw/apply/pushed/

@@ -24,6 +24,8 @@ TRI2_SURVIVORS, TRI2_FEATURES = 0, 1      # mvosr_batch.tri2_ids
 N_COUNTS = 8
 TILE_W = 512                              # MVOSR_TILE_W
 HIST_BINS = 169
+FD_POPULATIONS = 3           # MVOSR_FD_POPULATIONS
+FD_HIST_WORDS = 172          # MVOSR_FD_HIST_WORDS: the 169 bins, then the counts on edges 29, 49, 99
 
 
 ERR_ALLOC = -5
@@ -228,6 +230,8 @@ SYMBOLS = {
     "mvosr_region_grow_batch": (C.c_int, [_P, C.POINTER(Batch), _P, _P, C.POINTER(GrowParams), C.POINTER(GrowOutputs), C.c_int64]),
     "mvosr_tri_graph_batch": (C.c_int, [_P, C.POINTER(Params), C.POINTER(Batch), _P, _P, C.POINTER(TriGraphOutputs)]),
     "mvosr_static_tri_batch": (C.c_int, [_P, C.c_int64, _P, _P, _P, _P, C.c_int32, C.c_double, _P, _P, _P, _P, _P]),
+    "mvosr_feature_distribution_batch": (C.c_int, [_P, C.c_int64, _P, _P, _P, _P, _P, C.c_int32, _P, _P, _P, _P, _P, _P]),
+    "mvosr_featdist_max_features": (C.c_int, []),
     "mvosr_slew_median": (C.c_int, [_P, _P, _P, C.c_int64, C.c_double, C.c_double, C.c_int, _P, C.c_int, _P, _P]),
     "mvosr_slew_median_host": (C.c_int, [_P, _P, C.c_int64, C.c_double, C.c_double, C.c_int, _P, C.c_int, _P, _P, _P]),
     "mvosr_ransac_plane_batch": (C.c_int, [_P, C.c_int64, _P, _P, _P, _P, _P, _P, C.c_int, C.c_double, C.c_double,

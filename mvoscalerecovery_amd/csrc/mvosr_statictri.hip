@@ -26,6 +26,7 @@
 // The file is built with -ffp-contract=off and needs no fused operation: every operation here is an IEEE operation of its own.
 #include "mvosr_device.hpp"
 #include "mvosr_host.hpp"
+#include "mvosr_select.hpp"
 
 #include <math.h>
 
@@ -86,48 +87,12 @@ __device__ __forceinline__ int st_bin_of(double hi) {
 
 __device__ __forceinline__ unsigned long long st_pattern(double h) { return (unsigned long long)__double_as_longlong(1.0 / h); }
 
-// The pattern of rank `rank` (0-based, ascending) among the counted entries' 1/h: four bits a pass from the top; lane b < 16
-// counts the entries whose pattern continues the prefix with digit b.
-__device__ __forceinline__ unsigned long long st_select(const double *H, const uint8_t *FL, int64_t len, int rank) {
-    const int lane = lane_id();
-    unsigned long long prefix = 0ull;
-    for (int shift = 60; shift >= 0; shift -= 4) {
-        int mine = 0;
-        st_for_each(H, FL, len, [&](bool counted, double h) {
-            const unsigned long long p = st_pattern(h);
-            const bool match = counted && (shift == 60 || (p >> (shift + 4)) == (prefix >> (shift + 4)));
-            const int digit = match ? (int)((p >> shift) & 15ull) : -1;
-            if (__ballot(match) == 0ull) return;
-#pragma unroll
-            for (int b = 0; b < 16; ++b) {
-                const int c = __popcll(__ballot(digit == b));
-                mine += lane == b ? c : 0;
-            }
-        });
-        const int incl = wave_scan_incl(lane < 16 ? mine : 0);
-        // (the rank lies inside the entries that share the prefix, so a lane below 16 answers)
-        const int sel = max(__ffsll((long long)__ballot(lane < 16 && incl > rank)) - 1, 0);
-        const int before = __shfl(incl, max(sel - 1, 0));
-        rank -= sel > 0 ? before : 0;
-        prefix |= (unsigned long long)sel << shift;
-    }
-    return prefix;
-}
-
-// np.median of the counted entries' 1/h (n >= 1 of them): the middle order statistic, or (a + b) / 2 of the two middle ones
+// np.median of the counted entries' 1/h (n >= 1 of them): the middle order statistic, or (a + b) / 2 of the two middle ones — the
+// radix select of mvosr_select.hpp over the entries' patterns, each pass re-reading the list
 __device__ __forceinline__ double st_median(const double *H, const uint8_t *FL, int64_t len, int n) {
-    const unsigned long long lo = st_select(H, FL, len, (n - 1) >> 1);
+    unsigned long long lo, hi;
+    wave_middle_keys([&](auto visit) { st_for_each(H, FL, len, [&](bool counted, double h) { visit(counted, st_pattern(h)); }); }, n, lo, hi);
     if (n & 1) return __longlong_as_double((long long)lo);
-    int le = 0;
-    unsigned long long above = ~0ull;
-    st_for_each(H, FL, len, [&](bool counted, double h) {
-        const unsigned long long p = st_pattern(h);
-        le += (counted && p <= lo) ? 1 : 0;
-        above = (counted && p > lo && p < above) ? p : above;
-    });
-    le = wave_sum(le);
-    above = wave_min_u64(above);
-    const unsigned long long hi = le > (n >> 1) ? lo : above;
     return (__longlong_as_double((long long)lo) + __longlong_as_double((long long)hi)) / 2.0;
 }
 

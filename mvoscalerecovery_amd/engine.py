@@ -504,6 +504,33 @@ class TriGraphOutputs:
         self.bufs = {}
 
 
+class FeatDistOutputs:
+    """Output arrays of ``ScaleEngine.feature_distribution_batch`` in one device block, per frame and population: ``n``,
+    ``hist`` / ``hist_scaled`` (the 169 bins of y / y * scale, then the counts on edges 29, 49, 99), ``stats`` (mean, std,
+    median); per frame ``status``."""
+
+    def __init__(self, ctx, n_frames):
+        F, P, W = max(int(n_frames), 1), _lib.FD_POPULATIONS, _lib.FD_HIST_WORDS
+        self.ctx = ctx
+        self.n_frames = int(n_frames)
+        self.block = ctx.block([("stats", (F, P, 3), np.float64), ("n", (F, P), np.int32), ("hist", (F, P, W), np.int32),
+                                ("hist_scaled", (F, P, W), np.int32), ("status", F, np.int32)])
+        self.bufs = dict(self.block.views)
+
+    def invalidate(self):
+        self.block.invalidate()
+        self.block.mark(False)
+
+    def get(self, name):
+        return self.bufs[name].download()[:self.n_frames]
+
+    def free(self):
+        if self.block is not None:
+            self.block.free()
+            self.block = None
+        self.bufs = {}
+
+
 class ScaleEngine:
     """Launches the hot-path kernels.  One engine = one context (device + stream) + parameters."""
 
@@ -570,6 +597,22 @@ class ScaleEngine:
             return {name: out[name].download()[:F] for name, _, _ in spec}
         finally:
             out.free()
+
+    def feature_distribution_max_features(self):
+        """The largest frame mvosr_feature_distribution_batch takes (its three lists in 160 KiB of LDS)."""
+        return int(self.lib.mvosr_featdist_max_features())
+
+    def feature_distribution_batch(self, n_frames, off, cnt, y, level, scale, max_feat, out: FeatDistOutputs, seq_tables=None):
+        """The feature-distribution analysis (/root/reference/src/scale_calculator.py:486-599) of ``n_frames`` frames: one launch
+        of mvosr_feature_distribution_batch.  ``off`` / ``cnt`` / ``y`` / ``level`` / ``scale`` are DEVICE buffers in the packed
+        layout (``cnt`` None: ``off`` has one more entry); ``seq_tables``: the resident int64 [3][172] sequence tables the frames'
+        scaled histograms are added to, or None."""
+        out.invalidate()
+        _lib.check(self.lib.mvosr_feature_distribution_batch(self.ctx.handle, int(n_frames), off.ptr, cnt.ptr if cnt is not None else None,
+                                                             y.ptr, level.ptr, scale.ptr, int(max_feat), out.bufs["n"].ptr,
+                                                             out.bufs["hist"].ptr, out.bufs["hist_scaled"].ptr, out.bufs["stats"].ptr,
+                                                             out.bufs["status"].ptr, seq_tables.ptr if seq_tables is not None else None),
+                   "mvosr_feature_distribution_batch")
 
     def road_model_batch(self, batch: DeviceBatch, out: DeviceOutputs, height_level=None, waves=0):
         b, o = batch.struct(), out.struct()

@@ -28,9 +28,10 @@ import numpy as np
 
 from . import _lib
 from . import constants as K
+from . import distribution
 from . import packing
 from . import stream
-from .engine import DeviceBatch, DeviceOutputs, ReliabilityOutputs, ScaleEngine, TriGraphOutputs
+from .engine import DeviceBatch, DeviceOutputs, FeatDistOutputs, ReliabilityOutputs, ScaleEngine, TriGraphOutputs
 
 
 def raise_for_status(status, frame=None):
@@ -515,12 +516,253 @@ class ScaleEstimator(stream.StreamKnobs):
             raise error
         return filtered, np.ones(F)
 
-    # dead-but-referenced methods of the reference (main.py:117-123 under ``if(False)``)
-    def check_full_distribution(self, *a, **k):
-        raise NotImplementedError("visualisation helper of the reference; not part of the hot path")
+    # ---- the reference's feature-distribution analysis (:49-54, :386-388, :428-599; main.py:117-123 under ``if(False)``) --------
+    # The three populations of a frame — every feature below the vanishing row, the ones the reliability vote keeps, the ones
+    # feature_selection_by_tri selects — come from the staged path; mvosr_feature_distribution_batch turns them into histograms,
+    # mean / std / median and the sequence tables; the few scalar operations on top are distribution.py's.
+    def check_distance(self, feature3d):
+        """scale_calculator.py:49-54 (host only)."""
+        return distribution.check_distance(feature3d, self.focus, verbose=self.verbose)
 
-    def plot_distribution(self, *a, **k):
-        raise NotImplementedError("visualisation helper of the reference; not part of the hot path")
+    def distribution(self, feature3d):
+        """scale_calculator.py:386-388 computes a histogram only to plot it: nothing is returned, nothing drawn here."""
+        return None
+
+    def check_mode(self, dis_data, bins):
+        """scale_calculator.py:446-483 (host only)."""
+        return distribution.check_mode(dis_data, bins, verbose=self.verbose)
+
+    def check_reverse_mode(self, dis_data):
+        """scale_calculator.py:428-443 (host only)."""
+        return distribution.check_reverse_mode(dis_data)
+
+    def _dist_engine(self):
+        """The un-remapped engine of the distribution path: ``_plain_engine()``, in the reference's vote mode whatever the estimator's."""
+        if self.check_triangle == "reference":
+            return self._plain_engine()
+        if getattr(self, "_dist_plain", None) is None:
+            self._dist_plain = ScaleEngine(self.absolute_reference, ctx=self.engine.ctx, camera_pitch=0.0, check_triangle="reference")
+        return self._dist_plain
+
+    def _dist_tables(self):
+        if getattr(self, "_dist_seq", None) is None:
+            self._dist_seq = self.engine.ctx.zeros((_lib.FD_POPULATIONS, _lib.FD_HIST_WORDS), np.int64)
+        return self._dist_seq
+
+    def _dist_check_cap(self, n):
+        cap = self.engine.feature_distribution_max_features()
+        if n > cap:
+            raise ValueError("feature distribution: %d features in one frame, at most %d fit the kernel's LDS plan" % (n, cap))
+
+    def _dist_launch(self, off, cnt, y, level, scale, max_feat, tables):
+        """One launch of mvosr_feature_distribution_batch over host arrays in the packed layout -> (n, words, words_scaled, stats, status)."""
+        eng, ctx, F = self._dist_engine(), self.engine.ctx, len(cnt)
+        total = max(len(y), 2)
+        blk = ctx.block([("off", max(F, 1), np.int64), ("cnt", max(F, 1), np.int32), ("y", total, np.float64),
+                         ("scale", max(F, 1), np.float64), ("level", total, np.uint8)])
+        out = FeatDistOutputs(ctx, F)
+        try:
+            pad = lambda a, n, dt: np.concatenate([np.asarray(a, dtype=dt), np.zeros(n - len(a), dtype=dt)])
+            blk.upload({"off": pad(off, max(F, 1), np.int64), "cnt": pad(cnt, max(F, 1), np.int32), "y": pad(y, total, np.float64),
+                        "scale": pad(scale, max(F, 1), np.float64), "level": pad(level, total, np.uint8)})
+            eng.feature_distribution_batch(F, blk["off"], blk["cnt"], blk["y"], blk["level"], blk["scale"], max_feat, out, tables)
+            return tuple(out.get(k) for k in ("n", "hist", "hist_scaled", "stats", "status"))
+        finally:
+            out.free()
+            blk.free()
+
+    def _dist_of_list(self, data):
+        """One list through the kernel as population 0 of one frame -> (words[172], mean, std, median)."""
+        y = np.ascontiguousarray(np.asarray(data, dtype=np.float64).reshape(-1))
+        self._dist_check_cap(y.size)
+        n, words, _, stats, _ = self._dist_launch([0], [y.size], y, np.zeros(y.size, np.uint8), [1.0], y.size, None)
+        return words[0, 0], stats[0, 0, 0], stats[0, 0, 1], stats[0, 0, 2]
+
+    def _dist_of_attribute(self, name):
+        """(words, mean, std, median) of the y column of ``all_feature`` / ``correct_distance_feature`` / ``flat_feature``: what the
+        last ``check_full_distribution`` left for that very array, else one launch on it."""
+        value = getattr(self, name)
+        y = value[:, 1]                                               # (TypeError on the initial [] — or on None —, as in the reference)
+        kept = getattr(self, "_dist_kept", {}).get(name)
+        if kept is not None and kept[0] is value:
+            return kept[1]
+        return self._dist_of_list(y)
+
+    def check_skewness(self, data, mode=None, method='p1'):
+        """scale_calculator.py:486-497 on arbitrary data: one launch of the kernel on the list, the skew from its outputs."""
+        return self._skew_from(self._dist_of_list(data), mode, method)
+
+    def _skew_from(self, dist, mode, method):
+        words, mean, std, median = dist
+        if self.verbose:
+            print('mean,meidan,std', mean, median, std)
+        if method == 'p2':
+            return distribution.skews(mean, std, median, 0.0)[1]          # :489
+        if method == 'p1':
+            if mode is None:
+                mode = distribution.p1_mode(words)                        # :492-495
+            return distribution.skews(mean, std, median, mode)[0]         # :496
+        raise UnboundLocalError("cannot access local variable 'skew' where it is not associated with a value")   # :497
+
+    def skewness_analysis(self):
+        """scale_calculator.py:498-503: the p1 skew of the selected features' y."""
+        flat_skew = self._skew_from(self._dist_of_attribute("flat_feature"), None, 'p1')
+        if self.verbose:
+            print('skewness', flat_skew)
+        return flat_skew
+
+    def mode_analysis(self):
+        """scale_calculator.py:505-507: check_mode over the DENSITY of the selected features' 99-bin histogram (its thresholds 2
+        are applied to density values, as in the reference)."""
+        words = self._dist_of_attribute("flat_feature")[0]
+        return self.check_mode(distribution.density_of(distribution.narrow_histogram(words, 99), 99), distribution.EDGES[:100])
+
+    def plot_distribution(self, label, img, scale=1):
+        """scale_calculator.py:509-560 without the figure: the curves it would plot, as a dict — ``bins`` (``bins[:-1]``) and
+        ``selected`` (``0.1 * dis``, the density of the selected features over 49 bins), ``all_hist`` / ``correct_hist`` (the two
+        count histograms it computes), ``all_points`` / ``correct_points`` / ``selected_points`` (the ``(z, -y)`` sets of the
+        scatter) and ``img``.  Raises the reference's TypeError while no frame was analysed."""
+        bins = distribution.EDGES[:50]
+        res = {"label": label, "bins": bins[:-1], "all_hist": None, "correct_hist": None, "selected": None, "selected_points": None}
+        if self.all_feature is not None and len(self.all_feature) > 0:                                 # :526-528
+            res["all_hist"] = distribution.narrow_histogram(self._dist_of_attribute("all_feature")[0], 49)
+        if len(self.correct_distance_feature) > 0:                                                     # :530-532
+            res["correct_hist"] = distribution.narrow_histogram(self._dist_of_attribute("correct_distance_feature")[0], 49)
+        flat = self.flat_feature
+        if flat is not None and len(flat) > 0:                                                         # :534-537
+            res["selected"] = 0.1 * distribution.density_of(distribution.narrow_histogram(self._dist_of_attribute("flat_feature")[0], 49), 49)
+        res["all_points"] = (self.all_feature[:, 2], -self.all_feature[:, 1])                          # :546 (TypeError on [])
+        res["correct_points"] = (self.correct_distance_feature[:, 2], -self.correct_distance_feature[:, 1])    # :547
+        if flat is not None and len(flat) > 0:                                                         # :551-552
+            res["selected_points"] = (flat[:, 2], -flat[:, 1])
+        res["img"] = self.img                                                                          # :557
+        return res
+
+    def reset_distribution(self):
+        """Zero the sequence tables on the device and empty the accumulated lists (``all_features`` and its siblings)."""
+        self._dist_tables().fill(0)
+        self.all_features, self.correct_distance_features, self.flat_features = [], [], []
+
+    def cumulative_histograms(self, bins=29, density=False):
+        """The three histograms of the sequence — np.histogram of the y column of ``all_features``, ``correct_distance_features`` and
+        ``flat_features`` over ``np.array(range(0, bins + 1)) * 0.1`` (:513-520 has bins = 29) — from the tables resident on the
+        device: ``[3, bins]``, int64 counts or, with ``density``, float64."""
+        self.engine.ctx.sync()
+        h = distribution.narrow_histogram(self._dist_tables().download(), bins)
+        return np.stack([distribution.density_of(r, bins) for r in h]) if density else h
+
+    def check_full_distribution(self, feature3d, feature2d, scale, img=None):
+        """scale_calculator.py:562-599: sets ``all_feature``, ``correct_distance_feature``, ``flat_feature``, ``height_level`` and
+        ``img``, appends the scaled rows to ``all_features`` and its siblings, returns early and raises where the reference does
+        — after the state changes the reference has made by then.  The frame's statistics stay in ``last_distribution``."""
+        res = self.check_full_distribution_batch([feature3d], [feature2d], [scale], _img=img)
+        if 0 in res.errors:
+            raise res.errors[0]
+
+    def check_full_distribution_batch(self, feature3ds, feature2ds, scales, accumulate=True, _img=None, _launch=True):
+        """``check_full_distribution`` once per frame, in order, on this estimator: one staged pass (reliability vote on SciPy's rows,
+        ``feature_selection_by_tri``) and ONE launch of mvosr_feature_distribution_batch per chunk of ``PIPELINE_CHUNK`` frames; the
+        sequence tables stay on the device.  Returns a ``distribution.FeatureDistribution``.  It does not raise at a frame where the
+        per-frame call returns early or raises: such a frame gets a status, NaNs and its exception in ``errors``, and contributes
+        what the reference had appended by then.  ``accumulate=False``: the Python lists ``all_features`` ... are not extended
+        (one array object per feature and frame; the device tables are added to all the same)."""
+        F = len(feature3ds)
+        if not (len(feature2ds) == F and len(scales) == F):
+            raise ValueError("feature3ds, feature2ds and scales must have one entry per frame")
+        f2s = [np.asarray(a) for a in feature2ds]
+        for f2 in f2s:
+            self._dist_check_cap(int(np.count_nonzero(f2[:, 1] > self.vanish)) if f2.size else 0)
+        parts = []
+        for a in range(0, F, self.PIPELINE_CHUNK):
+            b = min(F, a + self.PIPELINE_CHUNK)
+            parts.append(self._distribution_chunk(feature3ds[a:b], f2s[a:b], scales[a:b], accumulate, _img, _launch))
+        if not parts:
+            parts.append((np.zeros((0, 3), np.int32), np.zeros((0, 3, _lib.FD_HIST_WORDS), np.int32), np.zeros((0, 3, _lib.FD_HIST_WORDS), np.int32),
+                          np.zeros((0, 3, 3)), np.zeros(0), np.zeros(0, np.int32), {}))
+        errors, base = {}, 0
+        for part in parts:
+            errors.update({base + f: e for f, e in part[6].items()})
+            base += len(part[5])
+        res = distribution.FeatureDistribution(*(np.concatenate([part[k] for part in parts]) for k in range(6)), errors)
+        self.last_distribution = res
+        return res
+
+    def _distribution_levels(self, f3s, f2s):
+        """The staged pass of a chunk (:564-591) -> the packed frames, the vote's masks, one level per packed feature (0 below the
+        vanishing row, 1 kept, 2 selected), how each frame ends (DIST_*), the exceptions, the selections over the survivors and the
+        frames' height levels."""
+        eng, F = self._dist_engine(), len(f3s)
+        _, status, level, _, host_errors, st = self._chunk_staged(f3s, f2s, stage=True, _remapped=True, _distribution=eng)
+        pf, masks, selected = st["pf"], st["masks"], st["out"].get("selected")
+        tri1_errors = pf.extra["tri1_errors"]
+        cnt = np.asarray(pf.feat_cnt)
+        levels = np.zeros(max(pf.total_padded, 2), dtype=np.uint8)
+        outcome, errors, picks = np.zeros(F, dtype=np.int32), {}, [None] * F
+        for f in range(F):
+            sl = pf.frame_slice(f)
+            if f in tri1_errors:                                              # :572 raised
+                outcome[f], errors[f] = distribution.DIST_RAISED_TRI1, tri1_errors[f]
+            elif cnt[f] <= 3:                                                 # :576, :586 (the LENGTH of the mask)
+                outcome[f] = distribution.DIST_EARLY
+            else:
+                levels[sl] = masks[f]                                         # :577-582
+                if f in host_errors:                                          # :583 raised
+                    outcome[f], errors[f] = distribution.DIST_RAISED_TRI2, host_errors[f]
+                elif int(status[f]) in (K.ST_ERR_SINGULAR, K.ST_ERR_MASK, K.ST_ERR_EMPTY):      # :588 raised (:229)
+                    outcome[f] = distribution.DIST_RAISED_SELECTION
+                    try:
+                        raise_for_status(int(status[f]))
+                    except Exception as exc:                                  # noqa: BLE001 - kept for the caller, who raises it
+                        errors[f] = exc
+                else:
+                    o, kept = int(pf.feat_off[f]), int(np.count_nonzero(masks[f]))
+                    pick = selected[o:o + kept] != 0                          # over the survivors (:247, sorted unique ids)
+                    where = np.nonzero(masks[f])[0][pick]
+                    levels[o + where] = 2                                     # :590-595
+                    picks[f] = pick
+                    outcome[f] = distribution.DIST_OK if pick.any() else distribution.DIST_NO_SELECTION
+        return pf, masks, levels, outcome, errors, picks, level
+
+    def _distribution_chunk(self, f3s, f2s, scales, accumulate, img, launch):
+        F = len(f3s)
+        pf, masks, levels, outcome, errors, picks, level = self._distribution_levels(f3s, f2s)
+        cnt = np.asarray(pf.feat_cnt)
+        scale_arr = np.array([float(s) for s in scales], dtype=np.float64)
+        if launch:
+            n, words, words_s, stats, kstatus = self._dist_launch(pf.feat_off, cnt, pf.y, levels, scale_arr, int(pf.max_feat), self._dist_tables())
+        else:                                                                 # (profiles/featdist_bench.py: the staged pass alone)
+            W = _lib.FD_HIST_WORDS
+            n, words, words_s = np.zeros((F, 3), np.int32), np.zeros((F, 3, W), np.int32), np.zeros((F, 3, W), np.int32)
+            stats, kstatus = np.full((F, 3, 3), np.nan), np.zeros(F, np.int32)
+        outcome = np.where(kstatus != 0, kstatus, outcome).astype(np.int32)
+        # the attributes, frame by frame, as the per-frame calls would leave them
+        kept_stats = dict(getattr(self, "_dist_kept", {}))
+        of = lambda f, p: (words[f, p], stats[f, p, 0], stats[f, p, 1], stats[f, p, 2])
+        for f in range(F):
+            f3 = np.asarray(f3s[f])[pf.lower_index[f], :]                     # :564-565
+            self.all_feature = f3.copy()                                      # :567
+            kept_stats["all_feature"] = (self.all_feature, of(f, 0))
+            if accumulate:
+                self.all_features.extend(f3 * scales[f])                     # :568-569
+            if outcome[f] in (distribution.DIST_RAISED_TRI1, distribution.DIST_EARLY) or kstatus[f] != 0:
+                continue
+            f3 = f3[masks[f], :]                                              # :578
+            self.correct_distance_feature = f3.copy()                         # :580
+            kept_stats["correct_distance_feature"] = (self.correct_distance_feature, of(f, 1))
+            if accumulate:
+                self.correct_distance_features.extend(f3 * scales[f])        # :581-582
+            if picks[f] is None:
+                continue
+            self.height_level = level[f]                                      # :241
+            if picks[f].any():                                                # :590
+                self.flat_feature = f3[picks[f]].copy()                       # :591-593
+                kept_stats["flat_feature"] = (self.__dict__["_flat_value"], of(f, 2))
+                if accumulate:
+                    self.flat_features.extend(self.flat_feature * scales[f]) # :594-595
+            self.img = img                                                    # :599
+        self._dist_kept = kept_stats
+        hl = np.where([p is not None for p in picks], level, np.nan) if F else np.zeros(0)
+        return n, words, words_s, stats, hl, outcome, errors
 
     # ---- batched surface ---------------------------------------------------------------------
     def scale_calculation_batch(self, feature3ds, feature2ds, tri1s=None, tri2s=None, _single=False, _raw_only=False):
@@ -751,22 +993,24 @@ class ScaleEstimator(stream.StreamKnobs):
 
     # -- vote="reliability" / selection="tri_graph": the staged path with the reference's commented alternatives in place of its
     # live lines (:259 for :260, :589 at :273)
-    def _chunk_staged(self, f3s, f2s, tri1s=None, stage=False, _remapped=False):
+    def _chunk_staged(self, f3s, f2s, tri1s=None, stage=False, _remapped=False, _distribution=None):
         """One chunk of frames: vanishing-row filter, packing and Delaunay #1 on the host (SciPy's rows verbatim: the reliability
         vote reads their ORDER, :91-98), the configured vote on the device (mvosr_reliability_batch or mvosr_outlier_vote_batch),
         the survivors compacted and Delaunay #2 on the host (:263-267), then the survivors as frames of their own.
         selection="tri": no first triangulation, so every one of them passes the scale kernel's own vote, the arrangement of
         ``feature_selection_by_tri`` — through mvosr_scale_batch (:225-248, :324-354, :419), every frame in the exact mode.
-        selection="tri_graph": ``_select_tri_graph``.  Returns ``(raw, status, level, counts, host_errors, state)``."""
+        selection="tri_graph": ``_select_tri_graph``.  Returns ``(raw, status, level, counts, host_errors, state)``.
+        ``_distribution`` (an engine; ``check_full_distribution``, :562-599): on that engine, the reliability vote (:575) and
+        ``feature_selection_by_tri`` (:588) on SciPy's rows as they come, whatever the estimator was built with."""
         F = len(f3s)
-        eng = self._plain_engine() if _remapped else self.engine
+        eng = _distribution if _distribution is not None else (self._plain_engine() if _remapped else self.engine)
         ctx = eng.ctx
         pf = packing.pack_features(f3s, f2s, self.vanish)             # raw values, packed BEFORE the in-place remap below
         if self.mutate_inputs and not _remapped:
             for f3 in f3s:
                 if isinstance(f3, np.ndarray) and f3.size:
                     self.feature_remap(f3)                             # :414
-        reliability = self.vote == "reliability"
+        reliability = self.vote == "reliability" or _distribution is not None
         pf.extra["canonical"] = (not reliability) and self.check_triangle == "fixed"
         packing.attach_tri1(pf, tri1s if tri1s is not None else packing.submit_tri1(pf, self.delaunay_workers, slot=stream.SLOT_CHUNK),
                             self.delaunay_workers)
@@ -804,7 +1048,7 @@ class ScaleEstimator(stream.StreamKnobs):
         status[np.asarray(vote_status[:F]) != 0] = K.ST_ERR_MASK        # (rows the vote refused: precomputed tri1s only)
         todo = [f for f in range(F) if cnt[f] > 3 and f not in host_errors and vote_status[f] == 0]
         pts = packing.survivor_points(pf, masks)
-        fixed = self.check_triangle == "fixed"
+        fixed = self.check_triangle == "fixed" and _distribution is None
         rows = packing.delaunay_submit([pts[f] for f in todo], self.delaunay_workers, slot=stream.SLOT_CHUNK_TRI2, canonical=fixed).get()   # :266
         go = []
         for f, t in zip(todo, rows):
@@ -813,7 +1057,7 @@ class ScaleEstimator(stream.StreamKnobs):
             else:
                 go.append((f, np.ascontiguousarray(t, dtype=np.int32)))
         selected = np.zeros(max(pf.total_padded, 1), dtype=np.uint8)
-        if go and self.selection == "tri_graph":
+        if go and self.selection == "tri_graph" and _distribution is None:
             self._select_tri_graph(eng, pf, masks, go, raw, status, level, counts, selected)
         elif go:
             kept = np.array([int(np.count_nonzero(masks[f])) for f, _ in go], dtype=np.int32)
