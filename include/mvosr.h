@@ -818,6 +818,65 @@ int mvosr_feature_distribution_batch(mvosr_ctx *ctx, int64_t n_frames, const int
 int mvosr_featdist_max_features(void);
 
 /*
+ * Scoring the repeated runs (/root/reference/test_off_line.sh:11-23): the paths of C cases, their KITTI segment errors against a
+ * ground-truth path (script/evaluate_vo.py:5-96) and pose2motion with its two users (script/transformation.py:23-32,
+ * change_scale.py:12-18, calculate_speed.py:8-11).  Every array is a device array of doubles unless stated; a pose or a motion
+ * is 12 doubles, the upper 3 x 4 of [R t; 0 1].  fp64, no contraction, no floating-point atomics: the same bytes every run, and
+ * a case's results do not depend on the cases beside it.
+ * Operation orders.  Product: (A B)[r][j] = ((A[r][0] B[0][j] + A[r][1] B[1][j]) + A[r][2] B[2][j]) + A[r][3] B[3][j], with B's
+ * last row 0 0 0 1 written out.  Inverse: of the affine matrix as it is — R^-1 = adj(R) / det(R), det by the first row
+ * ((R00 C00 + R01 C10) + R02 C20), then -(R^-1 t) with the same k-ascending sum; never R^T.  Norm: sqrt((x x + y y) + z z).
+ *
+ * mvosr_paths_batch (paths_kernel; main_offline.py:100-119): motions [n][12], scales [C][n] or NULL (ones) -> poses [C][n + 1][12],
+ * row 0 the identity, row i + 1 = row i * step_i strictly left to right, step_i = motions[i] with its translation multiplied by
+ * scales[c][i] first (one rounding).  case_stride = 0: every case integrates the same motions; else case c reads its own
+ * motions + c * case_stride doubles (>= 12 n; what pose2motion wrote).  n = 0: the identity rows.  MVOSR_ERR_ARG: null ctx / poses,
+ * null motions with n > 0, n < 0, C < 1, 0 < case_stride < 12 n.
+ *
+ * mvosr_segment_table (segment_table_kernel; evaluate_vo.py:5-19, 52-65) of a ground-truth path poses_gt [n_poses][12]:
+ *   dist [n_poses]: dist[0] = 0, dist[i] = dist[i - 1] + |t[i - 1] - t[i]|, summed left to right.
+ *   last [F][MVOSR_SCORE_LENGTHS] int32, F = mvosr_score_firsts(n_poses) = ceil(n_poses / MVOSR_SCORE_STEP): for first = 10 f and
+ *   length = 100 (l + 1) the first i >= first with dist[i] > dist[first] + length (strict), else -1 — found by binary search, which
+ *   is the reference's scan where dist never decreases (it cannot, unless a norm is NaN).  Not compacted.
+ *   gdelta [F][8][24]: inv(G_first) G_last as an unevaluated sum of two doubles — 12 high parts, then 12 low parts — computed in
+ *   double-double (error-free products and sums); high parts NaN where there is no segment.
+ *   status [1] int32: 0, or MVOSR_ST_ERR_SINGULAR — the rotation block of a segment's first pose is all zeros (the reference's .I
+ *   raises LinAlgError).  Other singular or near-singular blocks are not detected: the result is what the division gives.
+ * MVOSR_ERR_ARG: a null argument, n_poses < 1.
+ *
+ * mvosr_score_cases_batch (score_cases_kernel; evaluate_vo.py:64-96), one workgroup per case: paths [C][rows][12], the table of
+ * n_first firsts.  For every (case, first, length) with last >= 0: q = inv(P_first) P_last, e = inv(q) g,
+ * r_err = acos(max(min(0.5 (((e00 + e11) + e22) - 1), 1), -1)), t_err = sqrt((e03^2 + e13^2) + e23^2) — q, e, the trace and the sum
+ * of squares in double-double from the float64 poses, rounded to a double once in front of acos and sqrt: acos of a small angle
+ * multiplies the roundings of the trace by 1 / sin(r_err), and in plain doubles the kernel's own noise would equal the reference's.
+ *   r_seg, t_seg (each optional) [C][n_first][8]: r_err / length, t_err / length; NaN where there is no segment.
+ *   means [C][2][8]: per length the sum of r_seg (row 0) / t_seg (row 1) over the segments in ascending first, left to right from
+ *   the first term, divided by their number; NaN for a length without segments.  counts [C][8] int32.
+ *   status [C] int32: 0; MVOSR_ST_ERR_SINGULAR — an all-zero rotation block in a P_first or a q; MVOSR_ST_ERR_MASK — a segment
+ *   names a row >= rows (the path is shorter than the table's ground truth): such a segment is NaN and no pose of it is read.
+ * MVOSR_ERR_ARG: a null argument other than r_seg / t_seg (last / gdelta may be null where n_first = 0), C < 1, rows < 1.
+ *
+ * mvosr_pose2motion_batch (pose2motion_kernel), one lane per (path, frame): poses [C][n + 1][12] ->
+ *   motions (optional) [C][n][12] = inv(P_i) P_{i+1}; with speed [n] given, each translation replaced by
+ *   (speed[i] * t) / (|t| + 0.00001) (change_scale.py:15-17; |t| of the translation before the change).
+ *   norms (optional) [C][n] = |t| (calculate_speed.py:9-11).
+ *   status [C] int32: 0, or MVOSR_ST_ERR_SINGULAR (an all-zero rotation block in a P_i).
+ * n = 0: status zeroed, nothing launched.  MVOSR_ERR_ARG: null ctx / poses / status, neither output given, n < 0, C < 1;
+ * MVOSR_ERR_TOO_LARGE above 65535 paths.
+ */
+#define MVOSR_SCORE_LENGTHS 8    /* 100, 200 .. 800 m */
+#define MVOSR_SCORE_STEP 10
+int64_t mvosr_score_firsts(int64_t n_poses);
+int mvosr_paths_batch(mvosr_ctx *ctx, int64_t n, int64_t n_cases, const double *motions, int64_t case_stride, const double *scales,
+                      double *poses);
+int mvosr_segment_table(mvosr_ctx *ctx, int64_t n_poses, const double *poses_gt, double *dist, int32_t *last, double *gdelta,
+                        int32_t *status);
+int mvosr_score_cases_batch(mvosr_ctx *ctx, int64_t n_cases, int64_t rows, const double *paths, int64_t n_first, const int32_t *last,
+                            const double *gdelta, double *r_seg, double *t_seg, double *means, int32_t *counts, int32_t *status);
+int mvosr_pose2motion_batch(mvosr_ctx *ctx, int64_t n_cases, int64_t n, const double *poses, const double *speed, double *motions,
+                            double *norms, int32_t *status);
+
+/*
  * The cross-frame tail of scale_calculation_ransac (rescale.py:169-178) over a run of frames, on the device: the slew
  * limiter — a frame with apply[i] != 0 moves the running scale towards raw[i] by at most `slew` (0.3), any other frame
  * leaves it — followed by the window median of the pushed values (np.median(self.scale_queue)).  raw/apply/pushed/

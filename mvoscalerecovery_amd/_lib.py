@@ -26,6 +26,8 @@ TILE_W = 512                              # MVOSR_TILE_W
 HIST_BINS = 169
 FD_POPULATIONS = 3           # MVOSR_FD_POPULATIONS
 FD_HIST_WORDS = 172          # MVOSR_FD_HIST_WORDS: the 169 bins, then the counts on edges 29, 49, 99
+SCORE_LENGTHS, SCORE_STEP = 8, 10    # MVOSR_SCORE_LENGTHS, MVOSR_SCORE_STEP
+ST_ERR_SINGULAR, ST_ERR_MASK = 7, 8  # MVOSR_ST_ERR_SINGULAR, MVOSR_ST_ERR_MASK
 
 
 ERR_ALLOC = -5
@@ -232,6 +234,11 @@ SYMBOLS = {
     "mvosr_static_tri_batch": (C.c_int, [_P, C.c_int64, _P, _P, _P, _P, C.c_int32, C.c_double, _P, _P, _P, _P, _P]),
     "mvosr_feature_distribution_batch": (C.c_int, [_P, C.c_int64, _P, _P, _P, _P, _P, C.c_int32, _P, _P, _P, _P, _P, _P]),
     "mvosr_featdist_max_features": (C.c_int, []),
+    "mvosr_score_firsts": (C.c_int64, [C.c_int64]),
+    "mvosr_paths_batch": (C.c_int, [_P, C.c_int64, C.c_int64, _P, C.c_int64, _P, _P]),
+    "mvosr_segment_table": (C.c_int, [_P, C.c_int64, _P, _P, _P, _P, _P]),
+    "mvosr_score_cases_batch": (C.c_int, [_P, C.c_int64, C.c_int64, _P, C.c_int64, _P, _P, _P, _P, _P, _P, _P]),
+    "mvosr_pose2motion_batch": (C.c_int, [_P, C.c_int64, C.c_int64, _P, _P, _P, _P, _P]),
     "mvosr_slew_median": (C.c_int, [_P, _P, _P, C.c_int64, C.c_double, C.c_double, C.c_int, _P, C.c_int, _P, _P]),
     "mvosr_slew_median_host": (C.c_int, [_P, _P, C.c_int64, C.c_double, C.c_double, C.c_int, _P, C.c_int, _P, _P, _P]),
     "mvosr_ransac_plane_batch": (C.c_int, [_P, C.c_int64, _P, _P, _P, _P, _P, _P, C.c_int, C.c_double, C.c_double,

@@ -2,7 +2,10 @@
 segment error of /root/reference/script/evaluate_vo.py:5-96, the scale error statistics of
 /root/reference/script/evaluate_scale.py:4-29 and pose <-> motion conversion of
 /root/reference/script/transformation.py:6-32.  Host NumPy, like the reference: this is evaluation of
-the path's output (a few thousand 3x4 poses), not part of the per-frame hot path."""
+the path's output (a few thousand 3x4 poses), not part of the per-frame hot path.  The repeated runs score ten such paths at
+once, which is where these loops cost many times the runs themselves: :class:`Scorer`, :func:`calculate_speed` and
+:func:`change_scale` at the end of this file do that on the device (csrc/mvosr_score.hip); the host functions are unchanged and are
+their comparators."""
 from __future__ import annotations
 
 import numpy as np
@@ -123,3 +126,191 @@ def repeat_scores(poses_gt, paths):
                       "rot": np.array([trimmed_mean(rot[:, k]) for k in range(rot.shape[1])]),
                       "tra_mean": trimmed_mean(out["tra_mean"]), "rot_mean": trimmed_mean(out["rot_mean"])}
     return out
+
+
+# ---- the same scores on the device (csrc/mvosr_score.hip) ---------------------------------------------------------------------------
+def _reduce_scores(tra, rot):
+    """The dict of :func:`repeat_scores` from its two ``(C, L)`` tables."""
+    import warnings
+    with warnings.catch_warnings():
+        warnings.simplefilter("ignore")
+        out = {"tra": tra, "rot": rot, "tra_mean": tra.mean(axis=1), "rot_mean": rot.mean(axis=1)}      # evaluate_vo.py:107
+    out["trimmed"] = {"tra": np.array([trimmed_mean(tra[:, k]) for k in range(tra.shape[1])]),
+                      "rot": np.array([trimmed_mean(rot[:, k]) for k in range(rot.shape[1])]),
+                      "tra_mean": trimmed_mean(out["tra_mean"]), "rot_mean": trimmed_mean(out["rot_mean"])}
+    return out
+
+
+def _context(ctx, device):
+    from . import _lib
+    return ctx if ctx is not None else _lib.default_context(device)
+
+
+def _stack_of_paths(poses):
+    """``(rows, 12)`` or ``(C, rows, 12)`` -> (the stack, whether the input was one path)."""
+    p = np.asarray(poses, dtype=np.float64)
+    single = p.ndim == 2
+    p = np.ascontiguousarray(p.reshape((1,) + p.shape if single else p.shape))
+    if p.ndim != 3 or p.shape[2] != 12 or p.shape[0] < 1 or p.shape[1] < 1:
+        raise ValueError("a path is (rows, 12) with at least one pose, a stack (C, rows, 12); got %r" % (np.shape(poses),))
+    return p, single
+
+
+def _raise_status(status, what):
+    from . import _lib
+    status = np.asarray(status).reshape(-1)
+    if (status == _lib.ST_ERR_MASK).any():
+        raise IndexError("%s: case %d's path has fewer poses than a segment of the ground truth needs (evaluate_vo.py:66)"
+                         % (what, int(np.nonzero(status == _lib.ST_ERR_MASK)[0][0])))
+    if (status == _lib.ST_ERR_SINGULAR).any():
+        raise np.linalg.LinAlgError("%s: singular matrix (case %d: a pose with an all-zero rotation block)"
+                                    % (what, int(np.nonzero(status == _lib.ST_ERR_SINGULAR)[0][0])))
+
+
+def pose2motion_batch(poses, speed=None, ctx=None, device=0, want="motions"):
+    """mvosr_pose2motion_batch for one path or a stack: ``want`` = "motions" (``(C, n, 12)``; with ``speed`` change_scale.py's
+    re-scaled ones), "norms" (``(C, n)``) or "device" (the motions left on the device: buffer, C, n)."""
+    from . import _lib
+    ctx = _context(ctx, device)
+    p, single = _stack_of_paths(poses)
+    C, n = p.shape[0], p.shape[1] - 1
+    d_speed = None
+    if speed is not None:
+        s = np.asarray(speed, dtype=np.float64)
+        if s.ndim == 0:
+            s = np.full(n, float(s))
+        if s.shape != (n,):
+            raise ValueError("change_scale: %d speeds for %d motions (change_scale.py:15 broadcasts one per frame)" % (s.size, n))
+        d_speed = ctx.to_device(s)
+    d_poses = ctx.to_device(p)
+    d_status = ctx.empty(C, np.int32)
+    d_motions = ctx.empty((C, n, 12), np.float64) if want != "norms" else None
+    d_norms = ctx.empty((C, n), np.float64) if want == "norms" else None
+    _lib.check(ctx.lib.mvosr_pose2motion_batch(ctx.handle, C, n, d_poses.ptr, d_speed.ptr if d_speed else None,
+                                               d_motions.ptr if d_motions else None, d_norms.ptr if d_norms else None, d_status.ptr),
+               "mvosr_pose2motion_batch")
+    _raise_status(d_status.download(), "pose2motion")
+    if want == "device":
+        return d_motions, C, n
+    out = (d_norms if want == "norms" else d_motions).download()
+    return out[0] if single else out
+
+
+def calculate_speed(poses, ctx=None, device=0):
+    """script/calculate_speed.py:8-11 on the device: the norms of a path's relative translations, ``(n,)`` — ``(C, n)`` for a stack."""
+    return pose2motion_batch(poses, ctx=ctx, device=device, want="norms")
+
+
+def change_scale(poses, speed, ctx=None, device=0):
+    """script/change_scale.py:12-18 on the device: every relative translation divided by (its norm + 0.00001) and multiplied by
+    ``speed`` (one value, or one per frame as the script reads them from the ground truth's speed file), then integrated again.
+    One path or a stack; the result has the input's shape."""
+    from . import _lib
+    ctx = _context(ctx, device)
+    single = np.ndim(poses) == 2
+    d_motions, C, n = pose2motion_batch(poses, speed=speed, ctx=ctx, want="device")
+    d_out = ctx.empty((C, n + 1, 12), np.float64)
+    _lib.check(ctx.lib.mvosr_paths_batch(ctx.handle, n, C, d_motions.ptr, n * 12, None, d_out.ptr), "mvosr_paths_batch")
+    out = d_out.download()
+    return out[0] if single else out
+
+
+class Scorer:
+    """:func:`repeat_scores` on the device for one ground-truth path: the segment table (evaluate_vo.py:5-19, 52-65) is built once,
+    here, by mvosr_segment_table; every call then scores C paths with mvosr_score_cases_batch — one workgroup per case — and brings
+    back the per-length means and counts only.
+
+    ``segments``: ``first``, ``last`` and ``length_index`` of every segment in the reference's order (host integers), ``speed`` per
+    segment (evaluate_vo.py:72-73, from the integers).  ``columns``: which of the eight lengths have a segment — the columns of
+    ``tra`` and ``rot``, as calculate_ave_errors drops an empty length."""
+
+    def __init__(self, poses_gt, device=0, ctx=None):
+        from . import _lib
+        self.ctx = ctx = _context(ctx, device)
+        gt, _ = _stack_of_paths(np.asarray(poses_gt, dtype=np.float64).reshape(-1, 12))
+        self.n_poses = N = gt.shape[1]
+        self.n_first = F = int(ctx.lib.mvosr_score_firsts(N))
+        self._gt = ctx.to_device(gt[0])
+        self._dist = ctx.empty(N, np.float64)
+        self._last = ctx.empty((F, _lib.SCORE_LENGTHS), np.int32)
+        self._gdelta = ctx.empty((F, _lib.SCORE_LENGTHS, 24), np.float64)        # hi, lo
+        status = ctx.empty(1, np.int32)
+        _lib.check(ctx.lib.mvosr_segment_table(ctx.handle, N, self._gt.ptr, self._dist.ptr, self._last.ptr, self._gdelta.ptr, status.ptr),
+                   "mvosr_segment_table")
+        _raise_status(status.download(), "Scorer")
+        self.last = self._last.download()
+        self.has = self.last >= 0
+        self.columns = self.has.any(axis=0)
+        self.counts = self.has.sum(axis=0).astype(np.int32)
+        f, li = np.nonzero(self.has)                                                        # row-major: first, then length
+        first, last = f * STEP, self.last[f, li].astype(np.int64)
+        self.segments = {"first": first, "last": last, "length_index": li,
+                         "speed": np.asarray(LENGTHS, dtype=np.float64)[li] / (0.1 * (last - first + 1).astype(np.float64))}
+
+    def dist(self):
+        """evaluate_vo.py:5-13's cumulative distances as the table was built from them."""
+        return self._dist.download()
+
+    # -- launches
+    def _paths_on_device(self, motions, scales):
+        from . import _lib
+        ctx = self.ctx
+        m = np.ascontiguousarray(np.asarray(motions, dtype=np.float64).reshape(-1, 12))
+        s = np.ascontiguousarray(np.asarray(scales, dtype=np.float64))
+        s = s.reshape(1, -1) if s.ndim == 1 else s
+        if s.ndim != 2 or s.shape[0] < 1 or s.shape[1] != m.shape[0]:
+            raise ValueError("scales is (C, n) for motions (n, 12); got %r and %r" % (s.shape, m.shape))
+        C, n = s.shape
+        d_paths = ctx.empty((C, n + 1, 12), np.float64)
+        d_m, d_s = ctx.to_device(m), ctx.to_device(s)
+        _lib.check(ctx.lib.mvosr_paths_batch(ctx.handle, n, C, d_m.ptr, 0, d_s.ptr, d_paths.ptr), "mvosr_paths_batch")
+        return d_paths
+
+    def _score(self, d_paths, rows=False):
+        """``d_paths``: a device buffer ``(C, rows, 12)``.  Returns (means (C, 2, 8), r_seg, t_seg) — the two tables only with ``rows``."""
+        from . import _lib
+        ctx = self.ctx
+        C, n_rows = d_paths.shape[0], d_paths.shape[1]
+        L = _lib.SCORE_LENGTHS
+        res = ctx.block([("means", (C, 2, L), np.float64), ("counts", (C, L), np.int32), ("status", (C,), np.int32)])
+        seg = ctx.empty((2, C, self.n_first, L), np.float64) if rows else None
+        half = C * self.n_first * L * 8
+        _lib.check(ctx.lib.mvosr_score_cases_batch(ctx.handle, C, n_rows, d_paths.ptr, self.n_first, self._last.ptr, self._gdelta.ptr,
+                                                   seg.ptr if rows else None, seg.ptr + half if rows else None, res["means"].ptr,
+                                                   res["counts"].ptr, res["status"].ptr), "mvosr_score_cases_batch")
+        means, counts, status = res["means"].download(), res["counts"].download(), res["status"].download()
+        _raise_status(status, "Scorer")
+        assert np.array_equal(counts, np.broadcast_to(self.counts, counts.shape)), "segment counts differ from the table's"
+        if not rows:
+            return means, None, None
+        both = seg.download()
+        return means, both[0], both[1]
+
+    def _to_device(self, paths):
+        from . import _lib
+        if isinstance(paths, _lib.DeviceBuffer):
+            return paths
+        return self.ctx.to_device(_stack_of_paths(paths)[0])
+
+    def _dict(self, means):
+        rot = means[:, 0, :][:, self.columns] * 180 / np.pi                                 # evaluate_vo.py:96
+        tra = np.ascontiguousarray(means[:, 1, :][:, self.columns])
+        return _reduce_scores(tra, rot)
+
+    # -- the public calls
+    def score_paths(self, paths):
+        """``paths``: ``(C, rows, 12)`` (host array, list of paths, or a device buffer).  The dict of :func:`repeat_scores`."""
+        return self._dict(self._score(self._to_device(paths))[0])
+
+    def score_scales(self, motions, scales):
+        """Integrate ``motions (n, 12)`` under every row of ``scales (C, n)`` (offline.get_path) and score the C paths: two launches,
+        one small download."""
+        return self._dict(self._score(self._paths_on_device(motions, scales))[0])
+
+    def errors(self, paths=None, motions=None, scales=None):
+        """Per case the rows ``[first, r_err/len, t_err/len, len, speed]`` of calculate_sequence_error, in its order."""
+        d_paths = self._to_device(paths) if paths is not None else self._paths_on_device(motions, scales)
+        _, r, t = self._score(d_paths, rows=True)
+        seg = self.segments
+        first, length, speed = seg["first"].tolist(), [LENGTHS[i] for i in seg["length_index"].tolist()], seg["speed"].tolist()
+        return [list(map(list, zip(first, r[c][self.has].tolist(), t[c][self.has].tolist(), length, speed))) for c in range(r.shape[0])]

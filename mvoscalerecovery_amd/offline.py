@@ -191,3 +191,25 @@ def get_path(motions, scales):
     m = np.array(motions, dtype=np.float64, copy=True)
     m[:, 3:12:4] = m[:, 3:12:4] * np.asarray(scales, dtype=np.float64)[:, None]
     return motion2pose(m)
+
+
+def get_path_batch(motions, scales, ctx=None, on_device=False):
+    """:func:`get_path` for every row of ``scales (C, n)`` at once, on the device (mvosr_paths_batch: one wavefront per case, the
+    chain strictly left to right as in :func:`motion2pose`): ``(C, n + 1, 12)``.  ``scales=None``: ones, a single path's
+    motion2pose.  ``on_device``: the device buffer instead of a host array."""
+    from . import _lib
+    ctx = ctx if ctx is not None else _lib.default_context(0)
+    m = np.ascontiguousarray(np.asarray(motions, dtype=np.float64).reshape(-1, 12))
+    n = m.shape[0]
+    if scales is None:
+        C, d_s = 1, None
+    else:
+        s = np.ascontiguousarray(np.asarray(scales, dtype=np.float64))
+        s = s.reshape(1, -1) if s.ndim == 1 else s
+        if s.ndim != 2 or s.shape[0] < 1 or s.shape[1] != n:
+            raise ValueError("scales is (C, n) for motions (n, 12); got %r and %r" % (s.shape, m.shape))
+        C, d_s = s.shape[0], ctx.to_device(s)
+    d_m = ctx.to_device(m)
+    d_paths = ctx.empty((C, n + 1, 12), np.float64)
+    _lib.check(ctx.lib.mvosr_paths_batch(ctx.handle, n, C, d_m.ptr, 0, d_s.ptr if d_s is not None else None, d_paths.ptr), "mvosr_paths_batch")
+    return d_paths if on_device else d_paths.download()

@@ -1211,15 +1211,49 @@ class RepeatedRuns:
         """``(C, n)`` over every frame run so far."""
         return np.concatenate(self._scales, axis=1) if self._scales else np.zeros((self.cases, 0))
 
-    def paths(self, data=None):
+    def paths(self, data=None, on_device=False):
         """The C integrated trajectories (offline.get_path, main_offline.py:92): of ``data`` — run first when given —, else of
-        everything run so far."""
+        everything run so far.  ``on_device``: integrated by mvosr_paths_batch (offline.get_path_batch) instead of the host loop."""
         from . import offline
         if data is not None:
             scales, motions = self.run(data)["scales"], np.array(data["motions"], dtype=np.float64).reshape(len(data["move_flags"]), -1)
         else:
             scales, motions = self.scales(), (np.concatenate(self._motions) if self._motions else np.zeros((0, 12)))
+        if on_device:
+            return list(offline.get_path_batch(motions, scales, ctx=self.estimator.ctx))
         return [offline.get_path(motions, scales[c]) for c in range(self.cases)]
+
+    def scores(self, poses_gt, speed_gt=None):
+        """What /root/reference/test_off_line.sh:11-23 computes from the runs' paths, on the device (evaluate.Scorer): the dict of
+        ``evaluate.repeat_scores(poses_gt, self.paths())`` for everything run so far, from the scales and motions kept here — the
+        paths never leave the device.  ``speed_gt`` (one value or one per frame, script/calculate_speed.py's file): adds
+        ``"speed_scaled"``, the same dict for the paths re-scaled to that speed (script/change_scale.py).  The reference re-scales
+        ONE path — the last case's, through the loop variable its first loop leaves behind (test_off_line.sh:18) — and prints its
+        score; here every case is re-scaled and scored, row C - 1 being the reference's.  The ground truth's segment table is
+        kept for the next call with the same ``poses_gt``."""
+        from . import _lib, evaluate
+        ctx = self.estimator.ctx
+        gt = np.ascontiguousarray(np.asarray(poses_gt, dtype=np.float64).reshape(-1, 12))
+        cached = getattr(self, "_scorer", None)
+        if cached is None or not np.array_equal(cached[0], gt):
+            cached = self._scorer = (gt, evaluate.Scorer(gt, ctx=ctx))
+        scorer = cached[1]
+        motions = np.concatenate(self._motions) if self._motions else np.zeros((0, 12))
+        d_paths = scorer._paths_on_device(motions, self.scales())
+        out = scorer.score_paths(d_paths)
+        if speed_gt is not None:
+            C, n = self.cases, motions.shape[0]
+            speed = np.asarray(speed_gt, dtype=np.float64)
+            speed = np.full(n, float(speed)) if speed.ndim == 0 else speed
+            if speed.shape != (n,):
+                raise ValueError("scores: %d speeds for %d motions (change_scale.py:15 broadcasts one per frame)" % (speed.size, n))
+            d_speed, d_motions, d_status = ctx.to_device(speed), ctx.empty((C, n, 12), np.float64), ctx.empty(C, np.int32)
+            _lib.check(ctx.lib.mvosr_pose2motion_batch(ctx.handle, C, n, d_paths.ptr, d_speed.ptr, d_motions.ptr, None, d_status.ptr),
+                       "mvosr_pose2motion_batch")
+            _lib.check(ctx.lib.mvosr_paths_batch(ctx.handle, n, C, d_motions.ptr, n * 12, None, d_paths.ptr), "mvosr_paths_batch")
+            evaluate._raise_status(d_status.download(), "scores")
+            out["speed_scaled"] = scorer.score_paths(d_paths)
+        return out
 
     def write_results(self, res_addr, tag):
         """``<res_addr>scales.txt<tag><num>`` and ``<res_addr>path.txt<tag><num>``, num = 0 .. C - 1: the files main_offline.py:90-93
