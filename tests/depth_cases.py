@@ -58,6 +58,54 @@ def synth_features(n, seed, scale=1.0, integer_pixels=False, cam=None):
     return np.ascontiguousarray(f3[low]), np.ascontiguousarray(f2[low])
 
 
+def strip_frame(width, height, n, seed, integer_pixels=False):
+    """A frame for an image of ANY shape — a scaled KITTI frame would leave a strip of 5 000 x 5 pixels nearly empty —: ``n``
+    pixels drawn uniformly over [0, width) x [0, height), depths z in [4, 60], x = (u - cx) z / fx and y = (v - cy) z / fy with
+    the 1241-wide camera scaled to ``width``, rows from SciPy's Delaunay triangulation of the pixels.  ``integer_pixels``: the
+    pixels rounded, duplicates dropped (x and y from the rounded pixels) — pixels ON edges abound, as in depth_ties.
+    Returns the dict of a fixture frame without the recorded parts: cam, f3, f2, rows."""
+    from scipy.spatial import Delaunay
+    cam, _ = scaled_camera(width, height)
+    rng = np.random.default_rng([seed, width, height, n])
+    f2 = np.stack([rng.uniform(0.0, width, n), rng.uniform(0.0, height, n)], axis=1)
+    z = rng.uniform(4.0, 60.0, n)
+    if integer_pixels:
+        f2 = np.round(f2)
+        _, ui = np.unique(f2, axis=0, return_index=True)
+        ui.sort()
+        f2, z = f2[ui], z[ui]
+    f3 = np.stack([(f2[:, 0] - cam.cx) * z / cam.fx, (f2[:, 1] - cam.cy) * z / cam.fy, z], axis=1)
+    rows = Delaunay(f2).simplices.astype(np.int32)
+    return dict(cam=cam, f3=np.ascontiguousarray(f3), f2=np.ascontiguousarray(f2), rows=np.ascontiguousarray(rows))
+
+
+def band_rows(width):
+    """The band plan of mvosr_dense_depth_batch, restated: an even number of image rows whose ids fit 10240 words (40 KB) of
+    LDS, at most 16, at least 2 however wide the image — the request then grows with the width."""
+    return min(max((10240 // width) & ~1, 2), 16)
+
+
+LDS_160K = 160 * 1024                      # the LDS a workgroup can ask for on the MI355X (mvosr_ctx_device_info)
+
+
+def max_width(lds_per_block):
+    """The widest image the rasteriser takes: two rows of ids plus 64 B within the device's LDS per workgroup."""
+    return (lds_per_block - 64) // 8
+
+
+def strip_shapes(wmax):
+    """(width, height, band rows) of the wide-image tests: every value the band plan takes, heights that end in a band of one
+    or two rows, the tile at exactly 40 KB, the first request above it, and the widest image the device takes."""
+    return [(641, 30, 14), (682, 15, 14), (310, 17, 16), (2561, 5, 2), (5120, 5, 2), (5121, 5, 2), (8193, 4, 2), (wmax, 3, 2)]
+
+
+def strip_pair(width, height):
+    """The two frames of a wide-image test — float pixels, integer pixels —: about one feature per 40 pixels (at least 120,
+    so that the small shapes are covered too), seeds fixed."""
+    n = max(120, width * height // 40)
+    return strip_frame(width, height, n, 1), strip_frame(width, height, n, 2, integer_pixels=True)
+
+
 # ---- point location ------------------------------------------------------------------------------------------------------
 
 def _sorted_vertices(f2, rows):

@@ -98,3 +98,112 @@ def test_crafted_batches_are_what_they_say():
         assert ("tail" in cnt) == (n % cc.SEGMENT != 0)
         assert np.array_equal((tri >= 0)[:-1], (depth != 0)[:-1])            # the two coverage rules agree off the hostile frame
         assert np.isnan(depth[-1]).any() and (depth[-1] == 0).any() and (tri[-1] >= 0).all()
+
+
+# ---- large images, many frames, strides: the inputs of the GPU tests are what they are meant to be -------------------------
+
+def test_divmod_small_restatement_over_its_whole_range():
+    """cl_span / cloud_fill_kernel / depth_raster_kernel: divmod_small(i, d, 1.0f / d) — the float32 estimate and its two
+    corrections equal divmod(i, d) for EVERY i in [0, 2^22), the range the launchers keep it in (kClMaxSide = 2^21 plus a
+    segment), at the divisors of the tests (widths, strides) and at the range's top."""
+    i = np.arange(1 << 22, dtype=np.int64)
+    for d in (1, 2, 3, 5, 7, 63, 64, 65, 311, 1241, 4095, 4096, 4097, 5121, 8200, 20472, (1 << 21) - 1, 1 << 21):
+        q, r = cc.divmod_small(i, d)
+        assert np.array_equal(q, i // d) and np.array_equal(r, i % d), d
+    for d in (8199, 8201, 2 ** 31 - 1):                                          # the other strides; float32 cannot represent the last: 2^31 - 1 -> 2^31
+        assert d in cc.STRIDES
+        q, r = cc.divmod_small(i, d)
+        assert np.array_equal(q, i // d) and np.array_equal(r, i % d), d
+    assert np.float32(2 ** 31 - 1) == np.float32(2 ** 31) and np.float32(8201) == 8201
+
+
+def test_large_batch_cuts_land_where_they_are_meant_to():
+    """The cuts of the many-segment and thin / wide images: an edge one pixel before / at / after a segment boundary, and
+    inside a row or at a row end as the size's note says.  (Masks only: no frame of 2 M pixels is drawn here.)"""
+    S = cc.SEGMENT
+    for label, (w, h, cuts) in list(cc.MANY_SEGMENTS.items()) + list(cc.THIN_WIDE.items()):
+        n = w * h
+        nseg = -(-n // S)
+        names = cc.large_names(cuts, teeth=label == "2097152x1")
+        assert names[:2] == ["all", "checker"] and len(names) == len(set(names)) == 2 + 6 * len(cuts) + (6 if "teeth_0+0" in names else 0)
+        assert cc.large_mask("all", w, h).all() and cc.large_mask("checker", w, h).sum() in (n // 2, (n + 1) // 2)
+        for c in cuts:
+            assert 0 < c < n, (label, c)
+            at_boundary = c % S == 0
+            assert at_boundary or (c + 1) % S == 0, (label, c)                   # a boundary, or the last pixel before one
+            for delta in (-1, 0, 1):
+                e = c + delta
+                up, fr = cc.large_mask("upto_%d%+d" % (c, delta), w, h), cc.large_mask("from_%d%+d" % (c, delta), w, h)
+                assert up.sum() == e and up[:e].all() and not up[e:].any(), (label, c, delta)
+                assert np.array_equal(fr, ~up), (label, c, delta)
+                # the segments' counts: full ones, then e % S pixels in the segment of the edge, then empty ones
+                per = np.add.reduceat(up.astype(np.int64), np.arange(0, n, S))
+                assert len(per) == nseg and (per[:e // S] == S).all() and (per[e // S + 1:] == 0).all() and (e % S == 0 or per[e // S] == e % S)
+            if at_boundary:                                                      # one pixel before / at / after: the edge is in the segment before, between two, in the one after
+                assert (c - 1) // S == c // S - 1 and (c + 1) // S == c // S
+        bounds = {c for c in cuts if c % S == 0}
+        if label in ("1x5000", "5000x1", "4097x3"):
+            assert bounds == set(range(S, n, S)), (label, "every boundary the image reaches")
+    # the sizes are what the table says
+    assert [-(-w * h // S) for w, h, _ in cc.MANY_SEGMENTS.values()] == [256, 258, 515]
+    w, h, cuts = cc.MANY_SEGMENTS["4096x256"]
+    assert all(c % w in (0, w - 1) for c in cuts)                                # every segment is one row: a cut is a row end too
+    w, h, cuts = cc.MANY_SEGMENTS["4100x257"]
+    assert all(c % w > 0 and (c % w) + S > w for c in cuts)                      # the segment that begins at the cut straddles a row end
+    w, h, cuts = cc.MANY_SEGMENTS["8200x257"]
+    assert w > 2 * S and [c // S for c in cuts] == [256, 512, 513]               # the scan's second and third round begin at 256 and 512
+    assert any((c % w) + S <= w for c in cuts) and any((c % w) + S > w for c in cuts)    # a segment inside one row, and one across a row end
+    w, h, cuts = cc.THIN_WIDE["2097152x1"]
+    assert w == cc.MAX_SIDE and -(-w // S) == 512 and [c // S for c in cuts] == [256, 511]
+    for delta in (-1, 0, 1):                                                     # teeth / gaps: an edge at EVERY boundary + delta
+        t, g = cc.large_mask("teeth_0%+d" % delta, w, h), cc.large_mask("gaps_0%+d" % delta, w, h)
+        assert np.array_equal(t, ~g)
+        edges = np.nonzero(t[1:] != t[:-1])[0] + 1
+        want = np.arange(0, w + S, S) + delta                                    # (the image's two ends shifted into it count as well)
+        assert np.array_equal(edges, want[(want > 0) & (want < w)]), delta
+    # a small batch is drawn as crafted_batch draws it, and a part of it holds the values of the whole
+    names, depth, tri, images, scales = cc.large_batch(311, 95, [S], seed=3)
+    assert names == cc.large_names([S]) and depth.shape == (8, 95, 311) and images.shape == (8, 95, 311, 3) and scales.shape == (8,)
+    assert (tri[0] == 5).all() and np.isnan(depth[0]).any() and (depth[0] == 0).any()                    # "all" holds the hostile pattern
+    assert np.array_equal((tri >= 0)[1:], (depth != 0)[1:]) and (depth[1:][tri[1:] >= 0] >= 0.5).all()
+    for f, k in enumerate(names):
+        assert np.array_equal((tri[f] >= 0).reshape(-1), cc.large_mask(k, 311, 95)), k
+    part = cc.large_batch(311, 95, [S], seed=3, frames=names[3:5])
+    assert part[0] == names[3:5] and all(cc.same_bytes(a, b[3:5]) for a, b in zip(part[1:], (depth, tri, images, scales)))
+
+
+def test_stride_cases_counts():
+    """The restatement on the stride cases: from max(width, height) upward only pixel (0, 0) is on the grid, so a frame's count
+    is 1 when it covers that pixel and 0 otherwise; below, the grid's size bounds it and the fully covered frame reaches it."""
+    from mvoscalerecovery_amd.reconstruct import grid_points
+    for w, h in cc.STRIDE_SIZES:
+        cam = SimpleNamespace(width=w, height=h, fx=0.6 * w, fy=0.6 * w, cx=0.5 * w, cy=0.5 * h)
+        names, depth, tri, images, scales = cc.large_batch(w, h, [cc.SEGMENT])
+        covers_origin = tri[:, 0, 0] >= 0
+        assert covers_origin.any() and not covers_origin.all()
+        for s in cc.STRIDES:
+            off = cc.clouds(depth, tri, cam, stride=s)[2]
+            cnt = np.diff(off)
+            assert (cnt <= grid_points(w, h, s)).all() and cnt[0] == grid_points(w, h, s), (w, h, s)     # "all" (ids): the whole grid
+            if s >= max(w, h):
+                assert grid_points(w, h, s) == 1 and np.array_equal(cnt, covers_origin.astype(np.int64)), (w, h, s)
+            else:
+                assert grid_points(w, h, s) > 1
+        assert [s >= max(w, h) for s in cc.STRIDES] == ([False] * 4 + [True] * 3 if w == 8200 else [False] + [True] * 6)
+
+
+def test_many_frames_batches_are_what_they_say():
+    for F in (257, 513):
+        seen = {}
+        for turn in range(3):
+            kinds = cc.special_kinds(F, turn)
+            assert sorted(kinds) == [f for f in (255, 256, 257, 511, 512) if f < F]
+            depth, tri, images, scales = cc.many_frames(7, 5, F, kinds, seed=turn)
+            cnt = (tri.reshape(F, -1) >= 0).sum(1)
+            assert np.array_equal(tri >= 0, depth != 0)
+            for f, kind in kinds.items():
+                assert cnt[f] == {"empty": 0, "full": 35, "single": 1}[kind], (F, turn, f)
+                seen.setdefault(f, set()).add(kind)
+            others = np.delete(cnt, sorted(kinds))
+            assert others.min() >= 0 and 10 < others.mean() < 25                 # random coverage elsewhere
+        assert all(v == {"empty", "full", "single"} for v in seen.values())      # every one of them each kind in turn

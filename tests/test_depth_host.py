@@ -59,6 +59,39 @@ def test_bad_arguments_are_refused_before_any_gpu_work():
     assert b"triangle_model" in lib.mvosr_last_error()
 
 
+def test_strip_frames_are_fit_for_the_wide_image_tests():
+    """The inputs of test_gpu_depth's wide-image tests, by the restatement alone: every frame covers at least half its image,
+    a triangle crosses every boundary between two bands (band height by the launcher's formula, restated here), no row is
+    singular, and the reference-order float64 depths are finite."""
+    import depth_cases as dc
+    wmax = dc.max_width(dc.LDS_160K)
+    assert wmax == 20472
+    for w, h, band in dc.strip_shapes(wmax):
+        rows_per_band = (10240 // w) & ~1                                          # mvosr_dense_depth_batch's band plan
+        rows_per_band = 2 if rows_per_band < 2 else (16 if rows_per_band > 16 else rows_per_band)
+        assert rows_per_band == band == dc.band_rows(w), (w, h)
+        assert (4 * band * w <= 40960) == (w <= 5120)                              # the tile leaves 40 KB only by the clamp to two rows
+        assert 4 * band * w + 64 <= dc.LDS_160K
+        for fr in dc.strip_pair(w, h):
+            f2, rows, cam = fr["f2"], fr["rows"], fr["cam"]
+            assert (cam.width, cam.height) == (w, h) and len(rows) > 0 and len(rows) < 2 * len(f2)
+            tri, claims = dc.locate(f2, rows, w, h)
+            assert (tri >= 0).sum() >= 0.5 * w * h, (w, h, "coverage", float((tri >= 0).mean()))
+            v = f2[rows][:, :, 1]
+            y0, y1 = np.maximum(np.ceil(v.min(1)), 0), np.minimum(np.floor(v.max(1)), h - 1)
+            for b in range(band, h, band):                                         # image rows b - 1 and b lie in two bands
+                assert ((y0 <= b - 1) & (y1 >= b)).any(), (w, h, "no triangle crosses the band boundary at row", b)
+            datas = dc.model64(fr["f3"], rows)                                     # (np.linalg.inv raises on a singular row)
+            assert np.isfinite(datas).all(), (w, h)
+            d = dc.depth64(datas, tri, cam)
+            assert np.isfinite(d).all() and (d[tri >= 0] != 0).all(), (w, h)
+        a, b = dc.strip_pair(w, h)
+        assert (b["f2"] == np.round(b["f2"])).all() and len(np.unique(b["f2"], axis=0)) == len(b["f2"])
+        assert not (a["f2"] == np.round(a["f2"])).all()
+    assert [h % band for _, h, band in dc.strip_shapes(wmax)[:3]] == [2, 1, 1]     # the last band: 2 rows, 1 row, 1 row
+    assert 4 * dc.band_rows(wmax + 1) * (wmax + 1) + 64 > dc.LDS_160K              # one pixel wider is refused
+
+
 def test_plan_chunks():
     from mvoscalerecovery_amd import reconstruct as rc
     per = 1241 * 376 * 8

@@ -75,24 +75,44 @@ def test_crafted_images(gpu, size):
 def raw_call(ctx, cam, depth, tri, images, scales, capacity, dtype=np.float64, stride=1, rng=None, room=64):
     """mvosr_point_cloud_batch through ctypes; points / colours / frame_off / overflow pre-filled with SENTINEL bytes, the point
     buffers ``room`` rows longer than ``capacity``."""
+    call = raw_prepare(ctx, cam, depth, tri, images, scales, capacity, dtype, stride, rng, room)
+    raw_launch(ctx, call)
+    ctx.sync()
+    return raw_collect(ctx, call)
+
+
+def raw_prepare(ctx, cam, depth, tri, images, scales, capacity, dtype=np.float64, stride=1, rng=None, room=64, ins=None):
+    """The buffers and argument structs of one ``raw_call``: inputs uploaded (or another call's ``ins``, shared), outputs
+    pre-filled.  Uploading waits for the stream, so calls that are to be queued back to back are all prepared first."""
     from mvoscalerecovery_amd import _lib
     F = len(depth)
-    ins = [ctx.to_device(depth), ctx.to_device(tri) if tri is not None else None, ctx.to_device(images) if images is not None else None,
-           ctx.to_device(scales) if scales is not None else None]
+    own = ins is None
+    if own:
+        ins = [ctx.to_device(depth), ctx.to_device(tri) if tri is not None else None, ctx.to_device(images) if images is not None else None,
+               ctx.to_device(scales) if scales is not None else None]
     outs = {"points": ctx.empty((capacity + room, 3), dtype), "colors": ctx.empty((capacity + room, 3), dtype),
             "frame_off": ctx.empty(F + 2, np.int64), "overflow": ctx.empty(2, np.int32)}
     for b in outs.values():
         b.fill(SENTINEL)
     i = _lib.CloudInputs(*[b.ptr if b is not None else None for b in ins], F)
     p = _lib.CloudParams(rng[0] if rng else 0.0, rng[1] if rng else 0.0, stride, (1 if rng else 0) | (2 if np.dtype(dtype) == np.float32 else 0))
-    o = _lib.CloudOutputs(outs["points"].ptr, outs["colors"].ptr if images is not None else None, outs["frame_off"].ptr, outs["overflow"].ptr,
+    o = _lib.CloudOutputs(outs["points"].ptr, outs["colors"].ptr if ins[2] is not None else None, outs["frame_off"].ptr, outs["overflow"].ptr,
                           capacity)
     c = _lib.Camera(cam.width, cam.height, cam.fx, cam.fy, cam.cx, cam.cy)
-    rc = ctx.lib.mvosr_point_cloud_batch(ctx.handle, C.byref(i), C.byref(c), C.byref(p), C.byref(o))
-    ctx.sync()
-    got = {k: b.download() for k, b in outs.items()}
-    got["rc"] = rc
-    for b in list(outs.values()) + [b for b in ins if b is not None]:
+    return {"ins": ins, "own": own, "outs": outs, "args": (i, c, p, o), "rc": None}
+
+
+def raw_launch(ctx, call):
+    """Queue a prepared call on the context's stream; nothing is waited for."""
+    i, c, p, o = call["args"]
+    call["rc"] = ctx.lib.mvosr_point_cloud_batch(ctx.handle, C.byref(i), C.byref(c), C.byref(p), C.byref(o))
+
+
+def raw_collect(ctx, call):
+    """Download a launched call's outputs (the download waits for the stream) and free its buffers."""
+    got = {k: b.download() for k, b in call["outs"].items()}
+    got["rc"] = call["rc"]
+    for b in list(call["outs"].values()) + ([b for b in call["ins"] if b is not None] if call["own"] else []):
         b.free()
     return got
 
@@ -293,3 +313,177 @@ def test_second_call_allocates_nothing(gpu):
     a1 = gpu.alloc_stats()
     assert a1["hip_malloc"] == a0["hip_malloc"] and a1["host_malloc"] == a0["host_malloc"], (a0, a1)
     assert_cloud(second, (first.points, first.colors, first.offsets), "second call")
+
+
+# ---- 8. large images, many frames, queued calls, thin and wide images, strides, the size limit ----------------------------------
+
+F64, F32 = np.float64, np.float32
+# (ids, range, scales, dtype, colours, stride): between them every option on and off; a batch of a large image takes one, in turn
+OPTIONS = [(True, None, False, F64, True, 1), (False, (-1.0, 60.0), True, F32, False, 1), (True, (-1.0, 60.0), False, F32, True, 1),
+           (False, None, True, F64, False, 1), (True, None, True, F64, False, 3)]
+LIGHT = [o for o in OPTIONS if o[3] is F32 and not o[4]] + [(True, None, False, F32, False, 1), (False, None, False, F32, False, 3)]
+
+
+def run_large(gpu, w, h, cuts, per_batch, options, teeth=False):
+    """The frames of ``cc.large_batch`` through cloud_from_depth, ``per_batch`` of them resident at a time, each batch with the
+    next of ``options``: frame_off, points and colours against ``cc.clouds``.  Returns the number of batches."""
+    from mvoscalerecovery_amd.reconstruct import Reconstruct
+    cam = crafted_camera(w, h)
+    rec = Reconstruct(cam, ctx=gpu)
+    names = cc.large_names(cuts, teeth)
+    seen = set()
+    for b, at in enumerate(range(0, len(names), per_batch)):
+        part, depth, tri, images, scales = cc.large_batch(w, h, cuts, frames=names[at:at + per_batch], teeth=teeth)
+        ids, rng, sc, dtype, col, stride = options[b % len(options)]
+        seen.add(options[b % len(options)])
+        res = rec.cloud_from_depth(depth, tri if ids else None, images=images if col else None, scales=scales if sc else None,
+                                   depth_range=rng, stride=stride, dtype=dtype)
+        want = cc.clouds(depth, tri if ids else None, cam, images if col else None, scales if sc else None, rng, stride, dtype)
+        assert_cloud(res, want, ((w, h), part, ids, rng, sc, np.dtype(dtype).name, col, stride))
+        if ids and rng is None and stride == 1:
+            assert np.array_equal(np.diff(res.offsets), [cc.large_mask(k, w, h).sum() for k in part]), part
+    assert len(seen) == len(options), "fewer batches than option combinations"
+    return b + 1
+
+
+@pytest.mark.parametrize("case", list(cc.MANY_SEGMENTS))
+def test_many_segments(gpu, case):
+    """cloud_scan_kernel: ``for (i0 < nseg; i0 += kClBlock)`` takes a second (4100 x 257: 258 segments) and a third (8200 x 257:
+    515) trip, so ``base += all`` carries something other than 0 and cl_block_excl<int> writes its LDS slot again behind the
+    second __syncthreads; 4096 x 256 is the last size without a second trip (exactly 256 segments).  cl_segment / cl_span /
+    cloud_fill_kernel: a width of at least kClSeg — a segment is one row (4096), lies inside a row or crosses exactly one row
+    end (4100, 8200), where ``dr`` of divmod_small(col0 + j, width) is only ever 0 or 1."""
+    w, h, cuts = cc.MANY_SEGMENTS[case]
+    n = run_large(gpu, w, h, cuts, 2 if w == 8200 else 3, LIGHT if w == 8200 else OPTIONS)
+    print("%s: %d segments, %d frames in %d batches" % (case, -(-w * h // cc.SEGMENT), len(cc.large_names(cuts)), n))
+
+
+@pytest.mark.parametrize("case", list(cc.THIN_WIDE))
+def test_thin_and_wide(gpu, case):
+    """cl_span / cloud_fill_kernel: width 1 (``dr`` of divmod_small runs to 4095: every pixel of a segment is a row of its own),
+    height 1 (``dr`` is always 0, ``col`` runs to the width), 4097 x 3 (a segment crosses a row end, three times at another
+    column), and 2^21 x 1: kClMaxSide, the top of divmod_small's range (col0 + j reaches 2^21 - 1) — the last 4096 columns are
+    compared value by value as well."""
+    w, h, cuts = cc.THIN_WIDE[case]
+    wide = w == cc.MAX_SIDE
+    n = run_large(gpu, w, h, cuts, 2 if wide else 1, LIGHT if wide else OPTIONS, teeth=wide)
+    print("%s: %d segments, %d batches" % (case, -(-w * h // cc.SEGMENT), n))
+    if wide:
+        from mvoscalerecovery_amd.reconstruct import Reconstruct
+        cam = crafted_camera(w, h)
+        name = "from_%d+0" % cuts[-1]                                              # exactly the last segment: columns 2^21 - 4096 ... 2^21 - 1
+        _, depth, tri, _, _ = cc.large_batch(w, h, cuts, frames=[name], teeth=True)
+        res = Reconstruct(cam, ctx=gpu).cloud_from_depth(depth, tri)
+        col = np.arange(w - cc.SEGMENT, w)
+        d = depth[0, 0, col]
+        assert res.offsets.tolist() == [0, cc.SEGMENT] and (d > 0).all()
+        assert np.array_equal(res.points[:, 2], d) and np.array_equal(res.points[:, 0], (col.astype(np.float64) - cam.cx) / cam.fx * d)
+        assert np.array_equal(res.points[:, 1], np.full(cc.SEGMENT, (0.0 - cam.cy) / cam.fy) * d)
+
+
+def check_raw(got, want, F, K, dtype, colours, label):
+    """A raw call's outputs against the restatement: all F + 1 offsets, the first ``min(K, capacity)`` rows, every tail."""
+    pts, cols, off = want
+    assert got["rc"] == 0, label
+    assert np.array_equal(got["frame_off"][:F + 1], off), (label, "frame_off")
+    assert got["frame_off"][F + 1] == sentinel_like(got["frame_off"])[F + 1] and got["overflow"][1] == sentinel_like(got["overflow"])[1], label
+    assert cc.same_bytes(got["points"][:K], pts[:K]), (label, "points")
+    assert np.array_equal(got["points"][K:].view(np.uint8), sentinel_like(got["points"][K:]).view(np.uint8)), (label, "points' tail")
+    if colours:
+        assert cc.same_bytes(got["colors"][:K], cols[:K]), (label, "colours")
+    assert np.array_equal(got["colors"][K if colours else 0:].view(np.uint8), sentinel_like(got["colors"][K if colours else 0:]).view(np.uint8)), label
+
+
+@pytest.mark.parametrize("turn", [0, 1, 2])
+@pytest.mark.parametrize("size,F", [((7, 5), 257), ((7, 5), 513), ((65, 63), 513), ((311, 95), 513)], ids=lambda v: "%dx%d" % v if isinstance(v, tuple) else "F%d" % v)
+def test_many_frames(gpu, size, F, turn):
+    """cloud_scan_kernel, the last workgroup to arrive: ``for (i0 < n_frames; i0 += kClBlock)`` takes a second (F = 257) and a
+    third (F = 513) trip, ``run += all`` carries something other than 0, cl_block_excl<long long> writes its slot again.  The
+    frames on either side of a round — 255, 256, 257, 511, 512 — are empty, full and single-pixel in turn."""
+    w, h = size
+    cam = crafted_camera(w, h)
+    depth, tri, images, scales = cc.many_frames(w, h, F, cc.special_kinds(F, turn), seed=turn)
+    ids, rng, sc, dtype, col, _ = OPTIONS[turn]
+    a = (tri if ids else None, images if col else None, scales if sc else None)
+    want = cc.clouds(depth, a[0], cam, a[1], a[2], rng, 1, dtype)
+    K = int(want[2][-1])
+    assert K > 0 and len(want[2]) == F + 1
+    got = raw_call(gpu, cam, depth, *a, K, dtype, rng=rng)
+    check_raw(got, want, F, K, dtype, col, (size, F, turn))
+    assert got["overflow"][0] == 0
+    got = raw_call(gpu, cam, depth, *a, K - 1, dtype, rng=rng)                     # one row short: the true counts, overflow 1
+    check_raw(got, want, F, K - 1, dtype, col, (size, F, turn, "one row short"))
+    assert got["overflow"][0] == 1
+    print("%dx%d F=%d turn %d: %d points" % (w, h, F, turn, K))
+
+
+def test_back_to_back(gpu):
+    """cloud_count_kernel / cloud_scan_kernel: ``*a.arrive`` — the arrival counter lives in the context's workspace at an offset
+    that depends on the call's frame and segment counts; three calls of two sizes queued with nothing waited for in between
+    share the workspace, and each must find its counter at 0 and its segment counts its own."""
+    F = 513
+    big, small = crafted_camera(311, 95), crafted_camera(65, 63)
+    depth, tri, images, scales = cc.many_frames(311, 95, F, cc.special_kinds(F, 1), seed=5)
+    d3, t3, i3, s3 = cc.many_frames(65, 63, 3, {1: "empty"}, seed=6)
+    want = cc.clouds(depth, tri, big, None, scales, None, 1, np.float32)
+    want3 = cc.clouds(d3, t3, small, i3, None, (1.0, 50.0), 3, np.float64)
+    K, K3 = int(want[2][-1]), int(want3[2][-1])
+    first = raw_prepare(gpu, big, depth, tri, None, scales, K, np.float32)
+    middle = raw_prepare(gpu, small, d3, t3, i3, None, K3, np.float64, stride=3, rng=(1.0, 50.0))
+    third = raw_prepare(gpu, big, depth, tri, None, scales, K, np.float32, ins=first["ins"])
+    gpu.sync()
+    for call in (first, middle, third):                                            # queued: no sync, no copy in between
+        raw_launch(gpu, call)
+    got3, got2, got1 = raw_collect(gpu, third), raw_collect(gpu, middle), raw_collect(gpu, first)
+    check_raw(got1, want, F, K, np.float32, False, "first")
+    check_raw(got3, want, F, K, np.float32, False, "third")
+    check_raw(got2, want3, 3, K3, np.float64, True, "middle")
+    assert got1["overflow"][0] == got2["overflow"][0] == got3["overflow"][0] == 0
+    for k in ("points", "colors", "frame_off", "overflow"):
+        assert cc.same_bytes(got1[k], got3[k]), (k, "first and third call")
+
+
+@pytest.mark.parametrize("size", cc.STRIDE_SIZES, ids=lambda s: "%dx%d" % s)
+def test_large_strides(gpu, size):
+    """cl_span: divmod_small(row, stride) and divmod_small(col, stride) with a stride larger than a side (the quotient is
+    always 0), next to the segment size (4096, 4097), next to the width (8199, 8200, 8201) and one that float cannot
+    represent (2^31 - 1: ``rS`` is 2^-31).  From max(width, height) upward only pixel (0, 0) is on the grid."""
+    from mvoscalerecovery_amd.reconstruct import Reconstruct, grid_points
+    w, h = size
+    cam = crafted_camera(w, h)
+    names, depth, tri, images, scales = cc.large_batch(w, h, [cc.SEGMENT])
+    rec = Reconstruct(cam, ctx=gpu)
+    bufs = [gpu.to_device(a) for a in (depth, tri, images, scales)]
+    d_depth, d_tri, d_img, d_sc = bufs
+    try:
+        for k, stride in enumerate(cc.STRIDES):
+            for ids, rng, sc, dtype, col, _ in (OPTIONS[k % 2], OPTIONS[2 + k % 2]):
+                res = rec.cloud_from_depth(d_depth, d_tri if ids else None, images=d_img if col else None, scales=d_sc if sc else None,
+                                           depth_range=rng, stride=stride, dtype=dtype)
+                want = cc.clouds(depth, tri if ids else None, cam, images if col else None, scales if sc else None, rng, stride, dtype)
+                assert_cloud(res, want, (size, stride, ids, rng, sc, np.dtype(dtype).name, col))
+                cnt = np.diff(res.offsets)
+                if stride >= max(w, h):
+                    assert set(cnt.tolist()) <= {0, 1}, (size, stride, cnt.tolist())
+            full = np.diff(rec.cloud_from_depth(d_depth, d_tri, stride=stride).offsets)     # ids, no range: the grid pixels a frame covers
+            assert full[0] == grid_points(w, h, stride)
+            if stride >= max(w, h):
+                assert np.array_equal(full, (tri[:, 0, 0] >= 0).astype(np.int64)) and 0 < full.sum() < len(names), (size, stride)
+    finally:
+        for b in bufs:
+            b.free()
+
+
+@pytest.mark.parametrize("size", [(cc.MAX_SIDE + 1, 1), (1, cc.MAX_SIDE + 1)], ids=lambda s: "%dx%d" % s)
+def test_side_beyond_the_limit_is_refused(gpu, size):
+    """mvosr_point_cloud_batch: ``cam->width > kClMaxSide || cam->height > kClMaxSide`` — one pixel beyond divmod_small's range
+    is MVOSR_ERR_TOO_LARGE and nothing is launched: every output keeps its sentinel.  (The inputs are allocated at their
+    full size.)"""
+    w, h = size
+    cam = crafted_camera(w, h)
+    depth, tri = np.ones((1, h, w)), np.zeros((1, h, w), np.int32)
+    got = raw_call(gpu, cam, depth, tri, None, None, 64)
+    assert got["rc"] == -3                                                         # MVOSR_ERR_TOO_LARGE
+    assert b"point_cloud" in gpu.lib.mvosr_last_error()
+    for k in ("points", "colors", "frame_off", "overflow"):
+        assert np.array_equal(got[k].view(np.uint8), sentinel_like(got[k]).view(np.uint8)), k

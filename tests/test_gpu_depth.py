@@ -12,6 +12,7 @@ import os
 import numpy as np
 import pytest
 
+import cloud_cases as cc
 import depth_cases as dc
 
 pytestmark = pytest.mark.gpu
@@ -298,6 +299,115 @@ def test_hostile_input(gpu):
     assert lib.mvosr_triangle_model_batch(gpu.handle, C.byref(b), 1, None, None, dummy.ptr) == ERR_ARG
     assert lib.mvosr_triangle_model_batch(gpu.handle, C.byref(b), 5, None, dummy.ptr, dummy.ptr) == ERR_ARG
     dummy.free()
+
+
+# ---- 5b. wide images: every band plan, the tile beyond 40 KB, the widest image and one pixel more -----------------------------
+
+def reference_units(fr):
+    """The REFERENCE's largest depth error on a strip frame, in units: its arithmetic in float64 (depth64 over model64) against
+    the longdouble truth, on the CPU.  The bound of the device's depths comes from this, never from the device."""
+    cam = fr["cam"]
+    tri, _ = dc.locate(fr["f2"], fr["rows"], cam.width, cam.height)
+    d = dc.depth64(dc.model64(fr["f3"], fr["rows"]), tri, cam)
+    yy, xx, d_true, unit = dc.truth(fr["f3"], fr["rows"], tri, cam)
+    return float(dc.err_units(d[yy, xx], d_true, unit).max())
+
+
+def strip_batch(w, h):
+    """A wide-image batch: a float-pixel frame, an empty frame, an integer-pixel frame."""
+    a, b = dc.strip_pair(w, h)
+    empty = dict(cam=a["cam"], f3=np.zeros((0, 3)), f2=np.zeros((0, 2)), rows=np.zeros((0, 3), np.int32))
+    return [a, empty, b]
+
+
+def launch_frames(gpu, frames, **kw):
+    return launch(gpu, frames[0]["cam"], [fr["f3"] for fr in frames], [fr["f2"] for fr in frames], [fr["rows"] for fr in frames], **kw)
+
+
+def strip_shape_params():
+    return [pytest.param(i, id="%sx%d" % ("Wmax" if i == 7 else w, h)) for i, (w, h, _) in enumerate(dc.strip_shapes(0))]
+
+
+@pytest.mark.parametrize("index", strip_shape_params())
+def test_wide_images(gpu, index):
+    """mvosr_dense_depth_batch: ``band_rows = clamp((10240 / width) & ~1, 2, 16)`` — 14 rows (641, 682), 2 rows inside 40 KB
+    (2561, 5120), and the clamp to 2 rows beyond (5121, 8193, Wmax): the first launches of depth_raster_kernel with a dynamic
+    LDS request above kDpTileWords, up to ``max_lds_per_block - 64`` at Wmax.  depth_raster_kernel: ``y_hi = min(y_lo +
+    band_rows, height) - 1`` with a last band of one row (682 x 15, 310 x 17) and of two of fourteen (641 x 30); the sweep's
+    divmod_small(e, W) with W above 10240."""
+    wmax = dc.max_width(gpu.lds_per_block)
+    w, h, band = dc.strip_shapes(wmax)[index]
+    assert band == dc.band_rows(w) and 4 * band * w + 64 <= gpu.lds_per_block
+    frames = strip_batch(w, h)
+    out = launch_frames(gpu, frames)
+    assert out["rc"] == 0 and out["status"].tolist() == [0, ST_EMPTY, 0]
+    assert (out["depth"][1] == 0).all() and (out["tri_id"][1] == -1).all() and out["covered"][1] == 0
+    for f in (0, 2):
+        fr = frames[f]
+        u = reference_units(fr)
+        a, b = int(out["tri_off"][f]), int(out["tri_off"][f + 1])
+        got = check_image(fr, out["depth"][f], out["tri_id"][f], out["tri_model"][a:b], out["covered"][f], factor=dc.bound_factor(u),
+                          label="%dx%d[%d] (%d band rows, LDS %d B)" % (w, h, f, band, 4 * band * w))
+        print("%dx%d[%d]: reference %.3f units, factor %.2f, device %.3f units" % (w, h, f, u, dc.bound_factor(u), got))
+
+
+def test_one_pixel_wider_than_the_lds_is_refused(gpu):
+    """mvosr_dense_depth_batch: ``lds + 64 > max_lds_per_block`` — Wmax + 1 is MVOSR_ERR_TOO_LARGE and nothing is launched: every
+    output keeps its sentinel.  (The frames are those of the Wmax test: nothing depends on the answer.)"""
+    wmax = dc.max_width(gpu.lds_per_block)
+    frames = strip_batch(wmax, 3)
+    cam = dc.camera(wmax + 1, 3, *[getattr(frames[0]["cam"], k) for k in ("fx", "fy", "cx", "cy")])
+    out = launch(gpu, cam, [fr["f3"] for fr in frames], [fr["f2"] for fr in frames], [fr["rows"] for fr in frames])
+    assert out["rc"] == -3 and b"dense_depth" in gpu.lib.mvosr_last_error()          # MVOSR_ERR_TOO_LARGE
+    for k in ("depth", "tri_id", "tri_model", "covered", "status"):
+        assert np.array_equal(out[k].view(np.uint8), sentinel_like(out[k]).view(np.uint8)), k
+
+
+def test_first_width_above_the_tile(gpu):
+    """5121 x 5, the first width whose two-row band is more than kDpTileWords: the batch against per-frame calls and sub-ranges
+    (``first_frame``, ``n_launch``), as the batch's second triangulation, and without the id image — the sweep's ``par`` path
+    where a band's first pixel is not 16-byte aligned (an odd width: every other band) — all byte-identical to the batch;
+    then both stages together: point_clouds against the restatement on the device's own images."""
+    from mvoscalerecovery_amd.reconstruct import Reconstruct
+    w, h = 5121, 5
+    frames = strip_batch(w, h)
+    F = len(frames)
+    full = launch_frames(gpu, frames)
+    assert full["rc"] == 0 and full["status"].tolist() == [0, ST_EMPTY, 0] and (full["covered"][[0, 2]] > w * h // 2).all()
+    for f in range(F):
+        one = launch_frames(gpu, [frames[f]])
+        assert one["rc"] == 0 and cc.same_bytes(one["depth"][0], full["depth"][f]) and cc.same_bytes(one["tri_id"][0], full["tri_id"][f]), f
+        assert one["status"][0] == full["status"][f] and one["covered"][0] == full["covered"][f]
+        a, b = int(full["tri_off"][f]), int(full["tri_off"][f + 1])
+        assert cc.same_bytes(one["tri_model"][:b - a], full["tri_model"][a:b])
+    for first, n in ((0, 1), (1, 2), (2, 1)):
+        sub = launch_frames(gpu, frames, first=first, n=n)
+        inside = np.zeros(F, bool)
+        inside[first:first + n] = True
+        assert sub["rc"] == 0
+        for k in ("depth", "tri_id", "covered", "status"):
+            assert cc.same_bytes(sub[k][inside], full[k][inside]), (first, n, k)
+            assert np.array_equal(sub[k][~inside], sentinel_like(sub[k][~inside])), (first, n, k, "untouched frames")
+    as_tri2 = launch_frames(gpu, frames, which=2)
+    assert as_tri2["rc"] == 0
+    for k in ("depth", "tri_id", "tri_model", "covered", "status"):
+        assert cc.same_bytes(as_tri2[k], full[k]), ("which = 2", k)
+    no_ids = launch_frames(gpu, frames, ids=False)
+    assert no_ids["rc"] == 0 and cc.same_bytes(no_ids["depth"], full["depth"]) and cc.same_bytes(no_ids["covered"], full["covered"])
+    assert np.array_equal(no_ids["tri_id"], sentinel_like(no_ids["tri_id"]))
+    # the two stages together
+    pair = [frames[0], frames[2]]
+    cam = pair[0]["cam"]
+    rec = Reconstruct(cam, ctx=gpu)
+    f3s, f2s, rows = [fr["f3"] for fr in pair], [fr["f2"] for fr in pair], [fr["rows"] for fr in pair]
+    dm = rec.depth_maps(f3s, f2s, tris=rows, ids=True)
+    assert cc.same_bytes(dm.depth, full["depth"][[0, 2]]) and cc.same_bytes(dm.tri_id, full["tri_id"][[0, 2]])
+    for stride in (1, 3):
+        res = rec.point_clouds(f3s, f2s, tris=rows, stride=stride)
+        pts, _, off = cc.clouds(dm.depth, dm.tri_id, cam, stride=stride)
+        assert np.array_equal(res.offsets, off) and cc.same_bytes(res.points, pts) and len(pts) > 0, stride
+        if stride == 1:
+            assert np.array_equal(np.diff(off), dm.covered)
 
 
 # ---- 6. metric depth next to the scale -------------------------------------------------------------------------------------
