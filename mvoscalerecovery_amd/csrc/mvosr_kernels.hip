@@ -745,12 +745,15 @@ struct RoadResult {
 // (:284-293)  `single` = bins whose raw count is exactly 1; an interval is built from the bin's
 // RIGHT edge r as [r-0.1, r] for the first single bin and (r-0.1, r] for the others — r-0.1 is
 // not always the bin's own left edge in floating point, so neighbours are checked too.
-__device__ __forceinline__ bool dropped_by_single(double y, int bin, const Bits192 &single, int first_single) {
+// (the three words of `single` by value: a reference keeps the whole Bits192 in scratch memory, read there per suspect)
+__device__ __forceinline__ bool dropped_by_single(double y, int bin, unsigned long long s0, unsigned long long s1, unsigned long long s2,
+                                                  int first_single) {
     bool d = false;
 #pragma unroll
     for (int dk = -1; dk <= 1; ++dk) {
         const int k = bin + dk;
-        const bool is_single = (k >= 0) && (k < kBins) && single.test_lane(max(k, 0));
+        const int kk = max(k, 0);
+        const bool is_single = (k >= 0) && (k < kBins) && (((kk < 64 ? s0 : (kk < 128 ? s1 : s2)) >> (kk & 63)) & 1ull);
         const double r = bin_edge(k + 1);
         const double lo = r - 0.1;
         const bool in = (k == first_single) ? (y >= lo && y <= r) : (y > lo && y <= r);
@@ -766,12 +769,15 @@ __device__ unsigned long long g_road_exact_count[3];
 #endif
 constexpr int kRoadRC = 20;              // deepest tier: rows of 64 values whose bins stay in registers (one byte each, four per VGPR); longer
                                          // lists (dense frames) re-read their tail once, for the suspects
-constexpr int kRoadSub = 4;              // lane-interleaved copies of the histogram (lane & 3): a clustered row's same-bin ds_add_u32 serialise
+constexpr int kRoadRCHot = 24;           // deepest tier of the lean (HOT) variant: 1536 values, the 2000-feature bench's lists whole (at 22 rows
+                                         // 7 of its 1024 frames went to the cold list; the packed bins take six VGPRs either way)
+constexpr int kRoadSub = 4;             // lane-interleaved copies of the histogram (lane & 3): a clustered row's same-bin ds_add_u32 serialise
                                          // four times less; the copies of a bin are adjacent ints, summed with one ds_read_b128
 constexpr int kRoadWaves = 4;          // frames (wavefronts) per workgroup
 constexpr int kTrash = 175;            // histogram slot for values that are not binned (bins are 0..168)
 constexpr int kStPending = -1;         // scale kernel -> road kernel: "road model still to run"
 constexpr int kStRedo = -2;            // HOT scale kernel -> EXACT pass: "needs height_level in NumPy's summation order"
+constexpr int kStCold = -3;            // RoadResult of the HOT road variant only, never stored: "needs a path this variant does not have"
 static_assert(kStRedo == MVOSR_ST_REDO, "include/mvosr.h");
 constexpr int kMaxVoteRows = 32765;    // a 16-bit biased vote counter stays in [1, 0xFFFE] whatever the rows say while a vertex has at most this many
 
@@ -791,6 +797,8 @@ struct RoadArgs {
     int wide;                    // one WORKGROUP per frame (dense batches: long lists, few frames)
     const uint8_t *listed_mask = nullptr;   // with level_redo: frames whose byte is set are ON that list already (append_mask_kernel put
                                  // them there behind the HOT kernel) — marked for the exact pass, not appended a second time
+    int32_t *cold = nullptr;     // HOT variant: frames that need a path it does not have are left as they are and appended here
+                                 // ([0] = count, like level_redo); LIST variant: a second list, worked off behind `list`
 };
 
 // bin of y against the workgroup's table edges[k] = {edge k, edge k+1} (same doubles as bin_edge)
@@ -817,7 +825,13 @@ __device__ __forceinline__ int bin_of_table(double y, const double2 *edges) {
 // only the bins of the first RC rows (a byte each), for the suspect test.
 // hist: kRoadSub lane-interleaved copies, bin b of copy c at int 4*b + c; comb: the summed counts (176 ints);
 // nearflag: 176 bytes, 1 for a bin that is single or next to a single one.
-template <int RC, int WW = 1>
+//
+// HOT: the lean product instantiation (as MODE_HOT is for the scale kernel) — the one-pass loop over at most RC rows, the
+// histogram logic, the suspects, the band test and the decision.  It has no packed list (NumPy-order sums, median), no
+// loops beyond the register tier and no statistics / histogram output: a list that needs one of them comes back kStCold
+// and the caller puts the frame on the cold list, which the full LIST instantiation works off.  The caller keeps lists
+// longer than RC rows away from it.
+template <int RC, int WW = 1, bool HOT = false>
 __device__ __forceinline__ RoadResult road_wave(int *hist, int *comb, uint8_t *nearflag, const double2 *edges,
                                                 const double *yv_all, double *scratch,
                                                 int Mall, double height_level, const mvosr_params &P, int32_t *g_hist, bool exact_stats,
@@ -871,11 +885,17 @@ __device__ __forceinline__ RoadResult road_wave(int *hist, int *comb, uint8_t *n
             s2 = __builtin_fma(d, d, s2);
             pk[k >> 2] = (k & 3) ? (pk[k >> 2] | ((unsigned)bin << (8 * (k & 3)))) : (unsigned)bin;
         }
+        // (the sums and the packed bins are DONE here: left alone, the compiler sinks the additions behind the suspects'
+        // loop — their first use — and keeps all RC values of the lane alive for it, in registers and in scratch memory)
+        asm volatile("" : "+v"(s1), "+v"(s2));
+        static_assert(kG == 4, "one word of pk per group");
+        asm volatile("" : "+v"(pk[k0 >> 2]));
         __builtin_amdgcn_sched_barrier(0);              // (the next group's loads stay behind this one: kG values in flight, not RC)
     }
     // (lists longer than the register tier — dense frames: two loads in flight per trip instead of one dependent
     // round trip per value; the same in the suspects' pass further down)
     constexpr int kLongUnroll = 2;
+    if constexpr (!HOT) {
     for (int i0 = RC * kWave + lane; i0 < M; i0 += kLongUnroll * kWave) {
         double yl[kLongUnroll];
 #pragma unroll
@@ -889,6 +909,7 @@ __device__ __forceinline__ RoadResult road_wave(int *hist, int *comb, uint8_t *n
             s1 += d;
             s2 = __builtin_fma(d, d, s2);
         }
+    }
     }
     MVOSR_RSTAMP(2);
     if constexpr (WW > 1) __syncthreads();              // every part's values are in the shared histogram
@@ -910,12 +931,13 @@ __device__ __forceinline__ RoadResult road_wave(int *hist, int *comb, uint8_t *n
     }
     mx = wave_max(mx);
     mn = wave_min(mn);
-    if (g_hist && (WW == 1 || wave_id() == 0)) {
+    if (!HOT && g_hist && (WW == 1 || wave_id() == 0)) {
 #pragma unroll
         for (int c = 0; c < 3; ++c) { const int b = lane + 64 * c; if (b < kBins) { g_hist[b] = hraw[c]; g_hist[kBins + b] = hz[c]; } }
     }
     MVOSR_RSTAMP(3);
     const int first_single = single.lowest_from(0);
+    const unsigned long long sg0 = single.w[0], sg1 = single.w[1], sg2 = single.w[2];
     // a value can only be dropped if its own bin or a neighbouring one has count 1
     Bits192 near;
     near.w[0] = single.w[0] | (single.w[0] << 1) | (single.w[0] >> 1) | (single.w[1] << 63);
@@ -938,7 +960,7 @@ __device__ __forceinline__ RoadResult road_wave(int *hist, int *comb, uint8_t *n
             const int k = __ffs(sus) - 1;
             sus &= sus - 1u;
             const double y = yv[k * kWave + lane];
-            if (dropped_by_single(y, bin_of_table(y, edges), single, first_single)) {
+            if (dropped_by_single(y, bin_of_table(y, edges), sg0, sg1, sg2, first_single)) {
                 const double d = y - sh;
                 t1 += d;
                 t2 = __builtin_fma(d, d, t2);
@@ -946,6 +968,7 @@ __device__ __forceinline__ RoadResult road_wave(int *hist, int *comb, uint8_t *n
             }
         }
     }
+    if constexpr (!HOT) {
     for (int i0 = RC * kWave + lane; i0 < M; i0 += kLongUnroll * kWave) {   // lists longer than the register tier
         double yl[kLongUnroll];
 #pragma unroll
@@ -955,13 +978,14 @@ __device__ __forceinline__ RoadResult road_wave(int *hist, int *comb, uint8_t *n
             if (i0 + j * kWave >= M) continue;
             const double y = yl[j];
             const int bin = bin_of_table(y, edges);
-            if (bin >= 0 && nearflag[bin] && dropped_by_single(y, bin, single, first_single)) {
+            if (bin >= 0 && nearflag[bin] && dropped_by_single(y, bin, sg0, sg1, sg2, first_single)) {
                 const double d = y - sh;
                 t1 += d;
                 t2 = __builtin_fma(d, d, t2);
                 ++nd;
             }
         }
+    }
     }
     double S1 = wave_sum(s1 - t1), S2 = wave_sum(s2 - t2), Q = wave_sum(s2);
     nd = wave_sum(nd);
@@ -990,7 +1014,7 @@ __device__ __forceinline__ RoadResult road_wave(int *hist, int *comb, uint8_t *n
             if (i < Mall) {
                 y = yv_all[i];
                 const int bin = bin_of_table(y, edges);
-                keep = !(bin >= 0 && nearflag[bin] && dropped_by_single(y, bin, single, first_single));
+                keep = !(bin >= 0 && nearflag[bin] && dropped_by_single(y, bin, sg0, sg1, sg2, first_single));
             }
             const unsigned long long m = __ballot(keep);
             if (keep) scratch[nlist + __popcll(m & ((1ull << lane) - 1ull))] = y;
@@ -1002,6 +1026,7 @@ __device__ __forceinline__ RoadResult road_wave(int *hist, int *comb, uint8_t *n
     if (!have_modes) {
         if constexpr (WW > 1) { if (wave_id() != 0) return R; }                             // (no barrier lies ahead on this branch)
         if (nkept == 0) { R.height = height_level; R.status = MVOSR_ST_LEVEL; return R; }   // :334-335
+        if constexpr (HOT) { R.status = kStCold; return R; }                                // (the median: the full variant's)
         // np.median (:333): pack the kept values into `scratch` (index <= source index, so in place
         // is safe when scratch == yv), then rank counting: the two middle order statistics
         pack_kept();
@@ -1104,7 +1129,9 @@ __device__ __forceinline__ RoadResult road_wave(int *hist, int *comb, uint8_t *n
             if (!(margin > bound)) atomicAdd(&g_road_exact_count[2], 1ull);
         }
 #endif
-        if (!(margin > bound) || exact_stats) {
+        if constexpr (HOT) {
+            if (!(margin > bound)) { R.status = kStCold; return R; }                        // (NumPy's order: the full variant's)
+        } else if (!(margin > bound) || exact_stats) {
             const int nl = pack_kept();
             __threadfence_block();               // the wave's own stores, visible to all its lanes
             mean_o = np_pairwise_sum_cold(scratch, nl, 0.0, 0, np_stack) / (double)nl;    // np.mean
@@ -1118,15 +1145,20 @@ __device__ __forceinline__ RoadResult road_wave(int *hist, int *comb, uint8_t *n
     return R;
 }
 
-constexpr int kRoadOcc = 6;              // wavefronts per SIMD the product variants are compiled for (their VGPR budget)
+constexpr int kRoadOcc = 6;              // wavefronts per SIMD the full product variants are compiled for (their VGPR budget)
+constexpr int kRoadOccHot = 7;           // the same for the lean (HOT) variant: 59 VGPRs, no spills, no scratch (at 8 the SGPR budget of 80
+                                         // leaves ten scalar spills in a VGPR's lanes)
 // LIST: the frames of a.list, grid-strided (the rare second pass over the frames that ended on the fallback level); otherwise
 // frame first_frame + wavefront index, no loop (a loop around the body costs the product variant 57 VGPRs, i.e. half its occupancy)
-// LDS per workgroup ~18 KB; the launch bound gives the product variants kRoadOcc wavefronts per SIMD (6: at most
-// 80 VGPRs, six workgroups per CU; 8 needs 64 VGPRs and spills inside the loops, 5 runs without spills but slower).
-template <bool LIST, int WW = 1>
-__global__ __launch_bounds__(kRoadWaves *kWave, (LIST ? 1 : kRoadOcc)) void road_model_kernel(const RoadArgs a) {
-    static_assert(kRoadRC >= 16 && kRoadRC <= 32, "the row masks are 32 bits");
+// LDS per workgroup ~18 KB; the launch bound gives the full product variants kRoadOcc wavefronts per SIMD (6: at most
+// 80 VGPRs, six workgroups per CU; 5 runs slower).
+// HOT: road_wave's lean instantiation at kRoadOccHot wavefronts per SIMD; what it cannot finish goes to a.cold.  The LIST
+// variant keeps every path and takes two lists in one launch: a.list (the redo list), then a.cold.
+template <bool LIST, int WW = 1, bool HOT = false>
+__global__ __launch_bounds__(kRoadWaves *kWave, (LIST ? 1 : HOT ? kRoadOccHot : kRoadOcc)) void road_model_kernel(const RoadArgs a) {
+    static_assert(kRoadRC >= 16 && kRoadRC <= 32 && kRoadRCHot >= 16 && kRoadRCHot <= 32, "the row masks are 32 bits");
     static_assert(WW == 1 || (WW == kRoadWaves && !LIST), "wide variant: the whole workgroup on one frame");
+    static_assert(!HOT || (!LIST && WW == 1), "the lean variant: one wavefront per frame, no list");
     __shared__ __attribute__((aligned(16))) int hist_all[kRoadWaves][kRoadSub * 176];
     __shared__ int comb_all[kRoadWaves][176];
     __shared__ uint8_t near_all[kRoadWaves][176];
@@ -1137,18 +1169,24 @@ __global__ __launch_bounds__(kRoadWaves *kWave, (LIST ? 1 : kRoadOcc)) void road
     __syncthreads();
     const int64_t slot = WW > 1 ? (int64_t)blockIdx.x : (int64_t)blockIdx.x * kRoadWaves + wave_id();
     auto one_frame = [&](const int64_t f) {
-    if (a.pending_only && a.o.status[f] != kStPending) return;          // (wide: the same answer in every wavefront)
+    // (the frame's four header words in one round trip: the status test does not wait in front of the other three)
+    // (f is the wavefront's: status, length and offset are told to the compiler as wave-uniform, so that the tiers below are
+    // scalar branches and the list's base a scalar address)
+    const int st_in = a.pending_only ? __builtin_amdgcn_readfirstlane(a.o.status[f]) : kStPending;
+    const int M = __builtin_amdgcn_readfirstlane(a.cnt[f]);
+    const int64_t off_l = a.off[f];
+    const int64_t off = (int64_t)(((uint64_t)(uint32_t)__builtin_amdgcn_readfirstlane((int)(off_l >> 32)) << 32) |
+                                  (uint64_t)(uint32_t)__builtin_amdgcn_readfirstlane((int)off_l));
+    const double hl = a.height_level ? a.height_level[f] : nan("");
+    if (st_in != kStPending) return;                                    // (wide: the same answer in every wavefront)
     MVOSR_STAMP_DECL
     MVOSR_RSTAMP(0);
-    const int M = a.cnt[f];
-    const int64_t off = a.off[f];
-    const double hl = a.height_level ? a.height_level[f] : nan("");
     MVOSR_RSTAMP(1);
     // rows of bins kept in registers: as few as the list (wide: this wavefront's part of it) needs (the pass over
     // them is branch-free, so a short list would otherwise pay for rows of padding)
     int *h0 = hist_all[WW > 1 ? 0 : wave_id()];
-    int32_t *gh = a.o.hist ? a.o.hist + f * 2 * kBins : nullptr;
-    const bool ex = a.o.stats != nullptr;
+    int32_t *gh = (!HOT && a.o.hist) ? a.o.hist + f * 2 * kBins : nullptr;
+    const bool ex = !HOT && a.o.stats != nullptr;
     int lo = 0, hi = M;
     if constexpr (WW > 1) {
         const int q = ((M + WW * kWave - 1) / (WW * kWave)) * kWave;     // values per wavefront, whole rows of 64
@@ -1156,12 +1194,30 @@ __global__ __launch_bounds__(kRoadWaves *kWave, (LIST ? 1 : kRoadOcc)) void road
         hi = min(M, lo + q);
     }
     const int Mp = hi - lo;
-#define MVOSR_ROAD_CALL(RC_) road_wave<RC_, WW>(h0, comb_all[wave_id()], near_all[wave_id()], edges, a.y + off, a.scratch + off, M, hl, a.P, gh, ex, lo, hi, part, np_stack_all[wave_id()] MVOSR_STAMP_PASS)
-    const RoadResult R = (Mp <= 4 * kWave) ? MVOSR_ROAD_CALL(4)
-                       : (Mp <= 8 * kWave) ? MVOSR_ROAD_CALL(8)
-                       : (Mp <= 12 * kWave) ? MVOSR_ROAD_CALL(12)
-                       : (Mp <= 16 * kWave) ? MVOSR_ROAD_CALL(16)
-                                            : MVOSR_ROAD_CALL(kRoadRC);
+#define MVOSR_ROAD_CALL(RC_) road_wave<RC_, WW, HOT>(h0, comb_all[wave_id()], near_all[wave_id()], edges, a.y + off, a.scratch + off, M, hl, a.P, gh, ex, lo, hi, part, np_stack_all[wave_id()] MVOSR_STAMP_PASS)
+    RoadResult R;
+    if constexpr (HOT) {
+        // the lean variant's deepest tier holds the 2000-feature lists whole; a longer list is the full variant's
+        if (Mp > kRoadRCHot * kWave) R.status = kStCold;
+        else R = (Mp <= 4 * kWave) ? MVOSR_ROAD_CALL(4)
+               : (Mp <= 8 * kWave) ? MVOSR_ROAD_CALL(8)
+               : (Mp <= 12 * kWave) ? MVOSR_ROAD_CALL(12)
+               : (Mp <= 16 * kWave) ? MVOSR_ROAD_CALL(16)
+               : (Mp <= 20 * kWave) ? MVOSR_ROAD_CALL(20)
+                                    : MVOSR_ROAD_CALL(kRoadRCHot);
+        if (R.status == kStCold) {
+            // left as it is (fused path: pending) for the LIST pass over the cold list — unless the exact mask has put the frame on
+            // the redo list, which that pass takes as well: two wavefronts would compact one list in place
+            if (lane_id() == 0 && !(a.listed_mask && a.listed_mask[f])) a.cold[1 + atomicAdd(a.cold, 1)] = (int32_t)f;
+            return;
+        }
+    } else {
+        R = (Mp <= 4 * kWave) ? MVOSR_ROAD_CALL(4)
+          : (Mp <= 8 * kWave) ? MVOSR_ROAD_CALL(8)
+          : (Mp <= 12 * kWave) ? MVOSR_ROAD_CALL(12)
+          : (Mp <= 16 * kWave) ? MVOSR_ROAD_CALL(16)
+                               : MVOSR_ROAD_CALL(kRoadRC);
+    }
 #undef MVOSR_ROAD_CALL
     MVOSR_RSTAMP(6);
 #ifdef MVOSR_STAMPS
@@ -1190,12 +1246,16 @@ __global__ __launch_bounds__(kRoadWaves *kWave, (LIST ? 1 : kRoadOcc)) void road
             c[MVOSR_CNT_SELECTED] = R.n_sel; c[MVOSR_CNT_KEPT] = R.n_kept; c[MVOSR_CNT_MODES] = R.n_modes;
             c[MVOSR_CNT_MODE_LEFT] = R.mode_left; c[MVOSR_CNT_MODE_RIGHT] = R.mode_right;
         }
-        if (a.o.stats) { double *st = a.o.stats + 4 * f; st[0] = R.mean; st[1] = R.std; st[2] = R.skew; st[3] = R.median; }
+        if constexpr (!HOT) {
+            if (a.o.stats) { double *st = a.o.stats + 4 * f; st[0] = R.mean; st[1] = R.std; st[2] = R.skew; st[3] = R.median; }
+        }
     }
     };
     if constexpr (LIST) {
-        const int64_t n_todo = (int64_t)a.list[0];
+        // the two lists one after the other (either may be absent); no frame is on both
+        const int64_t n_todo = a.list ? (int64_t)a.list[0] : 0, n_cold = a.cold ? (int64_t)a.cold[0] : 0;
         for (int64_t it = slot; it < n_todo; it += (int64_t)gridDim.x * kRoadWaves) one_frame((int64_t)a.list[1 + it]);
+        for (int64_t it = slot; it < n_cold; it += (int64_t)gridDim.x * kRoadWaves) one_frame((int64_t)a.cold[1 + it]);
     } else {
         if (slot < a.n_frames) one_frame(a.first_frame + slot);
     }
@@ -2436,6 +2496,15 @@ static int launch_append_mask(mvosr_ctx *ctx, const KArgs &ka, int64_t nl, bool 
 // known on the device, and is almost always zero).
 constexpr int kRedoGrid = 512;
 constexpr int kModeExactList = 3;
+
+// The road model's cold list (RoadArgs::cold) lies right behind the redo list's 1 + n_frames words, in the workspace's second
+// block of that size.  One fill zeroes both counts (whole 16-byte words; the list slots it crosses hold nothing yet).
+static inline int32_t *cold_list_of(int32_t *redo, int64_t n_frames) { return redo + 1 + n_frames; }
+static int zero_lists(mvosr_ctx *ctx, int32_t *redo, int64_t n_frames) {
+    const size_t bytes = (((size_t)n_frames + 2) * sizeof(int32_t) + 15) & ~(size_t)15;
+    const hipError_t e = hipMemsetAsync(redo, 0, bytes, ctx_stream(ctx));
+    return e == hipSuccess ? MVOSR_OK : set_hip_error("hipMemsetAsync(redo and cold lists)", e);
+}
 static inline KArgs &kargs_of(KArgs &a) { return a; }
 static inline KArgs &kargs_of(DenseArgs &a) { return a.k; }
 
@@ -2467,8 +2536,7 @@ static int launch_modes(mvosr_ctx *ctx, void (*k_hot)(const Args), void (*k_exac
         return check_launch(name);
     }
     if ((rc = prepare_kernel(k_hot, lds_hot))) return rc;
-    const hipError_t e = hipMemsetAsync(kargs_of(args).redo, 0, sizeof(int32_t), ctx_stream(ctx));
-    if (e != hipSuccess) return set_hip_error("hipMemsetAsync(redo list)", e);
+    if ((rc = zero_lists(ctx, kargs_of(args).redo, kargs_of(args).b.n_frames))) return rc;
     hipLaunchKernelGGL(k_hot, dim3((unsigned)nl), dim3(threads_hot), lds_hot, ctx_stream(ctx), args);
     if ((rc = check_launch(name))) return rc;
     if (!g_hot_only && (rc = launch_append_mask(ctx, kargs_of(args), nl, true))) return rc;
@@ -2541,14 +2609,20 @@ static int launch_scale_dense(mvosr_ctx *ctx, const KArgs &ka, int64_t nl, int m
 }
 
 // one wavefront per frame, kRoadWaves frames per workgroup
-static int launch_road(mvosr_ctx *ctx, const RoadArgs &ra, hipStream_t stream) {
+// lists: the LIST pass over ra.list and ra.cold (the full code); otherwise every frame of the range — wide, or lean (HOT)
+// when the caller gave a cold list, or full
+static int launch_road(mvosr_ctx *ctx, const RoadArgs &ra, hipStream_t stream, bool lists = false) {
     if (ra.n_frames <= 0) return MVOSR_OK;
-    if (ra.wide && !ra.list) {
+    if (lists) {
+        hipLaunchKernelGGL(road_model_kernel<true>, dim3(64u), dim3(kRoadWaves * kWave), 0, stream, ra);
+        return check_launch("road_model_kernel (lists)");
+    }
+    if (ra.wide) {
         hipLaunchKernelGGL((road_model_kernel<false, kRoadWaves>), dim3((unsigned)ra.n_frames), dim3(kRoadWaves * kWave), 0, stream, ra);
         return check_launch("road_model_kernel (wide)");
     }
-    const unsigned blocks = ra.list ? 64u : (unsigned)((ra.n_frames + kRoadWaves - 1) / kRoadWaves);
-    if (ra.list) hipLaunchKernelGGL(road_model_kernel<true>, dim3(blocks), dim3(kRoadWaves * kWave), 0, stream, ra);
+    const unsigned blocks = (unsigned)((ra.n_frames + kRoadWaves - 1) / kRoadWaves);
+    if (ra.cold) hipLaunchKernelGGL((road_model_kernel<false, 1, true>), dim3(blocks), dim3(kRoadWaves * kWave), 0, stream, ra);
     else hipLaunchKernelGGL(road_model_kernel<false>, dim3(blocks), dim3(kRoadWaves * kWave), 0, stream, ra);
     return check_launch("road_model_kernel");
 }
@@ -2615,8 +2689,7 @@ static int launch_scale_classes(mvosr_ctx *ctx, const KArgs &ka, int64_t nl) {
     }
     if ((e = hipMemsetAsync(hdr, 0, kClassHeader * sizeof(int32_t), ctx_stream(ctx))) != hipSuccess)
         return set_hip_error("hipMemsetAsync(class lists)", e);
-    if ((e = hipMemsetAsync(ka.redo, 0, sizeof(int32_t), ctx_stream(ctx))) != hipSuccess)
-        return set_hip_error("hipMemsetAsync(redo list)", e);
+    if ((rc = zero_lists(ctx, ka.redo, ka.b.n_frames))) return rc;
     const int cb = kClassifyWaves * kWave;
     hipLaunchKernelGGL(classify_frames_kernel, dim3((unsigned)((nl + cb - 1) / cb)), dim3(cb), 0, ctx_stream(ctx), ca);
     if ((rc = check_launch("classify_frames_kernel"))) return rc;
@@ -2681,7 +2754,7 @@ int mvosr_scale_batch(mvosr_ctx *ctx, const mvosr_params *p, const mvosr_batch *
     if (b->total_feat <= 0) return set_error(MVOSR_ERR_ARG, "scale_batch: batch.total_feat (length of the feature planes) not set");
     if (b->n_frames >= ((int64_t)1 << 31) - 1) return set_error(MVOSR_ERR_TOO_LARGE, "scale_batch: more than 2^31-2 frames in one batch");
     if ((rc = ctx_workspace(ctx, b->n_frames, b->total_feat, &ka.ysel, &ka.nsel))) return rc;
-    ka.redo = ka.nsel + b->n_frames;            // [1 + n_frames] ints behind the nsel array; the [1 + n_frames] behind it are unused
+    ka.redo = ka.nsel + b->n_frames;            // [1 + n_frames] ints behind the nsel array; the [1 + n_frames] behind it: the road model's cold list
     // FULL: per-triangle debug outputs; EXACT: stage outputs requested (height_level bit-equal to NumPy's for every
     // frame); HOT: the product path + its exact pass over the frames that need it
     const int mode = hot_only ? MODE_HOT : (o->tri_normals || o->tri_pitch_deg || o->tri_heights) ? MODE_FULL
@@ -2720,11 +2793,11 @@ int mvosr_scale_batch(mvosr_ctx *ctx, const mvosr_params *p, const mvosr_batch *
     }
     // (a -DMVOSR_STAMPS build launches no road model: the scale kernel's stamps are written over outputs.hist, where the road
     // model writes its histograms)
-    auto road = [&]() {
+    auto road = [&](bool lists = false) {
 #ifdef MVOSR_STAMPS
         return MVOSR_OK;
 #else
-        return launch_road(ctx, ra, ctx_stream(ctx));
+        return launch_road(ctx, ra, ctx_stream(ctx), lists);
 #endif
     };
     auto standin_rows = [&](const int32_t *list) {
@@ -2741,8 +2814,7 @@ int mvosr_scale_batch(mvosr_ctx *ctx, const mvosr_params *p, const mvosr_batch *
         if (standin && (rc = standin_rows(ka.redo))) return rc;
         if ((rc = dense ? launch_scale_dense(ctx, ka, n_launch, kModeExactList, false) : dispatch_scale(ctx, ka, waves, n_launch, kModeExactList))) return rc;
         ra.first_frame = first_frame; ra.n_frames = n_launch; ra.list = ka.redo;
-        ra.wide = dense ? 1 : 0;
-        return road();
+        return road(true);
     }
     // HOT: ONE exact pass per call (round 5; two before: one behind the HOT kernel, one behind the road model).  The HOT kernel
     // and the exact mask put their frames on the redo list; the road model runs over every other frame and APPENDS the frames that
@@ -2759,18 +2831,29 @@ int mvosr_scale_batch(mvosr_ctx *ctx, const mvosr_params *p, const mvosr_batch *
     if (pev && (ee = hipEventRecord(pev[1], ctx_stream(ctx))) != hipSuccess) return set_hip_error("hipEventRecord(profile)", ee);
     ra.first_frame = first_frame; ra.n_frames = n_launch;
     ra.wide = dense ? 1 : 0;                    // dense batches: thousands of values per list, few frames
+    // The lean road variant and its cold list, finished by the LIST pass: wherever that pass follows in the same call and no
+    // statistics / histogram output is asked for.  (Dense batches run the wide variant; MVOSR_WAVES_HOT_ONLY — a call of a frame
+    // or two, with no LIST pass behind it — keeps the full variant rather than gain a launch.)
+    const bool lean = !dense && !hot_only && !o->stats && !o->hist;
     if (mode == MODE_HOT) {
         ra.level_redo = ka.redo;
         ra.listed_mask = hot_only ? nullptr : b->exact_mask;    // (hot_only: append_mask_kernel did not run)
+        ra.cold = lean ? cold_list_of(ka.redo, b->n_frames) : nullptr;  // (zeroed with the redo list, in front of the HOT kernel)
         if ((rc = road())) return rc;
         ra.listed_mask = nullptr;
         if (hot_only) return MVOSR_OK;            // (the list's frames stay MVOSR_ST_REDO: the caller's)
         if (standin && (rc = standin_rows(ka.redo))) return rc;          // SciPy's own rows for the frames the exact pass redoes
         if ((rc = dense ? launch_scale_dense(ctx, ka, n_launch, kModeExactList, false) : dispatch_scale(ctx, ka, waves, n_launch, kModeExactList))) return rc;
-        ra.level_redo = nullptr; ra.list = ka.redo;
+        ra.level_redo = nullptr; ra.list = ka.redo;     // the redo list's frames behind their exact scale pass; the cold list's need none
+        if ((rc = road(true))) return rc;
+    } else {
+        // EXACT / FULL: no redo list
+        if (lean) {
+            ra.cold = cold_list_of(ka.redo, b->n_frames);
+            if ((ee = hipMemsetAsync(ra.cold, 0, sizeof(int32_t), ctx_stream(ctx))) != hipSuccess) return set_hip_error("hipMemsetAsync(cold list)", ee);
+        }
         if ((rc = road())) return rc;
-    } else if ((rc = road())) {
-        return rc;
+        if (lean && (rc = road(true))) return rc;
     }
     if (pev) {
         if ((ee = hipEventRecord(pev[2], ctx_stream(ctx))) != hipSuccess) return set_hip_error("hipEventRecord(profile)", ee);
@@ -2828,13 +2911,20 @@ int mvosr_road_model_batch(mvosr_ctx *ctx, const mvosr_params *p, const mvosr_ba
     if ((rc = ctx_activate(ctx))) return rc;
     RoadArgs ra;
     double *scratch = nullptr;
-    int32_t *unused = nullptr;
-    if ((rc = ctx_workspace(ctx, b->n_frames, b->total_feat, &scratch, &unused))) return rc;
+    int32_t *ints = nullptr;
+    if ((rc = ctx_workspace(ctx, b->n_frames, b->total_feat, &scratch, &ints))) return rc;
     ra.P = *p; ra.off = b->feat_off; ra.cnt = b->feat_cnt; ra.y = b->y; ra.scratch = scratch;
     ra.height_level = height_level_in; ra.o = *o;
     ra.first_frame = 0; ra.n_frames = b->n_frames; ra.pending_only = 0; ra.level_redo = nullptr; ra.list = nullptr;
     ra.wide = b->max_feat > 4 * kRoadRC * kWave ? 1 : 0;        // lists beyond four wavefronts' register caches
-    return launch_road(ctx, ra, ctx_stream(ctx));
+    if (ra.wide || o->stats || o->hist) return launch_road(ctx, ra, ctx_stream(ctx));
+    // the lean variant, then the full code over the frames it left on the cold list (the workspace's block of that name, as
+    // in mvosr_scale_batch)
+    ra.cold = cold_list_of(ints + b->n_frames, b->n_frames);
+    const hipError_t e = hipMemsetAsync(ra.cold, 0, sizeof(int32_t), ctx_stream(ctx));
+    if (e != hipSuccess) return set_hip_error("hipMemsetAsync(cold list)", e);
+    if ((rc = launch_road(ctx, ra, ctx_stream(ctx)))) return rc;
+    return launch_road(ctx, ra, ctx_stream(ctx), true);
 }
 
 static int launch_window_median(mvosr_ctx *ctx, const double *raw, int64_t n, int n_blocks, int64_t stride, int window,
