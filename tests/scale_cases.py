@@ -614,10 +614,12 @@ def redo_cases():
 # ============================================================================================================================
 # on the device
 # ============================================================================================================================
-def run_scale(ctx, cases, kind="hot", waves=0, vote="reference", layout="survivors", hot_only=False):
+def run_scale(ctx, cases, kind="hot", waves=0, vote="reference", layout="survivors", hot_only=False, hist=None, mutate=None, far_table=True):
     """mvosr_scale_batch on `cases` as one batch.  kind: "hot" (the product kernel + its exact pass), "exact" (stage outputs),
     "full" (per-triangle outputs).  layout: "survivors", "features" (tri2 numbered over the features: the dense kernels),
-    "tiled".  Returns (PackedFrames, {name: host array})."""
+    "tiled".  hist: ask for the histogram / statistics outputs (default: with "exact"; they do not change the mode).  mutate(pf):
+    called on the packed batch before it is uploaded.  far_table=False: the tiled layout without the packer's table of far
+    vertices (tile_far / tile_far_off cleared).  Returns (PackedFrames, {name: host array})."""
     from mvoscalerecovery_amd import packing
     from mvoscalerecovery_amd.engine import DeviceBatch, DeviceOutputs, ScaleEngine
     pf = packing.pack_features([c.f3 for c in cases], [c.f2 for c in cases], vanish=VANISH)
@@ -625,13 +627,19 @@ def run_scale(ctx, cases, kind="hot", waves=0, vote="reference", layout="survivo
     masks = [np.asarray(c.oracle().valid) for c in cases]
     if layout == "tiled":
         packing.apply_tile_order(pf)
-        masks = [m[pf.extra["perm"][f]] for f, m in enumerate(masks)]
+        masks = [m if pf.extra["perm"][f] is None else m[pf.extra["perm"][f]] for f, m in enumerate(masks)]
     packing.attach_tri2(pf, [c.tri2 for c in cases], masks, feature_ids=layout != "survivors")
     if layout == "tiled":
         assert pf.tile_w == packing.TILE_W
+    if mutate is not None:
+        mutate(pf)
     eng = ScaleEngine(ABS_REF, ctx=ctx, camera_pitch=0.0, check_triangle=vote)
     db = DeviceBatch(ctx, pf)
-    out = DeviceOutputs(ctx, db, counts=True, stage=kind in ("exact", "full"), per_triangle=kind == "full", hist=kind == "exact")
+    if not far_table:
+        st = db.struct()
+        st.tile_far, st.tile_far_off = None, None
+    out = DeviceOutputs(ctx, db, counts=True, stage=kind in ("exact", "full"), per_triangle=kind == "full",
+                        hist=kind == "exact" if hist is None else hist)
     eng.scale_batch(db, out, waves=waves, hot_only=hot_only)
     ctx.sync()
     res = {k: out.get(k) for k in out.bufs}
