@@ -818,6 +818,48 @@ int mvosr_feature_distribution_batch(mvosr_ctx *ctx, int64_t n_frames, const int
 int mvosr_featdist_max_features(void);
 
 /*
+ * The pairwise depth-order check (/root/reference/script/data_check.py:19-34, depth_check — what it computes, not what it draws)
+ * for n_frames frames.  Frame f is the entries i in [off[f], off[f] + cnt[f]) of `y`, `z` and `level` — cnt == NULL: off has
+ * n_frames + 1 entries —, the packed planes of the staged path; level as for mvosr_feature_distribution_batch (0, 1 or 2).
+ * A point is selected iff y > 0 (:20; a NaN y is not).  For selected points vn = y / z (:23), and for EVERY ordered pair (i, j) of
+ * them, the diagonal included, q = (z_j - z_i) / ((vn_j - vn_i) + 0.000001) (:26-28): IEEE double operations, one at a time.
+ * The pair belongs to population p = 0, 1, 2 iff min(level_i, level_j) >= p.  Per frame and population, row = f * 3 + p:
+ *   hist[row][k], k < MVOSR_DC_BINS: pairs with 50 * (k - 40) <= q < 50 * (k - 39), the last bin also q == 950 — the counts of
+ *   np.histogram(q, np.array(range(-40, 20)) * 50) (:30-31), decided by comparison with the edges; -0.0 is in the bin of 0.
+ *   below[row]: pairs with q < -2000 (-inf too); above[row]: q > 950 (+inf too); nan[row]: q is NaN.
+ *   n[row]: the selected points of the population; hist + below + above + nan == n * n.
+ *   max[row]: np.max of the population's pairs (:32) — NaN if one of them is NaN, else the largest (+inf included; a zero maximum
+ *   is +0.0, the diagonal's value); NaN for an empty population.
+ * status[f]: 0; MVOSR_ST_DC_NO_POINT — no point of population 0 is selected (np.max raises there): zero counts, NaN maxima —;
+ * MVOSR_ST_ERR_MASK — a level above 2, a negative offset or length, or more entries than params->max_feat: zero counts, n = 0,
+ * NaN maxima, nothing added to the tables.
+ * tables (optional): int64 [3][MVOSR_DC_TABLE_WORDS] in device memory, owned and zeroed by the caller, kept across launches: the
+ * 59 bins, then below, above, nan, of every frame with status 0 are ADDED to it.
+ * A frame spans as many workgroups as its n^2 pairs ask for (mvosr_depthcheck_plan.hpp): params->max_feat sizes the grid, there
+ * is no cap on a frame's features from LDS.  Counts are combined by integer atomics, the maximum as an integer key over the
+ * non-NaN values: no floating-point atomics, the same bytes every run.  The per-frame outputs are zeroed by the call itself, on
+ * the context's stream.  n_frames <= 0: MVOSR_OK, nothing launched.  MVOSR_ERR_ARG: a null argument other than cnt / tables, or
+ * max_feat < 0; MVOSR_ERR_TOO_LARGE: more than 2^31-1 frames, or a frame that would need more than 65535 workgroups.
+ */
+#define MVOSR_DC_BINS 59
+#define MVOSR_DC_TABLE_WORDS 62  /* MVOSR_DC_BINS, then below, above, nan */
+#define MVOSR_ST_DC_NO_POINT 12  /* no point of population 0 with y > 0 */
+typedef struct mvosr_depth_check_params {
+    int32_t max_feat;            /* the largest feat_cnt of the launch: sizes the grid */
+    int32_t reserved;            /* 0 */
+} mvosr_depth_check_params;
+typedef struct mvosr_depth_check_outputs {
+    int64_t *hist;               /* [F][3][MVOSR_DC_BINS] */
+    int64_t *below, *above, *nan;/* [F][3] */
+    double *max;                 /* [F][3] */
+    int64_t *n;                  /* [F][3] */
+    int32_t *status;             /* [F] */
+} mvosr_depth_check_outputs;
+int mvosr_depth_check_batch(mvosr_ctx *ctx, int64_t n_frames, const int64_t *off, const int32_t *cnt, const double *y,
+                            const double *z, const uint8_t *level, const mvosr_depth_check_params *params,
+                            const mvosr_depth_check_outputs *outputs, int64_t *tables);
+
+/*
  * Scoring the repeated runs (/root/reference/test_off_line.sh:11-23): the paths of C cases, their KITTI segment errors against a
  * ground-truth path (script/evaluate_vo.py:5-96) and pose2motion with its two users (script/transformation.py:23-32,
  * change_scale.py:12-18, calculate_speed.py:8-11).  Every array is a device array of doubles unless stated; a pose or a motion

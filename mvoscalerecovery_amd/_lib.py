@@ -26,7 +26,9 @@ TILE_W = 512                              # MVOSR_TILE_W
 HIST_BINS = 169
 FD_POPULATIONS = 3           # MVOSR_FD_POPULATIONS
 FD_HIST_WORDS = 172          # MVOSR_FD_HIST_WORDS: the 169 bins, then the counts on edges 29, 49, 99
-SCORE_LENGTHS, SCORE_STEP = 8, 10    # MVOSR_SCORE_LENGTHS, MVOSR_SCORE_STEP
+DC_BINS, DC_TABLE_WORDS = 59, 62         # MVOSR_DC_BINS, MVOSR_DC_TABLE_WORDS: the bins, then below, above, nan
+ST_DC_NO_POINT = 12                      # MVOSR_ST_DC_NO_POINT
+SCORE_LENGTHS, SCORE_STEP = 8, 10   # MVOSR_SCORE_LENGTHS, MVOSR_SCORE_STEP
 ST_ERR_SINGULAR, ST_ERR_MASK = 7, 8  # MVOSR_ST_ERR_SINGULAR, MVOSR_ST_ERR_MASK
 
 
@@ -120,6 +122,17 @@ class Camera(C.Structure):
 class DepthOutputs(C.Structure):
     """mvosr_depth_outputs"""
     _fields_ = [("depth", C.c_void_p), ("tri_id", C.c_void_p), ("tri_model", C.c_void_p), ("covered", C.c_void_p), ("status", C.c_void_p)]
+
+
+class DepthCheckParams(C.Structure):
+    """mvosr_depth_check_params"""
+    _fields_ = [("max_feat", C.c_int32), ("reserved", C.c_int32)]
+
+
+class DepthCheckOutputs(C.Structure):
+    """mvosr_depth_check_outputs"""
+    _fields_ = [("hist", C.c_void_p), ("below", C.c_void_p), ("above", C.c_void_p), ("nan", C.c_void_p), ("max", C.c_void_p),
+                ("n", C.c_void_p), ("status", C.c_void_p)]
 
 
 class HeightPitchParams(C.Structure):
@@ -234,6 +247,7 @@ SYMBOLS = {
     "mvosr_static_tri_batch": (C.c_int, [_P, C.c_int64, _P, _P, _P, _P, C.c_int32, C.c_double, _P, _P, _P, _P, _P]),
     "mvosr_feature_distribution_batch": (C.c_int, [_P, C.c_int64, _P, _P, _P, _P, _P, C.c_int32, _P, _P, _P, _P, _P, _P]),
     "mvosr_featdist_max_features": (C.c_int, []),
+    "mvosr_depth_check_batch": (C.c_int, [_P, C.c_int64, _P, _P, _P, _P, _P, C.POINTER(DepthCheckParams), C.POINTER(DepthCheckOutputs), _P]),
     "mvosr_score_firsts": (C.c_int64, [C.c_int64]),
     "mvosr_paths_batch": (C.c_int, [_P, C.c_int64, C.c_int64, _P, C.c_int64, _P, _P]),
     "mvosr_segment_table": (C.c_int, [_P, C.c_int64, _P, _P, _P, _P, _P]),

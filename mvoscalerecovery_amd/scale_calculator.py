@@ -28,6 +28,7 @@ import numpy as np
 
 from . import _lib
 from . import constants as K
+from . import data_check
 from . import distribution
 from . import packing
 from . import stream
@@ -763,6 +764,54 @@ class ScaleEstimator(stream.StreamKnobs):
         self._dist_kept = kept_stats
         hl = np.where([p is not None for p in picks], level, np.nan) if F else np.zeros(0)
         return n, words, words_s, stats, hl, outcome, errors
+
+    # ---- the reference's pairwise depth-order check (script/data_check.py:19-34) over the same three populations --------------------
+    # The staged pass of the distribution analysis gives one level per packed feature; mvosr_depth_check_batch turns the packed y and
+    # z planes into the pair histograms of the three populations.  The sequence tables stay on the device.
+    def _depth_check_seq(self):
+        if getattr(self, "_dc_seq", None) is None:
+            self._dc_seq = data_check.new_tables(ctx=self.engine.ctx)
+        return self._dc_seq
+
+    def reset_depth_check(self):
+        """Zero the depth check's sequence tables on the device."""
+        self._depth_check_seq().fill(0)
+
+    def depth_check_tables(self):
+        """The sequence tables: int64 ``[3, 62]`` — per population the 59 bins, then below, above, nan — of every frame
+        ``depth_check_batch`` accumulated since the last ``reset_depth_check``."""
+        self.engine.ctx.sync()
+        return self._depth_check_seq().download()
+
+    def depth_check_batch(self, feature3ds, feature2ds, accumulate=True):
+        """``data_check.depth_check`` of every frame's three populations — every feature below the vanishing row, the ones the
+        reliability vote keeps, the ones ``feature_selection_by_tri`` selects — on un-remapped input: one staged pass and ONE launch
+        of mvosr_depth_check_batch per chunk of ``PIPELINE_CHUNK`` frames.  Returns a ``data_check.DepthCheckBatch``.  A frame that
+        returns early or raises in the staged pass keeps the populations it reached (as in ``check_full_distribution_batch``); its
+        exception is in ``errors``, not raised.  ``accumulate``: the frames are added to the sequence tables."""
+        F = len(feature3ds)
+        if len(feature2ds) != F:
+            raise ValueError("feature3ds and feature2ds must have one entry per frame")
+        f2s = [np.asarray(a) for a in feature2ds]
+        tables = self._depth_check_seq() if accumulate else None
+        parts, errors = [], {}
+        for a in range(0, F, self.PIPELINE_CHUNK):
+            b = min(F, a + self.PIPELINE_CHUNK)
+            pf, _, levels, _, errs, _, _ = self._distribution_levels(feature3ds[a:b], f2s[a:b])
+            parts.append(data_check.launch_packed(self.engine.ctx, pf.feat_off, np.asarray(pf.feat_cnt), pf.y, pf.z, levels,
+                                                  int(pf.max_feat), tables))
+            errors.update({a + f: e for f, e in errs.items()})
+        res = data_check.concatenate(parts, errors)
+        self.last_depth_check = res
+        return res
+
+    def depth_check(self, feature3d, feature2d):
+        """One frame through ``depth_check_batch`` (the tables are added to); raises what the staged pass raised at the frame, after
+        the launch — the result stays in ``last_depth_check``."""
+        res = self.depth_check_batch([feature3d], [feature2d])
+        if 0 in res.errors:
+            raise res.errors[0]
+        return res
 
     # ---- batched surface ---------------------------------------------------------------------
     def scale_calculation_batch(self, feature3ds, feature2ds, tri1s=None, tri2s=None, _single=False, _raw_only=False):
