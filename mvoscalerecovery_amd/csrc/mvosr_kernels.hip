@@ -102,7 +102,9 @@ enum { M_WCNT = 0 /* [0..15] per-wave survivor counts */, M_LIST = 16, M_MEDLO =
 // ---------------------------------------------------------------------------------------------
 // Triangle ids are streamed in chunks of kTC triangles per thread: all loads of a chunk are in
 // flight together, and the first chunk of each sweep is issued a phase early (tri1 with the
-// feature loads, tri2 before the compaction barriers) so that its latency is off the sweep.
+// feature loads, tri2 before the compaction barriers) so that its latency is off the sweep, and is waited
+// for in front of the sweep's loop (TriChunk::arrive), so that inside a loop the only wait for rows is the
+// one at the end of a trip, for the chunk the next trip needs.  profiles/waitcnt_report.py shows the waits.
 // ---------------------------------------------------------------------------------------------
 constexpr int kTC = 2;   // triangles per thread per chunk (3 VGPRs each)
 
@@ -138,6 +140,31 @@ struct TriChunk {
                 }
             }
         }
+    }
+    // The LDS-resident kernels' pipeline: every lane loads, a lane past the end re-reading the frame's last row (count
+    // >= 1; the lane's rows are then not used).  A load under a per-lane branch that is consumed under another branch
+    // has a path on which it is never consumed, and the compiler's wait bookkeeping then answers the next wait on
+    // anything issued around it with vmcnt(0): with no branch around the loads, the waits below are counted ones.
+    template <bool STREAM = false>
+    __device__ __forceinline__ void load_clamped(const int32_t *tri, int64_t begin, int count, int base, int tid) {
+#pragma unroll
+        for (int k = 0; k < kTC; ++k) {
+            const int t = min(base + k * B + tid, count - 1);
+            if constexpr (STREAM) {
+                const int32_t *p = tri + 3 * begin + 3 * t;
+                q[k].a = __builtin_nontemporal_load(p); q[k].b = __builtin_nontemporal_load(p + 1); q[k].c = __builtin_nontemporal_load(p + 2);
+            } else {
+                q[k] = load_tri(tri + 3 * begin, t);
+            }
+        }
+    }
+    // The chunk's consumption point: the wait for its loads is placed here, in front of a loop, and not at the first
+    // use inside it (where it would also cover whatever the loop has issued for its next trip).  One id per row is
+    // enough — a row is one load — and as an input only: tied outputs made the allocator copy the ids out of the
+    // load's register triple right behind the load, which is a wait at the wrong end.
+    __device__ __forceinline__ void arrive() const {
+#pragma unroll
+        for (int k = 0; k < kTC; ++k) asm volatile("" :: "v"(q[k].a));
     }
 };
 
@@ -175,7 +202,7 @@ __device__ __forceinline__ int phase_vote(const Smem &s, int n, const double *gx
     const int tid = threadIdx.x;
     const int npad2 = (n + 1) >> 1;
     TriChunk<B> tc;
-    tc.template load<true>(tri1, t1_begin, t1_count, 0, tid);          // in flight while the features stream in
+    if (t1_count > 0) tc.template load_clamped<true>(tri1, t1_begin, t1_count, 0, tid);   // in flight while the features stream in
     // planes are 16-byte aligned per frame: two features per lane and load, two loads per plane in flight
     const double2 *gy2 = reinterpret_cast<const double2 *>(gy);
     const double2 *gz2 = reinterpret_cast<const double2 *>(gz);
@@ -185,41 +212,55 @@ __device__ __forceinline__ int phase_vote(const Smem &s, int n, const double *gx
     for (int i0 = tid; i0 < npad2; i0 += 2 * B) {
         const int i1 = i0 + B;
         const bool two = i1 < npad2;
+        // all six loads are issued together: a lane without a second half reads its first pair again (not used)
+        const int i1c = two ? i1 : i0;
         const double2 ya = stream_load2(gy2 + i0), za = stream_load2(gz2 + i0), va = stream_load2(gv2 + i0);
-        double2 yb = ya, zb = za, vb = va;
-        if (two) { yb = stream_load2(gy2 + i1); zb = stream_load2(gz2 + i1); vb = stream_load2(gv2 + i1); }
+        const double2 yb = stream_load2(gy2 + i1c), zb = stream_load2(gz2 + i1c), vb = stream_load2(gv2 + i1c);
+        asm volatile("" ::: "memory");        // (keeps the second half's loads here: their only users are under `two`, where they would be sunk to)
         double2 yr, p0, p1;
         yr.x = ya.x * cp - za.x * sp;  yr.y = ya.y * cp - za.y * sp;      // :391
         p0.x = va.x; p0.y = ya.x * sp + za.x * cp;                        // :392
         p1.x = va.y; p1.y = ya.y * sp + za.y * cp;
         sY2[i0] = yr; s.P[2 * i0] = p0; s.P[2 * i0 + 1] = p1; s.c32[i0] = ones;
-        if (two) {
-            yr.x = yb.x * cp - zb.x * sp;  yr.y = yb.y * cp - zb.y * sp;
-            p0.x = vb.x; p0.y = yb.x * sp + zb.x * cp;
-            p1.x = vb.y; p1.y = yb.y * sp + zb.y * cp;
-            sY2[i1] = yr; s.P[2 * i1] = p0; s.P[2 * i1 + 1] = p1; s.c32[i1] = ones;
-        }
+        // (the second half is consumed on every path: left pending by the lanes without one, its registers would make the
+        // next trip — and through the loop header's merge the first one, in front of the first tri1 chunk — wait)
+        asm volatile("" :: "v"(yb.x), "v"(zb.x), "v"(vb.x));      // (all three: the compiler orders the loads as it likes)
+        yr.x = yb.x * cp - zb.x * sp;  yr.y = yb.y * cp - zb.y * sp;
+        p0.x = vb.x; p0.y = yb.x * sp + zb.x * cp;
+        p1.x = vb.y; p1.y = yb.y * sp + zb.y * cp;
+        if (two) { sY2[i1] = yr; s.P[2 * i1] = p0; s.P[2 * i1 + 1] = p1; s.c32[i1] = ones; }
     }
+    // the first tri1 chunk was issued before the features, so for a lane that staged any it has arrived: its wait is
+    // taken here, where nothing else is in flight, and the vote loop below starts with no load of its own pending
+    // (not under `t1_count > 0`: behind a branch the compiler would not count on it inside the loop)
+    tc.arrive();
     __syncthreads();
     MVOSR_STAMP(1);
 
-    // x is needed only after the vote: fetch it now in the compaction's slice layout, park it in registers
+    // x is needed only after the vote: fetch it now in the compaction's slice layout, park it in registers.  Every lane
+    // loads (one past the frame's end reads the last feature's x, which the compaction never stores): the SC loads go
+    // out back to back and stay in flight over the vote — their first wait is the next chunk's at the end of the
+    // first trip, which was issued after them, or the compaction's
     const int w = wave_id(), lane = lane_id();
     const int begin = w * (SC * kWave);
     double xs[SC];
 #pragma unroll
-    for (int k = 0; k < SC; ++k) {
-        const int i = begin + k * kWave + lane;
-        xs[k] = (gx && i < n) ? stream_load(gx + i) : 0.0;
+    for (int k = 0; k < SC; ++k) xs[k] = 0.0;
+    if (gx && n > 0) {
+#pragma unroll
+        for (int k = 0; k < SC; ++k) xs[k] = stream_load(gx + min(begin + k * kWave + lane, n - 1));
     }
 
     // the vote: +1 on a vertex the triangle does not flag, -1 on one it flags (:160-163)
     TriChunk<B> tn;                                   // the next chunk streams in while this one is processed
     for (int base = 0; base < t1_count; base += kTC * B) {
         const bool more = base + kTC * B < t1_count;
-        if (more) tn.template load<true>(tri1, t1_begin, t1_count, base + kTC * B, tid);
+        if (more) tn.template load_clamped<true>(tri1, t1_begin, t1_count, base + kTC * B, tid);
         // all vertex reads of the chunk first: the reads of one triangle cannot be moved across the
-        // LDS atomics of another by the compiler, and issued together their latencies overlap
+        // LDS atomics of another by the compiler, and issued together their latencies overlap.  (In the compiled loop
+        // each read still waits for the previous trip's atomics to drain to two: a read under `vok` that is consumed
+        // under a second branch has a path on which it stays pending.  Reading and testing for every lane, vertex 0
+        // for a lane without a row, removes those waits and was 1.2 % slower: LABNOTES 3.1.)
         double2 vp[kTC][3];
         bool vok[kTC];
 #pragma unroll
@@ -248,7 +289,7 @@ __device__ __forceinline__ int phase_vote(const Smem &s, int n, const double *gx
         }
         if (more) tc = tn;
     }
-    if (tri2) next.load(tri2, t2_begin, t2_count, 0, tid);   // lands while the survivors are compacted
+    if (tri2 && t2_count > 0) next.load_clamped(tri2, t2_begin, t2_count, 0, tid);   // lands while the survivors are compacted
     __syncthreads();
     MVOSR_STAMP(2);
 
@@ -659,12 +700,14 @@ __device__ __forceinline__ SelectResult phase_select(const Smem &s, int n_valid,
         ++npitch;
     }
     };
-    // `tc` arrives with the first chunk of tri2 already loaded (phase_vote); the next chunk streams
-    // in while the current one is processed.
+    // `tc` comes with the first chunk of tri2 in flight (phase_vote issued it before the compaction); its wait is
+    // taken in front of the loop.  The next chunk streams in while the current one is processed: inside the
+    // loop the only wait for rows is the one at the end of a trip.
     TriChunk<B> tn;
+    tc.arrive();
     for (int base = 0; base < t2_count; base += kTC * B) {
         const bool more = base + kTC * B < t2_count;
-        if (more) tn.load(tri2, t2_begin, t2_count, base + kTC * B, tid);
+        if (more) tn.load_clamped(tri2, t2_begin, t2_count, base + kTC * B, tid);
 #pragma unroll
         for (int k = 0; k < kTC; ++k) {
             const int t = base + k * B + tid;
@@ -675,7 +718,7 @@ __device__ __forceinline__ SelectResult phase_select(const Smem &s, int n_valid,
     // second sweep: its first chunk is re-read now, under the reduction's barrier (unless the whole
     // triangulation was one chunk and is still in registers)
     const bool in_regs = t2_count <= kTC * B;
-    if (!in_regs && t2_count > 0) tc.template load<true>(tri2, t2_begin, t2_count, 0, tid);
+    if (!in_regs && t2_count > 0) tc.template load_clamped<true>(tri2, t2_begin, t2_count, 0, tid);
     if constexpr (MODE == MODE_HOT) block_sum3<WAVES>(hsum, hcnt, habs, s.red + R_SEL_H * 2 * WAVES, s.red + R_SEL_ABS * 2 * WAVES);
     else block_sum2<WAVES>(hsum, hcnt, s.red + R_SEL_H * 2 * WAVES);
     MVOSR_STAMP(4);
@@ -704,9 +747,12 @@ __device__ __forceinline__ SelectResult phase_select(const Smem &s, int n_valid,
             atomicOr(&s.sel[qc >> 5], 1u << (qc & 31));
         }
     };
+    // the re-read first chunk has had the reduction's barriers to land: it is waited for here, before the loop's own
+    // prefetch is issued, so that no trip waits for the rows it has just asked for
+    tc.arrive();
     for (int base = 0; base < t2_count; base += kTC * B) {
         const bool more = base + kTC * B < t2_count;
-        if (more) tn.template load<true>(tri2, t2_begin, t2_count, base + kTC * B, tid);
+        if (more) tn.template load_clamped<true>(tri2, t2_begin, t2_count, base + kTC * B, tid);
 #pragma unroll
         for (int k = 0; k < kTC; ++k) {
             if (base + k * B + tid < t2_count) mark_triangle(base / B + k, tc.q[k].a, tc.q[k].b, tc.q[k].c);
@@ -1408,6 +1454,10 @@ __global__ __launch_bounds__(WAVES *kWave, (WAVES == 8 && MODE == MODE_HOT ? 6 :
     const int64_t off = a.b.feat_off[f];
     const int64_t t1b = a.b.tri1_off[f], t2b = a.b.tri2_off[f];
     const int t1n = tri_rows(a.b.tri1_off, a.b.tri1_cnt, f), t2n = tri_rows(a.b.tri2_off, a.b.tri2_cnt, f);
+    // (asked for here, with the frame's other scalars and ahead of every store, so that it is a scalar load: read where
+    // it is compared, behind the compaction's barriers, it was a vector load and a full wait in front of the selection)
+    const bool has_n2 = a.b.n2_expected != nullptr;
+    const int n2_expected = has_n2 ? a.b.n2_expected[f] : 0;
     const Smem s = carve(smem, n, WAVES);
 #ifdef MVOSR_STAMPS
     if (n < 0) return;                             // (never: makes the stamp below wait for the frame's counts)
@@ -1429,7 +1479,7 @@ __global__ __launch_bounds__(WAVES *kWave, (WAVES == 8 && MODE == MODE_HOT ? 6 :
                                              a.P.cos_pitch, a.P.sin_pitch,
                                              a.o.vote_counters ? a.o.vote_counters + off : nullptr, bad,
                                              a.b.tri2, t2b, t2n, tc2, a.P.vote_mode == MVOSR_VOTE_FIXED MVOSR_STAMP_PASS);
-    const bool mask_mismatch = a.b.n2_expected && a.b.n2_expected[f] != nvalid;
+    const bool mask_mismatch = has_n2 && n2_expected != nvalid;
 
     SelectResult S;
     S.height_level = nan(""); S.n_pitch = S.n_tri_valid = 0; S.singular = 0; S.bad = 1; S.n_steep = 0; S.near = 0;
