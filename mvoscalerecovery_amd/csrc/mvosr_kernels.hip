@@ -785,6 +785,7 @@ struct RoadResult {
     int status;
     int n_sel, n_kept, n_modes, mode_left, mode_right;
     double mean, std, skew, median;
+    double raw;                  // lean variant, MODE / RIGHT: absolute_reference / height, out of the round that gave the skewness
 };
 
 // is y (histogram bin `bin`) inside the interval remove_single deletes for a single-count bin?
@@ -804,6 +805,35 @@ __device__ __forceinline__ bool dropped_by_single(double y, int bin, unsigned lo
         const double lo = r - 0.1;
         const bool in = (k == first_single) ? (y >= lo && y <= r) : (y > lo && y <= r);
         d |= is_single && in;
+    }
+    return d;
+}
+
+// The interior test in front of dropped_by_single.  With e(k) = (double)k * 0.1 (bin_edge) and
+//     delta = max over k = 0..169 of |fl(e(k+1) - 0.1) - e(k)| = 2^-48 = 3.5527e-15     (exact, at k = 161;
+//                                                                                         tests/test_road_single_interior.py)
+// a value y of bin b with  e(b) + c < y < e(b+1) - c,  c > delta,  is dropped iff bin b ITSELF is single:
+//   k = b:    lo = fl(e(b+1) - 0.1) <= e(b) + delta < y  and  y < e(b+1) = r: inside, closed or half-open alike;
+//   k = b-1:  r = e(b) < y: outside;
+//   k = b+1:  lo = fl(e(b+2) - 0.1) >= e(b+1) - delta > y: outside, closed or half-open alike.
+// c = 2^-40 = 9.1e-13 = 256 * delta: the roundings of y - e(b) and e(b+1) - y in the test below (exact by Sterbenz for
+// b >= 1, at most half an ulp of 0.1 = 7e-18 in bin 0) vanish in the slack, and a bin keeps 1 - 2e-11 of its width.
+constexpr double kSingleMargin = 0x1p-40;
+// flags of a bin (the nearflag table): it is single itself / one of its neighbours is
+constexpr int kOwnSingle = 1, kNextSingle = 2;
+// y lies strictly inside bin `bin` (edges e = {e(bin), e(bin+1)}), at least kSingleMargin from both of its edges
+__device__ __forceinline__ bool single_interior(double y, const double2 e) {
+    return (y - e.x > kSingleMargin) & (e.y - y > kSingleMargin);
+}
+// does remove_single drop y of bin `bin` (0..168), whose flags `flag` are not 0?  The three-interval test runs only for a
+// value within kSingleMargin of an edge of its bin: a skipped region, as in div3 (if-converted it costs every suspect
+// the three intervals again).
+__device__ __forceinline__ bool dropped_suspect(double y, int bin, int flag, const double2 *edges, unsigned long long s0, unsigned long long s1,
+                                                unsigned long long s2, int first_single) {
+    bool d = (flag & kOwnSingle) != 0;
+    if (!single_interior(y, edges[bin])) {
+        asm volatile("" : "+v"(y));
+        d = dropped_by_single(y, bin, s0, s1, s2, first_single);
     }
     return d;
 }
@@ -867,10 +897,11 @@ __device__ __forceinline__ int bin_of_table(double y, const double2 *edges) {
 // ONE pass over the values: it bins a value, adds it to the histogram and to the lane's shifted sums
 // S1 = sum(y - sh), S2 = sum((y - sh)^2) (sh: the list's first value, a frame-uniform shift close to the data).  Which
 // values remove_single drops is known only once the histogram is complete: those few are re-read (their bin or a
-// neighbour has count 1 — the "suspects") and their terms subtracted from the lane's sums.  No value is kept in registers,
+// neighbour has count 1 — the "suspects") and their terms subtracted from the lane's sums; a suspect inside its bin by
+// kSingleMargin is dropped iff its own bin is single, only one on an edge takes the interval test.  No value is kept in registers,
 // only the bins of the first RC rows (a byte each), for the suspect test.
 // hist: kRoadSub lane-interleaved copies, bin b of copy c at int 4*b + c; comb: the summed counts (176 ints);
-// nearflag: 176 bytes, 1 for a bin that is single or next to a single one.
+// nearflag: 176 bytes, kOwnSingle for a bin that is single, kNextSingle for one next to a single one.
 //
 // HOT: the lean product instantiation (as MODE_HOT is for the scale kernel) — the one-pass loop over at most RC rows, the
 // histogram logic, the suspects, the band test and the decision.  It has no packed list (NumPy-order sums, median), no
@@ -886,7 +917,7 @@ __device__ __forceinline__ RoadResult road_wave(int *hist, int *comb, uint8_t *n
     const int lane = lane_id();
     RoadResult R;
     R.height = nan(""); R.status = MVOSR_ST_MODE; R.n_sel = Mall; R.n_kept = 0; R.n_modes = 0; R.mode_left = -1; R.mode_right = -1;
-    R.mean = R.std = R.skew = R.median = nan("");
+    R.mean = R.std = R.skew = R.median = R.raw = nan("");
     if (Mall == 0) { R.status = MVOSR_ST_NO_FLAT; return R; }
     const double *yv = yv_all + (part_hi > part_lo ? part_lo : 0);     // my part of the list (WW == 1: all of it; an empty part: any legal address)
     const int M = part_hi - part_lo;                    // (may be 0 for the last wavefronts of a short list)
@@ -913,6 +944,27 @@ __device__ __forceinline__ RoadResult road_wave(int *hist, int *comb, uint8_t *n
 #pragma unroll
     for (int k0 = 0; k0 < RC; k0 += kG) {
         double yg[kG];
+        if ((k0 + kG) * kWave <= M) {
+            // a group of whole rows (wave-uniform: a scalar branch) — all but the list's last one: no index clamp, no
+            // `valid` bit, no selects for a value that is not there.  The same terms into s1, s2 in the same order.
+#pragma unroll
+            for (int j = 0; j < kG; ++j) yg[j] = yv[(k0 + j) * kWave + lane];
+#pragma unroll
+            for (int j = 0; j < kG; ++j) {
+                const int k = k0 + j;
+                const double y = yg[j];
+                const bool inr = (y >= 0.0) && (y <= bin_edge(kBins));
+                const int g = inr ? min((int)(y * 10.0), kBins - 1) : 0;
+                const double2 e = edges[g];
+                int bin = g + ((g < kBins - 1 && y >= e.y) ? 1 : 0) - ((y < e.x) ? 1 : 0);
+                bin = inr ? bin : kTrash;
+                atomicAdd(&hsub[4 * bin], 1);
+                const double d = y - sh;
+                s1 += d;
+                s2 = __builtin_fma(d, d, s2);
+                pk[k >> 2] = (k & 3) ? (pk[k >> 2] | ((unsigned)bin << (8 * (k & 3)))) : (unsigned)bin;
+            }
+        } else {
 #pragma unroll
         for (int j = 0; j < kG && k0 + j < RC; ++j) yg[j] = yv[max(min((k0 + j) * kWave + lane, M - 1), 0)];   // clamped: always a legal address
 #pragma unroll
@@ -931,10 +983,11 @@ __device__ __forceinline__ RoadResult road_wave(int *hist, int *comb, uint8_t *n
             s2 = __builtin_fma(d, d, s2);
             pk[k >> 2] = (k & 3) ? (pk[k >> 2] | ((unsigned)bin << (8 * (k & 3)))) : (unsigned)bin;
         }
+        }
         // (the sums and the packed bins are DONE here: left alone, the compiler sinks the additions behind the suspects'
         // loop — their first use — and keeps all RC values of the lane alive for it, in registers and in scratch memory)
         asm volatile("" : "+v"(s1), "+v"(s2));
-        static_assert(kG == 4, "one word of pk per group");
+        static_assert(kG == 4 && RC % kG == 0, "one word of pk per group; whole groups");
         asm volatile("" : "+v"(pk[k0 >> 2]));
         __builtin_amdgcn_sched_barrier(0);              // (the next group's loads stay behind this one: kG values in flight, not RC)
     }
@@ -985,12 +1038,17 @@ __device__ __forceinline__ RoadResult road_wave(int *hist, int *comb, uint8_t *n
     const int first_single = single.lowest_from(0);
     const unsigned long long sg0 = single.w[0], sg1 = single.w[1], sg2 = single.w[2];
     // a value can only be dropped if its own bin or a neighbouring one has count 1
-    Bits192 near;
-    near.w[0] = single.w[0] | (single.w[0] << 1) | (single.w[0] >> 1) | (single.w[1] << 63);
-    near.w[1] = single.w[1] | (single.w[1] << 1) | (single.w[1] >> 1) | (single.w[0] >> 63) | (single.w[2] << 63);
-    near.w[2] = single.w[2] | (single.w[2] << 1) | (single.w[2] >> 1) | (single.w[1] >> 63);
+    // (and, unless it lies within kSingleMargin of an edge of its bin, only if its own bin has: the table keeps the two apart)
+    Bits192 next;
+    next.w[0] = (single.w[0] << 1) | (single.w[0] >> 1) | (single.w[1] << 63);
+    next.w[1] = (single.w[1] << 1) | (single.w[1] >> 1) | (single.w[0] >> 63) | (single.w[2] << 63);
+    next.w[2] = (single.w[2] << 1) | (single.w[2] >> 1) | (single.w[1] >> 63);
 #pragma unroll
-    for (int c = 0; c < 3; ++c) { const int b = lane + 64 * c; if (b < 176) nearflag[b] = (b < kBins) ? (uint8_t)((near.w[c] >> lane) & 1ull) : 0; }
+    for (int c = 0; c < 3; ++c) {
+        const int b = lane + 64 * c;
+        const int fl = (int)((single.w[c] >> lane) & 1ull) * kOwnSingle + (int)((next.w[c] >> lane) & 1ull) * kNextSingle;
+        if (b < 176) nearflag[b] = (b < kBins) ? (uint8_t)fl : 0;
+    }
     // check_mode returns no modes iff max <= 2 (:451-452); otherwise the maximum bin itself is one
     const bool have_modes = mx > P.mode_min;
 
@@ -1006,7 +1064,15 @@ __device__ __forceinline__ RoadResult road_wave(int *hist, int *comb, uint8_t *n
             const int k = __ffs(sus) - 1;
             sus &= sus - 1u;
             const double y = yv[k * kWave + lane];
-            if (dropped_by_single(y, bin_of_table(y, edges), sg0, sg1, sg2, first_single)) {
+            // (a suspect lies in [0, 16.9]; strictly inside the guessed bin's edges, that bin IS its bin)
+            const int g = min((int)(y * 10.0), kBins - 1);
+            bool drop = (nearflag[g] & kOwnSingle) != 0;
+            if (!single_interior(y, edges[g])) {
+                double ye = y;
+                asm volatile("" : "+v"(ye));             // (a skipped region, as in dropped_suspect)
+                drop = dropped_by_single(ye, bin_of_table(ye, edges), sg0, sg1, sg2, first_single);
+            }
+            if (drop) {
                 const double d = y - sh;
                 t1 += d;
                 t2 = __builtin_fma(d, d, t2);
@@ -1024,7 +1090,8 @@ __device__ __forceinline__ RoadResult road_wave(int *hist, int *comb, uint8_t *n
             if (i0 + j * kWave >= M) continue;
             const double y = yl[j];
             const int bin = bin_of_table(y, edges);
-            if (bin >= 0 && nearflag[bin] && dropped_by_single(y, bin, sg0, sg1, sg2, first_single)) {
+            const int fl = bin >= 0 ? nearflag[bin] : 0;
+            if (fl && dropped_suspect(y, bin, fl, edges, sg0, sg1, sg2, first_single)) {
                 const double d = y - sh;
                 t1 += d;
                 t2 = __builtin_fma(d, d, t2);
@@ -1060,7 +1127,8 @@ __device__ __forceinline__ RoadResult road_wave(int *hist, int *comb, uint8_t *n
             if (i < Mall) {
                 y = yv_all[i];
                 const int bin = bin_of_table(y, edges);
-                keep = !(bin >= 0 && nearflag[bin] && dropped_by_single(y, bin, sg0, sg1, sg2, first_single));
+                const int fl = bin >= 0 ? nearflag[bin] : 0;
+                keep = !(fl && dropped_suspect(y, bin, fl, edges, sg0, sg1, sg2, first_single));
             }
             const unsigned long long m = __ballot(keep);
             if (keep) scratch[nlist + __popcll(m & ((1ull << lane) - 1ull))] = y;
@@ -1133,12 +1201,30 @@ __device__ __forceinline__ RoadResult road_wave(int *hist, int *comb, uint8_t *n
     const int ir = mins.lowest_from(mr);                                        // :342,:344  bins mr..168
     if (ir < 0) { R.status = MVOSR_ST_ERR_RIGHT; return R; }
     const double right = bin_edge(ir + 1);
+    // From here on every operand is wave-uniform, and an fp64 division or square root is some thirty vector instructions
+    // whatever the lanes hold (the scalar unit has no fp64): the tail's quotients and roots are taken in three rounds,
+    // the operand pairs of a round in different lanes of ONE division / root, the results read back by lane.  Each is the
+    // IEEE operation on the two doubles the expression names — the same bits as evaluated one by one.
+    const double N = (double)Mall;
+    double q1;
+    {   // round 1: the quotients by the count, and mode / 10
+        const double num = lane == 0 ? S1 : lane == 1 ? S2 : lane == 2 ? Q : lane == 3 ? N : mode;
+        const double den = lane == 4 ? 10.0 : cntd;
+        q1 = num / den;
+    }
     // np.mean / np.std from the shifted sums
-    const double m1 = S1 / cntd;
+    const double m1 = readlane_d(q1, 0);                                        // S1 / cntd
     const double mean = sh + m1;
-    const double var = S2 / cntd - m1 * m1;
+    const double var = readlane_d(q1, 1) - m1 * m1;                             // S2 / cntd - m1 * m1
+    const double a2 = readlane_d(q1, 2);                                        // Q / cntd
+    const double mode10 = readlane_d(q1, 4);                                    // mode / 10.0
+    double q2;
+    {   // round 2: the roots
+        const double rad = lane == 0 ? var : lane == 1 ? a2 : lane == 2 ? readlane_d(q1, 3) : mean * mean + var;
+        q2 = sqrt(rad);
+    }
     double mean_o = mean;
-    double sd = sqrt(var);
+    double sd = readlane_d(q2, 0);                                              // sqrt(var)
     // The sums above run in the wavefront's order and in one pass, NumPy's in its pairwise order and in two: mean and std
     // differ in the last bits, which decides `skew > thr` differently only when both sides of
     //     (mean - mode/10) - thr*sd
@@ -1160,14 +1246,21 @@ __device__ __forceinline__ RoadResult road_wave(int *hist, int *comb, uint8_t *n
     // The band below is the earlier two-pass band plus this one: a list the old band sent to the exact path still goes.
     {
         const double thr = fabs(P.skew_threshold);
-        const double N = (double)Mall;
         const double g = 0x1p-52 * (2.0 * (double)((Mall + kWave - 1) / kWave) + 64.0 + N / (double)kNpBufSize);
-        const double a2 = Q / cntd, r = sqrt(a2), rho = sqrt(N / cntd), Mg = fabs(sh) + r;
-        const double rms = sqrt(mean * mean + var);
-        const double margin = fabs((mean - mode / 10.0) - P.skew_threshold * sd);
-        const double bound_two_pass = 1e-11 * (rms + sd) + 1e-22 * rms * rms / sd;
+        const double r = readlane_d(q2, 1), rho = readlane_d(q2, 2), Mg = fabs(sh) + r;     // sqrt(a2), sqrt(N / cntd)
+        const double rms = readlane_d(q2, 3);                                               // sqrt(mean * mean + var)
+        double q3;
+        {   // round 3: the quotients by the one-pass std — the band's two, and for the lean variant, which decides on this std
+            // or not at all, the skewness and the raw scale of either outcome
+            const double num = lane == 0 ? 1e-22 * rms * rms : lane == 1 ? (1.0 + thr) * (a2 * (6.0 + 2.0 * rho) + g * Mg * Mg)
+                             : lane == 2 ? mean - mode10 : P.absolute_reference;
+            const double den = lane <= 2 ? sd : lane == 3 ? right : mode10;
+            q3 = num / den;
+        }
+        const double margin = fabs((mean - mode10) - P.skew_threshold * sd);
+        const double bound_two_pass = 1e-11 * (rms + sd) + readlane_d(q3, 0);
         const double bound = bound_two_pass
-                           + g * ((Mg + rho * r) + fabs(mode / 10.0) + (1.0 + thr) * sd + (1.0 + thr) * (a2 * (6.0 + 2.0 * rho) + g * Mg * Mg) / sd);
+                           + g * ((Mg + rho * r) + fabs(mode10) + (1.0 + thr) * sd + readlane_d(q3, 1));
 #ifdef MVOSR_ROAD_EXACT_COUNT
         if (lane == 0) {
             atomicAdd(&g_road_exact_count[0], 1ull);
@@ -1177,6 +1270,11 @@ __device__ __forceinline__ RoadResult road_wave(int *hist, int *comb, uint8_t *n
 #endif
         if constexpr (HOT) {
             if (!(margin > bound)) { R.status = kStCold; return R; }                        // (NumPy's order: the full variant's)
+            const double skew = readlane_d(q3, 2);                                          // (mean - mode / 10.0) / sd, :496
+            R.mean = mean_o; R.std = sd; R.skew = skew;
+            if (skew > P.skew_threshold) { R.height = right; R.raw = readlane_d(q3, 3); R.status = MVOSR_ST_RIGHT; }   // :348-352
+            else { R.height = mode10; R.raw = readlane_d(q3, 4); R.status = MVOSR_ST_MODE; }                         // :354
+            return R;
         } else if (!(margin > bound) || exact_stats) {
             const int nl = pack_kept();
             __threadfence_block();               // the wave's own stores, visible to all its lanes
@@ -1184,16 +1282,16 @@ __device__ __forceinline__ RoadResult road_wave(int *hist, int *comb, uint8_t *n
             sd = sqrt(np_pairwise_sum_cold(scratch, nl, mean_o, 1, np_stack) / (double)nl);
         }
     }
-    const double skew = (mean_o - mode / 10.0) / sd;                            // :496
+    const double skew = (mean_o - mode10) / sd;                                 // :496
     R.mean = mean_o; R.std = sd; R.skew = skew;
     if (skew > P.skew_threshold) { R.height = right; R.status = MVOSR_ST_RIGHT; }   // :348-352
-    else { R.height = mode / 10.0; R.status = MVOSR_ST_MODE; }                      // :354
+    else { R.height = mode10; R.status = MVOSR_ST_MODE; }                           // :354
     return R;
 }
 
 constexpr int kRoadOcc = 6;              // wavefronts per SIMD the full product variants are compiled for (their VGPR budget)
-constexpr int kRoadOccHot = 7;           // the same for the lean (HOT) variant: 59 VGPRs, no spills, no scratch (at 8 the SGPR budget of 80
-                                         // leaves ten scalar spills in a VGPR's lanes)
+constexpr int kRoadOccHot = 7;           // the same for the lean (HOT) variant: 57 VGPRs, no spills, no scratch (at 8 the SGPR budget of 80
+                                         // leaves nine scalar spills in a VGPR's lanes)
 // LIST: the frames of a.list, grid-strided (the rare second pass over the frames that ended on the fallback level); otherwise
 // frame first_frame + wavefront index, no loop (a loop around the body costs the product variant 57 VGPRs, i.e. half its occupancy)
 // LDS per workgroup ~18 KB; the launch bound gives the full product variants kRoadOcc wavefronts per SIMD (6: at most
@@ -1283,6 +1381,7 @@ __global__ __launch_bounds__(kRoadWaves *kWave, (LIST ? 1 : HOT ? kRoadOccHot : 
     if (lane_id() == 0) {
         double height = nan(""), raw = nan("");
         if (R.status == MVOSR_ST_NO_FLAT) raw = a.P.absolute_reference / hl;                        // :421
+        else if (HOT && (R.status == MVOSR_ST_MODE || R.status == MVOSR_ST_RIGHT)) { height = R.height; raw = R.raw; }              // :419, the same division
         else if (R.status <= MVOSR_ST_LEVEL) { height = R.height; raw = a.P.absolute_reference / height; }   // :419
         a.o.raw_scale[f] = raw; a.o.height[f] = height; a.o.status[f] = R.status;
         if (!a.pending_only && a.o.height_level) a.o.height_level[f] = hl;
