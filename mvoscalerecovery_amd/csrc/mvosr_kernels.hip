@@ -293,7 +293,10 @@ __device__ __forceinline__ int phase_vote(const Smem &s, int n, const double *gx
     __syncthreads();
     MVOSR_STAMP(2);
 
-    // compaction, step 1: every wave reads its slice (flags, y', z') into registers and counts
+    // compaction, step 1: every wave reads its slice (flags, y', z') into registers and counts.  (Compiled, each
+    // sub-chunk's three reads are waited for before the next sub-chunk's are issued — a read under `i < n` is consumed
+    // under another branch.  All 3*SC reads back to back for every lane, index clamped and the flag masked afterwards,
+    // give one round trip in the listing and measured flat, alone and on top of the new tail: LABNOTES 3.1.)
     unsigned keepmask = 0u;                      // bit k: my feature of sub-chunk k survives
     double yk[SC], zk[SC];
     int cnt = 0;
@@ -1461,7 +1464,18 @@ __device__ __forceinline__ bool early_frame_exit(const KArgs &a, int64_t f, int 
 // when its result could depend on the last bits of height_level: a flat triangle within rounding of the level
 // (S.near), or so few selected points that the level itself may become the height — nothing selected
 // (:277-279,:421) or every point alone in its bin, at most one per bin (:334-335).
-template <int BW, int MODE>
+//
+// SC > 0 (the LDS-resident kernels: at most BW * SC * 64 survivors, so the bit-set is at most BW * SC * 2 words and a
+// wave's slice at most SC rows of 64): no count is exchanged between the waves.  Behind phase_select's last barrier the
+// bit-set is final, and every wave reads ALL of it (BW * SC / 32 words per lane, at least one), popcounts, and takes
+// both the frame's total and the count in front of its own slice from one in-wave DPP sum — slices start at multiples
+// of 64, i.e. on word boundaries.  The same batch of reads fetches, for each of the slice's rows, the word that holds
+// the lane's own bit, so that one LDS round trip serves the count and the rows' masks; the y' of all rows are then read
+// together and the stores follow.  Words at or past (nvalid + 31) / 32 are NOT part of the bit-set (the region held the
+// vote counters: stale values) and are masked by index; bits at or past nvalid inside the last word are zero, since
+// only survivors' ids are ever set.
+// SC == 0 (the dense kernel: y' in global memory, thousands of words): count per wave slice -> barrier -> ordered store.
+template <int BW, int MODE, int SC = 0>
 __device__ __forceinline__ void frame_tail(const KArgs &a, const Smem &s, int64_t f, int64_t off, int nvalid, bool refused,
                                            SelectResult &S, RoadResult &R) {
     constexpr int B = BW * kWave;
@@ -1473,6 +1487,58 @@ __device__ __forceinline__ void frame_tail(const KArgs &a, const Smem &s, int64_
         status = MVOSR_ST_ERR_MASK;
     } else if (S.singular) {
         status = MVOSR_ST_ERR_SINGULAR;
+    } else if constexpr (SC > 0) {
+        constexpr int WPL = (BW * SC * 2 + kWave - 1) / kWave;      // bit-set words per lane
+        const int w = wave_id(), lane = lane_id();
+        const int per = ((nvalid + B - 1) / B) * kWave;             // <= SC * 64
+        const int begin = w * per, end = min(nvalid, begin + per);
+        const int nwords = (nvalid + 31) >> 5, front = begin >> 5;  // the bit-set's words / those in front of my slice
+        const int last = max(nvalid - 1, 0);
+        // one batch of reads: the whole bit-set, and the word of my bit in each of my slice's rows (a lane past the
+        // end reads the last survivor's word and y', n >= 4, and is masked afterwards)
+        uint32_t wd[WPL], wr[SC];
+#pragma unroll
+        for (int r = 0; r < WPL; ++r) wd[r] = s.sel[min(lane + r * kWave, max(nwords - 1, 0))];
+#pragma unroll
+        for (int k = 0; k < SC; ++k) wr[k] = s.sel[min(begin + k * kWave + lane, last) >> 5];
+        asm volatile("" ::: "memory");
+        int packed = 0;                                             // low half: selected in all words; high half: in the words in front
+#pragma unroll
+        for (int r = 0; r < WPL; ++r) {
+            const int wi = lane + r * kWave;
+            const int pc = wi < nwords ? __popc(wd[r]) : 0;
+            packed += pc + (wi < front ? pc << 16 : 0);
+        }
+        packed = wave_sum(packed);                                  // (at most 8192 selected: the halves cannot meet)
+        nsel = packed & 0xFFFF;
+        int base = packed >> 16;
+        unsigned selmask = 0u;                                      // bit k: my point of row k is selected
+#pragma unroll
+        for (int k = 0; k < SC; ++k) {
+            const int j = begin + k * kWave + lane;
+            const bool sel = (j < end) & ((wr[k] >> (j & 31)) & 1u);
+            if (a.o.selected) { if (j < end) a.o.selected[off + j] = (uint8_t)sel; }             // :247
+            if (sel) selmask |= 1u << k;
+        }
+        if constexpr (MODE == MODE_HOT) {
+            if (S.near || nsel == 0) {
+                if (tid == 0) { a.redo[1 + atomicAdd(a.redo, 1)] = (int32_t)f; a.o.status[f] = kStRedo; a.nsel[f] = 0; }
+                return;
+            }
+        }
+        double ys[SC];
+#pragma unroll
+        for (int k = 0; k < SC; ++k) ys[k] = s.Y[min(begin + k * kWave + lane, last)];
+        asm volatile("" ::: "memory");
+        double *dst = a.ysel + off;
+#pragma unroll
+        for (int k = 0; k < SC; ++k) {
+            const bool sel = (selmask >> k) & 1u;
+            const unsigned long long m = __ballot(sel);
+            if (sel) dst[base + __popcll(m & ((1ull << lane) - 1ull))] = ys[k];
+            base += __popcll(m);
+        }
+        if (nsel == 0) { status = MVOSR_ST_NO_FLAT; raw = a.P.absolute_reference / S.height_level; }   // :277-279,:421
     } else {
         const int w = wave_id(), lane = lane_id();
         const int per = ((nvalid + B - 1) / B) * kWave;
@@ -1587,7 +1653,7 @@ __global__ __launch_bounds__(WAVES *kWave, (WAVES == 8 && MODE == MODE_HOT ? 6 :
     if (!mask_mismatch && !too_many_rows)
         S = phase_select<WAVES, MODE>(s, nvalid, a.b.tri2, t2b, t2n, tc2, a.pt, a.o.tri_normals, a.o.tri_pitch_deg,
                                       a.o.tri_heights, bad, a.ysel ? a.ysel + off : nullptr, n MVOSR_STAMP_PASS);
-    frame_tail<WAVES, MODE>(a, s, f, off, nvalid, mask_mismatch || too_many_rows, S, R);
+    frame_tail<WAVES, MODE, SC>(a, s, f, off, nvalid, mask_mismatch || too_many_rows, S, R);
     MVOSR_STAMP(9);
 #ifdef MVOSR_STAMPS
     if (threadIdx.x == 0 && a.o.hist) { unsigned long long *d = reinterpret_cast<unsigned long long *>(a.o.hist + f * 2 * kBins); for (int i = 0; i < 12; ++i) d[i] = stamps[i]; }
