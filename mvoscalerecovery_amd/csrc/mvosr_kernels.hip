@@ -29,6 +29,7 @@
 #include "mvosr_device.hpp"
 #include "mvosr_host.hpp"
 #include "mvosr_npsum.hpp"
+#include "mvosr_scale_plan.hpp"
 
 namespace mvosr {
 
@@ -50,54 +51,41 @@ namespace mvosr {
 #endif
 
 // ---------------------------------------------------------------------------------------------
-// LDS carve-up (byte offsets, all multiples of 16)
+// LDS pointers, taken from the plans of mvosr_scale_plan.hpp
 // ---------------------------------------------------------------------------------------------
-struct LdsPlan {
-    uint32_t p, y, c, hist, red, misc, total;
-};
-__host__ __device__ inline uint32_t align16(uint32_t v) { return (v + 15u) & ~15u; }
-constexpr int kRedSlots = 6;                       // one scratch slot per block reduction site
-enum { R_SEL_H = 0, R_SEL_CNT = 1, R_SEL_ABS = 2, R_ROAD_SUM = 3, R_ROAD_SS = 4, R_MISC = 5 };
-__host__ __device__ inline LdsPlan lds_plan(int n, int waves) {
-    LdsPlan p;
-    const uint32_t npad = (uint32_t)((n + 1) & ~1);
-    p.p = 0;                                      // double2 {v|x, z'} per feature
-    p.y = p.p + 16u * npad;                       // y' per feature
-    p.c = p.y + 8u * npad;                        // 16-bit vote counter per feature; later the selected bit-set
-    p.hist = align16(p.c + 2u * npad + 16u);
-    p.red = p.hist + 4u * 176u;                   // 169 bins (+pad)
-    p.misc = p.red + 8u * (uint32_t)(kRedSlots * 2 * waves);   // reduction scratch: 2*waves doubles per site
-    p.total = p.misc + 4u * 32u;                  // 32 ints of per-frame scalars
-    return p;
-}
-
 struct Smem {
-    double2 *P;
+    double2 *P;           // (the dense kernels: the survivors' planes in the workspace)
     double *Y;
     uint16_t *c16;
-    uint32_t *c32;
-    uint32_t *sel;        // aliases the counters once they are consumed
-    int *hist;
+    uint32_t *c32, *sel;  // (sel of lds_plan: aliases the counters once they are consumed)
     double *red;
     int *misc;
 };
+template <class T>
+__device__ __forceinline__ T *lds_at(char *base, uint32_t off) { return reinterpret_cast<T *>(base + off); }
 __device__ __forceinline__ Smem carve(char *base, int n, int waves) {
     const LdsPlan p = lds_plan(n, waves);
-    Smem s;
-    s.P = reinterpret_cast<double2 *>(base + p.p);
-    s.Y = reinterpret_cast<double *>(base + p.y);
-    s.c16 = reinterpret_cast<uint16_t *>(base + p.c);
-    s.c32 = reinterpret_cast<uint32_t *>(base + p.c);
-    s.sel = reinterpret_cast<uint32_t *>(base + p.c);
-    s.hist = reinterpret_cast<int *>(base + p.hist);
-    s.red = reinterpret_cast<double *>(base + p.red);
-    s.misc = reinterpret_cast<int *>(base + p.misc);
-    return s;
+    return {lds_at<double2>(base, p.p), lds_at<double>(base, p.y), lds_at<uint16_t>(base, p.c), lds_at<uint32_t>(base, p.c),
+            lds_at<uint32_t>(base, p.c), lds_at<double>(base, p.red), lds_at<int>(base, p.misc)};
+}
+__device__ __forceinline__ Smem carve_dense(char *base, int n, int waves, double2 *P = nullptr, double *Y = nullptr) {
+    const DensePlan p = dense_plan(n, waves);
+    return {P, Y, lds_at<uint16_t>(base, p.c), lds_at<uint32_t>(base, p.c), lds_at<uint32_t>(base, p.sel), lds_at<double>(base, p.red),
+            lds_at<int>(base, p.misc)};
 }
 
-// misc[] slots
-enum { M_WCNT = 0 /* [0..15] per-wave survivor counts */, M_LIST = 16, M_MEDLO = 18, M_MEDHI = 20 /* doubles at 18..21 */ };
-
+// "My count into slot array `slots`, barrier, {the counts of the waves in front of mine, all waves' sum}"
+struct WaveShare { int before, total; };
+template <int W>
+__device__ __forceinline__ WaveShare wave_exchange(int *slots, int cnt) {
+    const int w = wave_id();
+    if (lane_id() == 0) slots[w] = cnt;
+    __syncthreads();
+    WaveShare r = {0, 0};
+#pragma unroll
+    for (int i = 0; i < W; ++i) { const int c = slots[i]; if (i < w) r.before += c; r.total += c; }
+    return r;
+}
 
 // ---------------------------------------------------------------------------------------------
 // Triangle ids are streamed in chunks of kTC triangles per thread: all loads of a chunk are in
@@ -315,6 +303,7 @@ __device__ __forceinline__ int phase_vote(const Smem &s, int n, const double *gx
         if (keep) keepmask |= 1u << k;
         cnt += __popcll(__ballot(keep));
     }
+    // (wave_exchange, written out: with the helper the product kernels' listing gains an instruction)
     if (lane == 0) s.misc[M_WCNT + w] = cnt;
     __syncthreads();                             // every slice is in registers: LDS may be overwritten
     // step 2: survivors go to their compacted positions; the counters' space becomes the selected bit-set
@@ -1418,7 +1407,7 @@ struct KArgs {
     mvosr_outputs o;
     PitchTest pt;
     int64_t first_frame;
-    const double *height_level_in;
+    const double *unused_pad = nullptr;   // (never read: without these 8 bytes the kernel-argument loads regroup and the product kernels' listing moves)
     int32_t *redo;           // workspace: redo[0] = number of frames the HOT kernel left for the EXACT pass, redo[1..] their indices
     int redo_pass;           // EXACT kernels: 1 = process the redo list (grid-strided), 0 = frame first_frame + blockIdx.x
     double *ysel;            // workspace plane (laid out like x): the selected y' of every frame, dense
@@ -1428,14 +1417,45 @@ struct KArgs {
     const int32_t *cls_cnt;
 };
 
-__device__ __forceinline__ void write_counts(const KArgs &a, int64_t f, int nvalid, int npitch, int ntv, const RoadResult &R) {
+// The frame's scalars, loaded together at the top of a scale kernel (scalar loads, ahead of every store)
+struct FrameIn { int n; int64_t off, t1b, t2b; int t1n, t2n; };      // features, where they start; the triangulations' first rows, row counts
+__device__ __forceinline__ FrameIn load_frame(const mvosr_batch &b, int64_t f) {
+    return {b.feat_cnt[f], b.feat_off[f], b.tri1_off[f], b.tri2_off[f], tri_rows(b.tri1_off, b.tri1_cnt, f), tri_rows(b.tri2_off, b.tri2_cnt, f)};
+}
+// (the road model's counts are its kernel's to fill in: nothing kept, no modes)
+__device__ __forceinline__ void write_counts(const KArgs &a, int64_t f, int nvalid, int npitch, int ntv, int nsel) {
     if (!a.o.counts) return;
     int32_t *c = a.o.counts + f * MVOSR_N_COUNTS;
     c[MVOSR_CNT_VALID] = nvalid; c[MVOSR_CNT_TRI_PITCH] = npitch; c[MVOSR_CNT_TRI_VALID] = ntv;
-    c[MVOSR_CNT_SELECTED] = R.n_sel; c[MVOSR_CNT_KEPT] = R.n_kept; c[MVOSR_CNT_MODES] = R.n_modes;
-    c[MVOSR_CNT_MODE_LEFT] = R.mode_left; c[MVOSR_CNT_MODE_RIGHT] = R.mode_right;
+    c[MVOSR_CNT_SELECTED] = nsel; c[MVOSR_CNT_KEPT] = 0; c[MVOSR_CNT_MODES] = 0;
+    c[MVOSR_CNT_MODE_LEFT] = -1; c[MVOSR_CNT_MODE_RIGHT] = -1;
 }
-
+// What a scale kernel leaves of a frame (thread 0): with kStPending the road-model kernel finishes it
+__device__ __forceinline__ void finish_frame(const KArgs &a, int64_t f, double raw, double height_level, int status, int nvalid, int npitch, int ntv, int nsel) {
+    if (threadIdx.x != 0) return;
+    a.o.raw_scale[f] = raw;
+    a.o.height[f] = nan("");
+    a.o.height_level[f] = height_level;
+    a.o.status[f] = status;
+    a.nsel[f] = nsel;
+    write_counts(a, f, nvalid, npitch, ntv, nsel);
+    if (a.o.stats) { double *st = a.o.stats + 4 * f; st[0] = st[1] = st[2] = st[3] = nan(""); }
+}
+// A frame refused before anything was computed (thread 0): no level, no stats.  (Not through finish_frame: its arguments are
+// evaluated ahead of its stores, which reorders early_frame_exit's block in the product kernels' listing.)
+#define MVOSR_REFUSE_FRAME(a, f, status_, nvalid_) do {                                                     \
+        (a).o.raw_scale[f] = nan(""); (a).o.height[f] = nan(""); (a).o.height_level[f] = nan("");         \
+        (a).o.status[f] = (status_); (a).nsel[f] = 0; write_counts(a, f, (nvalid_), 0, 0, 0); } while (0)
+// HOT mode: the frame goes on the redo list, for the EXACT pass
+__device__ __forceinline__ void hand_to_exact(const KArgs &a, int64_t f) {
+    if (threadIdx.x == 0) { a.redo[1 + atomicAdd(a.redo, 1)] = (int32_t)f; a.o.status[f] = kStRedo; a.nsel[f] = 0; }
+}
+// The scale kernels' status rule: true, and the status, for a frame that is refused
+__device__ __forceinline__ bool frame_refused(bool masked, bool singular, int &status) {
+    if (masked) { status = MVOSR_ST_ERR_MASK; return true; }
+    if (singular) { status = MVOSR_ST_ERR_SINGULAR; return true; }
+    return false;
+}
 // Frames the sweeps never see: nothing below the vanishing row / no second triangulation (build-side
 // MVOSR_ST_ERR_EMPTY), and the reference's "no enough feature for triangulation" branch
 // (scale_calculator.py:263-270): with at most 3 features below the vanishing row it skips the second
@@ -1448,14 +1468,7 @@ __device__ __forceinline__ bool early_frame_exit(const KArgs &a, int64_t f, int 
     // a frame larger than the batch header says (max_feat sized this launch's LDS and variant): refused, not processed
     const bool oversize = n > a.b.max_feat;
     if (!(n <= 2 || too_few || t2n <= 0 || oversize)) return false;
-    if (threadIdx.x == 0) {
-        RoadResult R;
-        R.n_sel = R.n_kept = R.n_modes = 0; R.mode_left = R.mode_right = -1;
-        a.o.raw_scale[f] = nan(""); a.o.height[f] = nan(""); a.o.height_level[f] = nan("");
-        a.o.status[f] = oversize ? MVOSR_ST_ERR_MASK : (too_few ? MVOSR_ST_TOO_FEW : MVOSR_ST_ERR_EMPTY);
-        a.nsel[f] = 0;
-        write_counts(a, f, too_few ? n : 0, 0, 0, R);
-    }
+    if (threadIdx.x == 0) MVOSR_REFUSE_FRAME(a, f, oversize ? MVOSR_ST_ERR_MASK : (too_few ? MVOSR_ST_TOO_FEW : MVOSR_ST_ERR_EMPTY), too_few ? n : 0);
     return true;
 }
 
@@ -1477,12 +1490,12 @@ __device__ __forceinline__ bool early_frame_exit(const KArgs &a, int64_t f, int 
 // SC == 0 (the dense kernel: y' in global memory, thousands of words): count per wave slice -> barrier -> ordered store.
 template <int BW, int MODE, int SC = 0>
 __device__ __forceinline__ void frame_tail(const KArgs &a, const Smem &s, int64_t f, int64_t off, int nvalid, bool refused,
-                                           SelectResult &S, RoadResult &R) {
+                                           const SelectResult &S) {
     constexpr int B = BW * kWave;
-    const int tid = threadIdx.x;
     int status = kStPending;
     double raw = nan("");
     int nsel = 0;
+    // (frame_refused, written out: through the helper the rule arrives here as selects and the product kernels' listing moves)
     if (refused || S.bad) {
         status = MVOSR_ST_ERR_MASK;
     } else if (S.singular) {
@@ -1522,7 +1535,7 @@ __device__ __forceinline__ void frame_tail(const KArgs &a, const Smem &s, int64_
         }
         if constexpr (MODE == MODE_HOT) {
             if (S.near || nsel == 0) {
-                if (tid == 0) { a.redo[1 + atomicAdd(a.redo, 1)] = (int32_t)f; a.o.status[f] = kStRedo; a.nsel[f] = 0; }
+                hand_to_exact(a, f);
                 return;
             }
         }
@@ -1550,14 +1563,11 @@ __device__ __forceinline__ void frame_tail(const KArgs &a, const Smem &s, int64_
             if (a.o.selected && j < end) a.o.selected[off + j] = (uint8_t)sel;                   // :247
             cnt += __popcll(__ballot(sel));
         }
-        if (lane == 0) s.misc[M_WCNT + w] = cnt;
-        __syncthreads();
-        int base = 0;
-#pragma unroll
-        for (int i = 0; i < BW; ++i) { const int c = s.misc[M_WCNT + i]; if (i < w) base += c; nsel += c; }
+        const WaveShare ws = wave_exchange<BW>(s.misc + M_WCNT, cnt);
+        int base = ws.before; nsel = ws.total;
         if constexpr (MODE == MODE_HOT) {
             if (S.near || nsel == 0) {
-                if (tid == 0) { a.redo[1 + atomicAdd(a.redo, 1)] = (int32_t)f; a.o.status[f] = kStRedo; a.nsel[f] = 0; }
+                hand_to_exact(a, f);
                 return;
             }
         }
@@ -1571,16 +1581,7 @@ __device__ __forceinline__ void frame_tail(const KArgs &a, const Smem &s, int64_
         }
         if (nsel == 0) { status = MVOSR_ST_NO_FLAT; raw = a.P.absolute_reference / S.height_level; }   // :277-279,:421
     }
-    if (tid == 0) {
-        a.o.raw_scale[f] = raw;
-        a.o.height[f] = nan("");
-        a.o.height_level[f] = S.height_level;
-        a.o.status[f] = status;                  // kStPending: the road-model kernel finishes the frame
-        a.nsel[f] = nsel;
-        R.n_sel = nsel;
-        write_counts(a, f, nvalid, S.n_pitch, S.n_tri_valid, R);
-        if (a.o.stats) { double *st = a.o.stats + 4 * f; st[0] = st[1] = st[2] = st[3] = nan(""); }
-    }
+    finish_frame(a, f, raw, S.height_level, status, nvalid, S.n_pitch, S.n_tri_valid, nsel);
 }
 
 // The frames of a launch: frame first_frame + blockIdx.x — or, in the EXACT pass over the redo list, the list's entries
@@ -1615,10 +1616,9 @@ __global__ __launch_bounds__(WAVES *kWave, (WAVES == 8 && MODE == MODE_HOT ? 6 :
     constexpr int B = WAVES * kWave;
     MVOSR_STAMP_DECL
     MVOSR_STAMP(11);                               // (before the frame's offsets and counts are asked for)
-    const int n = a.b.feat_cnt[f];
-    const int64_t off = a.b.feat_off[f];
-    const int64_t t1b = a.b.tri1_off[f], t2b = a.b.tri2_off[f];
-    const int t1n = tri_rows(a.b.tri1_off, a.b.tri1_cnt, f), t2n = tri_rows(a.b.tri2_off, a.b.tri2_cnt, f);
+    const FrameIn fr = load_frame(a.b, f);
+    const int n = fr.n, t1n = fr.t1n, t2n = fr.t2n;
+    const int64_t off = fr.off, t1b = fr.t1b, t2b = fr.t2b;
     // (asked for here, with the frame's other scalars and ahead of every store, so that it is a scalar load: read where
     // it is compared, behind the compaction's barriers, it was a vector load and a full wait in front of the selection)
     const bool has_n2 = a.b.n2_expected != nullptr;
@@ -1634,9 +1634,6 @@ __global__ __launch_bounds__(WAVES *kWave, (WAVES == 8 && MODE == MODE_HOT ? 6 :
     }
 #endif
 
-    RoadResult R;
-    R.height = nan(""); R.n_sel = R.n_kept = R.n_modes = 0; R.mode_left = R.mode_right = -1;
-    R.mean = R.std = R.skew = R.median = nan("");
     if (early_frame_exit(a, f, n, t2n)) return;
     int bad = 0;
     TriChunk<B> tc2;
@@ -1653,7 +1650,7 @@ __global__ __launch_bounds__(WAVES *kWave, (WAVES == 8 && MODE == MODE_HOT ? 6 :
     if (!mask_mismatch && !too_many_rows)
         S = phase_select<WAVES, MODE>(s, nvalid, a.b.tri2, t2b, t2n, tc2, a.pt, a.o.tri_normals, a.o.tri_pitch_deg,
                                       a.o.tri_heights, bad, a.ysel ? a.ysel + off : nullptr, n MVOSR_STAMP_PASS);
-    frame_tail<WAVES, MODE, SC>(a, s, f, off, nvalid, mask_mismatch || too_many_rows, S, R);
+    frame_tail<WAVES, MODE, SC>(a, s, f, off, nvalid, mask_mismatch || too_many_rows, S);
     MVOSR_STAMP(9);
 #ifdef MVOSR_STAMPS
     if (threadIdx.x == 0 && a.o.hist) { unsigned long long *d = reinterpret_cast<unsigned long long *>(a.o.hist + f * 2 * kBins); for (int i = 0; i < 12; ++i) d[i] = stamps[i]; }
@@ -1670,11 +1667,6 @@ __global__ __launch_bounds__(WAVES *kWave, (WAVES == 8 && MODE == MODE_HOT ? 6 :
 // compacted into a second workspace copy (no in-place hazard, no registers held across barriers).
 // ---------------------------------------------------------------------------------------------
 struct DenseWs { double2 *P2; double *Y2; };      // per-batch planes of the survivors, laid out like x (feat_off)
-
-__host__ __device__ inline uint32_t dense_lds_bytes(int n, int waves) {
-    const uint32_t npad = (uint32_t)((n + 1) & ~1);
-    return align16(2u * npad + 16u) + align16(4u * ((uint32_t)(n + 31) / 32u)) + 8u * (uint32_t)(kRedSlots * 2 * waves) + 4u * 32u;
-}
 
 template <int DW, bool FUSED>
 __device__ __forceinline__ int phase_vote_dense(uint32_t *c32, int *misc, int n, const double *gx, const double *gy, const double *gz,
@@ -1732,11 +1724,8 @@ __device__ __forceinline__ int phase_vote_dense(uint32_t *c32, int *misc, int n,
         }
         cnt += __popcll(__ballot(keep));
     }
-    if (lane == 0) misc[M_WCNT + w] = cnt;
-    __syncthreads();
-    int base = 0, total = 0;
-#pragma unroll
-    for (int i = 0; i < DW; ++i) { const int c = misc[M_WCNT + i]; if (i < w) base += c; total += c; }
+    const WaveShare ws = wave_exchange<DW>(misc + M_WCNT, cnt);
+    int base = ws.before;
     if constexpr (FUSED) {
         for (int i0 = begin; i0 < end; i0 += kWave) {
             const int i = i0 + lane;
@@ -1754,7 +1743,7 @@ __device__ __forceinline__ int phase_vote_dense(uint32_t *c32, int *misc, int n,
         __threadfence_block();
     }
     __syncthreads();
-    return total;
+    return ws.total;
 }
 
 struct DenseArgs { KArgs k; DenseWs ws; };
@@ -1766,24 +1755,11 @@ __global__ __launch_bounds__(DW *kWave) void scale_frames_dense_kernel(const Den
     for_frames<MODE, false>(a, [&](const int64_t f) {
     constexpr int B = DW * kWave;
     const int tid = threadIdx.x;
-    const int n = a.b.feat_cnt[f];
-    const int64_t off = a.b.feat_off[f];
-    const int64_t t1b = a.b.tri1_off[f], t2b = a.b.tri2_off[f];
-    const int t1n = tri_rows(a.b.tri1_off, a.b.tri1_cnt, f), t2n = tri_rows(a.b.tri2_off, a.b.tri2_cnt, f);
-    RoadResult R;
-    R.height = nan(""); R.n_sel = R.n_kept = R.n_modes = 0; R.mode_left = R.mode_right = -1;
-    R.mean = R.std = R.skew = R.median = nan("");
+    const FrameIn fr = load_frame(a.b, f);
+    const int n = fr.n, t1n = fr.t1n, t2n = fr.t2n;
+    const int64_t off = fr.off, t1b = fr.t1b, t2b = fr.t2b;
     if (early_frame_exit(a, f, n, t2n)) return;
-    const uint32_t npad = (uint32_t)((n + 1) & ~1);
-    Smem s;
-    s.c32 = reinterpret_cast<uint32_t *>(smem);
-    s.c16 = reinterpret_cast<uint16_t *>(smem);
-    s.sel = reinterpret_cast<uint32_t *>(smem + align16(2u * npad + 16u));
-    s.red = reinterpret_cast<double *>(smem + align16(2u * npad + 16u) + align16(4u * ((uint32_t)(n + 31) / 32u)));
-    s.misc = reinterpret_cast<int *>(s.red + kRedSlots * 2 * DW);
-    s.hist = nullptr;
-    s.P = da.ws.P2 + off;              // what the second triangulation indexes: the compacted copy
-    s.Y = da.ws.Y2 + off;
+    const Smem s = carve_dense(smem, n, DW, da.ws.P2 + off, da.ws.Y2 + off);     // (P, Y: what the second triangulation indexes, the compacted copy)
     for (int i = tid; i < (n + 31) / 32; i += B) s.sel[i] = 0u;
     int bad = 0;
     const int nvalid = phase_vote_dense<DW, true>(s.c32, s.misc, n, a.b.x + off, a.b.y + off, a.b.z + off, a.b.v + off, a.b.tri1, t1b, t1n,
@@ -1798,7 +1774,7 @@ __global__ __launch_bounds__(DW *kWave) void scale_frames_dense_kernel(const Den
         S = phase_select<DW, MODE, 2>(s, nvalid, a.b.tri2, t2b, t2n, tc2, a.pt, a.o.tri_normals, a.o.tri_pitch_deg,
                                       a.o.tri_heights, bad, nullptr, 0);
     }
-    frame_tail<DW, MODE>(a, s, f, off, nvalid, mask_mismatch, S, R);
+    frame_tail<DW, MODE>(a, s, f, off, nvalid, mask_mismatch, S);
     });
 }
 
@@ -1819,25 +1795,16 @@ __global__ __launch_bounds__(DW *kWave) void scale_frames_dense_feat_kernel(cons
     constexpr int B = DW * kWave;
     constexpr bool FULL = MODE == MODE_FULL;
     const int tid = threadIdx.x, w = wave_id(), lane = lane_id();
-    const int n = a.b.feat_cnt[f];
-    const int64_t off = a.b.feat_off[f];
-    const int64_t t1b = a.b.tri1_off[f], t2b = a.b.tri2_off[f];
-    const int t1n = tri_rows(a.b.tri1_off, a.b.tri1_cnt, f), t2n = tri_rows(a.b.tri2_off, a.b.tri2_cnt, f);
-    RoadResult R;
-    R.height = nan(""); R.n_sel = R.n_kept = R.n_modes = 0; R.mode_left = R.mode_right = -1;
-    R.mean = R.std = R.skew = R.median = nan("");
+    const FrameIn fr = load_frame(a.b, f);
+    const int n = fr.n, t1n = fr.t1n, t2n = fr.t2n;
+    const int64_t off = fr.off, t1b = fr.t1b, t2b = fr.t2b;
     if (early_frame_exit(a, f, n, t2n)) return;
-    const uint32_t npad = (uint32_t)((n + 1) & ~1);
-    uint32_t *c32 = reinterpret_cast<uint32_t *>(smem);
-    const uint16_t *c16 = reinterpret_cast<const uint16_t *>(smem);
-    uint32_t *sel = reinterpret_cast<uint32_t *>(smem + align16(2u * npad + 16u));
-    double *red = reinterpret_cast<double *>(smem + align16(2u * npad + 16u) + align16(4u * ((uint32_t)(n + 31) / 32u)));
-    int *misc = reinterpret_cast<int *>(red + kRedSlots * 2 * DW);
+    const Smem s = carve_dense(smem, n, DW);
     const double *gx = a.b.x + off, *gy = a.b.y + off, *gz = a.b.z + off;
     const double cp = a.P.cos_pitch, sp = a.P.sin_pitch;
-    for (int i = tid; i < (n + 31) / 32; i += B) sel[i] = 0u;
+    for (int i = tid; i < (n + 31) / 32; i += B) s.sel[i] = 0u;
     int bad = 0;
-    const int nvalid = phase_vote_dense<DW, false>(c32, misc, n, nullptr, gy, gz, a.b.v + off, a.b.tri1, t1b, t1n, cp, sp,
+    const int nvalid = phase_vote_dense<DW, false>(s.c32, s.misc, n, nullptr, gy, gz, a.b.v + off, a.b.tri1, t1b, t1n, cp, sp,
                                                    a.o.vote_counters ? a.o.vote_counters + off : nullptr, bad, nullptr, nullptr,
                                                    a.P.vote_mode == MVOSR_VOTE_FIXED);
     const bool mask_mismatch = a.b.n2_expected && a.b.n2_expected[f] != nvalid;
@@ -1848,7 +1815,7 @@ __global__ __launch_bounds__(DW *kWave) void scale_frames_dense_feat_kernel(cons
     auto fetch = [=](const TriIds q, double &x0, double &y0, double &z0, double &x1, double &y1, double &z1,
                      double &x2, double &y2, double &z2) -> bool {
         const bool ok = (unsigned)q.a < (unsigned)n && (unsigned)q.b < (unsigned)n && (unsigned)q.c < (unsigned)n &&
-                        c16[q.a] >= kCounterBias && c16[q.b] >= kCounterBias && c16[q.c] >= kCounterBias;      // survivors only (:166)
+                        s.c16[q.a] >= kCounterBias && s.c16[q.b] >= kCounterBias && s.c16[q.c] >= kCounterBias;      // survivors only (:166)
         if (!ok) return false;
         const double ya = gy[q.a], za = gz[q.a], yb = gy[q.b], zb = gz[q.b], yc = gy[q.c], zc = gz[q.c];
         x0 = gx[q.a]; x1 = gx[q.b]; x2 = gx[q.c];
@@ -1882,8 +1849,8 @@ __global__ __launch_bounds__(DW *kWave) void scale_frames_dense_feat_kernel(cons
         }
         cur = {0, 0, 0};
         if (tid < t2s) cur = load_tri(tri, tid);
-        if constexpr (MODE == MODE_HOT) block_sum3<DW>(hsum, hcnt, habs, red + R_SEL_H * 2 * DW, red + R_SEL_ABS * 2 * DW);
-        else block_sum2<DW>(hsum, hcnt, red + R_SEL_H * 2 * DW);
+        if constexpr (MODE == MODE_HOT) block_sum3<DW>(hsum, hcnt, habs, s.red + R_SEL_H * 2 * DW, s.red + R_SEL_ABS * 2 * DW);
+        else block_sum2<DW>(hsum, hcnt, s.red + R_SEL_H * 2 * DW);
         double hl = hsum / hcnt;                      // np.mean of an empty set -> 0/0 = NaN, like :240
         const double guard = kLevelGuard * (habs / hcnt);
         if constexpr (MODE != MODE_HOT)
@@ -1898,25 +1865,21 @@ __global__ __launch_bounds__(DW *kWave) void scale_frames_dense_feat_kernel(cons
                 if constexpr (MODE == MODE_HOT) { if (fabs(h - hl) <= guard) near = 1; }
                 if (h > hl) {                                                                    // :243-244
                     ++ntv;
-                    atomicOr(&sel[q.a >> 5], 1u << (q.a & 31));                                  // :247
-                    atomicOr(&sel[q.b >> 5], 1u << (q.b & 31));
-                    atomicOr(&sel[q.c >> 5], 1u << (q.c & 31));
+                    atomicOr(&s.sel[q.a >> 5], 1u << (q.a & 31));                                  // :247
+                    atomicOr(&s.sel[q.b >> 5], 1u << (q.b & 31));
+                    atomicOr(&s.sel[q.c >> 5], 1u << (q.c & 31));
                 }
             }
         }
         int sn = singular | (near << 16);
-        block_sum4i<DW>(npitch, ntv, sn, bad, red + R_SEL_CNT * 2 * DW);   // also orders the atomicOr's
+        block_sum4i<DW>(npitch, ntv, sn, bad, s.red + R_SEL_CNT * 2 * DW);   // also orders the atomicOr's
         S.height_level = hl; S.n_steep = (int)hcnt; S.near = sn >> 16;
         S.n_pitch = npitch; S.n_tri_valid = ntv; S.singular = sn & 0xFFFF; S.bad = bad;
     }
     int status = kStPending;
     double raw = nan("");
     int nsel = 0;
-    if (mask_mismatch || S.bad) {
-        status = MVOSR_ST_ERR_MASK;
-    } else if (S.singular) {
-        status = MVOSR_ST_ERR_SINGULAR;
-    } else {
+    if (!frame_refused(mask_mismatch || S.bad, S.singular, status)) {
         // per wave slice of the features: survivors before it (for the `selected` output, which is indexed
         // by survivor) and selected ones before it (for the dense list of y' handed to the road-model kernel)
         const int per = ((n + B - 1) / B) * kWave;
@@ -1924,27 +1887,28 @@ __global__ __launch_bounds__(DW *kWave) void scale_frames_dense_feat_kernel(cons
         int nv = 0, ns = 0;
         for (int i0 = begin; i0 < end; i0 += kWave) {
             const int i = i0 + lane;
-            const bool valid = (i < end) && c16[i] >= kCounterBias;
-            const bool on = valid && ((sel[i >> 5] >> (i & 31)) & 1u);
+            const bool valid = (i < end) && s.c16[i] >= kCounterBias;
+            const bool on = valid && ((s.sel[i >> 5] >> (i & 31)) & 1u);
             nv += __popcll(__ballot(valid));
             ns += __popcll(__ballot(on));
         }
-        if (lane == 0) { misc[M_WCNT + w] = ns; misc[M_WCNT + DW + w] = nv; }
+        // (wave_exchange for two counts at once, written out: as a helper it cost the EXACT instantiation four more spills)
+        if (lane == 0) { s.misc[M_WCNT + w] = ns; s.misc[M_WCNT2 + w] = nv; }
         __syncthreads();
         int base_s = 0, base_v = 0;
 #pragma unroll
-        for (int i = 0; i < DW; ++i) { const int c = misc[M_WCNT + i]; if (i < w) { base_s += c; base_v += misc[M_WCNT + DW + i]; } nsel += c; }
+        for (int i = 0; i < DW; ++i) { const int c = s.misc[M_WCNT + i]; if (i < w) { base_s += c; base_v += s.misc[M_WCNT2 + i]; } nsel += c; }
         if constexpr (MODE == MODE_HOT) {
             if (S.near || nsel == 0) {           // the level's last bits may matter: leave the frame to the EXACT pass
-                if (tid == 0) { a.redo[1 + atomicAdd(a.redo, 1)] = (int32_t)f; a.o.status[f] = kStRedo; a.nsel[f] = 0; }
+                hand_to_exact(a, f);
                 return;
             }
         }
         double *dst = a.ysel + off;
         for (int i0 = begin; i0 < end; i0 += kWave) {
             const int i = i0 + lane;
-            const bool valid = (i < end) && c16[i] >= kCounterBias;
-            const bool on = valid && ((sel[i >> 5] >> (i & 31)) & 1u);
+            const bool valid = (i < end) && s.c16[i] >= kCounterBias;
+            const bool on = valid && ((s.sel[i >> 5] >> (i & 31)) & 1u);
             const unsigned long long mv = __ballot(valid), ms = __ballot(on);
             const unsigned long long below = (1ull << lane) - 1ull;
             if (valid && a.o.selected) a.o.selected[off + base_v + __popcll(mv & below)] = (uint8_t)on;      // :247
@@ -1954,16 +1918,7 @@ __global__ __launch_bounds__(DW *kWave) void scale_frames_dense_feat_kernel(cons
         }
         if (nsel == 0) { status = MVOSR_ST_NO_FLAT; raw = a.P.absolute_reference / S.height_level; }   // :277-279,:421
     }
-    if (tid == 0) {
-        a.o.raw_scale[f] = raw;
-        a.o.height[f] = nan("");
-        a.o.height_level[f] = S.height_level;
-        a.o.status[f] = status;
-        a.nsel[f] = nsel;
-        R.n_sel = nsel;
-        write_counts(a, f, nvalid, S.n_pitch, S.n_tri_valid, R);
-        if (a.o.stats) { double *st = a.o.stats + 4 * f; st[0] = st[1] = st[2] = st[3] = nan(""); }
-    }
+    finish_frame(a, f, raw, S.height_level, status, nvalid, S.n_pitch, S.n_tri_valid, nsel);
     });
 }
 
@@ -1996,31 +1951,21 @@ __global__ __launch_bounds__(DW *kWave) void scale_frames_dense_feat_kernel(cons
 // the result, or whose pending lists overflow goes on the redo list and the EXACT pass runs
 // scale_frames_dense_feat_kernel on it; stage outputs select that kernel too.
 // ---------------------------------------------------------------------------------------------
-constexpr int kTileW = 512;                 // features per tile (MVOSR_TILE_W in the header; the host's index uses the same)
 constexpr int kTiledWaves = 8;
-constexpr int kRing = 3;                    // tiles in the LDS ring: one barrier per tile (tile k-1 retires and tile k+2 takes its slot while the
-                                            // rows of tile k are still being walked)
-constexpr int kPendCap = 1024;              // pending votes for vertices whose tile has not arrived yet (4 B each) ...
-constexpr int kPendCapH = 576;              // ... and pending heights (12 B each): what fits two workgroups per CU
 constexpr int kTileRows = 2;                // rows per thread and triangulation prefetched for the coming step
 
-struct TiledPlan { uint32_t ringA, ringB, ringH, ringC, used, pendV, pendH, toff, red, misc, total; };
-__host__ __device__ inline TiledPlan tiled_plan(int n, int waves) {
-    TiledPlan p;
-    const uint32_t ntiles = (uint32_t)((n + kTileW - 1) / kTileW);
-    constexpr uint32_t RW = (uint32_t)kRing * kTileW;            // vertices in the ring
-    p.ringA = 0;                                                 // double2 {v, z'}
-    p.ringB = p.ringA + 16u * RW;                                // double2 {x, y'}
-    p.ringH = p.ringB + 16u * RW;                                // uint64 key of the largest flat height
-    p.ringC = p.ringH + 8u * RW;                                 // int32 vote counters
-    p.used = p.ringC + 4u * RW;                                  // uint8 "a tri2 row names this vertex"
-    p.pendV = align16(p.used + RW);                              // vertex << 1 | (vote is -1)
-    p.pendH = p.pendV + 4u * kPendCap;                           // key64 x kPendCapH, then vertex x kPendCapH
-    p.toff = align16(p.pendH + 12u * kPendCapH);                 // the frame's tile index: 2 x (ntiles + 1) ints
-    p.red = align16(p.toff + 8u * (ntiles + 2u));
-    p.misc = p.red + 8u * (uint32_t)(kRedSlots * 2 * waves);
-    p.total = p.misc + 4u * 64u;
-    return p;
+struct TiledSmem {
+    double2 *ringA, *ringB;
+    unsigned long long *ringH, *pendH;
+    int *ringC, *pendV, *pendHv, *toff1, *misc;
+    uint8_t *used;
+    double *red;
+};
+__device__ __forceinline__ TiledSmem carve_tiled(char *base, int max_feat, int waves) {
+    const TiledPlan p = tiled_plan(max_feat, waves);
+    return {lds_at<double2>(base, p.ringA), lds_at<double2>(base, p.ringB), lds_at<unsigned long long>(base, p.ringH),
+            lds_at<unsigned long long>(base, p.pendH), lds_at<int>(base, p.ringC), lds_at<int>(base, p.pendV), lds_at<int>(base, p.pendH + 8u * kPendCapH),
+            lds_at<int>(base, p.toff), lds_at<int>(base, p.misc), lds_at<uint8_t>(base, p.used), lds_at<double>(base, p.red)};
 }
 
 // order-preserving map of a double onto uint64 (0 is never produced)
@@ -2042,29 +1987,14 @@ __global__ __launch_bounds__(DW *kWave, (DW == 8 ? 4 : 1)) void scale_frames_til
     static_assert(W % B == 0 || B > W, "tile width / block size");
     const int tid = threadIdx.x, w = wave_id(), lane = lane_id();
     const int64_t f = a.first_frame + blockIdx.x;
-    const int n = a.b.feat_cnt[f];
-    const int64_t off = a.b.feat_off[f];
-    const int64_t t1b = a.b.tri1_off[f], t2b = a.b.tri2_off[f];
-    const int t1n = tri_rows(a.b.tri1_off, a.b.tri1_cnt, f), t2n = tri_rows(a.b.tri2_off, a.b.tri2_cnt, f);
-    RoadResult R;
-    R.height = nan(""); R.n_sel = R.n_kept = R.n_modes = 0; R.mode_left = R.mode_right = -1;
-    R.mean = R.std = R.skew = R.median = nan("");
+    const FrameIn fr = load_frame(a.b, f);
+    const int n = fr.n, t1n = fr.t1n, t2n = fr.t2n;
+    const int64_t off = fr.off, t1b = fr.t1b, t2b = fr.t2b;
     if (early_frame_exit(a, f, n, t2n)) return;
-    const TiledPlan pl = tiled_plan(a.b.max_feat, DW);
-    double2 *ringA = reinterpret_cast<double2 *>(smem + pl.ringA);
-    double2 *ringB = reinterpret_cast<double2 *>(smem + pl.ringB);
-    unsigned long long *ringH = reinterpret_cast<unsigned long long *>(smem + pl.ringH);
-    int *ringC = reinterpret_cast<int *>(smem + pl.ringC);
-    uint8_t *used = reinterpret_cast<uint8_t *>(smem + pl.used);
-    int *pendV = reinterpret_cast<int *>(smem + pl.pendV);
-    unsigned long long *pendH = reinterpret_cast<unsigned long long *>(smem + pl.pendH);
-    int *pendHv = reinterpret_cast<int *>(pendH + kPendCapH);
-    int *toff1 = reinterpret_cast<int *>(smem + pl.toff);
-    double *red = reinterpret_cast<double *>(smem + pl.red);
-    int *misc = reinterpret_cast<int *>(smem + pl.misc);
-    int *n_pendV = misc + 40, *n_pendH = misc + 41;
+    const TiledSmem sm = carve_tiled(smem, a.b.max_feat, DW);
+    int *const n_pendV = sm.misc + M_PENDV, *const n_pendH = sm.misc + M_PENDH;
     const int ntiles = (n + W - 1) / W;
-    int *toff2 = toff1 + ntiles + 1;
+    int *toff2 = sm.toff1 + ntiles + 1;
     const double *gx = a.b.x + off, *gy = a.b.y + off, *gz = a.b.z + off, *gv = a.b.v + off;
     const double cp = a.P.cos_pitch, sp = a.P.sin_pitch;
     const int32_t *rows1 = a.b.tri1 + 3 * t1b, *rows2 = a.b.tri2 + 3 * t2b;
@@ -2082,7 +2012,7 @@ __global__ __launch_bounds__(DW *kWave, (DW == 8 ? 4 : 1)) void scale_frames_til
         if ((int64_t)(a.b.tile_base[f + 1] - tb) != (int64_t)(ntiles + 1)) bad = 1;
         for (int k = tid; k <= ntiles; k += B) {
             const int o1 = bad ? 0 : a.b.tile1_off[tb + k], o2 = bad ? 0 : a.b.tile2_off[tb + k];
-            toff1[k] = o1; toff2[k] = o2;
+            sm.toff1[k] = o1; toff2[k] = o2;
             if (k == 0 && (o1 != 0 || o2 != 0)) bad = 1;
             if (k == ntiles && (o1 > t1n || o2 > t2n)) bad = 1;
             if (k > 0 && !bad && (o1 < a.b.tile1_off[tb + k - 1] || o2 < a.b.tile2_off[tb + k - 1])) bad = 1;
@@ -2113,10 +2043,10 @@ __global__ __launch_bounds__(DW *kWave, (DW == 8 ? 4 : 1)) void scale_frames_til
             double2 pa, pb;
             pa.x = tv[j]; pa.y = ty[j] * sp + tz[j] * cp;          // {v, z'}
             pb.x = tx[j]; pb.y = ty[j] * cp - tz[j] * sp;          // {x, y'}
-            if (i < n) { ringA[slot] = pa; ringB[slot] = pb; }
-            ringC[slot] = 1;                                        // np.ones, :153
-            ringH[slot] = 0ull;
-            used[slot] = 0;
+            if (i < n) { sm.ringA[slot] = pa; sm.ringB[slot] = pb; }
+            sm.ringC[slot] = 1;                                        // np.ones, :153
+            sm.ringH[slot] = 0ull;
+            sm.used[slot] = 0;
         }
     };
     tile_load(0); tile_store(0);
@@ -2125,15 +2055,11 @@ __global__ __launch_bounds__(DW *kWave, (DW == 8 ? 4 : 1)) void scale_frames_til
     // the block agrees on the index before anyone walks it
     {
         int b0 = bad, b1 = 0, b2 = 0, b3 = 0;
-        block_sum4i<DW>(b0, b1, b2, b3, red + R_MISC * 2 * DW);
+        block_sum4i<DW>(b0, b1, b2, b3, sm.red + R_MISC * 2 * DW);
         bad = b0;
     }
     if (bad) {
-        if (tid == 0) {
-            a.o.raw_scale[f] = nan(""); a.o.height[f] = nan(""); a.o.height_level[f] = nan("");
-            a.o.status[f] = MVOSR_ST_ERR_MASK; a.nsel[f] = 0;
-            write_counts(a, f, 0, 0, 0, R);
-        }
+        if (tid == 0) MVOSR_REFUSE_FRAME(a, f, MVOSR_ST_ERR_MASK, 0);
         return;
     }
     MVOSR_TSTAMP(0);
@@ -2149,7 +2075,7 @@ __global__ __launch_bounds__(DW *kWave, (DW == 8 ? 4 : 1)) void scale_frames_til
     // step), and what the row contributes to them waits in the pending lists until their tiles are in the ring.
     // With the packer's far table (mvosr_batch.tile_far) the vertices are one contiguous block per frame, 72 bytes per
     // row; without it they are gathered from the planes (a 128-byte line per element).
-    const int far1 = toff1[ntiles], far2 = toff2[ntiles];
+    const int far1 = sm.toff1[ntiles], far2 = toff2[ntiles];
     const double *fart = nullptr;
     if (a.b.tile_far && a.b.tile_far_off) {
         const int64_t fb = a.b.tile_far_off[f];
@@ -2176,9 +2102,9 @@ __global__ __launch_bounds__(DW *kWave, (DW == 8 ? 4 : 1)) void scale_frames_til
         const int e = atomicAdd(n_pendV, 3);
         if (e + 3 <= kPendCap) {
             const VoteFlags vf = vote_flags(pa, pb, pc, fixed);
-            pendV[e] = q.a << 1 | (vf.f0 ? 1 : 0);
-            pendV[e + 1] = q.b << 1 | (vf.f1 ? 1 : 0);
-            pendV[e + 2] = q.c << 1 | (vf.f2 ? 1 : 0);
+            sm.pendV[e] = q.a << 1 | (vf.f0 ? 1 : 0);
+            sm.pendV[e + 1] = q.b << 1 | (vf.f1 ? 1 : 0);
+            sm.pendV[e + 2] = q.c << 1 | (vf.f2 ? 1 : 0);
         } else overflow = 1;
     }
     for (int t = far2 + tid; t < t2n; t += B) {
@@ -2201,8 +2127,8 @@ __global__ __launch_bounds__(DW *kWave, (DW == 8 ? 4 : 1)) void scale_frames_til
         const unsigned long long key = ((r & 1) && h == h) ? height_key64(h) : 0ull;
         const int e = atomicAdd(n_pendH, 3);
         if (e + 3 <= kPendCapH) {
-            pendH[e] = key; pendH[e + 1] = key; pendH[e + 2] = key;
-            pendHv[e] = q.a; pendHv[e + 1] = q.b; pendHv[e + 2] = q.c;
+            sm.pendH[e] = key; sm.pendH[e + 1] = key; sm.pendH[e + 2] = key;
+            sm.pendHv[e] = q.a; sm.pendHv[e + 1] = q.b; sm.pendHv[e + 2] = q.c;
         } else overflow = 1;
     }
     __syncthreads();
@@ -2210,12 +2136,12 @@ __global__ __launch_bounds__(DW *kWave, (DW == 8 ? 4 : 1)) void scale_frames_til
     auto apply_pending = [&](int tile) {
         const int nv = min(n_pendV[0], kPendCap), nh = min(n_pendH[0], kPendCapH), sb = tile_slot(tile);
         for (int e = tid; e < nv; e += B) {
-            const int p = pendV[e], vtx = p >> 1;
-            if (vtx / W == tile) atomicAdd(&ringC[sb + vtx - tile * W], (p & 1) ? -1 : 1);
+            const int p = sm.pendV[e], vtx = p >> 1;
+            if (vtx / W == tile) atomicAdd(&sm.ringC[sb + vtx - tile * W], (p & 1) ? -1 : 1);
         }
         for (int e = tid; e < nh; e += B) {
-            const int vtx = pendHv[e];
-            if (vtx / W == tile) { const unsigned long long key = pendH[e]; if (key) atomicMax(&ringH[sb + vtx - tile * W], key); used[sb + vtx - tile * W] = 1; }
+            const int vtx = sm.pendHv[e];
+            if (vtx / W == tile) { const unsigned long long key = sm.pendH[e]; if (key) atomicMax(&sm.ringH[sb + vtx - tile * W], key); sm.used[sb + vtx - tile * W] = 1; }
         }
     };
     apply_pending(0);
@@ -2226,10 +2152,10 @@ __global__ __launch_bounds__(DW *kWave, (DW == 8 ? 4 : 1)) void scale_frames_til
     // (clamped to the tile's OWN last row: a slot beyond it re-reads that row's line instead of pulling in rows of the
     // next tile, which the next step would fetch a second time — tri2 has ~830 rows per tile against 1024 slots)
     auto prefetch_rows = [&](int k) {
-        const int last1 = max(min(toff1[k + 1], max(t1n, 1)) - 1, 0), last2 = max(min(toff2[k + 1], t2n) - 1, 0);
+        const int last1 = max(min(sm.toff1[k + 1], max(t1n, 1)) - 1, 0), last2 = max(min(toff2[k + 1], t2n) - 1, 0);
 #pragma unroll
         for (int j = 0; j < kTileRows; ++j) {
-            n1[j] = load_tri(rows1c, min(toff1[k] + j * B + rid, last1));
+            n1[j] = load_tri(rows1c, min(sm.toff1[k] + j * B + rid, last1));
             n2[j] = load_tri(rows2, min(toff2[k] + j * B + rid, last2));
         }
     };
@@ -2256,11 +2182,11 @@ __global__ __launch_bounds__(DW *kWave, (DW == 8 ? 4 : 1)) void scale_frames_til
             bool survivor = false, is_cand = false;
             double cy = 0.0, ch = 0.0;
             if (i < n) {
-                survivor = ringC[slot] >= 0;                                                 // :166
-                if (used[slot] && !survivor) bad = 1;                                  // tri2 names a feature the vote dropped
-                const unsigned long long hk = ringH[slot];
+                survivor = sm.ringC[slot] >= 0;                                                 // :166
+                if (sm.used[slot] && !survivor) bad = 1;                                  // tri2 names a feature the vote dropped
+                const unsigned long long hk = sm.ringH[slot];
                 is_cand = hk != 0ull;
-                cy = ringB[slot].y; ch = height_of_key64(hk);                          // y', largest flat height
+                cy = sm.ringB[slot].y; ch = height_of_key64(hk);                          // y', largest flat height
             }
             nvalid += __popcll(__ballot(survivor));
             const unsigned long long mc = __ballot(is_cand);
@@ -2271,7 +2197,7 @@ __global__ __launch_bounds__(DW *kWave, (DW == 8 ? 4 : 1)) void scale_frames_til
     // ---- the walk over the tiles
     for (int k = 0; k < ntiles; ++k) {
         const int lo = k * W;
-        const int b1 = toff1[k], e1 = toff1[k + 1], b2 = toff2[k], e2 = toff2[k + 1];
+        const int b1 = sm.toff1[k], e1 = sm.toff1[k + 1], b2 = toff2[k], e2 = toff2[k + 1];
         const int sbk = tile_slot(k);
         auto S = [&](int v) { return slot_at(sbk, v - lo); };            // (a checked row: 0 <= v - lo <= 2W - 1)
         TriIds c1[kTileRows], c2[kTileRows];
@@ -2287,14 +2213,14 @@ __global__ __launch_bounds__(DW *kWave, (DW == 8 ? 4 : 1)) void scale_frames_til
         };
         auto vote_row = [&](const TriIds q) {
             if (!row_ok(q)) { bad = 1; return; }
-            const double2 p0 = ringA[S(q.a)], p1 = ringA[S(q.b)], p2 = ringA[S(q.c)];      // {v, z'}
+            const double2 p0 = sm.ringA[S(q.a)], p1 = sm.ringA[S(q.b)], p2 = sm.ringA[S(q.c)];      // {v, z'}
             const bool pa = (p0.x - p1.x) * (p0.y - p1.y) > 0.0;       // :107,:110
             const bool pb = (p0.x - p2.x) * (p0.y - p2.y) > 0.0;       // :108,:113  (marks vertices 0 and 1, as the reference does)
             const bool pc = (p1.x - p2.x) * (p1.y - p2.y) > 0.0;       // :109,:116
             const VoteFlags vf = vote_flags(pa, pb, pc, fixed);
-            atomicAdd(&ringC[S(q.a)], vf.f0 ? -1 : 1);
-            atomicAdd(&ringC[S(q.b)], vf.f1 ? -1 : 1);
-            atomicAdd(&ringC[S(q.c)], vf.f2 ? -1 : 1);
+            atomicAdd(&sm.ringC[S(q.a)], vf.f0 ? -1 : 1);
+            atomicAdd(&sm.ringC[S(q.b)], vf.f1 ? -1 : 1);
+            atomicAdd(&sm.ringC[S(q.c)], vf.f2 ? -1 : 1);
         };
         {
             // the prefetched rows: every ring read first (the compiler cannot move the reads of one row across the LDS
@@ -2307,7 +2233,7 @@ __global__ __launch_bounds__(DW *kWave, (DW == 8 ? 4 : 1)) void scale_frames_til
                 const bool live = b1 + j * B + rid < e1;
                 ok[j] = live && row_ok(q);
                 if (live && !ok[j]) bad = 1;
-                if (ok[j]) { vp[j][0] = ringA[S(q.a)]; vp[j][1] = ringA[S(q.b)]; vp[j][2] = ringA[S(q.c)]; }      // {v, z'}
+                if (ok[j]) { vp[j][0] = sm.ringA[S(q.a)]; vp[j][1] = sm.ringA[S(q.b)]; vp[j][2] = sm.ringA[S(q.c)]; }      // {v, z'}
             }
 #pragma unroll
             for (int j = 0; j < kTileRows; ++j) {
@@ -2318,9 +2244,9 @@ __global__ __launch_bounds__(DW *kWave, (DW == 8 ? 4 : 1)) void scale_frames_til
                 const bool pb = (p0.x - p2.x) * (p0.y - p2.y) > 0.0;       // :108,:113  (marks vertices 0 and 1, as the reference does)
                 const bool pc = (p1.x - p2.x) * (p1.y - p2.y) > 0.0;       // :109,:116
                 const VoteFlags vf = vote_flags(pa, pb, pc, fixed);
-                atomicAdd(&ringC[S(q.a)], vf.f0 ? -1 : 1);
-                atomicAdd(&ringC[S(q.b)], vf.f1 ? -1 : 1);
-                atomicAdd(&ringC[S(q.c)], vf.f2 ? -1 : 1);
+                atomicAdd(&sm.ringC[S(q.a)], vf.f0 ? -1 : 1);
+                atomicAdd(&sm.ringC[S(q.b)], vf.f1 ? -1 : 1);
+                atomicAdd(&sm.ringC[S(q.c)], vf.f2 ? -1 : 1);
             }
         }
         for (int t = b1 + kTileRows * B + rid; t < e1; t += B) vote_row(load_tri(rows1, t));
@@ -2328,9 +2254,9 @@ __global__ __launch_bounds__(DW *kWave, (DW == 8 ? 4 : 1)) void scale_frames_til
         // the selection sweep over this tile's rows of tri2 (:225-240)
         auto select_row = [&](const TriIds q) {
             if (!row_ok(q)) { bad = 1; return; }
-            const double2 a0 = ringA[S(q.a)], a1 = ringA[S(q.b)], a2 = ringA[S(q.c)];
-            const double2 g0_ = ringB[S(q.a)], g1_ = ringB[S(q.b)], g2_ = ringB[S(q.c)];
-            used[S(q.a)] = 1; used[S(q.b)] = 1; used[S(q.c)] = 1;        // (every writer stores the same value)
+            const double2 a0 = sm.ringA[S(q.a)], a1 = sm.ringA[S(q.b)], a2 = sm.ringA[S(q.c)];
+            const double2 g0_ = sm.ringB[S(q.a)], g1_ = sm.ringB[S(q.b)], g2_ = sm.ringB[S(q.c)];
+            sm.used[S(q.a)] = 1; sm.used[S(q.b)] = 1; sm.used[S(q.c)] = 1;        // (every writer stores the same value)
             // :238.  3h instead of h: the keys, their maxima and the level all scale by three, the comparisons of the tail are
             // the same outside the guard band (as in the LDS-resident product kernel), and no triangle pays the division
             const double h = (g0_.y + g1_.y) + g2_.y;
@@ -2342,7 +2268,7 @@ __global__ __launch_bounds__(DW *kWave, (DW == 8 ? 4 : 1)) void scale_frames_til
                 ++npitch;
                 if (h == h) {
                     const unsigned long long key = height_key64(h);
-                    atomicMax(&ringH[S(q.a)], key); atomicMax(&ringH[S(q.b)], key); atomicMax(&ringH[S(q.c)], key);
+                    atomicMax(&sm.ringH[S(q.a)], key); atomicMax(&sm.ringH[S(q.b)], key); atomicMax(&sm.ringH[S(q.c)], key);
                 }
             }
         };
@@ -2359,7 +2285,7 @@ __global__ __launch_bounds__(DW *kWave, (DW == 8 ? 4 : 1)) void scale_frames_til
     }
     retire(ntiles - 1);
 
-    block_sum2<DW>(hsum, hcnt, red + R_SEL_H * 2 * DW);
+    block_sum2<DW>(hsum, hcnt, sm.red + R_SEL_H * 2 * DW);
     {
         // flags: one vote per wavefront (<= 16 of them: the three 8-bit fields cannot carry into each other)
         const int wf = (__ballot(singular != 0) ? 1 : 0) | (__ballot(bad != 0) ? 1 << 8 : 0) | (__ballot(overflow != 0) ? 1 << 16 : 0);
@@ -2368,7 +2294,7 @@ __global__ __launch_bounds__(DW *kWave, (DW == 8 ? 4 : 1)) void scale_frames_til
         // steep heights of both signs: the level's rounding error is then relative to sum |h| / count, not to |level| (they
         // may cancel), and the guard band below, which is relative to |level|, is not wide enough — the EXACT pass takes the frame
         int z0 = (lane == 0) ? ((__ballot(sneg) ? 1 : 0) | (__ballot(spos) ? 1 << 8 : 0)) : 0;
-        block_sum4i<DW>(npitch, nv, sb, z0, red + R_SEL_CNT * 2 * DW);
+        block_sum4i<DW>(npitch, nv, sb, z0, sm.red + R_SEL_CNT * 2 * DW);
         nvalid = nv; singular = sb & 0xFF; bad = (sb >> 8) & 0xFF; overflow = sb >> 16;
         mixed_signs = (z0 & 0xFF) && (z0 >> 8);
     }
@@ -2380,14 +2306,10 @@ __global__ __launch_bounds__(DW *kWave, (DW == 8 ? 4 : 1)) void scale_frames_til
     int nsel = 0;
     if (overflow && !bad) {
         // more far rows than the pending lists hold: not what the tiled layout promises — the two-sweep kernel takes the frame
-        if (tid == 0) { a.redo[1 + atomicAdd(a.redo, 1)] = (int32_t)f; a.o.status[f] = kStRedo; a.nsel[f] = 0; }
+        hand_to_exact(a, f);
         return;
     }
-    if (mask_mismatch || bad) {
-        status = MVOSR_ST_ERR_MASK;
-    } else if (singular) {
-        status = MVOSR_ST_ERR_SINGULAR;
-    } else {
+    if (!frame_refused(mask_mismatch || bad, singular, status)) {
         // a vertex is selected when its largest flat height exceeds the level (:243-247): one comparison per candidate.
         // A wavefront owns a contiguous range of 64-feature groups.  The candidates' heights and y' were parked in two
         // planes, so the count reads one and the ordered store the other — every byte once — in batches of kTailBatch
@@ -2413,14 +2335,14 @@ __global__ __launch_bounds__(DW *kWave, (DW == 8 ? 4 : 1)) void scale_frames_til
             }
         }
         const int wave_near = __ballot(near != 0) != 0ull;
-        if (lane == 0) { misc[M_WCNT + w] = cnt; misc[M_WCNT + DW + w] = wave_near; }
+        if (lane == 0) { sm.misc[M_WCNT + w] = cnt; sm.misc[M_WCNT2 + w] = wave_near; }
         __syncthreads();
         int base = 0, any_near = 0;
 #pragma unroll
-        for (int i = 0; i < DW; ++i) { const int c = misc[M_WCNT + i]; if (i < w) base += c; nsel += c; any_near |= misc[M_WCNT + DW + i]; }
+        for (int i = 0; i < DW; ++i) { const int c = sm.misc[M_WCNT + i]; if (i < w) base += c; nsel += c; any_near |= sm.misc[M_WCNT2 + i]; }
         MVOSR_TSTAMP(8);
         if (any_near || nsel == 0) {                  // the level's last bits could matter, or the level is the result: EXACT pass
-            if (tid == 0) { a.redo[1 + atomicAdd(a.redo, 1)] = (int32_t)f; a.o.status[f] = kStRedo; a.nsel[f] = 0; }
+            hand_to_exact(a, f);
             return;
         }
         double *dst = a.ysel + off;
@@ -2447,16 +2369,7 @@ __global__ __launch_bounds__(DW *kWave, (DW == 8 ? 4 : 1)) void scale_frames_til
 #ifdef MVOSR_STAMPS
     if (tid == 0 && a.o.hist) { unsigned long long *d = reinterpret_cast<unsigned long long *>(a.o.hist + f * 2 * kBins); for (int i = 0; i < 12; ++i) d[i] = tacc[i]; }
 #endif
-    if (tid == 0) {
-        a.o.raw_scale[f] = raw;
-        a.o.height[f] = nan("");
-        a.o.height_level[f] = hl / 3.0;
-        a.o.status[f] = status;
-        a.nsel[f] = nsel;
-        R.n_sel = nsel;
-        write_counts(a, f, nvalid, npitch, -1, R);       // (the number of flat triangles above the level is not formed here)
-        if (a.o.stats) { double *st = a.o.stats + 4 * f; st[0] = st[1] = st[2] = st[3] = nan(""); }
-    }
+    finish_frame(a, f, raw, hl / 3.0, status, nvalid, npitch, -1, nsel);     // (-1: the number of flat triangles above the level is not formed here)
 }
 
 // The vote alone on a frame larger than the batch header says (max_feat sized this launch's LDS): refused before LDS is carved —
@@ -2483,16 +2396,13 @@ __global__ __launch_bounds__(DW *kWave) void outlier_vote_dense_kernel(const Den
     if (vote_frame_oversize(a, f, n, off)) return;
     const int64_t t1b = a.b.tri1_off[f];
     const int t1n = tri_rows(a.b.tri1_off, a.b.tri1_cnt, f);
-    const uint32_t npad = (uint32_t)((n + 1) & ~1);
-    uint32_t *c32 = reinterpret_cast<uint32_t *>(smem);
-    double *red = reinterpret_cast<double *>(smem + align16(2u * npad + 16u) + align16(4u * ((uint32_t)(n + 31) / 32u)));
-    int *misc = reinterpret_cast<int *>(red + kRedSlots * 2 * DW);
+    const Smem s = carve_dense(smem, n, DW);
     int bad = 0;
-    const int nvalid = phase_vote_dense<DW, false>(c32, misc, n, nullptr, a.b.y + off, a.b.z + off, a.b.v + off, a.b.tri1, t1b, t1n,
+    const int nvalid = phase_vote_dense<DW, false>(s.c32, s.misc, n, nullptr, a.b.y + off, a.b.z + off, a.b.v + off, a.b.tri1, t1b, t1n,
                                                a.P.cos_pitch, a.P.sin_pitch, a.o.vote_counters + off, bad,
                                                nullptr, nullptr, a.P.vote_mode == MVOSR_VOTE_FIXED);
     int b0 = bad, b1 = 0, b2 = 0, b3 = 0;
-    block_sum4i<DW>(b0, b1, b2, b3, red + R_MISC * 2 * DW);
+    block_sum4i<DW>(b0, b1, b2, b3, s.red + R_MISC * 2 * DW);
     if (threadIdx.x == 0) {
         if (a.o.counts) a.o.counts[f * MVOSR_N_COUNTS + MVOSR_CNT_VALID] = nvalid;
         if (a.o.status) a.o.status[f] = b0 ? MVOSR_ST_ERR_MASK : MVOSR_ST_MODE;
@@ -2785,7 +2695,7 @@ template <int DW>
 static int launch_scale_dense_w(mvosr_ctx *ctx, const KArgs &ka, int64_t nl, int mode, bool vote_only) {
     if ((int64_t)2 * ka.b.max_feat > (int64_t)128 * kWave * DW)
         return set_error(MVOSR_ERR_TOO_LARGE, "%d features give more triangles than %d wavefronts sweep", ka.b.max_feat, DW);
-    const size_t lds = dense_lds_bytes(ka.b.max_feat, DW);
+    const size_t lds = dense_plan(ka.b.max_feat, DW).total;
     if ((int64_t)lds > (int64_t)g_max_dyn_lds)
         return set_error(MVOSR_ERR_TOO_LARGE, "frame of %d features needs %zu B of LDS (> %d)", ka.b.max_feat, lds, g_max_dyn_lds);
     DenseArgs da;
@@ -2964,7 +2874,7 @@ int mvosr_scale_batch(mvosr_ctx *ctx, const mvosr_params *p, const mvosr_batch *
     if ((rc = ctx_activate(ctx))) return rc;
     KArgs ka;
     ka.P = *p; ka.b = *b; ka.o = *o; ka.pt = make_pitch_test(p->pitch_threshold_deg);
-    ka.first_frame = first_frame; ka.height_level_in = nullptr;
+    ka.first_frame = first_frame;
     ka.redo_pass = 0; ka.cls_list = nullptr; ka.cls_cnt = nullptr;
     if (b->total_feat <= 0) return set_error(MVOSR_ERR_ARG, "scale_batch: batch.total_feat (length of the feature planes) not set");
     if (b->n_frames >= ((int64_t)1 << 31) - 1) return set_error(MVOSR_ERR_TOO_LARGE, "scale_batch: more than 2^31-2 frames in one batch");
@@ -3105,7 +3015,7 @@ int mvosr_outlier_vote_batch(mvosr_ctx *ctx, const mvosr_params *p, const mvosr_
     if ((rc = ctx_activate(ctx))) return rc;
     KArgs ka;
     ka.P = *p; ka.b = *b; ka.o = *o; ka.pt = make_pitch_test(p->pitch_threshold_deg);
-    ka.first_frame = 0; ka.height_level_in = nullptr; ka.ysel = nullptr; ka.nsel = nullptr; ka.redo = nullptr; ka.redo_pass = 0;
+    ka.first_frame = 0; ka.ysel = nullptr; ka.nsel = nullptr; ka.redo = nullptr; ka.redo_pass = 0;
     ka.cls_list = nullptr; ka.cls_cnt = nullptr;
     if ((waves_per_frame == 0 || waves_per_frame == 16) && b->max_feat > lds_capacity_features()) {
         if (b->total_feat <= 0) return set_error(MVOSR_ERR_ARG, "outlier_vote: batch.total_feat not set");
