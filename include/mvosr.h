@@ -919,6 +919,39 @@ int mvosr_pose2motion_batch(mvosr_ctx *ctx, int64_t n_cases, int64_t n, const do
                             double *norms, int32_t *status);
 
 /*
+ * Scoring the scales (/root/reference/script/evaluate_scale.py, run by tesh.sh:4-8 on every scales file against the ground truth's
+ * speed file).  Device arrays of doubles unless stated; windows and thresholds are HOST arrays.  Every float is the reference's
+ * own double: single IEEE operations, and sums in np.add.reduce's order (pairwise: below 8 a plain loop, up to 128 eight
+ * accumulators, above that halves with the first rounded down to a multiple of 8; lists above 8192 in chunks added left to right).
+ *
+ * mvosr_scale_errors_batch (scale_errors_kernel; evaluate_scale.py:4-13 with patch, :19-23), C cases in one launch: gt [n_gt],
+ * scales [C][case_stride] of which n are used, e = gt[i] - scales[c][i], a = |e|.
+ *   stats [C][2]: np.mean(a), np.max(a) — NaN where an a is NaN.
+ *   counts [C][n_thresholds] int32: sum(a > thresholds[k]); the shares 1 - count / n are the caller's.
+ *   drift [C][n_windows]: for window w the np.mean over i = 0, step, 2 step .. < n - w of |np.sum(e[i : i + w])| / w; NaN where
+ *   n - w <= 0 (np.mean of an empty list).
+ *   status [C] int32: 0, or MVOSR_ST_ERR_EMPTY for n = 0 — mean and max NaN, counts zero (the reference's np.max raises).
+ * A case's errors and a window's segment values live in LDS up to 5120 scales and 1024 segments, in the context's scratch beyond;
+ * MVOSR_SCALE_ERRORS_GLOBAL in flags asks for the second form at any size.  Both give the same bytes.
+ * MVOSR_ERR_ARG: a null argument that is needed, n < 0, n > n_gt (the reference's subtraction fails to broadcast), C < 1,
+ * case_stride < n, more than MVOSR_SCALE_MAX_WINDOWS windows or MVOSR_SCALE_MAX_THRESHOLDS thresholds, a window outside 1..8192,
+ * step < 1.  MVOSR_ERR_TOO_LARGE: more than 2^31-1 scales or 65535 cases.
+ *
+ * mvosr_window_median_cases (window_median_cases_kernel; evaluate_scale.py:24-28, filter), C sequences in one launch:
+ * out[c][i] = np.median(data[c][max(i - window + 1, 0) : i + 1]) — mvosr_window_median's median with an empty queue; rows
+ * case_stride / out_stride doubles apart.  MVOSR_ERR_ARG: null data / out with n > 0, window outside 1..64, n < 0, C < 1, a stride
+ * below n.
+ */
+#define MVOSR_SCALE_MAX_WINDOWS 16
+#define MVOSR_SCALE_MAX_THRESHOLDS 8
+#define MVOSR_SCALE_ERRORS_GLOBAL 1
+int mvosr_scale_errors_batch(mvosr_ctx *ctx, int64_t n_gt, const double *gt, int64_t n_cases, int64_t n, const double *scales,
+                             int64_t case_stride, int n_windows, const int32_t *windows, int step, int n_thresholds,
+                             const double *thresholds, int flags, double *stats, int32_t *counts, double *drift, int32_t *status);
+int mvosr_window_median_cases(mvosr_ctx *ctx, const double *data, int64_t n_cases, int64_t n, int64_t case_stride, int window,
+                              double *out, int64_t out_stride);
+
+/*
  * The cross-frame tail of scale_calculation_ransac (rescale.py:169-178) over a run of frames, on the device: the slew
  * limiter — a frame with apply[i] != 0 moves the running scale towards raw[i] by at most `slew` (0.3), any other frame
  * leaves it — followed by the window median of the pushed values (np.median(self.scale_queue)).  raw/apply/pushed/

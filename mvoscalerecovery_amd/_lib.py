@@ -30,6 +30,10 @@ DC_BINS, DC_TABLE_WORDS = 59, 62         # MVOSR_DC_BINS, MVOSR_DC_TABLE_WORDS: 
 ST_DC_NO_POINT = 12                      # MVOSR_ST_DC_NO_POINT
 SCORE_LENGTHS, SCORE_STEP = 8, 10   # MVOSR_SCORE_LENGTHS, MVOSR_SCORE_STEP
 ST_ERR_SINGULAR, ST_ERR_MASK = 7, 8  # MVOSR_ST_ERR_SINGULAR, MVOSR_ST_ERR_MASK
+ST_ERR_EMPTY = 9                     # MVOSR_ST_ERR_EMPTY
+SCALE_MAX_WINDOWS, SCALE_MAX_THRESHOLDS, SCALE_ERRORS_GLOBAL = 16, 8, 1   # MVOSR_SCALE_MAX_WINDOWS, .._MAX_THRESHOLDS, .._ERRORS_GLOBAL
+SCALE_LDS_ERRORS, SCALE_LDS_SEGMENTS, SCALE_MAX_WINDOW = 5120, 1024, 8192  # csrc/mvosr_scalescore_plan.hpp
+MAX_MEDIAN_WINDOW = 64               # kMaxWindow (csrc/mvosr_window_median.hpp)
 
 
 ERR_ALLOC = -5
@@ -253,6 +257,9 @@ SYMBOLS = {
     "mvosr_segment_table": (C.c_int, [_P, C.c_int64, _P, _P, _P, _P, _P]),
     "mvosr_score_cases_batch": (C.c_int, [_P, C.c_int64, C.c_int64, _P, C.c_int64, _P, _P, _P, _P, _P, _P, _P]),
     "mvosr_pose2motion_batch": (C.c_int, [_P, C.c_int64, C.c_int64, _P, _P, _P, _P, _P]),
+    "mvosr_scale_errors_batch": (C.c_int, [_P, C.c_int64, _P, C.c_int64, C.c_int64, _P, C.c_int64, C.c_int, _P, C.c_int, C.c_int, _P, C.c_int,
+                                           _P, _P, _P, _P]),
+    "mvosr_window_median_cases": (C.c_int, [_P, _P, C.c_int64, C.c_int64, C.c_int64, C.c_int, _P, C.c_int64]),
     "mvosr_slew_median": (C.c_int, [_P, _P, _P, C.c_int64, C.c_double, C.c_double, C.c_int, _P, C.c_int, _P, _P]),
     "mvosr_slew_median_host": (C.c_int, [_P, _P, C.c_int64, C.c_double, C.c_double, C.c_int, _P, C.c_int, _P, _P, _P]),
     "mvosr_ransac_plane_batch": (C.c_int, [_P, C.c_int64, _P, _P, _P, _P, _P, _P, C.c_int, C.c_double, C.c_double,

@@ -30,6 +30,7 @@
 #include "mvosr_host.hpp"
 #include "mvosr_npsum.hpp"
 #include "mvosr_scale_plan.hpp"
+#include "mvosr_window_median.hpp"
 
 namespace mvosr {
 
@@ -2439,7 +2440,6 @@ __global__ __launch_bounds__(WAVES *kWave) void outlier_vote_kernel(const KArgs 
 // either one contiguous array or, after the all-gather of the per-rank records, `n_blocks` blocks
 // `stride` doubles apart holding the ranks' contiguous shares (the first `extra` blocks one frame more
 // than `base_len`): element i is read in place, the gathered buffer is never repacked.
-constexpr int kMaxWindow = 64;
 struct MedianArgs {
     const double *raw; double *out; int64_t n; int window; int n_queue;
     int n_blocks; int64_t base_len, extra, stride;
@@ -2461,21 +2461,10 @@ __global__ __launch_bounds__(256) void window_median_kernel(const MedianArgs a) 
     int64_t first = last - a.window + 1;
     if (first < 0) first = 0;
     const int m = (int)(last - first + 1);
-    double w[kMaxWindow];
-    bool has_nan = false;
-    for (int k = 0; k < m; ++k) {
+    a.out[i] = window_median_of(m, [&](int k) {      // mvosr_window_median.hpp
         const int64_t p = first + k;
-        const double x = (p < a.n_queue) ? a.queue[p] : median_seq_at(a, p - a.n_queue);
-        has_nan |= (x != x);
-        int j = k;                                   // insertion sort
-        while (j > 0 && w[j - 1] > x) { w[j] = w[j - 1]; --j; }
-        w[j] = x;
-    }
-    double r;
-    if (has_nan) r = nan("");                        // np.median propagates NaN
-    else if (m & 1) r = w[m >> 1];
-    else r = (w[(m >> 1) - 1] + w[m >> 1]) / 2.0;     // np.mean of the two middle values
-    a.out[i] = r;
+        return (p < a.n_queue) ? a.queue[p] : median_seq_at(a, p - a.n_queue);
+    });
 }
 
 // ---------------------------------------------------------------------------------------------

@@ -86,6 +86,16 @@ def evaluate_scale(gt, re):
     return head, drift
 
 
+def scale_filter(data, window=10):
+    """evaluate_scale.py:24-28, ``filter`` (named so as not to shadow the builtin): the running median over the last ``window``
+    values, the first entry the value itself."""
+    data = np.asarray(data)
+    out = [data[0]]
+    for i in range(1, data.shape[0]):
+        out.append(np.median(data[max(i - window + 1, 0):i + 1]))
+    return np.array(out)
+
+
 def pose2motion(poses):
     """transformation.py:23-32."""
     poses = np.asarray(poses)
@@ -307,6 +317,28 @@ class Scorer:
         one small download."""
         return self._dict(self._score(self._paths_on_device(motions, scales))[0])
 
+    def score_gt_rescaled(self, scales):
+        """tesh.sh:6-8 for every case ("evaluation gt+vo_scale"): the ground truth's own motions with their translations re-scaled
+        to case c's scales — ``scale * t / (|t| + 0.00001)``, change_scale.py:12-18 —, integrated and scored against the ground
+        truth: what is left is the scale's share of the path error.  ``scales``: ``(C, n)`` (host array or device buffer) with
+        ``n == n_poses - 1``.  One mvosr_pose2motion_batch per case (its speed argument is one case's), then mvosr_paths_batch and
+        mvosr_score_cases_batch once.  The dict of :meth:`score_scales`."""
+        from . import _lib
+        ctx = self.ctx
+        d_s, C, n, _ = _scales_stack(scales)
+        if n != self.n_poses - 1:
+            raise ValueError("score_gt_rescaled: %d scales per case for %d motions of the ground truth (change_scale.py:15 broadcasts "
+                             "one per frame)" % (n, self.n_poses - 1))
+        d_s = _on_device(ctx, d_s)
+        d_motions, d_status = ctx.empty((C, n, 12), np.float64), ctx.empty(C, np.int32)
+        for c in range(C):
+            _lib.check(ctx.lib.mvosr_pose2motion_batch(ctx.handle, 1, n, self._gt.ptr, d_s.ptr + c * n * 8, d_motions.ptr + c * n * 96,
+                                                       None, d_status.ptr + 4 * c), "mvosr_pose2motion_batch")
+        d_paths = ctx.empty((C, n + 1, 12), np.float64)
+        _lib.check(ctx.lib.mvosr_paths_batch(ctx.handle, n, C, d_motions.ptr, n * 12, None, d_paths.ptr), "mvosr_paths_batch")
+        _raise_status(d_status.download(), "score_gt_rescaled")
+        return self._dict(self._score(d_paths)[0])
+
     def errors(self, paths=None, motions=None, scales=None):
         """Per case the rows ``[first, r_err/len, t_err/len, len, speed]`` of calculate_sequence_error, in its order."""
         d_paths = self._to_device(paths) if paths is not None else self._paths_on_device(motions, scales)
@@ -314,3 +346,95 @@ class Scorer:
         seg = self.segments
         first, length, speed = seg["first"].tolist(), [LENGTHS[i] for i in seg["length_index"].tolist()], seg["speed"].tolist()
         return [list(map(list, zip(first, r[c][self.has].tolist(), t[c][self.has].tolist(), length, speed))) for c in range(r.shape[0])]
+
+
+# ---- the scales' own score on the device (csrc/mvosr_scalescore.hip; evaluate_scale.py, tesh.sh:4-8) ---------------------------------
+SCALE_WINDOWS = [10, 20, 50, 100, 200, 300, 400, 500, 600, 700, 800]        # evaluate_scale.py:10
+SCALE_STEP = 10                                                             # evaluate_scale.py:11
+SCALE_THRESHOLDS = [0.1, 0.2, 0.3, 0.5]                                     # evaluate_scale.py:7
+
+
+def _scales_stack(scales):
+    """``(n,)`` or ``(C, n)`` host scales, or a device buffer ``(C, n)`` of doubles -> (the ``(C, n)`` array or the buffer, C, n,
+    whether the input was one row).  Nothing is uploaded here: the callers check their arguments first."""
+    from . import _lib
+    if isinstance(scales, (_lib.DeviceBuffer, _lib.DeviceView)):
+        if len(scales.shape) != 2 or scales.dtype != np.float64 or scales.shape[0] < 1:
+            raise ValueError("scales on the device are (C, n) doubles; got %r %s" % (scales.shape, scales.dtype))
+        return scales, scales.shape[0], scales.shape[1], False
+    s = np.asarray(scales, dtype=np.float64)
+    single = s.ndim == 1
+    s = np.ascontiguousarray(s.reshape(1, -1) if single else s)
+    if s.ndim != 2 or s.shape[0] < 1:
+        raise ValueError("scales is (n,) or (C, n) with at least one case; got %r" % (np.shape(scales),))
+    return s, s.shape[0], s.shape[1], single
+
+
+def _on_device(ctx, s):
+    return s if not isinstance(s, np.ndarray) else ctx.to_device(s)
+
+
+def scale_errors(speed_gt, scales, windows=SCALE_WINDOWS, step=SCALE_STEP, thresholds=SCALE_THRESHOLDS, ctx=None, device=0, variant=None):
+    """:func:`evaluate_scale` for C cases in one launch (mvosr_scale_errors_batch), every float the reference's own double.
+
+    ``speed_gt``: the ground truth's speeds (host array, or a device buffer of doubles), at least as many as a case has scales —
+    the reference's subtraction raises ValueError otherwise, and so does this.  ``scales``: ``(n,)``, ``(C, n)`` or a device
+    buffer ``(C, n)``.  ``variant``: None (by size), "global" — the global-memory form at any size.
+    Returns ``{"mean", "max": (C,); "exceed_counts": (C, T) int; "within": (C, T) = 1 - count / n; "drift": (C, W); "n"}`` — for
+    ``(n,)`` scales without the leading axis.  No scale at all (n = 0): mean and max NaN, counts zero (the reference raises)."""
+    from . import _lib
+    d_s, C, n, single = _scales_stack(scales)
+    if isinstance(speed_gt, (_lib.DeviceBuffer, _lib.DeviceView)):
+        d_gt, n_gt = speed_gt, int(np.prod(speed_gt.shape))
+    else:
+        gt = np.ascontiguousarray(np.asarray(speed_gt, dtype=np.float64).reshape(-1))
+        d_gt, n_gt = None, gt.size
+    if n > n_gt:
+        raise ValueError("operands could not be broadcast together with shapes (%d,) (%d,) (evaluate_scale.py:6: more scales than "
+                         "ground-truth speeds)" % (n_gt, n))
+    w = np.ascontiguousarray(windows, dtype=np.int32).reshape(-1)
+    t = np.ascontiguousarray(thresholds, dtype=np.float64).reshape(-1)
+    if w.size > _lib.SCALE_MAX_WINDOWS or t.size > _lib.SCALE_MAX_THRESHOLDS or int(step) < 1 or (w.size and (w.min() < 1 or w.max() > _lib.SCALE_MAX_WINDOW)):
+        raise ValueError("scale_errors: at most %d windows in 1..%d, %d thresholds, step >= 1"
+                         % (_lib.SCALE_MAX_WINDOWS, _lib.SCALE_MAX_WINDOW, _lib.SCALE_MAX_THRESHOLDS))
+    if variant not in (None, "global"):
+        raise ValueError("scale_errors: variant is None or 'global'")
+    W, T = int(w.size), int(t.size)
+    ctx = _context(ctx, device)
+    d_s = _on_device(ctx, d_s)
+    if d_gt is None:
+        d_gt, n_gt = ctx.to_device(gt[:n]), n
+    res = ctx.block([("stats", (C, 2), np.float64), ("drift", (C, max(W, 1)), np.float64), ("counts", (C, max(T, 1)), np.int32),
+                     ("status", (C,), np.int32)])
+    _lib.check(ctx.lib.mvosr_scale_errors_batch(ctx.handle, n_gt, d_gt.ptr, C, n, d_s.ptr, n, W, _lib.addr(w) if W else None, int(step), T,
+                                                _lib.addr(t) if T else None, _lib.SCALE_ERRORS_GLOBAL if variant == "global" else 0,
+                                                res["stats"].ptr, res["counts"].ptr, res["drift"].ptr, res["status"].ptr),
+               "mvosr_scale_errors_batch")
+    stats, drift = res["stats"].download(), res["drift"].download().reshape(C, -1)[:, :W]
+    counts, status = res["counts"].download().reshape(C, -1)[:, :T].astype(np.int64), res["status"].download()
+    assert ((status == 0) | (status == _lib.ST_ERR_EMPTY)).all() and ((status == _lib.ST_ERR_EMPTY).all() if n == 0 else (status == 0).all())
+    with np.errstate(all="ignore"):
+        within = 1 - counts / n if n else np.full(counts.shape, np.nan)                     # evaluate_scale.py:7, from the integers
+    out = {"mean": stats[:, 0].copy(), "max": stats[:, 1].copy(), "exceed_counts": counts, "within": within,
+           "drift": np.ascontiguousarray(drift), "n": n}
+    if single:
+        out = {k: (v[0] if k != "n" else v) for k, v in out.items()}
+    return out
+
+
+def filter_scales(scales, window=10, ctx=None, device=0, on_device=False):
+    """:func:`scale_filter` for C sequences in one launch (mvosr_window_median_cases), bit for bit.  ``scales``: ``(n,)``, ``(C, n)``
+    or a device buffer ``(C, n)``; the result has the input's shape — with ``on_device`` it is left there as a ``(C, n)`` buffer.
+    The device median holds its window in registers: ``window`` is 1..64."""
+    from . import _lib
+    if not 1 <= int(window) <= _lib.MAX_MEDIAN_WINDOW:
+        raise ValueError("filter_scales: window must be in 1..%d, got %r" % (_lib.MAX_MEDIAN_WINDOW, window))
+    d_s, C, n, single = _scales_stack(scales)
+    ctx = _context(ctx, device)
+    d_s = _on_device(ctx, d_s)
+    d_out = ctx.empty((C, n), np.float64)
+    _lib.check(ctx.lib.mvosr_window_median_cases(ctx.handle, d_s.ptr, C, n, n, int(window), d_out.ptr, n), "mvosr_window_median_cases")
+    if on_device:
+        return d_out
+    out = d_out.download()
+    return out[0] if single else out

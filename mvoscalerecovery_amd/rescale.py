@@ -1233,11 +1233,7 @@ class RepeatedRuns:
         kept for the next call with the same ``poses_gt``."""
         from . import _lib, evaluate
         ctx = self.estimator.ctx
-        gt = np.ascontiguousarray(np.asarray(poses_gt, dtype=np.float64).reshape(-1, 12))
-        cached = getattr(self, "_scorer", None)
-        if cached is None or not np.array_equal(cached[0], gt):
-            cached = self._scorer = (gt, evaluate.Scorer(gt, ctx=ctx))
-        scorer = cached[1]
+        scorer = self._scorer_for(poses_gt)
         motions = np.concatenate(self._motions) if self._motions else np.zeros((0, 12))
         d_paths = scorer._paths_on_device(motions, self.scales())
         out = scorer.score_paths(d_paths)
@@ -1253,6 +1249,50 @@ class RepeatedRuns:
             _lib.check(ctx.lib.mvosr_paths_batch(ctx.handle, n, C, d_motions.ptr, n * 12, None, d_paths.ptr), "mvosr_paths_batch")
             evaluate._raise_status(d_status.download(), "scores")
             out["speed_scaled"] = scorer.score_paths(d_paths)
+        return out
+
+    def _scorer_for(self, poses_gt):
+        """The evaluate.Scorer of ``poses_gt``, kept for the next call with the same ground truth."""
+        from . import evaluate
+        gt = np.ascontiguousarray(np.asarray(poses_gt, dtype=np.float64).reshape(-1, 12))
+        cached = getattr(self, "_scorer", None)
+        if cached is None or not np.array_equal(cached[0], gt):
+            cached = self._scorer = (gt, evaluate.Scorer(gt, ctx=self.estimator.ctx))
+        return cached[1]
+
+    def scale_scores(self, speed_gt, poses_gt=None, filter_window=None):
+        """What /root/reference/tesh.sh:4-8 computes from every case's scales file, on the device: ``"scales"``, the figures of
+        ``evaluate.scale_errors(speed_gt, self.scales())`` (script/evaluate_scale.py:4-13) for everything run so far.
+        ``filter_window``: adds ``"filtered"``, the same figures for the scales after evaluate_scale.py's running median
+        (``evaluate.filter_scales``).  ``poses_gt``: adds ``"gt_rescaled"`` (and ``"gt_rescaled_filtered"``), the ground truth's own
+        path re-scaled to every case's scales and scored against itself (``Scorer.score_gt_rescaled``, tesh.sh:6-8).
+        ``"trimmed"`` holds, per set of figures, the ``evaluate.trimmed_mean`` of each over the cases, as :meth:`scores` has it for
+        the path errors.  The tails assemble the scales on the host; they are uploaded once and every launch — errors, median,
+        re-scaling, integration, scoring — reads them or their filtered copy on the device."""
+        from . import evaluate
+        ctx = self.estimator.ctx
+        scales = self.scales()
+        n = scales.shape[1]
+        gt = np.asarray(speed_gt, dtype=np.float64).reshape(-1)
+        if n > gt.size:
+            raise ValueError("operands could not be broadcast together with shapes (%d,) (%d,) (evaluate_scale.py:6: more scales "
+                             "than ground-truth speeds)" % (gt.size, n))
+        d_gt, d_s = ctx.to_device(gt[:n]), ctx.to_device(scales)
+        scorer = self._scorer_for(poses_gt) if poses_gt is not None else None
+        out = {"scales": evaluate.scale_errors(d_gt, d_s, ctx=ctx)}
+        if scorer is not None:
+            out["gt_rescaled"] = scorer.score_gt_rescaled(d_s)
+        if filter_window is not None:
+            d_f = evaluate.filter_scales(d_s, filter_window, ctx=ctx, on_device=True)
+            out["filtered"] = evaluate.scale_errors(d_gt, d_f, ctx=ctx)
+            if scorer is not None:
+                out["gt_rescaled_filtered"] = scorer.score_gt_rescaled(d_f)
+
+        def trim(figs):
+            cols = lambda a: np.array([evaluate.trimmed_mean(a[:, k]) for k in range(a.shape[1])])
+            return {"mean": evaluate.trimmed_mean(figs["mean"]), "max": evaluate.trimmed_mean(figs["max"]),
+                    "within": cols(figs["within"]), "drift": cols(figs["drift"])}
+        out["trimmed"] = {k: trim(out[k]) for k in ("scales", "filtered") if k in out}
         return out
 
     def write_results(self, res_addr, tag):
