@@ -636,6 +636,33 @@ int mvosr_flat_ransac_cases_batch(mvosr_ctx *ctx, const mvosr_batch *b, const in
 /* dynamic LDS a launch asks for at (b->max_feat, max_tri (<= 0: 2 * max_feat), n_hyp) */
 size_t mvosr_flat_ransac_cases_lds_bytes(int max_feat, int64_t max_tri, int n_hyp);
 
+/* ---- flat_selection for several settings of its constants in one launch (the thresholds of rescale.py:85-96, the factor of :91) ---- */
+
+/*
+ * mvosr_flat_selection_batch's selection for n_sel settings (loose_deg[s], tight_deg[s], height_factor[s]; host arrays, n_sel in
+ * 1..mvosr_flat_selection_sweep_max_settings() = 16) on the device-resident form of a batch: it reads what mvosr_flat_ransac_batch
+ * reads — the features with keep[i] >= 0 compacted in order (keep == NULL: all), b->tri2 with b->tri2_cnt[f] rows at b->tri2_off[f]
+ * or the offsets' difference, dt_status (optional; non-zero: the frame is skipped) — and fits nothing.  Every row's height and the
+ * sine of its pitch are computed once per frame; per setting the two threshold bits are decided as that call decides them, the level
+ * is height_factor[s] * np.median(heights[pitch < loose_deg[s]]) (NaN for an empty set) and bit 2 is bit 1 && height > level, so for
+ * every s the flags, the level and the count equal, bit for bit, mvosr_flat_selection_batch's and mvosr_flat_ransac_batch's with that
+ * setting's constants.  loose_deg[s] < tight_deg[s] is legal and means what the formulas say.
+ * Outputs: tri_flags [n_sel][R] — one plane per setting, laid out like tri2, R = b->tri2_off[F] rows where the counts are the
+ * offsets' differences and 2 * b->total_feat rows with b->tri2_cnt (the form mvosr_delaunay_batch writes: a frame's rows start at
+ * twice its feature offset); plane s is what mvosr_flat_ransac_cases_batch takes as tri_flags —; height_level [F][n_sel]; n_kept
+ * [F][n_sel]; status [F]: 0, MVOSR_ST_ERR_SINGULAR, MVOSR_ST_ERR_MASK (a row with a vertex id outside the survivors) or
+ * MVOSR_ST_ERR_EMPTY (no features, no rows, skipped), the frame's, whatever the setting; tri_height (optional) [R] 1/|n|.
+ * b->max_feat and max_tri (<= 0: 2 * b->max_feat) size the launch's LDS: a frame with feat_cnt[f] > b->max_feat, more rows than
+ * max_tri, or rows outside a plane is refused before LDS is touched — status MVOSR_ST_ERR_MASK, its levels NaN, its counts 0, its
+ * tri_flags / tri_height rows not written.
+ */
+int mvosr_flat_selection_sweep_batch(mvosr_ctx *ctx, const mvosr_batch *b, const int32_t *keep, const int32_t *dt_status, int32_t n_sel,
+                                     const double *loose_deg, const double *tight_deg, const double *height_factor, uint8_t *tri_flags,
+                                     double *height_level, int32_t *n_kept, int32_t *status, double *tri_height, int64_t max_tri);
+/* dynamic LDS a launch asks for at (b->max_feat, max_tri (<= 0: 2 * max_feat), n_sel) */
+size_t mvosr_flat_selection_sweep_lds_bytes(int max_feat, int64_t max_tri, int n_sel);
+int mvosr_flat_selection_sweep_max_settings(void);
+
 /* ---- GraphGrow: the road region grown over triangle adjacency (/root/reference/src/graph.py:39-107) ---------------- */
 
 typedef struct mvosr_grow_params {

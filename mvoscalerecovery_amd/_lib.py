@@ -246,6 +246,9 @@ SYMBOLS = {
     "mvosr_flat_ransac_cases_batch": (C.c_int, [_P, C.POINTER(Batch), _P, C.POINTER(RescaleParams), _P, C.c_int32, C.c_int32, _P, _P, _P, _P,
                                                 C.POINTER(RescaleCasesOutputs), C.c_int64]),
     "mvosr_flat_ransac_cases_lds_bytes": (C.c_size_t, [C.c_int, C.c_int64, C.c_int]),
+    "mvosr_flat_selection_sweep_batch": (C.c_int, [_P, C.POINTER(Batch), _P, _P, C.c_int32, _P, _P, _P, _P, _P, _P, _P, _P, C.c_int64]),
+    "mvosr_flat_selection_sweep_lds_bytes": (C.c_size_t, [C.c_int, C.c_int64, C.c_int]),
+    "mvosr_flat_selection_sweep_max_settings": (C.c_int, []),
     "mvosr_region_grow_batch": (C.c_int, [_P, C.POINTER(Batch), _P, _P, C.POINTER(GrowParams), C.POINTER(GrowOutputs), C.c_int64]),
     "mvosr_tri_graph_batch": (C.c_int, [_P, C.POINTER(Params), C.POINTER(Batch), _P, _P, C.POINTER(TriGraphOutputs)]),
     "mvosr_static_tri_batch": (C.c_int, [_P, C.c_int64, _P, _P, _P, _P, C.c_int32, C.c_double, _P, _P, _P, _P, _P]),

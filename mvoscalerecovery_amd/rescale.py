@@ -40,10 +40,16 @@ same kernels on SciPy's triangulations brought to the same row form, with bit-id
 on the staged path: the mode of the flat triangles' inverse heights (mvosr_static_tri_batch, launched on flat_selection's device
 buffers; :179-187) and scale_calculator's road model on the selected points through the inner estimator ``self.sc`` (:31).  Both are
 deterministic: tests/golden/statictri.npz holds the reference's own sequences, reproduced bit for bit.
+
+The numbers of rescale.py:85-96,152,155,169-172 are a value, ``RescaleConstants`` (``constants=``; None: the reference's literals),
+and ``ConstantSweep`` runs K settings of them over a sequence in one pass of the stages that do not read them.
 """
 from __future__ import annotations
 
 import ctypes as C
+import dataclasses
+import itertools
+import math
 import os
 import random
 import time
@@ -68,6 +74,54 @@ MIN_VALID_FOR_RETRI = 10                              # rescale.py:133
 STATIC_TRI_MIN_COUNT = 12                             # rescale.py:181 (more than 12 heights)
 SLEW = 0.3                                            # rescale.py:169-172
 _FIELDS = ("raw_scale", "height_level", "model", "best_ic", "used", "n_kept", "status")     # a chunk's results, per frame
+MAX_HYP = 512                                         # mvosr_flat_ransac_batch's limit (include/mvosr.h)
+
+
+@dataclasses.dataclass(frozen=True)
+class RescaleConstants:
+    """The numbers of the estimator that the reference's author moved by hand, as one value.  The defaults are the reference's
+    live ones: the two pitch thresholds and the factor of the height level (rescale.py:85-96; rescale_test.py:132-150 spells
+    them again), the RANSAC's call (:152,155 — rescale.py.origin:218 fits with 30 hypotheses —; estimate_road_norm.py:68) and
+    the slew limiter's step (:169-172).  The vote's constants are not part of it: they decide the second triangulation."""
+    loose_deg: float = -80.0
+    tight_deg: float = -85.0
+    height_factor: float = 0.9
+    ransac_min_points: int = RANSAC_MIN_POINTS
+    n_hyp: int = RANSAC_ITERATIONS
+    threshold: float = RANSAC_THRESHOLD
+    goal_fraction: float = RANSAC_GOAL
+    slew: float = SLEW
+
+    def __post_init__(self):
+        for name in ("loose_deg", "tight_deg", "height_factor", "threshold", "goal_fraction", "slew"):
+            v = getattr(self, name)
+            if isinstance(v, bool) or not isinstance(v, (int, float, np.integer, np.floating)) or not math.isfinite(v):
+                raise ValueError("RescaleConstants.%s must be a finite number, not %r" % (name, v))
+            object.__setattr__(self, name, float(v))
+        for name in ("ransac_min_points", "n_hyp"):
+            v = getattr(self, name)
+            if isinstance(v, bool) or not isinstance(v, (int, np.integer)):
+                raise ValueError("RescaleConstants.%s must be an integer, not %r" % (name, v))
+            object.__setattr__(self, name, int(v))
+        for name in ("loose_deg", "tight_deg"):
+            if not -90.0 <= getattr(self, name) <= 90.0:
+                raise ValueError("RescaleConstants.%s is a pitch in degrees: -90 .. 90" % name)
+        if self.height_factor < 0.0:
+            raise ValueError("RescaleConstants.height_factor must not be negative")
+        if self.ransac_min_points < 3:
+            raise ValueError("RescaleConstants.ransac_min_points: a plane takes three points")
+        if not 1 <= self.n_hyp <= MAX_HYP:
+            raise ValueError("RescaleConstants.n_hyp must be in 1..%d" % MAX_HYP)
+        if self.threshold <= 0.0 or self.goal_fraction <= 0.0 or self.slew <= 0.0:
+            raise ValueError("RescaleConstants: threshold, goal_fraction and slew must be positive")
+
+    def selection(self):
+        """What flat_selection reads."""
+        return (self.loose_deg, self.tight_deg, self.height_factor)
+
+    def ransac(self):
+        """What the plane fit reads."""
+        return (self.ransac_min_points, self.n_hyp, self.threshold, self.goal_fraction)
 
 
 def good_bits(edge_potential=EDGE_POTENTIAL, prob_threshold=0.6):
@@ -98,7 +152,14 @@ class ScaleEstimator(stream.StreamKnobs):
     N_HYP = RANSAC_ITERATIONS
 
     def __init__(self, absolute_reference, window_size=6, device=0, ransac_seed=None, sampler=None,
-                 delaunay_workers=None, verbose=False, triangulation=None, sampling=None, region="threshold", model="ransac"):
+                 delaunay_workers=None, verbose=False, triangulation=None, sampling=None, region="threshold", model="ransac",
+                 constants=None):
+        # constants: a RescaleConstants (None: the reference's literals — the instance then is what the class always was)
+        if constants is not None and not isinstance(constants, RescaleConstants):
+            raise TypeError("constants must be a RescaleConstants")
+        self.constants = constants if constants is not None else RescaleConstants()
+        if constants is not None:
+            self.N_HYP = self.constants.n_hyp
         # region "threshold": the road rows are the reference's two thresholds (rescale.py:94-96); "grow": GraphGrow's region over
         # the rows' adjacency (graph.py:85-107, the call rescale.py:99 leaves commented out) — on the staged path only, which it
         # selects (checked first: no device is needed to refuse a combination).
@@ -182,7 +243,7 @@ class ScaleEstimator(stream.StreamKnobs):
         if self._sampler is not None:
             t = np.asarray(self._sampler(m), dtype=np.int32)
         else:                                                      # ransac.py:10, RANSAC_ITERATIONS draws
-            t = np.array([self._rng.sample(range(m), 3) for _ in range(RANSAC_ITERATIONS)], dtype=np.int32)
+            t = np.array([self._rng.sample(range(m), 3) for _ in range(self.constants.n_hyp)], dtype=np.int32)
         return np.ascontiguousarray(t.reshape(-1, 3))
 
     # ---- the three GPU stages over a list of frames ------------------------------------------------
@@ -216,7 +277,7 @@ class ScaleEstimator(stream.StreamKnobs):
         status = ctx.zeros(pf2.n_frames, np.int32)
         max_tri = int(np.max(np.diff(pf2.tri2_off))) if pf2.n_frames else 0
         b = db.struct()
-        _lib.check(lib.mvosr_flat_selection_batch(ctx.handle, C.byref(b), -80.0, -85.0, 0.9, tri_h.ptr, tri_f.ptr, level.ptr,
+        _lib.check(lib.mvosr_flat_selection_batch(ctx.handle, C.byref(b), *self.constants.selection(), tri_h.ptr, tri_f.ptr, level.ptr,
                                                   nkept.ptr, status.ptr, max_tri), "mvosr_flat_selection_batch")
         if static_tri:                                                                      # rescale.py:194
             try:
@@ -255,7 +316,7 @@ class ScaleEstimator(stream.StreamKnobs):
         best = ctx.zeros(F, np.int32)
         used = ctx.zeros(F, np.int32)
         _lib.check(lib.mvosr_ransac_plane_batch(ctx.handle, F, d_off.ptr, d_cnt.ptr, d["x"].ptr, d["y"].ptr, d["z"].ptr,
-                                                d_tri.ptr, H, RANSAC_THRESHOLD, RANSAC_GOAL, None, model.ptr, best.ptr,
+                                                d_tri.ptr, H, self.constants.threshold, self.constants.goal_fraction, None, model.ptr, best.ptr,
                                                 used.ptr), "mvosr_ransac_plane_batch")
         ctx.sync()
         out = model.download(), best.download(), used.download()
@@ -341,10 +402,11 @@ class ScaleEstimator(stream.StreamKnobs):
             norm_norm = np.sqrt(norm @ norm) / h_bar                                        # :162-163
             ransac_camera_height = 1 / norm_norm                                            # :165
             scale = self.absolute_reference / ransac_camera_height                          # :167
-            if scale - self.scale > SLEW:                                                   # :169-174
-                self.scale += SLEW
-            elif scale - self.scale < -SLEW:
-                self.scale -= SLEW
+            slew = self.constants.slew
+            if scale - self.scale > slew:                                                   # :169-174
+                self.scale += slew
+            elif scale - self.scale < -slew:
+                self.scale -= slew
             else:
                 self.scale = scale
         self.scale_queue.append(self.scale)                                                 # :175-177
@@ -352,7 +414,7 @@ class ScaleEstimator(stream.StreamKnobs):
             self.scale_queue.popleft()
 
     def scale_calculation_ransac_batch(self, point_lists):
-        idx = [i for i, p in enumerate(point_lists) if p.shape[0] >= 12]                    # :152
+        idx = [i for i, p in enumerate(point_lists) if p.shape[0] >= self.constants.ransac_min_points]   # :152
         models = {}
         if idx:
             triples = [self._triples(point_lists[i].shape[0]) for i in idx]
@@ -454,9 +516,11 @@ class ScaleEstimator(stream.StreamKnobs):
         return self.scale_calculation_ransac_batch([s[0] for s in sel])
 
     # ---- the device-resident path ------------------------------------------------------------------------------
-    def _rescale_params(self, frame_base):
-        return _lib.RescaleParams(self._good_bits, MIN_VALID_FOR_RETRI, -80.0, -85.0, 0.9, RANSAC_MIN_POINTS, self.N_HYP,
-                                  RANSAC_THRESHOLD, RANSAC_GOAL, float(self.absolute_reference), self._seed, int(frame_base))
+    def _rescale_params(self, frame_base, constants=None):
+        k = constants or self.constants
+        return _lib.RescaleParams(self._good_bits, MIN_VALID_FOR_RETRI, k.loose_deg, k.tight_deg, k.height_factor, k.ransac_min_points,
+                                  k.n_hyp if constants is not None else self.N_HYP, k.threshold, k.goal_fraction,
+                                  float(self.absolute_reference), self._seed, int(frame_base))
 
     def _launch_flat_ransac(self, db, keep_ptr, dt2_ptr, frame_base, frame_ids, id_triples, stage, max_tri, ctx=None):
         """mvosr_flat_ransac_batch over a DeviceBatch; returns the outputs' block (download queued)."""
@@ -502,6 +566,23 @@ class ScaleEstimator(stream.StreamKnobs):
     def _chunk_dev_gpu(self, f3s, f2s, frame_base, id_triples, stage, tables=False, early_status=False):
         """One chunk, both triangulations on the device: pack (C packer into page-locked memory) -> ONE upload -> every
         launch and the download of the results queued; nothing is waited for here."""
+        st = self._chunk_dev_front(f3s, f2s, frame_base, tables, early_status)
+        if not st["gpu"]:
+            return st
+        pf, db = st["pf"], st["db"]
+        out, flags, side = self._launch_flat_ransac(db, db.bufs["vote_counters"].ptr, db.bufs["dt2_status"].ptr, frame_base, None, id_triples,
+                                                    stage, 2 * int(db.max_feat))
+        if stage or not self.GPU_SIDE_DOWNLOADS:
+            db.prefetch_info()
+        else:
+            db.mark_info_done()
+        db.mark()
+        return {"gpu": True, "pf": pf, "db": db, "out": out, "flags": flags, "side": side}
+
+    def _chunk_dev_front(self, f3s, f2s, frame_base, tables=False, early_status=False):
+        """The stages of a chunk that no constant of ``RescaleConstants`` enters — the pack and its upload, the first
+        triangulation, the vote, the second triangulation — launched on the device: ``{"gpu": True, "pf", "db"}`` with the keep
+        words in the batch's ``vote_counters`` plane, or ``{"gpu": False}`` where the chunk takes the host's path."""
         ctx, lib = self.ctx, self.ctx.lib
         if tables is False:
             tables = frame_tables(f3s, f2s) if len(f3s) else None
@@ -544,14 +625,7 @@ class ScaleEstimator(stream.StreamKnobs):
             self.alloc_fallbacks = getattr(self, "alloc_fallbacks", 0) + 1
             return {"gpu": False}
         db.n_rows2 = 2 * pf.total_padded
-        out, flags, side = self._launch_flat_ransac(db, keep.ptr, bufs["dt2_status"].ptr, frame_base, None, id_triples, stage,
-                                                    2 * int(db.max_feat))
-        if stage or not self.GPU_SIDE_DOWNLOADS:
-            db.prefetch_info()
-        else:
-            db.mark_info_done()
-        db.mark()
-        return {"gpu": True, "pf": pf, "db": db, "out": out, "flags": flags, "side": side}
+        return {"gpu": True, "pf": pf, "db": db}
 
     def _trace(self, what, chunk, frames):
         """MVOSR_TRACE_CHUNKS=1: (what, chunk, frames, seconds since the call began) into ``self.chunk_trace`` — when this process
@@ -862,7 +936,7 @@ class ScaleEstimator(stream.StreamKnobs):
     def _launch_cases(self, db, keep_ptr, dt2_ptr, flags_ptr, seeds, frame_base, frame_ids, id_triples, max_tri, opts, ctx=None):
         """mvosr_flat_ransac_cases_batch behind the chunk's mvosr_flat_ransac_batch, on the same resident batch, keep words and
         flags; returns the outputs' block (download queued) and the side blocks."""
-        ctx, F, H, Cn = ctx or self.ctx, db.n_frames, self.N_HYP, len(seeds)
+        ctx, F, H, Cn = ctx or self.ctx, db.n_frames, (opts["constants"].n_hyp if opts.get("constants") else self.N_HYP), len(seeds)
         spec = [("raw_scale", (F, Cn), np.float64), ("model", (F, Cn, 4), np.float64), ("best_ic", (F, Cn), np.int32),
                 ("used", (F, Cn), np.int32), ("status", (F, Cn), np.int32), ("count_form", F, np.int32)]
         if opts.get("hyp_counts"):
@@ -878,7 +952,7 @@ class ScaleEstimator(stream.StreamKnobs):
         side.upload(up)
         o = _lib.RescaleCasesOutputs(out["raw_scale"].ptr, out["model"].ptr, out["best_ic"].ptr, out["used"].ptr, out["status"].ptr,
                                      out["hyp_counts"].ptr if "hyp_counts" in out else None, out["count_form"].ptr)
-        rp = self._rescale_params(frame_base)
+        rp = self._rescale_params(frame_base, opts.get("constants"))
         b = db.struct()
         _lib.check(ctx.lib.mvosr_flat_ransac_cases_batch(ctx.handle, C.byref(b), keep_ptr, C.byref(rp), side["seeds"].ptr, Cn,
                                                          int(opts.get("cases_per_group", 0)),
@@ -1054,7 +1128,7 @@ class ScaleEstimator(stream.StreamKnobs):
             pushed, filtered = np.empty(n_ok, np.float64), np.empty(n_ok, np.float64)
             q = np.ascontiguousarray(np.asarray(list(self.scale_queue), dtype=np.float64))
             if 1 <= int(self.window_size) <= 64 and q.size <= 64:
-                _lib.check(ctx.lib.mvosr_slew_median_host(_lib.addr(r), _lib.addr(ap), n_ok, SLEW, float(self.scale), int(self.window_size),
+                _lib.check(ctx.lib.mvosr_slew_median_host(_lib.addr(r), _lib.addr(ap), n_ok, self.constants.slew, float(self.scale), int(self.window_size),
                                                           _lib.addr(q) if q.size else None, int(q.size), _lib.addr(pushed),
                                                           _lib.addr(filtered), None), "mvosr_slew_median_host")
                 self.scale = float(pushed[-1])                                              # :169-174
@@ -1064,13 +1138,14 @@ class ScaleEstimator(stream.StreamKnobs):
             else:
                 # a window the C loop's ring buffer does not hold (the reference takes any: 0 gives the median of an empty deque,
                 # nan): the same recurrence, frame by frame, as the reference writes it (:169-178)
+                slew = self.constants.slew
                 with np.errstate(all="ignore"):
                     for i in range(n_ok):
                         if ap[i]:
-                            if r[i] - self.scale > SLEW:
-                                self.scale += SLEW
-                            elif r[i] - self.scale < -SLEW:
-                                self.scale -= SLEW
+                            if r[i] - self.scale > slew:
+                                self.scale += slew
+                            elif r[i] - self.scale < -slew:
+                                self.scale -= slew
                             else:
                                 self.scale = float(r[i])
                         self.scale_queue.append(self.scale)
@@ -1118,11 +1193,19 @@ class _CaseTail:
     (``ScaleEstimator._push_device``: mvosr_slew_median_host once per call, the raise sites)."""
     push = ScaleEstimator._push_device
 
-    def __init__(self, ctx, window_size):
-        self.ctx, self.window_size = ctx, window_size
+    def __init__(self, ctx, window_size, constants=None):
+        self.ctx, self.window_size, self.constants = ctx, window_size, constants or RescaleConstants()
         self.scale, self.scale_queue = 1, deque()                                           # rescale.py:28,30
         self.height_level, self._frame_counter = None, 0
         self.prev = (0, 100)                                                                # main_offline.py:46-47
+
+
+def _trim_scale_figures(figs):
+    """``evaluate.trimmed_mean`` over the cases of each figure of ``evaluate.scale_errors``."""
+    from . import evaluate
+    cols = lambda a: np.array([evaluate.trimmed_mean(a[:, k]) for k in range(a.shape[1])])
+    return {"mean": evaluate.trimmed_mean(figs["mean"]), "max": evaluate.trimmed_mean(figs["max"]),
+            "within": cols(figs["within"]), "drift": cols(figs["drift"])}
 
 
 class RepeatedRuns:
@@ -1149,6 +1232,8 @@ class RepeatedRuns:
         if self.estimator.sampling != "device":
             raise ValueError("RepeatedRuns needs a device-sampling mode: triangulation='gpu', or triangulation='scipy' with sampling='device'")
         self.tails = [_CaseTail(self.estimator.ctx, window_size) for _ in range(self.cases)]
+        for tail in self.tails:                          # (the slew limiter's step: the estimator's)
+            tail.constants = getattr(self.estimator, "constants", None) or RescaleConstants()
         self._scales, self._motions, self._raw, self.last = [], [], [], {}
 
     @staticmethod
@@ -1288,11 +1373,7 @@ class RepeatedRuns:
             if scorer is not None:
                 out["gt_rescaled_filtered"] = scorer.score_gt_rescaled(d_f)
 
-        def trim(figs):
-            cols = lambda a: np.array([evaluate.trimmed_mean(a[:, k]) for k in range(a.shape[1])])
-            return {"mean": evaluate.trimmed_mean(figs["mean"]), "max": evaluate.trimmed_mean(figs["max"]),
-                    "within": cols(figs["within"]), "drift": cols(figs["drift"])}
-        out["trimmed"] = {k: trim(out[k]) for k in ("scales", "filtered") if k in out}
+        out["trimmed"] = {k: _trim_scale_figures(out[k]) for k in ("scales", "filtered") if k in out}
         return out
 
     def write_results(self, res_addr, tag):
@@ -1315,3 +1396,394 @@ class RepeatedRuns:
         with warnings.catch_warnings(), np.errstate(all="ignore"):
             warnings.simplefilter("ignore")
             return {"scale_mean": s.mean(axis=0), "scale_std": s.std(axis=0), "raw_mean": np.nanmean(raw, axis=0), "raw_std": np.nanstd(raw, axis=0)}
+
+
+# ---- the estimator's constants swept over a sequence in one run -------------------------------------------------
+class _SweepEstimator(ScaleEstimator):
+    """The inner estimator of ``ConstantSweep``: a frame must also fit flat_selection_sweep_kernel's LDS
+    (csrc/mvosr_rescale_sweep_plan.hpp: 48 bytes per feature with two rows per feature, the tables, the histograms' floor)."""
+
+    def _max_points(self):
+        return min(ScaleEstimator._max_points(self), (self.ctx.lds_per_block - 1024) // 48)
+
+
+def _stack_dicts(dicts):
+    """A list of equally shaped (nested) dicts of arrays and numbers -> one dict with a leading axis; an int keeps its value."""
+    out = {}
+    for k, v in dicts[0].items():
+        if isinstance(v, dict):
+            out[k] = _stack_dicts([d[k] for d in dicts])
+        elif isinstance(v, (int, np.integer)) and not isinstance(v, bool):
+            out[k] = v
+        else:
+            out[k] = np.array([d[k] for d in dicts])
+    return out
+
+
+class ConstantSweep:
+    """``RepeatedRuns`` for K settings of ``RescaleConstants`` at once: what one gets today by patching the literals and running
+    the ten cases again per setting.  Both triangulations and the vote do not read the constants and run once per frame; the
+    selection of every distinct ``(loose_deg, tight_deg, height_factor)`` comes from one launch of
+    mvosr_flat_selection_sweep_batch per chunk, the plane fits of every distinct (selection, RANSAC constants) pair from one
+    launch of mvosr_flat_ransac_cases_batch on that selection's flag plane, all cases in it; ``slew`` and ``window_size`` live in
+    the tails, one per (config, case), and cost no launch.
+
+    ``configs``: a list of ``RescaleConstants`` (``ConstantSweep.grid`` builds a product).  Seeds as in ``RepeatedRuns``; every
+    config runs the same case seeds.  Row ``[k, c]`` of ``run`` equals, bit for bit, row c of
+    ``RepeatedRuns(absolute_reference, window_size, seeds=seeds, constants=configs[k]).run(data)``.  A frame must fit the kernels
+    of every config and the sweep kernel (``estimator._max_points()``)."""
+
+    MAX_SCORED_CASES = 32768                # rows of one scoring call (the scorers take 65535 cases a launch)
+
+    def __init__(self, absolute_reference, configs, window_size=5, cases=10, seed=None, seeds=None, **estimator_kw):
+        self.configs = list(configs)
+        if not self.configs or not all(isinstance(k, RescaleConstants) for k in self.configs):
+            raise ValueError("ConstantSweep: configs is a non-empty list of RescaleConstants")
+        if "constants" in estimator_kw:
+            raise TypeError("ConstantSweep takes its constants as configs")
+        if seeds is not None:
+            self.seeds = [int(s) & _MASK64 for s in seeds]
+        elif seed is not None:
+            self.seeds = case_seeds(seed, cases)
+        else:
+            self.seeds = [int.from_bytes(os.urandom(8), "little") for _ in range(int(cases))]
+        if not self.seeds:
+            raise ValueError("ConstantSweep: at least one case")
+        self.cases, self.window_size = len(self.seeds), window_size
+        # the distinct selections, the distinct (selection, RANSAC) pairs, and which pair a config reads
+        self._sels, self._pairs, self._pair_of = [], [], []
+        for k in self.configs:
+            if k.selection() not in self._sels:
+                self._sels.append(k.selection())
+            pair = (self._sels.index(k.selection()), k.ransac())
+            if pair not in self._pairs:
+                self._pairs.append(pair)
+            self._pair_of.append(self._pairs.index(pair))
+        self._pair_constants = [RescaleConstants(*self._sels[si], *rk) for si, rk in self._pairs]
+        widest = RescaleConstants(n_hyp=max(k.n_hyp for k in self.configs))      # (sizes the largest frame: every config's kernels take it)
+        self.estimator = _SweepEstimator(absolute_reference, window_size, ransac_seed=0, constants=widest, **estimator_kw)
+        if self.estimator.sampling != "device":
+            raise ValueError("ConstantSweep needs a device-sampling mode: triangulation='gpu', or triangulation='scipy' with sampling='device'")
+        self.max_settings = int(self.estimator.ctx.lib.mvosr_flat_selection_sweep_max_settings())
+        self.tails = [[_CaseTail(self.estimator.ctx, window_size, k) for _ in range(self.cases)] for k in self.configs]
+        self._scales, self._motions, self._raw, self.last = [], [], [], {}
+        self.launches = {"sweep": 0, "cases": 0}                 # launches made so far, by kernel
+        self._rr = None
+
+    @staticmethod
+    def grid(**axes):
+        """The product of the given values per field, the last named field varying fastest:
+        ``grid(loose_deg=[-80, -75], n_hyp=[100, 30])`` -> four ``RescaleConstants``; fields not named keep their defaults."""
+        names = list(axes)
+        known = {f.name for f in dataclasses.fields(RescaleConstants)}
+        for n in names:
+            if n not in known:
+                raise TypeError("ConstantSweep.grid: RescaleConstants has no field %r" % n)
+        values = [list(np.atleast_1d(axes[n]).tolist()) if not isinstance(axes[n], (list, tuple)) else list(axes[n]) for n in names]
+        return [RescaleConstants(**dict(zip(names, combo))) for combo in itertools.product(*values)]
+
+    # ---- a chunk: the launches behind the second triangulation ---------------------------------------------------------------
+    def _launch(self, db, keep_ptr, dt2_ptr, rows, max_tri, frame_base, frame_ids, ctx=None):
+        """mvosr_flat_selection_sweep_batch over the distinct selections (16 a launch), then mvosr_flat_ransac_cases_batch once
+        per distinct pair on its selection's plane; the outputs' downloads queued.  ``rows``: rows of a flag plane."""
+        est = self.estimator
+        ctx, F, S = ctx or est.ctx, db.n_frames, len(self._sels)
+        stride = max(int(rows), 1)
+        flags = ctx.block([("tri_flags", (S, stride), np.uint8)])
+        blocks, groups, cases = [flags], [], []
+        b = db.struct()
+        try:
+            for g0 in range(0, S, self.max_settings):
+                sel = self._sels[g0:g0 + self.max_settings]
+                out = ctx.block([("height_level", (F, len(sel)), np.float64), ("n_kept", (F, len(sel)), np.int32), ("status", F, np.int32)])
+                blocks.append(out)
+                loose, tight, factor = (np.array([x[i] for x in sel], dtype=np.float64) for i in range(3))
+                _lib.check(ctx.lib.mvosr_flat_selection_sweep_batch(ctx.handle, C.byref(b), keep_ptr, dt2_ptr, len(sel), _lib.addr(loose),
+                                                                    _lib.addr(tight), _lib.addr(factor), flags["tri_flags"].ptr + g0 * stride,
+                                                                    out["height_level"].ptr, out["n_kept"].ptr, out["status"].ptr, None,
+                                                                    int(max_tri)), "mvosr_flat_selection_sweep_batch")
+                self.launches["sweep"] += 1
+                out.prefetch()
+                groups.append(out)
+            for (si, _), k in zip(self._pairs, self._pair_constants):
+                out, side = est._launch_cases(db, keep_ptr, dt2_ptr, flags["tri_flags"].ptr + si * stride, self.seeds, frame_base, frame_ids,
+                                              None, max_tri, {"constants": k}, ctx=ctx)
+                self.launches["cases"] += 1
+                blocks += [out, side]
+                cases.append(out)
+        except Exception:
+            for blk in blocks:
+                blk.free()
+            raise
+        return {"groups": groups, "cases": cases, "blocks": blocks}
+
+    @staticmethod
+    def _collect(lp):
+        """A chunk's results, frames first: the sweep launch's geometry status merged into every case as
+        ``ScaleEstimator._collect_cases`` merges mvosr_flat_ransac_batch's."""
+        groups, cases = lp["groups"], lp["cases"]
+        res = {"status": np.array(groups[0]["status"].download(), copy=True),
+               "height_level": np.concatenate([g["height_level"].download() for g in groups], axis=1),
+               "n_kept": np.concatenate([g["n_kept"].download() for g in groups], axis=1),
+               "case_raw_scale": np.stack([c["raw_scale"].download() for c in cases], axis=1),          # (F, P, C)
+               "case_status": np.stack([c["status"].download() for c in cases], axis=1)}
+        bad = np.isin(res["status"], (K.ST_ERR_SINGULAR, K.ST_ERR_MASK, K.ST_ERR_EMPTY))
+        if bad.any():
+            res["case_status"][bad] = res["status"][bad][:, None, None]
+            res["case_raw_scale"][bad] = np.nan
+        return res
+
+    def _chunk_host(self, f3s, f2s, frame_base, frame_ids):
+        """One chunk on the host's triangulations: triangulation="scipy" with sampling="device", and the frames both device
+        triangulations declined (``frame_ids``: their own sample counters)."""
+        est = self.estimator
+        rec = est._host_begin(f3s, f2s, frame_base)
+        lp = None
+        try:
+            est._host_keep_start(rec)
+            est._host_tri2_start(rec)
+            pf, db = rec["pf"], rec["db"]
+            packing.attach_tri2(pf, rec.pop("h2"), rec["masks"], est.delaunay_workers)
+            db.set_tri2(pf)
+            db.n_rows2 = int(pf.tri2_off[-1])
+            max_tri = max(int(np.max(np.diff(pf.tri2_off))) if pf.n_frames else 0, 1)
+            lp = self._launch(db, rec["aux"]["keep"].ptr, None, db.n_rows2, max_tri, frame_base, frame_ids, ctx=rec["ctx"])
+            res = self._collect(lp)
+            res["host_errors"] = dict(pf.extra["tri2_errors"])
+            res["host_errors"].update(pf.extra["tri1_errors"])
+            return res
+        finally:
+            for blk in (lp["blocks"] if lp else ()):
+                blk.free()
+            stream.wait_out(rec.get("h1"), rec.get("h2"))
+            stream.free_blocks(rec)
+
+    def _gpu_start(self, f3s, f2s, frame_base):
+        est = self.estimator
+        st = est._chunk_dev_front(f3s, f2s, frame_base)
+        if st["gpu"]:
+            db = st["db"]
+            try:
+                st["launch"] = self._launch(db, db.bufs["vote_counters"].ptr, db.bufs["dt2_status"].ptr, db.n_rows2, 2 * int(db.max_feat),
+                                            frame_base, None)
+                db.prefetch_info()
+                db.mark()
+            except Exception:
+                stream.free_blocks(st)
+                raise
+        return st
+
+    @staticmethod
+    def _free(st):
+        if st.get("launch") is not None:
+            for blk in st.pop("launch")["blocks"]:
+                blk.free()
+        stream.free_blocks(st)
+
+    def _gpu_finish(self, st, f3s, f2s, frame_base):
+        est = self.estimator
+        if not st["gpu"]:
+            return self._chunk_host(f3s, f2s, frame_base, None)
+        try:
+            res = self._collect(st["launch"])
+            s1, s2 = st["db"].triangulation_status()
+        finally:
+            self._free(st)
+        res["host_errors"] = {}
+        redo = np.nonzero((s1 != 0) | (s2 != 0))[0]
+        est.last_declined += len(redo)
+        if len(redo):                                    # both device triangulations declined: the host's, with the frames' own counters
+            sub = self._chunk_host([f3s[f] for f in redo], [f2s[f] for f in redo], 0, frame_base + redo)
+            for k, v in sub.items():
+                if k != "host_errors":
+                    res[k][redo] = v
+            for j, e in sub["host_errors"].items():
+                res["host_errors"][int(redo[j])] = e
+        return res
+
+    def _raw_cases(self, f3, f2):
+        """The per-frame half for every pair and case (no cross-frame state touched): ``raw_scale`` / ``status`` ``(P, C, F)``,
+        ``height_level`` / ``n_kept`` ``(S, F)``, ``frame_status`` ``(F,)``, ``host_errors``.  Chunks as in
+        ``ScaleEstimator.raw_scale_cases_batch``: started one ahead of the one being collected."""
+        est = self.estimator
+        F, P, S, Cn = len(f3), len(self._pairs), len(self._sels), self.cases
+        if F == 0:
+            return {"raw_scale": np.zeros((P, Cn, 0)), "status": np.zeros((P, Cn, 0), np.int32), "height_level": np.zeros((S, 0)),
+                    "n_kept": np.zeros((S, 0), np.int32), "frame_status": np.zeros(0, np.int32), "host_errors": {}}
+        over = est._first_oversized(f2, [len(x) for x in f2], 0)
+        if over is not None:
+            raise est._oversized_error(*over)
+        base = est._frame_counter
+        est.last_declined = 0
+        gpu = est.triangulation == "gpu"
+        step = stream.chunk_size(F, est.GPU_CHUNK, est.GPU_MIN_CHUNK, est.GPU_CHUNK_POINTS, [len(x) for x in f3[:64]])[0] if gpu else 2048
+        bounds = [(a, min(F, a + step)) for a in range(0, F, step)]
+        results, pending = [], None
+        try:
+            for a, b in bounds:
+                if gpu:
+                    st = self._gpu_start(f3[a:b], f2[a:b], base + a)
+                    if pending is not None:
+                        pa, pb, pst = pending
+                        pending = None
+                        results.append(self._gpu_finish(pst, f3[pa:pb], f2[pa:pb], base + pa))
+                    pending = (a, b, st)
+                else:
+                    results.append(self._chunk_host(f3[a:b], f2[a:b], base + a, None))
+            if pending is not None:
+                pa, pb, pst = pending
+                pending = None
+                results.append(self._gpu_finish(pst, f3[pa:pb], f2[pa:pb], base + pa))
+        finally:
+            if pending is not None:
+                self._free(pending[2])
+        cat = lambda k: np.concatenate([r[k] for r in results])
+        return {"raw_scale": np.ascontiguousarray(np.moveaxis(cat("case_raw_scale"), 0, 2)),
+                "status": np.ascontiguousarray(np.moveaxis(cat("case_status"), 0, 2)),
+                "height_level": np.ascontiguousarray(cat("height_level").T), "n_kept": np.ascontiguousarray(cat("n_kept").T),
+                "frame_status": cat("status"),
+                "host_errors": {a + int(f): e for (a, b), r in zip(bounds, results) for f, e in r["host_errors"].items()}}
+
+    # ---- the sequence -----------------------------------------------------------------------------------------------------------
+    def run(self, data, minimum_feature_for_scale=None):
+        """``RepeatedRuns.run`` for every config: ``scales`` ``(K, C, n)``, ``error`` ``(K, C, n + 1)``, ``kinds``, and the
+        ``raw_scale`` / ``status`` ``(K, C, F)`` of the processed frames.  A second ``run`` continues the sequence."""
+        from . import offline
+        kinds = offline.plan_sequence(data, offline.MINIMUM_FEATURE_FOR_SCALE if minimum_feature_for_scale is None else minimum_feature_for_scale)
+        idx = [i for i, k in enumerate(kinds) if k == 1]
+        f3 = [np.asarray(data["feature3ds"][i], dtype=np.float64) for i in idx]
+        f2 = [np.asarray(data["feature2ds"][i], dtype=np.float64) for i in idx]
+        est = self.estimator
+        r = self._raw_cases(f3, f2)
+        Fp, Kn, Cn = len(idx), len(self.configs), self.cases
+        scales, errors, first_exc = [], [], None
+        for k, tails in enumerate(self.tails):
+            p, si = self._pair_of[k], self._pairs[self._pair_of[k]][0]
+            for c, tail in enumerate(tails):
+                try:
+                    filt, std = (tail.push(r["raw_scale"][p, c], r["status"][p, c], r["height_level"][si], r["host_errors"]) if Fp
+                                 else (np.zeros(0), np.zeros(0)))
+                except Exception as exc:                 # (a frame at which the reference raises: every tail has pushed the frames before it)
+                    first_exc = first_exc or exc
+                    continue
+                s, e = RepeatedRuns._assemble(kinds, list(filt), list(std), tail.prev)
+                tail.prev = (s[-1], e[-1])
+                scales.append(s[1:])
+                errors.append(e)
+        est._frame_counter = self.tails[0][0]._frame_counter if Fp else est._frame_counter
+        if first_exc is not None:
+            raise first_exc
+        take = np.asarray(self._pair_of)
+        out = {"scales": np.array(scales, dtype=np.float64).reshape(Kn, Cn, len(kinds)),
+               "error": np.array(errors, dtype=np.float64).reshape(Kn, Cn, len(kinds) + 1), "kinds": kinds,
+               "raw_scale": r["raw_scale"][take], "status": r["status"][take]}
+        self._scales.append(out["scales"])
+        self._raw.append(out["raw_scale"])
+        self._motions.append(np.array(data["motions"], dtype=np.float64).reshape(len(kinds), -1))
+        self.last = dict(r, **out)
+        return out
+
+    def scales(self):
+        """``(K, C, n)`` over every frame run so far."""
+        return np.concatenate(self._scales, axis=2) if self._scales else np.zeros((len(self.configs), self.cases, 0))
+
+    def _motions_all(self):
+        return np.concatenate(self._motions) if self._motions else np.zeros((0, 12))
+
+    # ---- scoring: the existing device scorers on the stacked (K C, n) scales ------------------------------------------------------
+    def _stacked_runs(self):
+        """Per group of configs ``(k0, k1, rr)``: a ``RepeatedRuns`` whose cases are the group's (config, case) rows."""
+        rr = self._rr
+        if rr is None:
+            rr = self._rr = object.__new__(RepeatedRuns)
+            rr.estimator = self.estimator
+        scales = self.scales()
+        per = max(1, self.MAX_SCORED_CASES // self.cases)
+        for k0 in range(0, len(self.configs), per):
+            k1 = min(len(self.configs), k0 + per)
+            rr.cases = (k1 - k0) * self.cases
+            rr._scales, rr._motions = [scales[k0:k1].reshape(rr.cases, -1)], self._motions
+            yield k0, k1, rr
+
+    def _config_rows(self, j):
+        return slice(j * self.cases, (j + 1) * self.cases)
+
+    def scores(self, poses_gt, speed_gt=None):
+        """``RepeatedRuns.scores`` per config, with a leading K axis on every entry: the paths of all (config, case) rows are
+        integrated and scored together by the device scorer; ``"trimmed"`` is ``evaluate.trimmed_mean`` over each config's cases."""
+        from . import evaluate
+        if self.cases < 3:
+            raise ValueError("trimmed_mean: at least three values (the best and the worst are dropped), got %d" % self.cases)
+        per = []
+        for k0, k1, rr in self._stacked_runs():
+            d = rr.scores(poses_gt, speed_gt)
+            for j in range(k1 - k0):
+                sl = self._config_rows(j)
+                one = evaluate._reduce_scores(np.ascontiguousarray(d["tra"][sl]), np.ascontiguousarray(d["rot"][sl]))
+                if "speed_scaled" in d:
+                    one["speed_scaled"] = evaluate._reduce_scores(np.ascontiguousarray(d["speed_scaled"]["tra"][sl]),
+                                                                  np.ascontiguousarray(d["speed_scaled"]["rot"][sl]))
+                per.append(one)
+        self.last_scores = _stack_dicts(per)
+        return self.last_scores
+
+    def scale_scores(self, speed_gt, poses_gt=None, filter_window=None):
+        """``RepeatedRuns.scale_scores`` per config, with a leading K axis on every entry."""
+        from . import evaluate
+        if self.cases < 3:
+            raise ValueError("trimmed_mean: at least three values (the best and the worst are dropped), got %d" % self.cases)
+        per = []
+        for k0, k1, rr in self._stacked_runs():
+            d = rr.scale_scores(speed_gt, poses_gt=poses_gt, filter_window=filter_window)
+            for j in range(k1 - k0):
+                sl = self._config_rows(j)
+                one = {}
+                for key in ("scales", "filtered"):
+                    if key in d:
+                        one[key] = {f: (v if f == "n" else np.ascontiguousarray(v[sl])) for f, v in d[key].items()}
+                for key in ("gt_rescaled", "gt_rescaled_filtered"):
+                    if key in d:
+                        one[key] = evaluate._reduce_scores(np.ascontiguousarray(d[key]["tra"][sl]), np.ascontiguousarray(d[key]["rot"][sl]))
+                one["trimmed"] = {key: _trim_scale_figures(one[key]) for key in ("scales", "filtered") if key in one}
+                per.append(one)
+        self.last_scale_scores = _stack_dicts(per)
+        return self.last_scale_scores
+
+    FIGURES = ("tra_mean", "rot_mean", "scale_mean", "scale_max")
+
+    def _figure(self, figure):
+        """Per config the trimmed mean over its cases of ``figure``: the path errors' two means from the last ``scores``, the
+        scale error's mean and maximum from the last ``scale_scores``."""
+        if figure in ("tra_mean", "rot_mean"):
+            if getattr(self, "last_scores", None) is None:
+                raise ValueError("ConstantSweep: %r comes from scores(); call it first" % figure)
+            return np.asarray(self.last_scores["trimmed"][figure], dtype=np.float64)
+        if figure in ("scale_mean", "scale_max"):
+            if getattr(self, "last_scale_scores", None) is None:
+                raise ValueError("ConstantSweep: %r comes from scale_scores(); call it first" % figure)
+            return np.asarray(self.last_scale_scores["trimmed"]["scales"][figure[6:]], dtype=np.float64)
+        raise ValueError("ConstantSweep: figure is one of %s" % ", ".join(self.FIGURES))
+
+    def table(self, figure="tra_mean"):
+        """One row per config: its index, its fields and the trimmed mean of ``figure`` over its cases."""
+        v = self._figure(figure)
+        return [dict(dataclasses.asdict(k), config=i, **{figure: float(v[i])}) for i, k in enumerate(self.configs)]
+
+    def best(self, figure="tra_mean"):
+        """The config with the smallest trimmed mean of ``figure`` (the first of equals; a NaN never wins)."""
+        v = self._figure(figure)
+        if np.isnan(v).all():
+            raise ValueError("ConstantSweep.best: every config's %s is NaN" % figure)
+        return self.configs[int(np.nanargmin(v))]
+
+    def write_results(self, res_addr, tag):
+        """``RepeatedRuns.write_results`` per config under the tags ``<tag>k<k>_<num>``.  Returns the file names."""
+        from . import offline
+        scales, motions = self.scales(), self._motions_all()
+        names = []
+        for k in range(len(self.configs)):
+            for c in range(self.cases):
+                t = "%sk%d_%d" % (tag, k, c)
+                offline.save_outputs(res_addr, t, scales[k, c], motions)
+                names += [res_addr + "scales.txt" + t, res_addr + "path.txt" + t]
+        return names
