@@ -590,6 +590,40 @@ int mvosr_flat_ransac_batch(mvosr_ctx *ctx, const mvosr_batch *b, const int32_t 
                             const int32_t *id_triples, const int64_t *frame_ids, const int32_t *dt_status,
                             const mvosr_rescale_outputs *o, int64_t max_tri);
 
+/* ---- the same two stages for frames beyond one workgroup's LDS ---- */
+
+/*
+ * mvosr_graph_keep_batch with no cap on a frame's features or rows: one workgroup per frame, {v, z} gathered from global
+ * memory, the tallies 32 bits wide and held in LDS one TILE of vertices at a time — the rows are swept ceil(feat_cnt / tile)
+ * times, with integer LDS atomics only.  `tile`: vertices per sweep (<= 0: the library's choice; clamped to 8192, the LDS it
+ * may take).  The tile changes no word of the result.
+ * keep, n_valid and status equal mvosr_graph_keep_batch's on every frame that one accepts.  Refusals: a frame with
+ * feat_cnt[f] <= 0 (status MVOSR_ST_ERR_EMPTY, n_valid 0), a declined first triangulation (dt_status[f] != 0: every keep word
+ * -1, n_valid 0, MVOSR_ST_ERR_EMPTY), a frame with feat_cnt[f] > b->max_feat (refused before anything is read: every keep word
+ * -1, n_valid 0, MVOSR_ST_ERR_MASK).  A row that names a vertex outside the frame is left out and gives MVOSR_ST_ERR_MASK, as
+ * there.  MVOSR_GRAPH_MAX_ROWS does not apply.  No workspace.  n_frames <= 0: MVOSR_OK, nothing launched.
+ */
+int mvosr_graph_keep_large_batch(mvosr_ctx *ctx, const mvosr_batch *b, uint32_t good_bits, int32_t min_valid, const int32_t *dt_status,
+                                 int32_t *keep, int32_t *n_valid, int32_t *status, int32_t tile);
+
+/*
+ * mvosr_flat_ransac_batch — same parameters, same sample sequence, same outputs — with nothing frame-sized in LDS: one
+ * workgroup per frame; the survivors' compacted x, y, z, every row's height and flags (where o->tri_height / o->tri_flags are
+ * NULL; else the caller's arrays are used) and the point list live in the context's grow-only workspace (the one
+ * mvosr_ctx_workspace_limit caps): 24 bytes per element of b->total_feat when keep is given, and n_frames * max_tri * (12 + 8
+ * + 1) bytes for the rows.  The point list holds 32-bit vertex ids and positions: 3 * n_kept may exceed 65 535.
+ * Every field of `o` equals, bit for bit, what mvosr_flat_ransac_batch writes on every frame that one accepts.  Refusals are
+ * that entry point's: feat_cnt[f] <= 0, no rows, or dt_status[f] != 0 -> MVOSR_ST_ERR_EMPTY; feat_cnt[f] > b->max_feat or more
+ * rows than max_tri (<= 0: 2 * b->max_feat) -> MVOSR_ST_ERR_MASK; in both raw_scale, height_level and model NaN, n_kept,
+ * best_ic and used 0, nothing else written.  b->total_feat must be stated.
+ * Returns MVOSR_ERR_TOO_LARGE only where 3 * max_tri or n_frames does not fit 32 bits, MVOSR_ERR_ALLOC where the workspace
+ * cannot grow (or would pass the context's limit), MVOSR_ERR_ARG as mvosr_flat_ransac_batch (n_hyp in 1..512).
+ * n_frames <= 0: MVOSR_OK, nothing launched, no workspace asked for.
+ */
+int mvosr_flat_ransac_large_batch(mvosr_ctx *ctx, const mvosr_batch *b, const int32_t *keep, const mvosr_rescale_params *rp,
+                                  const int32_t *id_triples, const int64_t *frame_ids, const int32_t *dt_status,
+                                  const mvosr_rescale_outputs *o, int64_t max_tri);
+
 /* ---- C runs of a sequence at once (/root/reference/test_off_line.sh:4-16 runs main_offline.py ten times on one saved dict) ---- */
 
 /* which form of the point list a frame's inlier counts were taken over (count_form; the counts do not depend on it) */

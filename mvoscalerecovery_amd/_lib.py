@@ -243,6 +243,9 @@ SYMBOLS = {
     "mvosr_graph_keep_batch": (C.c_int, [_P, C.POINTER(Batch), C.c_uint32, C.c_int32, _P, _P, _P, _P]),
     "mvosr_flat_ransac_batch": (C.c_int, [_P, C.POINTER(Batch), _P, C.POINTER(RescaleParams), _P, _P, _P, C.POINTER(RescaleOutputs),
                                           C.c_int64]),
+    "mvosr_graph_keep_large_batch": (C.c_int, [_P, C.POINTER(Batch), C.c_uint32, C.c_int32, _P, _P, _P, _P, C.c_int32]),
+    "mvosr_flat_ransac_large_batch": (C.c_int, [_P, C.POINTER(Batch), _P, C.POINTER(RescaleParams), _P, _P, _P, C.POINTER(RescaleOutputs),
+                                                C.c_int64]),
     "mvosr_flat_ransac_cases_batch": (C.c_int, [_P, C.POINTER(Batch), _P, C.POINTER(RescaleParams), _P, C.c_int32, C.c_int32, _P, _P, _P, _P,
                                                 C.POINTER(RescaleCasesOutputs), C.c_int64]),
     "mvosr_flat_ransac_cases_lds_bytes": (C.c_size_t, [C.c_int, C.c_int64, C.c_int]),

@@ -148,12 +148,67 @@ def good_bits(edge_potential=EDGE_POTENTIAL, prob_threshold=0.6):
     return bits
 
 
+def chunk_goes_large(sizes, cap):
+    """Does a chunk whose frames have ``sizes`` features below the vanishing row take the large-frame kernels?  It does, as a
+    whole, when its largest frame exceeds ``cap`` (the resident kernels' limit, ``ScaleEstimator._max_points()``)."""
+    return len(sizes) > 0 and int(max(sizes)) > int(cap)
+
+
+def size_class_runs(sizes, cap, limit):
+    """Where ``ScaleEstimator(large_frames=True)`` cuts a call: ``(runs, stop)``.  ``runs``: ``(a, b, large)`` — maximal runs of
+    consecutive frames on one side of ``cap``, so that the small frames of a call stay on the resident kernels and every chunk of
+    a large run takes the large-frame ones.  ``stop``: index of the first frame beyond ``limit`` (the runs end before it: the call
+    ends there with the oversized-frame error), or None."""
+    sizes = np.asarray(sizes, dtype=np.int64)
+    over = np.nonzero(sizes > limit)[0]
+    stop = int(over[0]) if len(over) else None
+    F = len(sizes) if stop is None else stop
+    runs, a = [], 0
+    while a < F:
+        large = bool(sizes[a] > cap)
+        b = a + 1
+        while b < F and bool(sizes[b] > cap) == large:
+            b += 1
+        runs.append((a, b, large))
+        a = b
+    return runs, stop
+
+
+def host_chunks(sizes, step, points=None):
+    """The chunks ``(a, b)`` a run of frames with ``sizes`` features takes on the host-triangulation path: ``step`` frames each —
+    and, with ``points`` (the runs of large frames: the large-frame kernels' workspace grows with frames x largest row count), cut
+    to ``points`` features and to frames x largest frame <= 2 ``points``, as ``stream.plan`` cuts the device path's; one frame at
+    least."""
+    out, a, F = [], 0, len(sizes)
+    while a < F:
+        b, total, largest = a, 0, 0
+        while b < F and b - a < step:
+            big = max(largest, int(sizes[b]))
+            if points is not None and b > a and (total + int(sizes[b]) > points or (b - a + 1) * big > 2 * points):
+                break
+            total, largest, b = total + int(sizes[b]), big, b + 1
+        out.append((a, b))
+        a = b
+    return out
+
+
 class ScaleEstimator(stream.StreamKnobs):
     N_HYP = RANSAC_ITERATIONS
 
     def __init__(self, absolute_reference, window_size=6, device=0, ransac_seed=None, sampler=None,
                  delaunay_workers=None, verbose=False, triangulation=None, sampling=None, region="threshold", model="ransac",
-                 constants=None):
+                 constants=None, large_frames=False):
+        # large_frames: opt-in (DESIGN.md §3.23).  False: a frame with more features below the vanishing row than one workgroup's LDS
+        # holds (``_max_points()``) is refused, as ever.  True: a chunk whose largest frame exceeds that limit sends its vote and its
+        # flat selection + RANSAC through the large-frame kernels (mvosr_graph_keep_large_batch, mvosr_flat_ransac_large_batch),
+        # up to ``_large_max_points()`` features.  The RANSAC model needs the device-resident path for it: triangulation="gpu", or
+        # "scipy" with sampling="device" (anything else is refused below, before a device is needed).  model="static_tri" (staged
+        # path) takes it too: its vote and its flat selection go through the same two kernels (_vote_masks, _flat_selection).
+        # Accepted and without effect: model="static" and region="grow" — they, RepeatedRuns and ConstantSweep keep the present
+        # limit and message whatever this says.
+        if not isinstance(large_frames, (bool, np.bool_)):
+            raise TypeError("large_frames must be a bool")
+        self.large_frames = bool(large_frames)
         # constants: a RescaleConstants (None: the reference's literals — the instance then is what the class always was)
         if constants is not None and not isinstance(constants, RescaleConstants):
             raise TypeError("constants must be a RescaleConstants")
@@ -162,7 +217,8 @@ class ScaleEstimator(stream.StreamKnobs):
             self.N_HYP = self.constants.n_hyp
         # region "threshold": the road rows are the reference's two thresholds (rescale.py:94-96); "grow": GraphGrow's region over
         # the rows' adjacency (graph.py:85-107, the call rescale.py:99 leaves commented out) — on the staged path only, which it
-        # selects (checked first: no device is needed to refuse a combination).
+        # selects (checked first: no device is needed to refuse a combination).  Its kernels hold a frame in LDS: large_frames does
+        # not reach it, an oversized frame gets the library's error as before.
         if region not in ("threshold", "grow"):
             raise ValueError("region must be 'threshold' or 'grow'")
         if region == "grow":
@@ -174,7 +230,8 @@ class ScaleEstimator(stream.StreamKnobs):
         # model "ransac": the road model is the RANSAC plane (rescale.py:193, the reference's live line).  "static_tri": the mode of
         # the flat triangles' inverse heights (:194, scale_calculation_static_tri :179-187).  "static": scale_calculator's road
         # model on the selected points, through an inner estimator with its own queue and camera pitch (:195, self.sc :31).  The two
-        # commented-out choices run on the staged path only, which they select.
+        # commented-out choices run on the staged path only, which they select.  large_frames reaches
+        # "static_tri" (its heights come from the large-frame kernel's tri_height / tri_flags rows, of any length), not "static".
         if model not in ("ransac", "static_tri", "static"):
             raise ValueError("model must be 'ransac', 'static_tri' or 'static'")
         if model != "ransac":
@@ -183,28 +240,6 @@ class ScaleEstimator(stream.StreamKnobs):
                                  "device-resident kernel ends in the RANSAC plane)" % model)
             triangulation, sampling = "scipy", "host"
         self.model = model
-        # reference attributes (rescale.py:24-35)
-        self.absolute_reference = absolute_reference
-        self.camera_pitch = 0
-        self.scale = 1
-        self.inliers = None
-        self.scale_queue = deque()
-        # (the reference takes any window; mvosr_slew_median_host's ring buffer holds 64 — other windows walk the recurrence in Python,
-        # _push_device)
-        self.window_size = window_size
-        self.vanish = VANISH
-        # build-side state
-        self.verbose = verbose
-        self.delaunay_workers = delaunay_workers
-        if delaunay_workers is None or delaunay_workers > 1:
-            packing.start_pool(delaunay_workers)     # fork the host stage's workers BEFORE the GPU runtime starts its threads
-        self.engine = ScaleEngine(absolute_reference, device=device, camera_pitch=0.0)
-        self.ctx = self.engine.ctx
-        self._good_bits = good_bits()
-        self._rng = random.Random(ransac_seed)
-        self._sampler = sampler
-        self.height_level = None
-        self.last = {}
         # triangulation "scipy": both Delaunay calls on the host, as the reference; "gpu": mvosr_delaunay_batch, everything
         # device-resident.  sampling "host": the triples are drawn here with Python's random, by LIST POSITION in SciPy's row
         # order (replays a recorded reference run); "device": the kernel's counter-based sequence over rows in canonical
@@ -225,6 +260,31 @@ class ScaleEstimator(stream.StreamKnobs):
         if sampling == "device" and sampler is not None:
             raise ValueError("a host sampler needs sampling='host'; the device path takes id_triples per call")
         self.triangulation, self.sampling = triangulation, sampling
+        self._sampler = sampler
+        if self.large_frames and sampling != "device" and region == "threshold" and model == "ransac":
+            raise ValueError("large_frames=True belongs to the device-resident path: triangulation='gpu', or triangulation='scipy' "
+                             "with sampling='device' (the staged RANSAC path's kernels hold a frame in one workgroup's LDS)")
+        # reference attributes (rescale.py:24-35)
+        self.absolute_reference = absolute_reference
+        self.camera_pitch = 0
+        self.scale = 1
+        self.inliers = None
+        self.scale_queue = deque()
+        # (the reference takes any window; mvosr_slew_median_host's ring buffer holds 64 — other windows walk the recurrence in Python,
+        # _push_device)
+        self.window_size = window_size
+        self.vanish = VANISH
+        # build-side state
+        self.verbose = verbose
+        self.delaunay_workers = delaunay_workers
+        if delaunay_workers is None or delaunay_workers > 1:
+            packing.start_pool(delaunay_workers)     # fork the host stage's workers BEFORE the GPU runtime starts its threads
+        self.engine = ScaleEngine(absolute_reference, device=device, camera_pitch=0.0)
+        self.ctx = self.engine.ctx
+        self._good_bits = good_bits()
+        self._rng = random.Random(ransac_seed)
+        self.height_level = None
+        self.last = {}
         self._seed = int.from_bytes(os.urandom(8), "little") if ransac_seed is None else int(ransac_seed) & ((1 << 64) - 1)
         self._frame_counter = 0                     # frames this estimator has processed: the sample sequence's counter
         self.grow_threshold_angle = 8               # graph.py:40 (rescale.py:33 builds GraphGrow with its default)
@@ -263,6 +323,35 @@ class ScaleEstimator(stream.StreamKnobs):
         db.free()
         return t, g, st
 
+    def _vote_masks(self, pf):
+        """Per frame of the packed batch the vote's mask (graph.py:34-35) and the launch's status words.  From the tallies of
+        mvosr_graph_inliers_batch — or, where ``_staged_large`` says so, from the keep words of mvosr_graph_keep_large_batch
+        (``keep > 0`` is the vote itself): the same masks, no limit on the frame."""
+        if not self._staged_large(pf.max_feat):
+            total, good, st = self._graph_vote(pf)
+            with np.errstate(all="ignore"):
+                return [(good[pf.frame_slice(f)] / total[pf.frame_slice(f)]) > 0.5 for f in range(pf.n_frames)], st
+        ctx = self.ctx
+        db = DeviceBatch(ctx, pf, with_tri2=False)
+        keep = ctx.zeros(max(pf.total_padded, 1), np.int32)
+        status = ctx.zeros(pf.n_frames, np.int32)
+        try:
+            bs = db.struct()
+            _lib.check(ctx.lib.mvosr_graph_keep_large_batch(ctx.handle, C.byref(bs), C.c_uint32(self._good_bits), MIN_VALID_FOR_RETRI, None,
+                                                            keep.ptr, None, status.ptr, 0), "mvosr_graph_keep_large_batch")
+            ctx.sync()
+            words, st = keep.download(), status.download()
+        finally:
+            keep.free()
+            status.free()
+            db.free()
+        return [words[pf.frame_slice(f)] > 0 for f in range(pf.n_frames)], st
+
+    def _staged_large(self, max_feat):
+        """model="static_tri" with large_frames=True: does a staged batch whose largest frame has ``max_feat`` features take the
+        large-frame kernels?  (As a whole, like a chunk of the device-resident path; beyond the opt-in limit: refused.)"""
+        return self.large_frames and self.model == "static_tri" and chunk_goes_large([max_feat], self._max_points())
+
     def _flat_selection(self, pf2, static_tri=False):
         """flat_selection (rescale.py:75-102) over the batch: ``(tri_height, tri_flags, height_level, status)``.  ``static_tri``:
         mvosr_static_tri_batch right behind it, in row form on its tri_height / tri_flags and the batch's tri2_off — the heights do
@@ -277,13 +366,35 @@ class ScaleEstimator(stream.StreamKnobs):
         status = ctx.zeros(pf2.n_frames, np.int32)
         max_tri = int(np.max(np.diff(pf2.tri2_off))) if pf2.n_frames else 0
         b = db.struct()
-        _lib.check(lib.mvosr_flat_selection_batch(ctx.handle, C.byref(b), *self.constants.selection(), tri_h.ptr, tri_f.ptr, level.ptr,
-                                                  nkept.ptr, status.ptr, max_tri), "mvosr_flat_selection_batch")
+        if static_tri and self._staged_large(pf2.max_feat):
+            # the large-frame kernel writes every row's height and flags, for any number of rows; a RANSAC minimum no list reaches
+            # (3 * n_kept is never 2^31 - 1) keeps it from fitting a plane nobody reads: a frame without a refusal reports
+            # MVOSR_ST_RS_FEW, which is this stage's 0
+            F = pf2.n_frames
+            tail = ctx.block([("raw_scale", F, np.float64), ("model", (F, 4), np.float64), ("best_ic", F, np.int32), ("used", F, np.int32)])
+            try:
+                k = self.constants
+                rp = _lib.RescaleParams(self._good_bits, MIN_VALID_FOR_RETRI, k.loose_deg, k.tight_deg, k.height_factor, (1 << 31) - 1, 1,
+                                        k.threshold, k.goal_fraction, float(self.absolute_reference), 0, 0)
+                o = _lib.RescaleOutputs(tail["raw_scale"].ptr, level.ptr, tail["model"].ptr, tail["best_ic"].ptr, tail["used"].ptr, nkept.ptr,
+                                        status.ptr, tri_h.ptr, tri_f.ptr, None)
+                _lib.check(lib.mvosr_flat_ransac_large_batch(ctx.handle, C.byref(b), None, C.byref(rp), None, None, None, C.byref(o),
+                                                             max(max_tri, 1)), "mvosr_flat_ransac_large_batch")
+                ctx.sync()
+                st = status.download()
+                st[st == K.ST_RS_FEW] = 0
+            finally:
+                tail.free()
+            large_status = st
+        else:
+            large_status = None
+            _lib.check(lib.mvosr_flat_selection_batch(ctx.handle, C.byref(b), *self.constants.selection(), tri_h.ptr, tri_f.ptr, level.ptr,
+                                                      nkept.ptr, status.ptr, max_tri), "mvosr_flat_selection_batch")
         if static_tri:                                                                      # rescale.py:194
             try:
                 res = self.engine.static_tri_batch(pf2.n_frames, db.bufs["tri2_off"], tri_h, flags=tri_f, min_count=STATIC_TRI_MIN_COUNT,
                                                    absolute_reference=self.absolute_reference)
-                return None, None, level.download(), status.download(), res
+                return None, None, level.download(), (status.download() if large_status is None else large_status), res
             finally:
                 for buf in (tri_h, tri_f, level, nkept, status):
                     buf.free()
@@ -334,14 +445,16 @@ class ScaleEstimator(stream.StreamKnobs):
         packing.attach_tri1(pf, None, self.delaunay_workers)                                # :124
         for f, err in sorted(pf.extra["tri1_errors"].items()):
             raise err
-        total, good, st = self._graph_vote(pf)
+        if self.large_frames and self.model == "static_tri" and pf.n_frames and pf.max_feat > self._large_max_points():
+            cnt = np.asarray(pf.feat_cnt)
+            f = int(np.argmax(cnt > self._large_max_points()))
+            raise self._oversized_error(f, int(cnt[f]), self._large_max_points())
+        masks, st = self._vote_masks(pf)
         if np.any(st == 8):
             raise _lib.MvosrLibraryError("triangulation with an out-of-range vertex id")
         low3, low2, tris, valids = [], [], [], []
         for f in range(pf.n_frames):
-            sl = pf.frame_slice(f)
-            with np.errstate(all="ignore"):
-                valid = (good[sl] / total[sl]) > 0.5                                        # graph.py:34-35,131-132
+            valid = masks[f]                                                                # graph.py:34-35,131-132
             valids.append(valid)
             a3, a2 = f3s[f][pf.lower_index[f]], f2s[f][pf.lower_index[f]]
             tri = pf.tri1[pf.tri1_off[f]:pf.tri1_off[f + 1]]
@@ -522,8 +635,9 @@ class ScaleEstimator(stream.StreamKnobs):
                                   k.n_hyp if constants is not None else self.N_HYP, k.threshold, k.goal_fraction,
                                   float(self.absolute_reference), self._seed, int(frame_base))
 
-    def _launch_flat_ransac(self, db, keep_ptr, dt2_ptr, frame_base, frame_ids, id_triples, stage, max_tri, ctx=None):
-        """mvosr_flat_ransac_batch over a DeviceBatch; returns the outputs' block (download queued)."""
+    def _launch_flat_ransac(self, db, keep_ptr, dt2_ptr, frame_base, frame_ids, id_triples, stage, max_tri, ctx=None, large=False):
+        """mvosr_flat_ransac_batch over a DeviceBatch — ``large``: mvosr_flat_ransac_large_batch, same parameters, same results on
+        every frame both take —; returns the outputs' block (download queued)."""
         ctx, F, H = ctx or self.ctx, db.n_frames, self.N_HYP
         spec = [("raw_scale", F, np.float64), ("height_level", F, np.float64), ("model", (F, 4), np.float64),
                 ("best_ic", F, np.int32), ("used", F, np.int32), ("n_kept", F, np.int32), ("status", F, np.int32)]
@@ -547,10 +661,11 @@ class ScaleEstimator(stream.StreamKnobs):
             side.append(d_tr)
         rp = self._rescale_params(frame_base)
         b = db.struct()
-        _lib.check(ctx.lib.mvosr_flat_ransac_batch(ctx.handle, C.byref(b), keep_ptr, C.byref(rp),
-                                                   d_tr["id_triples"].ptr if d_tr is not None else None,
-                                                   d_ids["frame_ids"].ptr if d_ids is not None else None, dt2_ptr,
-                                                   C.byref(o), int(max_tri)), "mvosr_flat_ransac_batch")
+        entry = "mvosr_flat_ransac_large_batch" if large else "mvosr_flat_ransac_batch"
+        _lib.check(getattr(ctx.lib, entry)(ctx.handle, C.byref(b), keep_ptr, C.byref(rp),
+                                           d_tr["id_triples"].ptr if d_tr is not None else None,
+                                           d_ids["frame_ids"].ptr if d_ids is not None else None, dt2_ptr,
+                                           C.byref(o), int(max_tri)), entry)
         # (the results reach their page-locked image through a copy KERNEL: a hipMemcpyAsync queued here would park a copy engine behind
         # this chunk's kernels, and an upload of the next chunk that lands on that engine waits with it — DeviceBlock.mark_done; the
         # per-frame call with stage outputs keeps the queued download)
@@ -571,13 +686,13 @@ class ScaleEstimator(stream.StreamKnobs):
             return st
         pf, db = st["pf"], st["db"]
         out, flags, side = self._launch_flat_ransac(db, db.bufs["vote_counters"].ptr, db.bufs["dt2_status"].ptr, frame_base, None, id_triples,
-                                                    stage, 2 * int(db.max_feat))
+                                                    stage, 2 * int(db.max_feat), large=st["large"])
         if stage or not self.GPU_SIDE_DOWNLOADS:
             db.prefetch_info()
         else:
             db.mark_info_done()
         db.mark()
-        return {"gpu": True, "pf": pf, "db": db, "out": out, "flags": flags, "side": side}
+        return {"gpu": True, "pf": pf, "db": db, "out": out, "flags": flags, "side": side, "large": st["large"]}
 
     def _chunk_dev_front(self, f3s, f2s, frame_base, tables=False, early_status=False):
         """The stages of a chunk that no constant of ``RescaleConstants`` enters — the pack and its upload, the first
@@ -589,7 +704,7 @@ class ScaleEstimator(stream.StreamKnobs):
         if tables is not None:
             pf, blk = pack_upload_native(ctx, f3s, f2s, self.vanish, None, tables=tables)             # rescale.py:115-117
             self._trace("packed", -1, len(f3s))
-            if pf.max_feat > self._max_points():           # (_stream_device cuts the stream before such a frame: a direct caller's)
+            if pf.max_feat > self._frame_limit():          # (_stream_device cuts the stream before such a frame: a direct caller's)
                 blk.free()
                 self._refuse_oversized(pf, frame_base)
             db = DeviceBatch(ctx, pf, with_tri2=False, device_triangulation=True, uploaded=blk)
@@ -598,9 +713,10 @@ class ScaleEstimator(stream.StreamKnobs):
             pf = packing.pack_features(f3s, f2s, self.vanish)
             if pf.n_frames == 0:
                 return {"gpu": False}
-            if pf.max_feat > self._max_points():
+            if pf.max_feat > self._frame_limit():
                 self._refuse_oversized(pf, frame_base)
             db = DeviceBatch(ctx, pf, with_tri2=False, device_triangulation=True)
+        large = chunk_goes_large([pf.max_feat], self._max_points())       # (the whole chunk: its small frames give the same bits)
         bufs = db.bufs
         db.info.invalidate()
         try:
@@ -612,8 +728,7 @@ class ScaleEstimator(stream.StreamKnobs):
                 db._queue_early_status()
             bs = db.struct()
             keep = bufs["vote_counters"]                                        # (the block's per-feature int32 plane: here the keep flags)
-            _lib.check(lib.mvosr_graph_keep_batch(ctx.handle, C.byref(bs), C.c_uint32(self._good_bits), MIN_VALID_FOR_RETRI,
-                                                  bufs["dt1_status"].ptr, keep.ptr, None, None), "mvosr_graph_keep_batch")   # graph.py:18-36, rescale.py:133
+            self._launch_keep(ctx, bs, bufs["dt1_status"].ptr, keep.ptr, large)                      # graph.py:18-36, rescale.py:133
             _lib.check(lib.mvosr_delaunay_batch_ex(ctx.handle, db.n_frames, bufs["feat_off"].ptr, bufs["feat_cnt"].ptr, bufs["u"].ptr,
                                                    bufs["v"].ptr, keep.ptr, int(db.max_feat), bufs["tri_off"].ptr, bufs["tri2"].ptr,
                                                    bufs["tri2_cnt"].ptr, bufs["n2_expected"].ptr, bufs["dt2_status"].ptr,
@@ -625,7 +740,16 @@ class ScaleEstimator(stream.StreamKnobs):
             self.alloc_fallbacks = getattr(self, "alloc_fallbacks", 0) + 1
             return {"gpu": False}
         db.n_rows2 = 2 * pf.total_padded
-        return {"gpu": True, "pf": pf, "db": db}
+        return {"gpu": True, "pf": pf, "db": db, "large": large}
+
+    def _launch_keep(self, ctx, bs, dt1_ptr, keep_ptr, large):
+        """The vote with the decision made on the device: mvosr_graph_keep_batch, or (``large``) mvosr_graph_keep_large_batch."""
+        if large:
+            _lib.check(ctx.lib.mvosr_graph_keep_large_batch(ctx.handle, C.byref(bs), C.c_uint32(self._good_bits), MIN_VALID_FOR_RETRI,
+                                                            dt1_ptr, keep_ptr, None, None, 0), "mvosr_graph_keep_large_batch")
+        else:
+            _lib.check(ctx.lib.mvosr_graph_keep_batch(ctx.handle, C.byref(bs), C.c_uint32(self._good_bits), MIN_VALID_FOR_RETRI,
+                                                      dt1_ptr, keep_ptr, None, None), "mvosr_graph_keep_batch")
 
     def _trace(self, what, chunk, frames):
         """MVOSR_TRACE_CHUNKS=1: (what, chunk, frames, seconds since the call began) into ``self.chunk_trace`` — when this process
@@ -634,18 +758,41 @@ class ScaleEstimator(stream.StreamKnobs):
         if tr is not None:
             tr.append((what, chunk, frames, time.perf_counter() - getattr(self, "_trace_t0", 0.0)))
 
-    def _oversized_error(self, frame, count):
-        """flat_selection + RANSAC hold a frame's survivors, heights and flags in ONE workgroup's LDS: a frame beyond that has no
+    def _oversized_error(self, frame, count, limit=None):
+        """``limit`` None: the resident kernels' (below); else the opt-in limit of ``large_frames=True``, named in its place.
+        flat_selection + RANSAC hold a frame's survivors, heights and flags in ONE workgroup's LDS: a frame beyond that has no
         kernel here (the reference takes any size — /root/reference/src/rescale.py:113-148 — at seconds per frame).  Said with the
         frame named, instead of a library error from the middle of the host path."""
+        if limit is not None:
+            return ValueError("rescale.ScaleEstimator: frame %d has %d features below the vanishing row; the device-resident path takes at "
+                              "most %d per frame with large_frames=True (the triangulation kernels' limit).  Thin the frame, or use "
+                              "scale_calculator.ScaleEstimator, whose dense kernels take any size." % (frame, count, limit))
         return ValueError("rescale.ScaleEstimator: frame %d has %d features below the vanishing row; the device-resident path takes at "
                           "most %d per frame (one workgroup's LDS).  Thin the frame, or use scale_calculator.ScaleEstimator, whose "
                           "dense kernels take any size." % (frame, count, self._max_points()))
 
     def _refuse_oversized(self, pf, frame_base):
         cnt = np.asarray(pf.feat_cnt)
-        f = int(np.argmax(cnt > self._max_points()))
-        raise self._oversized_error(frame_base - self._frame_counter + f, int(cnt[f]))
+        f = int(np.argmax(cnt > self._frame_limit()))
+        raise self._oversized_error(frame_base - self._frame_counter + f, int(cnt[f]), self._frame_limit() if self.large_frames else None)
+
+    def _large_max_points(self):
+        """Largest frame ``large_frames=True`` takes: what both triangulators take (mvosr_delaunay_max_points(); the same number
+        with triangulation="scipy", sampling="device").  The large-frame kernels themselves have no limit below 2^31 / 3 rows."""
+        return packing.delaunay_gpu_max_points()
+
+    def _frame_limit(self):
+        """Features below the vanishing row beyond which the streaming paths refuse a frame."""
+        return self._large_max_points() if self.large_frames else self._max_points()
+
+    def _below_vanish(self, feature2ds, lens, a, cap):
+        """Per frame of ``feature2ds[a:a + len(lens)]`` its features below the vanishing row — counted only where the frame's size
+        (an upper bound) exceeds ``cap``; elsewhere the size itself stands in (the frame is small either way)."""
+        below = np.asarray(lens, dtype=np.int64).copy()
+        for j in np.nonzero(below > cap)[0]:
+            f2 = np.asarray(feature2ds[a + int(j)], dtype=np.float64)
+            below[j] = int(np.count_nonzero(f2[:, 1] > self.vanish)) if f2.ndim == 2 and f2.size else 0
+        return below
 
     def _first_oversized(self, feature2ds, lens, a):
         """Index (within the call) of the first frame of ``feature2ds[a:a + len(lens)]`` with more features below the vanishing row
@@ -681,11 +828,11 @@ class ScaleEstimator(stream.StreamKnobs):
     # RANSAC launched, results on their way -> collected.
     def _host_begin(self, f3s, f2s, frame_base, slot=stream.SLOT_CHUNK, background=False, ctx=None):
         pf = packing.pack_features(f3s, f2s, self.vanish)                                   # rescale.py:115-117
-        if pf.n_frames and pf.max_feat > self._max_points():
+        if pf.n_frames and pf.max_feat > self._frame_limit():
             self._refuse_oversized(pf, frame_base if np.isscalar(frame_base) else self._frame_counter)
         pf.extra["canonical"] = True
         return {"pf": pf, "h1": packing.submit_tri1(pf, self.delaunay_workers, slot=slot, background=background),   # :124
-                "ctx": ctx or self.ctx}
+                "ctx": ctx or self.ctx, "large": bool(pf.n_frames) and chunk_goes_large([pf.max_feat], self._max_points())}
 
     def _host_keep_start(self, rec):
         ctx, lib, pf = rec["ctx"], self.ctx.lib, rec["pf"]
@@ -693,8 +840,7 @@ class ScaleEstimator(stream.StreamKnobs):
         db = DeviceBatch(ctx, pf, with_tri2=False)
         aux = ctx.block([("keep", max(pf.total_padded, 1), np.int32)])
         bs = db.struct()
-        _lib.check(lib.mvosr_graph_keep_batch(ctx.handle, C.byref(bs), C.c_uint32(self._good_bits), MIN_VALID_FOR_RETRI, None,
-                                              aux["keep"].ptr, None, None), "mvosr_graph_keep_batch")
+        self._launch_keep(ctx, bs, None, aux["keep"].ptr, rec.get("large", False))
         aux.mark_done()
         rec.update(db=db, aux=aux)
 
@@ -712,7 +858,7 @@ class ScaleEstimator(stream.StreamKnobs):
         db.n_rows2 = int(pf.tri2_off[-1])
         max_tri = int(np.max(np.diff(pf.tri2_off))) if pf.n_frames else 0
         rec["out"], rec["flags"], side = self._launch_flat_ransac(db, rec["aux"]["keep"].ptr, None, frame_base, frame_ids, id_triples, stage,
-                                                                  max(max_tri, 1), ctx=rec["ctx"])
+                                                                  max(max_tri, 1), ctx=rec["ctx"], large=rec.get("large", False))
         rec["side"] = side + [rec["aux"]]
 
     def _host_collect(self, rec, stage):
@@ -843,6 +989,42 @@ class ScaleEstimator(stream.StreamKnobs):
             self._scatter(r.res, r.redo, sub, first, stage)
             first += len(r.redo)
 
+    def _stream_run_gpu(self, feature3ds, feature2ds, ra, rb, base, triples, stage, n_collected):
+        """Frames ``ra:rb`` of a call streamed through the device in chunks (``stream.plan`` / ``stream.run``): the whole call in the
+        default construction, one size class of it with ``large_frames=True``.  ``(bounds within the call, results, found)`` —
+        ``found``: (frame of the call, count) of the oversized frame the stream stopped before (default construction only: with
+        large_frames the call was cut beforehand), or None."""
+        whole = (ra, rb) == (0, len(feature3ds))
+        f3r, f2r = (feature3ds, feature2ds) if whole else (feature3ds[ra:rb], feature2ds[ra:rb])
+        F = rb - ra
+        C, ramp = stream.chunk_size(F, self.GPU_CHUNK, self.GPU_MIN_CHUNK, self.GPU_CHUNK_POINTS, [len(x) for x in f3r[:64]],
+                                    self.GPU_RAMP_FRACTIONS if self.GPU_RAMP else ())
+        found = []
+
+        def stop(a, lens):                     # (the stream ends before the first oversized frame)
+            o = self._first_oversized(f2r, lens, a)
+            if o is not None:
+                found.append(o)
+                return o[0]
+        deferred = []
+        collected = iter(range(n_collected, n_collected + F))
+
+        def start(a, b, tables, k):
+            self._trace("launch", k, b - a)
+            st = self._chunk_dev_gpu(f3r[a:b], f2r[a:b], base + ra + a, triples(ra + a, ra + b), stage, tables=tables,
+                                     early_status=self.GPU_REDO_EARLY and not stage and b == (found[0][0] if found else F) and a > 0)
+            self._trace("launched", k, b - a)
+            return st
+
+        def collect(st, a, b, last):
+            self._trace("collect", next(collected), b - a)
+            return self._chunk_dev_finish(st, f3r[a:b], f2r[a:b], base + ra + a, triples(ra + a, ra + b), stage, defer=deferred)
+        chunks = stream.plan(F, stream.tables_of(f3r, f2r), C, ramp, self.GPU_CHUNK_POINTS, self._resident_frames,
+                             None if self.large_frames else stop)
+        bounds, _, results = stream.run(chunks, start, collect, self.GPU_PIPELINE, stream.free_blocks, deferred,
+                                        lambda: self._finish_reruns(deferred, stage))
+        return [(ra + a, ra + b) for a, b in bounds], results, ((ra + found[0][0], found[0][1]) if found else None)
+
     def _stream_device(self, feature3ds, feature2ds, id_triples, stage, push=True):
         F = len(feature3ds)
         if F == 0:
@@ -853,49 +1035,42 @@ class ScaleEstimator(stream.StreamKnobs):
         # before it go through the slew limiter, the window and the sample counter, nothing queued is dropped, then the exception —
         # what the reference's per-frame loop would have left behind.
         oversized = None
-        if self.triangulation != "gpu":
+        limit = None
+        # large_frames=True: the call is cut into size classes instead (size_class_runs) — runs of frames the resident kernels take
+        # and runs beyond them, each streamed on its own, the large runs' chunks through the large-frame kernels — and ends before
+        # the first frame beyond the opt-in limit
+        runs = None
+        if self.large_frames:
+            limit = self._frame_limit()
+            below = self._below_vanish(feature2ds, [len(x) for x in feature2ds], 0, self._max_points())
+            runs, stop_at = size_class_runs(below, self._max_points(), limit)
+            if stop_at is not None:
+                oversized, F = (stop_at, int(below[stop_at])), stop_at
+        elif self.triangulation != "gpu":
             oversized = self._first_oversized(feature2ds, [len(x) for x in feature2ds], 0)
             if oversized is not None:
                 F = oversized[0]
+        if runs is None:
+            runs = [(0, F, False)] if F else []
         triples = lambda a, b: None if id_triples is None else id_triples[a:b]
+        bounds, results = [], []
         if self.triangulation == "gpu":
-            C, ramp = stream.chunk_size(F, self.GPU_CHUNK, self.GPU_MIN_CHUNK, self.GPU_CHUNK_POINTS, [len(x) for x in feature3ds[:64]],
-                                        self.GPU_RAMP_FRACTIONS if self.GPU_RAMP else ())
-            found = []
-
-            def stop(a, lens):                     # (the stream ends before the first oversized frame)
-                o = self._first_oversized(feature2ds, lens, a)
-                if o is not None:
-                    found.append(o)
-                    return o[0]
-            deferred = []
             self.chunk_trace = [] if os.environ.get("MVOSR_TRACE_CHUNKS") else None
             self._trace_t0 = time.perf_counter()
-            collected = iter(range(F))
-
-            def start(a, b, tables, k):
-                self._trace("launch", k, b - a)
-                st = self._chunk_dev_gpu(feature3ds[a:b], feature2ds[a:b], base + a, triples(a, b), stage, tables=tables,
-                                         early_status=self.GPU_REDO_EARLY and not stage and b == (found[0][0] if found else F) and a > 0)
-                self._trace("launched", k, b - a)
-                return st
-
-            def collect(st, a, b, last):
-                self._trace("collect", next(collected), b - a)
-                return self._chunk_dev_finish(st, feature3ds[a:b], feature2ds[a:b], base + a, triples(a, b), stage, defer=deferred)
-            chunks = stream.plan(F, stream.tables_of(feature3ds, feature2ds), C, ramp, self.GPU_CHUNK_POINTS, self._resident_frames, stop)
-            bounds, _, results = stream.run(chunks, start, collect, self.GPU_PIPELINE, stream.free_blocks, deferred,
-                                            lambda: self._finish_reruns(deferred, stage))
-            if found:
-                oversized, F = found[0], found[0][0]
+            for ra, rb, _ in runs:                   # (the default construction: ONE run, the whole call)
+                rbounds, rresults, found = self._stream_run_gpu(feature3ds, feature2ds, ra, rb, base, triples, stage, len(results))
+                bounds += rbounds
+                results += rresults
+                if found is not None:
+                    oversized, F = found, found[0]
         else:
-            bounds, results = [], []
-            for a in range(0, F, 2048):          # (F: the frames before the first oversized one)
-                b = min(F, a + 2048)
-                bounds.append((a, b))
-                results.append(self._chunk_dev_host(feature3ds[a:b], feature2ds[a:b], base + a, None, triples(a, b), stage))
+            for ra, rb, large in runs:
+                for a, b in host_chunks([len(x) for x in feature2ds[ra:rb]], 2048, self.GPU_CHUNK_POINTS if large else None):
+                    bounds.append((ra + a, ra + b))  # (the runs end before the first oversized frame)
+                    results.append(self._chunk_dev_host(feature3ds[ra + a:ra + b], feature2ds[ra + a:ra + b], base + ra + a, None,
+                                                        triples(ra + a, ra + b), stage))
         if oversized is not None and not results:
-            raise self._oversized_error(*oversized)
+            raise self._oversized_error(*oversized, limit)
         cat, host_errors = stream.concat(bounds, results, _FIELDS, "host_errors")
         self.last = dict(zip(_FIELDS, cat))
         raw, status, level = self.last["raw_scale"], self.last["status"], self.last["height_level"]
@@ -904,7 +1079,7 @@ class ScaleEstimator(stream.StreamKnobs):
                 self.last[k] = [x for r in results for x in r["stage"][k]]
         if oversized is not None:
             host_errors = dict(host_errors)
-            host_errors[F] = self._oversized_error(*oversized)
+            host_errors[F] = self._oversized_error(*oversized, limit)
             raw = np.concatenate([raw, [np.nan]])
             status = np.concatenate([status, np.array([K.ST_ERR_EMPTY], dtype=status.dtype)])
             level = np.concatenate([level, [np.nan]])
@@ -1216,7 +1391,10 @@ class RepeatedRuns:
 
     ``seeds``: the case seeds; else ``case_seeds(seed, cases)``; else drawn from the OS.  Row c of ``run`` equals
     ``offline.run_sequence_batched`` with ``ScaleEstimator(ransac_seed=seeds[c])``.  A second ``run`` continues the sequence: the
-    frame counter, every tail and the "previous scale" of the too-few-features rule carry over."""
+    frame counter, every tail and the "previous scale" of the too-few-features rule carry over.
+
+    A frame beyond the resident kernels' limit (``ScaleEstimator._max_points()``) is refused up front with the estimator's message,
+    also where the inner estimator is built with ``large_frames=True``: the cases kernel holds a frame in one workgroup's LDS."""
 
     def __init__(self, absolute_reference, window_size=5, cases=10, seeds=None, seed=None, **estimator_kw):
         if seeds is not None:
@@ -1431,7 +1609,8 @@ class ConstantSweep:
     ``configs``: a list of ``RescaleConstants`` (``ConstantSweep.grid`` builds a product).  Seeds as in ``RepeatedRuns``; every
     config runs the same case seeds.  Row ``[k, c]`` of ``run`` equals, bit for bit, row c of
     ``RepeatedRuns(absolute_reference, window_size, seeds=seeds, constants=configs[k]).run(data)``.  A frame must fit the kernels
-    of every config and the sweep kernel (``estimator._max_points()``)."""
+    of every config and the sweep kernel (``estimator._max_points()``) — ``large_frames=True`` does not change that limit or its
+    message."""
 
     MAX_SCORED_CASES = 32768                # rows of one scoring call (the scorers take 65535 cases a launch)
 
