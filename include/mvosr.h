@@ -1184,6 +1184,53 @@ int mvosr_height_pitch_eval_batch(mvosr_ctx *ctx, const mvosr_batch *b, const mv
                                   const int32_t *samples, const mvosr_height_pitch_eval_outputs *o);
 size_t mvosr_height_pitch_eval_lds_bytes(int max_feat, int n_hyp, int model);
 
+/* outputs of mvosr_height_pitch_eval_budgets_batch (device pointers; C = n_cases, B = n_budgets, H = the last budget; the optional
+ * ones may be NULL): per quantity of mvosr_height_pitch_eval_outputs one value per (frame, case, budget) */
+typedef struct mvosr_height_pitch_eval_budgets_outputs {
+    double *ransac_height;       /* [F][C][B] */
+    double *model;               /* [F][C][B][4] */
+    int32_t *best_ic, *used;     /* [F][C][B]; used: budgets[k] unless the goal stop came earlier */
+    int32_t *n_selected;         /* [F] length of the point list (the same for every case and budget) */
+    int32_t *n_inliers;          /* [F][C][B] */
+    double *refined_normal;      /* [F][C][B][3] */
+    double *refined_pitch;       /* [F][C][B] */
+    double *refined_mean, *refined_std;   /* [F][C][B] */
+    double *height_t_mean;       /* [F][C][B] */
+    double *sum_y, *sum_z;       /* [F][C][B] */
+    int32_t *status;             /* [F][C][B] as mvosr_height_pitch_eval_outputs */
+    int32_t *best;               /* [F][C][B] the hypothesis number of the best model among the first budgets[k]; -1: none */
+    int32_t *point_list;         /* optional: as mvosr_height_pitch_outputs */
+    int32_t *hyp_counts;         /* optional [F][C][H]; written for fitted frames only */
+} mvosr_height_pitch_eval_budgets_outputs;
+
+/*
+ * mvosr_height_pitch_eval_batch at every iteration budget of a list in ONE launch (height_pitch_eval_budgets_kernel<model>; grid
+ * and workgroup as height_pitch_eval_kernel).  budgets: int32[n_budgets] on the HOST, 1 <= n_budgets <= 16, strictly ascending,
+ * budgets[0] >= 1 and the last <= 4096; anything else: MVOSR_ERR_ARG, nothing is launched.  H = the last budget.  p->n_hyp is
+ * IGNORED (not read); every other member of p means what it means to mvosr_height_pitch_eval_batch.  samples: NULL (the device
+ * draws) or [F][C][H][3].
+ * Contract: for every k, slot [f][c][k] of every output that mvosr_height_pitch_eval_batch also has holds, BYTE FOR BYTE, what
+ * that entry point writes at [f][c] when called with n_hyp = budgets[k] and the same batch, params, seed, frame_base and priors
+ * (with samples: the first budgets[k] samples of each (frame, case)) — `used` (budgets[k] unless the goal stop came earlier), the
+ * MVOSR_ST_RS_FEW case where none of the first budgets[k] hypotheses has an inlier (doubles NaN, counts 0, used = budgets[k],
+ * best = -1) and the MVOSR_ST_HP_REFINE_DEGENERATE bit included.  n_selected and point_list are those of any of these calls,
+ * hyp_counts the call's at H.  A frame that is not fitted (empty; feat_cnt > max_feat or more rows than 2 max_feat, refused
+ * before LDS is touched; an id outside the frame; a singular row; fewer than min_points list entries, n_selected written) has the
+ * refusal outputs of mvosr_height_pitch_eval_batch in all B slots of every case, best = -1, and leaves its neighbours alone.
+ * Results depend neither on cases_per_group, nor on how a sequence is cut into batches (frame_base), nor on which other budgets
+ * are in the list.
+ * How: the draw of hypothesis h is keyed by (seed, frame_base + f, c, h) and not by n_hyp, so planes and counts are computed ONCE
+ * per (frame, case) for H hypotheses; the replay runs over segments that end at the budgets and its state is kept per budget; the
+ * inliers, the refinement and the sums run once per distinct best model among a case's budgets.  With hyp_counts == NULL the tiles
+ * behind the goal stop are skipped.
+ * LDS: mvosr_height_pitch_eval_budgets_lds_bytes(max_feat, n_hyp_max, n_budgets, model) =
+ * mvosr_height_pitch_eval_lds_bytes(max_feat, n_hyp_max, model) + 48 n_budgets.  Limits as mvosr_height_pitch_eval_batch.
+ */
+int mvosr_height_pitch_eval_budgets_batch(mvosr_ctx *ctx, const mvosr_batch *b, const mvosr_height_pitch_eval_params *p, const int32_t *budgets,
+                                          int n_budgets, const double *frame_prior, const int32_t *samples,
+                                          const mvosr_height_pitch_eval_budgets_outputs *o);
+size_t mvosr_height_pitch_eval_budgets_lds_bytes(int max_feat, int n_hyp_max, int n_budgets, int model);
+
 /* ---- dense depth maps from the triangle planes (/root/reference/src/reconstruct.py) ------------------ */
 
 /* The pinhole camera of the reference's PinholeCamera (/root/reference/src/reconstruct.py:21-36 reads these six). */

@@ -280,6 +280,133 @@ def eval_file_names(model, input_id, input_date, iterations, cases=10):
             for c in range(cases) for stem, ext in EVAL_FILES]
 
 
+def _nonempty_runs(frames, batch):
+    """Contiguous runs of non-empty dumps, at most ``batch`` frames each: the sample sequence's frame counter is the dump's index,
+    so a split run draws what the whole run draws."""
+    runs = []
+    for i in range(len(frames)):
+        if not np.asarray(frames[i]).size:
+            continue
+        if runs and runs[-1][-1] == i - 1 and len(runs[-1]) < int(batch):
+            runs[-1].append(i)
+        else:
+            runs.append([i])
+    return runs
+
+
+def _eval_frame_rules(i, est, st, n_sel, value, prev, budget=None):
+    """The scripts' cross-frame rules for frame ``i`` of ONE run (one budget): ``st`` (cases,) the launch's statuses, ``n_sel`` the
+    list's length, ``value(name)`` -> (cases,) the launch's output, ``prev`` the last fitted frame's dict (None: none yet) ->
+    (the frame's dict: the six values, sum_y, sum_z, degenerate — per case, carried).  Raises what the scripts raise."""
+    if np.any(st == ST_ERR_SINGULAR):
+        raise np.linalg.LinAlgError("Singular matrix")                               # :101
+    if np.any((st == ST_ERR_MASK) | (st == ST_ERR_EMPTY)):
+        raise ValueError("frame %d: %s" % (i, "no features or no triangles" if np.any(st == ST_ERR_EMPTY) else
+                                           "a triangle names a vertex outside the frame"))
+    if np.any(st == ST_RS_FEW) and n_sel >= MIN_POINTS:
+        raise ValueError("frame %d: no sample of the RANSAC had an inlier" % i + ("" if budget is None else " at budget %d" % budget))
+    if n_sel < MIN_POINTS:
+        if prev is None:                                                             # :188 indexes the 1-D norm_prev of :55 with two indices
+            raise IndexError("too many indices for array: array is 1-dimensional, but 2 were indexed")
+        cur = dict(prev)
+        # :184-186 and the surviving `inliers`: everything repeats, but :223-224 see the new prior
+        cur["height_t_mean"] = np.where(prev["degenerate"], np.nan,
+                                        (prev["sum_z"] * math.sin(est) + prev["sum_y"] * math.cos(est)) / prev["n_inliers"])
+        return cur, True
+    cur = {k2: np.array(value(k2), dtype=np.float64) for k2 in RESULT_FIELDS + ("sum_y", "sum_z")}
+    cur["degenerate"] = (st & ST_HP_REFINE_DEGENERATE) != 0
+    return cur, False
+
+
+def _eval_launch(ev, H, budgets, points3d_list, priors, samples, tris, frame_base, stage, max_feat, timing, cases_per_group):
+    """The launch of both evaluation objects: ``budgets`` None — ``mvosr_height_pitch_eval_batch`` with ``H`` hypotheses, (F, C) per
+    quantity; a tuple — ``mvosr_height_pitch_eval_budgets_batch``, ``H`` its last, (F, C, B) per quantity and ``best``."""
+    ctx, lib = ev.ctx, ev.ctx.lib
+    pts = [np.ascontiguousarray(np.asarray(p, dtype=np.float64).reshape(-1, 3)) for p in points3d_list]
+    F, Cn = len(pts), ev.cases
+    if F == 0:
+        return None
+    rows = [np.ascontiguousarray(np.asarray(t, dtype=np.int32).reshape(-1, 3)) for t in tris] if tris is not None \
+        else _delaunay_rows(ctx, [np.ascontiguousarray(p[:, 0:2]) for p in pts], ev.triangulation, ev.delaunay_workers)
+    cnt = np.array([len(p) for p in pts], dtype=np.int32)
+    max_feat = int(cnt.max()) if max_feat is None else int(max_feat)
+    need = int(lib.mvosr_height_pitch_eval_lds_bytes(max_feat, H, EVAL_MODELS[ev.model])) if budgets is None else \
+        int(lib.mvosr_height_pitch_eval_budgets_lds_bytes(max_feat, H, len(budgets), EVAL_MODELS[ev.model]))
+    if need > ctx.lds_per_block:
+        raise ValueError("a frame of %d features needs %d bytes of LDS, the device has %d" % (max_feat, need, ctx.lds_per_block))
+    spec_in, arrays, off, toff, planes, T = _pack_frames(pts, rows, priors)
+    if samples is not None:
+        sm = np.full((F, Cn, H, 3), -1, dtype=np.int32)                             # (-1: outside every list, the sample is spent)
+        for f, t in enumerate(samples):
+            if t is None:
+                continue
+            t = np.asarray(t, dtype=np.int32)
+            if t.ndim != 3 or t.shape[0] != Cn or t.shape[2] not in (2, 3):
+                raise ValueError("samples[%d] must be shaped (cases, h, 2 or 3)" % f)
+            h = min(H, t.shape[1])
+            sm[f, :, :h, :t.shape[2]] = t[:, :h]
+        spec_in.append(("samples", (F, Cn, H, 3), np.int32))
+        arrays["samples"] = sm
+    FC = (F, Cn) if budgets is None else (F, Cn, len(budgets))
+    spec_out = [("ransac_height", FC, np.float64), ("model", FC + (4,), np.float64), ("best_ic", FC, np.int32), ("used", FC, np.int32),
+                ("n_selected", F, np.int32), ("n_inliers", FC, np.int32), ("refined_normal", FC + (3,), np.float64),
+                ("refined_pitch", FC, np.float64), ("refined_mean", FC, np.float64), ("refined_std", FC, np.float64),
+                ("height_t_mean", FC, np.float64), ("sum_y", FC, np.float64), ("sum_z", FC, np.float64), ("status", FC, np.int32)]
+    if budgets is not None:
+        spec_out.append(("best", FC, np.int32))
+    if stage:
+        spec_out += ([("list_mask", (Cn, 3 * T), np.uint8)] if budgets is None else []) + \
+            [("point_list", 3 * T, np.int32), ("hyp_counts", (F, Cn, H), np.int32)]
+    din, dout = ctx.block(spec_in), ctx.block(spec_out)
+    try:
+        din.upload(arrays)
+        dout.zero()
+        b = _batch_header(din, F, max_feat, planes.shape[1])
+        G = ev.cases_per_group if cases_per_group is None else int(cases_per_group)
+        p = _lib.HeightPitchEvalParams(ev.focus, ev.cx, ev.cy, MIN_POINTS, H, ev.threshold, GOAL_FRACTION, ev.inlier_threshold,
+                                       ev.seed, int(frame_base), EVAL_MODELS[ev.model], Cn, G)
+        o = _lib.HeightPitchEvalOutputs() if budgets is None else _lib.HeightPitchEvalBudgetsOutputs()
+        for k, tp in o._fields_:
+            if k == "list_stride":
+                o.list_stride = 3 * T
+            elif k in dout:
+                setattr(o, k, dout[k].ptr)
+        sp = din["samples"].ptr if samples is not None else None
+        if budgets is None:
+            def call():
+                _lib.check(lib.mvosr_height_pitch_eval_batch(ctx.handle, C.byref(b), C.byref(p), din["prior"].ptr, sp, C.byref(o)),
+                           "mvosr_height_pitch_eval_batch")
+        else:
+            bud = (C.c_int32 * len(budgets))(*budgets)
+            def call():
+                _lib.check(lib.mvosr_height_pitch_eval_budgets_batch(ctx.handle, C.byref(b), C.byref(p), bud, len(budgets), din["prior"].ptr,
+                                                                     sp, C.byref(o)), "mvosr_height_pitch_eval_budgets_batch")
+        call()
+        kernel_ms = None
+        if timing > 0:
+            ev2 = ctx.event(), ctx.event()
+            ctx.record(ev2[0])
+            for _ in range(int(timing)):
+                call()
+            ctx.record(ev2[1])
+            kernel_ms = ctx.elapsed_ms(*ev2) / int(timing)
+            for e in ev2:
+                lib.mvosr_event_destroy(ctx.handle, e)
+        res = {k: dout[k].download() for k, _, _ in spec_out}
+        if kernel_ms is not None:
+            res["kernel_ms"] = kernel_ms
+    finally:
+        din.free()
+        dout.free()
+    if stage:
+        nsel = [max(int(m), 0) for m in res["n_selected"]]
+        if budgets is None:
+            res["list_mask"] = [res["list_mask"][:, 3 * toff[f]:3 * toff[f] + nsel[f]].astype(bool) for f in range(F)]
+        res["point_list"] = [res["point_list"][3 * toff[f]:3 * toff[f] + nsel[f]] for f in range(F)]
+    res["rows"] = rows
+    return res
+
+
 class RansacEvaluation:
     """``calculate_height_pitch_eval.py`` (model "plane") and ``calculate_height_pitch_eval_line.py`` ("line"): the sequence run
     ``cases`` times with ``iterations`` hypotheses per frame, every case with a sample sequence of its own.  One launch per batch of
@@ -313,79 +440,7 @@ class RansacEvaluation:
         ``n_selected`` (F,)).  ``samples``: None (the device draws), or per frame an array of list positions shaped (C, h, 2 or 3),
         h <= iterations (None / shorter: the missing samples are spent).  ``stage``: also ``hyp_counts`` (F, C, H), ``list_mask``
         (per frame (C, n_selected) bool) and ``point_list``."""
-        ctx, lib = self.ctx, self.ctx.lib
-        pts = [np.ascontiguousarray(np.asarray(p, dtype=np.float64).reshape(-1, 3)) for p in points3d_list]
-        F, H, Cn = len(pts), self.iterations, self.cases
-        if F == 0:
-            return None
-        rows = [np.ascontiguousarray(np.asarray(t, dtype=np.int32).reshape(-1, 3)) for t in tris] if tris is not None \
-            else _delaunay_rows(ctx, [np.ascontiguousarray(p[:, 0:2]) for p in pts], self.triangulation, self.delaunay_workers)
-        cnt = np.array([len(p) for p in pts], dtype=np.int32)
-        max_feat = int(cnt.max()) if max_feat is None else int(max_feat)
-        need = int(lib.mvosr_height_pitch_eval_lds_bytes(max_feat, H, EVAL_MODELS[self.model]))
-        if need > ctx.lds_per_block:
-            raise ValueError("a frame of %d features needs %d bytes of LDS, the device has %d" % (max_feat, need, ctx.lds_per_block))
-        spec_in, arrays, off, toff, planes, T = _pack_frames(pts, rows, priors)
-        if samples is not None:
-            sm = np.full((F, Cn, H, 3), -1, dtype=np.int32)                         # (-1: outside every list, the sample is spent)
-            for f, t in enumerate(samples):
-                if t is None:
-                    continue
-                t = np.asarray(t, dtype=np.int32)
-                if t.ndim != 3 or t.shape[0] != Cn or t.shape[2] not in (2, 3):
-                    raise ValueError("samples[%d] must be shaped (cases, h, 2 or 3)" % f)
-                h = min(H, t.shape[1])
-                sm[f, :, :h, :t.shape[2]] = t[:, :h]
-            spec_in.append(("samples", (F, Cn, H, 3), np.int32))
-            arrays["samples"] = sm
-        FC = (F, Cn)
-        spec_out = [("ransac_height", FC, np.float64), ("model", (F, Cn, 4), np.float64), ("best_ic", FC, np.int32), ("used", FC, np.int32),
-                    ("n_selected", F, np.int32), ("n_inliers", FC, np.int32), ("refined_normal", (F, Cn, 3), np.float64),
-                    ("refined_pitch", FC, np.float64), ("refined_mean", FC, np.float64), ("refined_std", FC, np.float64),
-                    ("height_t_mean", FC, np.float64), ("sum_y", FC, np.float64), ("sum_z", FC, np.float64), ("status", FC, np.int32)]
-        if stage:
-            spec_out += [("list_mask", (Cn, 3 * T), np.uint8), ("point_list", 3 * T, np.int32), ("hyp_counts", (F, Cn, H), np.int32)]
-        din, dout = ctx.block(spec_in), ctx.block(spec_out)
-        try:
-            din.upload(arrays)
-            dout.zero()
-            b = _batch_header(din, F, max_feat, planes.shape[1])
-            G = self.cases_per_group if cases_per_group is None else int(cases_per_group)
-            p = _lib.HeightPitchEvalParams(self.focus, self.cx, self.cy, MIN_POINTS, H, self.threshold, GOAL_FRACTION, self.inlier_threshold,
-                                           self.seed, int(frame_base), EVAL_MODELS[self.model], Cn, G)
-            o = _lib.HeightPitchEvalOutputs()
-            for k, tp in _lib.HeightPitchEvalOutputs._fields_:
-                if k == "list_stride":
-                    o.list_stride = 3 * T
-                elif k in dout:
-                    setattr(o, k, dout[k].ptr)
-            def call():
-                _lib.check(lib.mvosr_height_pitch_eval_batch(ctx.handle, C.byref(b), C.byref(p), din["prior"].ptr,
-                                                             din["samples"].ptr if samples is not None else None, C.byref(o)),
-                           "mvosr_height_pitch_eval_batch")
-            call()
-            kernel_ms = None
-            if timing > 0:
-                ev = ctx.event(), ctx.event()
-                ctx.record(ev[0])
-                for _ in range(int(timing)):
-                    call()
-                ctx.record(ev[1])
-                kernel_ms = ctx.elapsed_ms(*ev) / int(timing)
-                for e in ev:
-                    lib.mvosr_event_destroy(ctx.handle, e)
-            res = {k: dout[k].download() for k, _, _ in spec_out}
-            if kernel_ms is not None:
-                res["kernel_ms"] = kernel_ms
-        finally:
-            din.free()
-            dout.free()
-        if stage:
-            nsel = [max(int(m), 0) for m in res["n_selected"]]
-            res["list_mask"] = [res["list_mask"][:, 3 * toff[f]:3 * toff[f] + nsel[f]].astype(bool) for f in range(F)]
-            res["point_list"] = [res["point_list"][3 * toff[f]:3 * toff[f] + nsel[f]] for f in range(F)]
-        res["rows"] = rows
-        return res
+        return _eval_launch(self, self.iterations, None, points3d_list, priors, samples, tris, frame_base, stage, max_feat, timing, cases_per_group)
 
     # ---- the scripts' run
     def run(self, frames, motion_ts, samples=None, tris=None, batch=512):
@@ -399,45 +454,16 @@ class RansacEvaluation:
         ests = estimated_pitches(motion_ts, 1, n) if n else np.zeros(0)
         out = {k: np.zeros((Cn, n), dtype=np.float64) for k in RESULT_FIELDS}
         self.carried, self.degenerate = np.zeros(n, dtype=bool), np.zeros((Cn, n), dtype=bool)
-        # contiguous runs of non-empty dumps, at most `batch` frames each: the sample sequence's frame counter is the dump's
-        # index, so a split run draws what the whole run draws
-        runs = []
-        for i in range(n):
-            if not np.asarray(frames[i]).size:
-                continue
-            if runs and runs[-1][-1] == i - 1 and len(runs[-1]) < int(batch):
-                runs[-1].append(i)
-            else:
-                runs.append([i])
         prev = None                                    # per case: the six values, sum_y, sum_z, degenerate — of the last fitted frame
-        for idx in runs:
+        for idx in _nonempty_runs(frames, batch):
             r = self.launch([frames[i] for i in idx], [frame_prior(ests[i]) for i in idx], None if samples is None else [samples[i] for i in idx],
                             None if tris is None else [tris[i] for i in idx], frame_base=idx[0])
             self.last = r
             for j, i in enumerate(idx):
-                st, n_sel = r["status"][j], int(r["n_selected"][j])
-                if np.any(st == ST_ERR_SINGULAR):
-                    raise np.linalg.LinAlgError("Singular matrix")                   # :101
-                if np.any((st == ST_ERR_MASK) | (st == ST_ERR_EMPTY)):
-                    raise ValueError("frame %d: %s" % (i, "no features or no triangles" if np.any(st == ST_ERR_EMPTY) else
-                                                       "a triangle names a vertex outside the frame"))
-                if np.any(st == ST_RS_FEW) and n_sel >= MIN_POINTS:
-                    raise ValueError("frame %d: no sample of the RANSAC had an inlier" % i)
-                if n_sel < MIN_POINTS:
-                    if prev is None:                                                 # :188 indexes the 1-D norm_prev of :55 with two indices
-                        raise IndexError("too many indices for array: array is 1-dimensional, but 2 were indexed")
-                    self.carried[i] = True
-                    cur = dict(prev)
-                    # :184-186 and the surviving `inliers`: everything repeats, but :223-224 see the new prior
-                    cur["height_t_mean"] = np.where(prev["degenerate"], np.nan,
-                                                    (prev["sum_z"] * math.sin(ests[i]) + prev["sum_y"] * math.cos(ests[i])) / prev["n_inliers"])
-                else:
-                    cur = {k2: np.array(r[k2][j], dtype=np.float64) for k2 in RESULT_FIELDS + ("sum_y", "sum_z")}
-                    cur["degenerate"] = (st & ST_HP_REFINE_DEGENERATE) != 0
-                prev = cur
+                prev, self.carried[i] = _eval_frame_rules(i, ests[i], r["status"][j], int(r["n_selected"][j]), lambda k2: r[k2][j], prev)
                 for k2 in RESULT_FIELDS:
-                    out[k2][:, i] = cur[k2]
-                self.degenerate[:, i] = cur["degenerate"]
+                    out[k2][:, i] = prev[k2]
+                self.degenerate[:, i] = prev["degenerate"]
         self.results = out
         return out
 
@@ -467,3 +493,161 @@ class RansacEvaluation:
                 np.savetxt(os.path.join(directory, names[c * len(RESULT_FIELDS) + k]), self.results[field][c])
         return [os.path.join(directory, x) for x in names]
 
+
+
+# ---- the evaluation runs at every budget of a list ---------------------------------------------------------------------------
+MAX_EVAL_BUDGETS = 16                                                                # kHpeMaxBudgets
+
+
+def check_budgets(budgets):
+    """The iteration budgets of a sweep as a tuple of ints: 1 to 16 of them, strictly ascending, each in 1..4096 — what
+    ``mvosr_height_pitch_eval_budgets_batch`` accepts.  Anything else raises ``ValueError``.  Needs no device."""
+    try:
+        out = tuple(int(b) for b in budgets)
+    except TypeError:
+        raise ValueError("budgets must be a sequence of integers")
+    if any(o != b for o, b in zip(out, budgets)):
+        raise ValueError("budgets must be integers")
+    if not 1 <= len(out) <= MAX_EVAL_BUDGETS:
+        raise ValueError("1 to %d budgets, got %d" % (MAX_EVAL_BUDGETS, len(out)))
+    if out[0] < 1 or out[-1] > MAX_EVAL_ITERATIONS:
+        raise ValueError("budgets must be in 1..%d" % MAX_EVAL_ITERATIONS)
+    if any(b <= a for a, b in zip(out, out[1:])):
+        raise ValueError("budgets must be strictly ascending")
+    return out
+
+
+class RansacBudgetSweep:
+    """What the two evaluation scripts are run for — how many RANSAC iterations the road-plane fit needs: the runs of
+    :class:`RansacEvaluation` at every iteration budget of ``budgets`` from ONE launch per batch of frames
+    (``mvosr_height_pitch_eval_budgets_batch``).  The sample sequence of a (frame, case) does not depend on the
+    budget, so the run at budget b is the first b hypotheses of the run at the largest: row k of every result equals, bit for bit,
+    ``RansacEvaluation(model, budgets[k], cases, seed=seed, ...)`` on the same inputs (recorded ``samples`` cut to that budget)."""
+
+    def __init__(self, model, budgets, cases=10, focus=FOCUS, cx=CX, cy=CY, threshold=0.005, inlier_threshold=0.01, seed=None,
+                 device=0, triangulation="scipy", cases_per_group=None, delaunay_workers=0):
+        if model not in EVAL_MODELS:
+            raise ValueError("model must be 'plane' or 'line'")
+        if triangulation not in ("scipy", "gpu"):
+            raise ValueError("triangulation must be 'scipy' or 'gpu'")
+        self.budgets = check_budgets(budgets)
+        if int(cases) < 1:
+            raise ValueError("cases must be at least 1")
+        self.ctx = _lib.default_context(device)
+        self.model, self.cases = model, int(cases)
+        self.focus, self.cx, self.cy = float(focus), float(cx), float(cy)
+        self.threshold, self.inlier_threshold = float(threshold), float(inlier_threshold)
+        self.seed = int.from_bytes(os.urandom(8), "little") if seed is None else int(seed) & (2 ** 64 - 1)
+        self.triangulation, self.delaunay_workers = triangulation, delaunay_workers
+        self.cases_per_group = 0 if cases_per_group is None else int(cases_per_group)
+        self.results = None                            # field -> (B, cases, frames) after run()
+        self.carried = None                            # (frames,) bool
+        self.degenerate = None                         # (B, cases, frames) bool
+        self.used = None                               # (B, cases, frames) hypotheses replayed; 0 on empty and carried frames
+        self.best = None                               # (B, cases, frames) the best hypothesis' number; -1 on empty and carried frames
+        self.last = None
+
+    # ---- one launch
+    def launch(self, points3d_list, priors, samples=None, tris=None, frame_base=0, stage=False, max_feat=None, timing=0, cases_per_group=None):
+        """``mvosr_height_pitch_eval_budgets_batch`` over the frames -> dict of host arrays, (F, C, B) per quantity of
+        :meth:`RansacEvaluation.launch` (``model`` (F, C, B, 4), ``n_selected`` (F,)) and ``best`` (F, C, B).  ``samples``: None (the
+        device draws), or per frame list positions shaped (C, h, 2 or 3), h <= the last budget (None / shorter: the missing samples are
+        spent).  ``stage``: also ``hyp_counts`` (F, C, last budget) and ``point_list``."""
+        return _eval_launch(self, self.budgets[-1], self.budgets, points3d_list, priors, samples, tris, frame_base, stage, max_feat, timing,
+                            cases_per_group)
+
+    # ---- the scripts' runs
+    def run(self, frames, motion_ts, samples=None, tris=None, batch=512):
+        """:meth:`RansacEvaluation.run` at every budget: dict field -> (B, cases, frames).  The scripts' cross-frame rules — the empty
+        dump, the carried frame under the new prior, the first frame's ``IndexError``, ``LinAlgError`` — apply per (budget, case).
+        Where a single run would raise "no sample of the RANSAC had an inlier", so does this, naming the frame and the smallest
+        such budget."""
+        n, Cn, B = len(frames), self.cases, len(self.budgets)
+        ests = estimated_pitches(motion_ts, 1, n) if n else np.zeros(0)
+        out = {k: np.zeros((B, Cn, n), dtype=np.float64) for k in RESULT_FIELDS}
+        self.carried, self.degenerate = np.zeros(n, dtype=bool), np.zeros((B, Cn, n), dtype=bool)
+        self.used, self.best = np.zeros((B, Cn, n), dtype=np.int32), np.full((B, Cn, n), -1, dtype=np.int32)
+        prev = [None] * B                              # per budget what RansacEvaluation.run carries
+        for idx in _nonempty_runs(frames, batch):
+            r = self.launch([frames[i] for i in idx], [frame_prior(ests[i]) for i in idx], None if samples is None else [samples[i] for i in idx],
+                            None if tris is None else [tris[i] for i in idx], frame_base=idx[0])
+            self.last = r
+            for j, i in enumerate(idx):
+                n_sel = int(r["n_selected"][j])
+                for k, budget in enumerate(self.budgets):
+                    prev[k], self.carried[i] = _eval_frame_rules(i, ests[i], r["status"][j][:, k], n_sel, lambda k2: r[k2][j][:, k], prev[k], budget)
+                    for k2 in RESULT_FIELDS:
+                        out[k2][k, :, i] = prev[k][k2]
+                    self.degenerate[k, :, i] = prev[k]["degenerate"]
+                if not self.carried[i]:
+                    self.used[:, :, i], self.best[:, :, i] = r["used"][j].T, r["best"][j].T
+        self.results = out
+        return out
+
+    def _need_results(self):
+        if self.results is None:
+            raise RuntimeError("run() first")
+
+    def results_at(self, budget):
+        """The run at ``budget`` (one of the list): dict field -> (cases, frames), as :meth:`RansacEvaluation.run` returns it."""
+        self._need_results()
+        if budget not in self.budgets:
+            raise ValueError("budget %r is not in the list %r" % (budget, self.budgets))
+        k = self.budgets.index(budget)
+        return {f: v[k] for f, v in self.results.items()}
+
+    def spread(self):
+        """Per budget and frame the mean and the (population) std over the cases: dict field -> (mean (B, frames), std (B, frames)),
+        with :meth:`RansacEvaluation.spread`'s NaN handling (refined values of degenerate pairs are left out)."""
+        self._need_results()
+        import warnings
+        out = {}
+        with np.errstate(all="ignore"), warnings.catch_warnings():
+            warnings.simplefilter("ignore", RuntimeWarning)
+            for k, v in self.results.items():
+                out[k] = (np.nanmean(v, axis=1), np.nanstd(v, axis=1))
+        return out
+
+    def table(self, field="ransac_height"):
+        """What the runs are for, a row (dict) per budget: ``budget``; ``mean_std`` and ``max_std``, the mean and the maximum over
+        the fitted frames of the std of ``field`` over the cases; ``mean_used``, the mean number of hypotheses replayed, and
+        ``stopped_share``, the share of (case, frame) pairs whose goal stop came before the budget — both over the fitted frames.
+        A fitted frame is one with a fit of its own at the largest budget: not an empty dump, not a carried frame."""
+        self._need_results()
+        fitted = np.any(self.used[-1] > 0, axis=0)                                   # (frames,)
+        std = self.spread()[field][1][:, fitted]                                     # (B, fitted frames)
+        rows = []
+        import warnings
+        with np.errstate(all="ignore"), warnings.catch_warnings():
+            warnings.simplefilter("ignore", RuntimeWarning)
+            for k, budget in enumerate(self.budgets):
+                u = self.used[k][:, fitted]
+                rows.append({"budget": budget,
+                             "mean_std": float(np.nanmean(std[k])) if std[k].size else float("nan"),
+                             "max_std": float(np.nanmax(std[k])) if std[k].size else float("nan"),
+                             "mean_used": float(u.mean()) if u.size else float("nan"),
+                             "stopped_share": float((u < budget).mean()) if u.size else float("nan")})
+        return rows
+
+    def smallest_budget(self, field="ransac_height", within=0.1):
+        """The smallest budget whose ``mean_std`` of :meth:`table` lies within ``within`` (relative) of the largest budget's."""
+        rows = self.table(field)
+        ref = rows[-1]["mean_std"]
+        for r in rows:
+            if abs(r["mean_std"] - ref) <= float(within) * abs(ref):
+                return r["budget"]
+        return rows[-1]["budget"]
+
+    def write_results(self, directory, input_id, input_date):
+        """The scripts' sixty files PER BUDGET under the scripts' own names — the budget is part of every name (_eval.py:250-265) —
+        in ``directory``/eval_ransac or ``directory``/eval_ransac_line (created if missing).  Returns the paths, budget-major."""
+        self._need_results()
+        os.makedirs(os.path.join(directory, EVAL_DIRS[self.model]), exist_ok=True)
+        paths = []
+        for b, budget in enumerate(self.budgets):
+            names = eval_file_names(self.model, input_id, input_date, budget, self.cases)
+            for c in range(self.cases):
+                for k, field in enumerate(RESULT_FIELDS):
+                    np.savetxt(os.path.join(directory, names[c * len(RESULT_FIELDS) + k]), self.results[field][b][c])
+            paths += [os.path.join(directory, x) for x in names]
+        return paths
