@@ -840,6 +840,48 @@ int mvosr_static_tri_batch(mvosr_ctx *ctx, int64_t n_lists, const int64_t *off, 
                            const uint8_t *flags, int32_t min_count, double absolute_reference, double *scale_norm,
                            double *raw_scale, int32_t *n_used, int32_t *hist, int32_t *status);
 
+/* per-frame outputs of mvosr_flat_static_tri_batch (device pointers; the optional ones may be NULL) */
+typedef struct mvosr_static_tri_outputs {
+    double *scale_norm, *raw_scale;   /* [F]; NaN unless status is MODE or MEDIAN */
+    double *height_level;             /* [F] as mvosr_flat_ransac_batch writes it */
+    int32_t *n_used, *n_kept, *status;/* [F] */
+    int32_t *hist;                    /* optional [F][19], after the ones are zeroed */
+    double *tri_height;               /* optional, laid out like tri2 */
+    uint8_t *tri_flags;               /* optional, bits 0..2 as mvosr_flat_ransac_batch */
+} mvosr_static_tri_outputs;
+
+/*
+ * flat_selection (rescale.py:75-102) and the histogram-mode road model over its loose heights (scale_calculation_static_tri,
+ * rescale.py:179-187) in ONE kernel per frame on the device-resident form of a batch (flat_static_tri_kernel):
+ * what mvosr_flat_ransac_batch with tri_height / tri_flags outputs followed by mvosr_static_tri_batch in row form computes, the
+ * heights and flags never leaving LDS.  It reads what mvosr_flat_ransac_batch reads: the batch, keep (survivors keep[i] >= 0,
+ * compacted in order at load; NULL: all), dt_status, b->tri2 / tri2_off / tri2_cnt, max_tri (<= 0: 2 * b->max_feat).
+ * Per frame: every row's height and bits 0 and 1 as mvosr_flat_selection_batch decides them; height_level = height_factor *
+ * median(h[loose]), bit 2 and n_kept as there; and over the loose rows' heights the road model exactly as mvosr_static_tri_batch
+ * states it above (hi = 1.0 / h, the 19 bins, ones zeroed, median or first run; n <= min_count or no loose row: MVOSR_ST_RS_FEW),
+ * raw_scale = scale_norm * absolute_reference, n_used = the number of loose rows.  Every output is compared for bit equality.
+ * Status: a flat-stage refusal or error takes precedence, as mvosr_flat_ransac_batch reports it — MVOSR_ST_ERR_EMPTY (no features
+ * or rows, dt_status[f] != 0), MVOSR_ST_ERR_MASK (feat_cnt[f] > b->max_feat or more rows than max_tri, refused before LDS is
+ * touched; or a row naming a vertex outside the frame), MVOSR_ST_ERR_SINGULAR —: scale_norm and raw_scale NaN, n_used 0, hist zero.
+ * Otherwise the model's status as mvosr_static_tri_batch gives it (MODE, MEDIAN, RS_FEW, or its own MVOSR_ST_ERR_MASK for a loose
+ * height that is not finite or not > 0).  height_level, n_kept, tri_height and tri_flags are always what mvosr_flat_ransac_batch
+ * writes for that frame (a refused frame: height_level NaN, n_kept 0, its tri_height / tri_flags rows not written).
+ * The given form — tri_height_in and tri_flags_in both non-NULL, laid out like tri2 (as mvosr_region_grow_batch takes heights):
+ * the rows' heights and bits 0 and 1 are read from those arrays; x / y / z, keep and tri2 are not read; everything behind them runs
+ * the same code; bit 0 says a row counts.  Nothing row-sized is kept in LDS, so max_tri bounds a frame's rows but not the request.
+ * One of the two pointers alone: MVOSR_ERR_ARG.
+ * LDS: mvosr_flat_static_tri_lds_bytes(b->max_feat, max_tri) — less than mvosr_flat_ransac_batch asks at the same sizes from 342
+ * features on, below 64 KiB before —: the launch accepts every frame that one accepts.
+ * n_frames <= 0: MVOSR_OK, nothing launched.  MVOSR_ERR_ARG: a NULL ctx, batch, o or mandatory output, or min_count < 0.
+ */
+int mvosr_flat_static_tri_batch(mvosr_ctx *ctx, const mvosr_batch *b, const int32_t *keep,
+                                double loose_deg, double tight_deg, double height_factor,
+                                int32_t min_count, double absolute_reference,
+                                const int32_t *dt_status,
+                                const double *tri_height_in, const uint8_t *tri_flags_in,
+                                const mvosr_static_tri_outputs *o, int64_t max_tri);
+size_t mvosr_flat_static_tri_lds_bytes(int max_feat, int64_t max_tri);
+
 /*
  * The feature-distribution analysis (/root/reference/src/scale_calculator.py:486-599: check_full_distribution, check_skewness,
  * skewness_analysis, mode_analysis, plot_distribution — what they compute, not what they draw) for n_frames frames, one workgroup

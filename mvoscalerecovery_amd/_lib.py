@@ -90,6 +90,13 @@ class RescaleOutputs(C.Structure):
                 ("tri_flags", C.c_void_p), ("hyp_counts", C.c_void_p)]
 
 
+class StaticTriOutputs(C.Structure):
+    """mvosr_static_tri_outputs"""
+    _fields_ = [("scale_norm", C.c_void_p), ("raw_scale", C.c_void_p), ("height_level", C.c_void_p), ("n_used", C.c_void_p),
+                ("n_kept", C.c_void_p), ("status", C.c_void_p), ("hist", C.c_void_p), ("tri_height", C.c_void_p),
+                ("tri_flags", C.c_void_p)]
+
+
 class RescaleCasesOutputs(C.Structure):
     """mvosr_rescale_cases_outputs"""
     _fields_ = [("raw_scale", C.c_void_p), ("model", C.c_void_p), ("best_ic", C.c_void_p), ("used", C.c_void_p),
@@ -263,6 +270,9 @@ SYMBOLS = {
     "mvosr_region_grow_batch": (C.c_int, [_P, C.POINTER(Batch), _P, _P, C.POINTER(GrowParams), C.POINTER(GrowOutputs), C.c_int64]),
     "mvosr_tri_graph_batch": (C.c_int, [_P, C.POINTER(Params), C.POINTER(Batch), _P, _P, C.POINTER(TriGraphOutputs)]),
     "mvosr_static_tri_batch": (C.c_int, [_P, C.c_int64, _P, _P, _P, _P, C.c_int32, C.c_double, _P, _P, _P, _P, _P]),
+    "mvosr_flat_static_tri_batch": (C.c_int, [_P, C.POINTER(Batch), _P, C.c_double, C.c_double, C.c_double, C.c_int32, C.c_double, _P,
+                                              _P, _P, C.POINTER(StaticTriOutputs), C.c_int64]),
+    "mvosr_flat_static_tri_lds_bytes": (C.c_size_t, [C.c_int, C.c_int64]),
     "mvosr_feature_distribution_batch": (C.c_int, [_P, C.c_int64, _P, _P, _P, _P, _P, C.c_int32, _P, _P, _P, _P, _P, _P]),
     "mvosr_featdist_max_features": (C.c_int, []),
     "mvosr_depth_check_batch": (C.c_int, [_P, C.c_int64, _P, _P, _P, _P, _P, C.POINTER(DepthCheckParams), C.POINTER(DepthCheckOutputs), _P]),

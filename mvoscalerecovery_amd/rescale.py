@@ -40,6 +40,9 @@ same kernels on SciPy's triangulations brought to the same row form, with bit-id
 on the staged path: the mode of the flat triangles' inverse heights (mvosr_static_tri_batch, launched on flat_selection's device
 buffers; :179-187) and scale_calculator's road model on the selected points through the inner estimator ``self.sc`` (:31).  Both are
 deterministic: tests/golden/statictri.npz holds the reference's own sequences, reproduced bit for bit.
+``model="static_tri", model_resident=True`` runs the first of them on the device-resident path instead: the same streamed stages as
+the RANSAC model, every frame ending in flat_selection + the histogram-mode road model in one kernel (mvosr_flat_static_tri_batch),
+the same sequence bit for bit.
 
 The numbers of rescale.py:85-96,152,155,169-172 are a value, ``RescaleConstants`` (``constants=``; None: the reference's literals),
 and ``ConstantSweep`` runs K settings of them over a sequence in one pass of the stages that do not read them.
@@ -74,6 +77,7 @@ MIN_VALID_FOR_RETRI = 10                              # rescale.py:133
 STATIC_TRI_MIN_COUNT = 12                             # rescale.py:181 (more than 12 heights)
 SLEW = 0.3                                            # rescale.py:169-172
 _FIELDS = ("raw_scale", "height_level", "model", "best_ic", "used", "n_kept", "status")     # a chunk's results, per frame
+_STATIC_FIELDS = ("raw_scale", "height_level", "scale_norm", "n_used", "n_kept", "status")   # the same with model_resident=True
 MAX_HYP = 512                                         # mvosr_flat_ransac_batch's limit (include/mvosr.h)
 
 
@@ -197,7 +201,27 @@ class ScaleEstimator(stream.StreamKnobs):
 
     def __init__(self, absolute_reference, window_size=6, device=0, ransac_seed=None, sampler=None,
                  delaunay_workers=None, verbose=False, triangulation=None, sampling=None, region="threshold", model="ransac",
-                 constants=None, large_frames=False):
+                 constants=None, large_frames=False, model_resident=False):
+        # model_resident: opt-in.  False: every path, message and state below is what it was.  True, with
+        # model="static_tri": the road model runs on the device-resident path — both triangulations, the vote, the flat selection and
+        # the histogram-mode road model in one kernel per frame (mvosr_flat_static_tri_batch) —, triangulation and sampling resolving
+        # as for the RANSAC model.  Every refusal below happens before a device or the worker pool is asked for.
+        if not isinstance(model_resident, (bool, np.bool_)):
+            raise TypeError("model_resident must be a bool")
+        self.model_resident = bool(model_resident)
+        if self.model_resident:
+            if model != "static_tri":
+                raise ValueError("model_resident=True belongs to model='static_tri' (the RANSAC model is device-resident as it is; "
+                                 "model='static' keeps the staged path: its sums follow SciPy's row order)")
+            if region == "grow":
+                raise ValueError("model_resident=True belongs to model='static_tri' with region='threshold' (region='grow' runs on "
+                                 "the staged path)")
+            if large_frames:
+                raise ValueError("model_resident=True belongs to model='static_tri' within the resident kernels' frame limit "
+                                 "(large_frames=True keeps the staged path for this model)")
+            if sampling == "host" or sampler is not None:
+                raise ValueError("model_resident=True belongs to the device-resident path: triangulation='gpu', or "
+                                 "triangulation='scipy' with sampling='device' (no samples are drawn: a host sampler has no part)")
         # large_frames: opt-in.  False: a frame with more features below the vanishing row than one workgroup's LDS
         # holds (``_max_points()``) is refused, as ever.  True: a chunk whose largest frame exceeds that limit sends its vote and its
         # flat selection + RANSAC through the large-frame kernels (mvosr_graph_keep_large_batch, mvosr_flat_ransac_large_batch),
@@ -234,7 +258,7 @@ class ScaleEstimator(stream.StreamKnobs):
         # "static_tri" (its heights come from the large-frame kernel's tri_height / tri_flags rows, of any length), not "static".
         if model not in ("ransac", "static_tri", "static"):
             raise ValueError("model must be 'ransac', 'static_tri' or 'static'")
-        if model != "ransac":
+        if model != "ransac" and not self.model_resident:
             if triangulation not in (None, "scipy") or sampling not in (None, "host"):
                 raise ValueError("model=%r runs on the staged path: triangulation='scipy', sampling='host' (the fused "
                                  "device-resident kernel ends in the RANSAC plane)" % model)
@@ -259,7 +283,11 @@ class ScaleEstimator(stream.StreamKnobs):
             raise ValueError("triangulation='gpu' draws its samples on the device (the point list never visits the host)")
         if sampling == "device" and sampler is not None:
             raise ValueError("a host sampler needs sampling='host'; the device path takes id_triples per call")
+        if self.model_resident and sampling != "device":
+            raise ValueError("model_resident=True belongs to the device-resident path: triangulation='gpu', or triangulation='scipy' "
+                             "with sampling='device' (triangulation=%r resolved sampling to %r)" % (triangulation, sampling))
         self.triangulation, self.sampling = triangulation, sampling
+        self._fields = _STATIC_FIELDS if self.model_resident else _FIELDS    # a chunk's results, per frame
         self._sampler = sampler
         if self.large_frames and sampling != "device" and region == "threshold" and model == "ransac":
             raise ValueError("large_frames=True belongs to the device-resident path: triangulation='gpu', or triangulation='scipy' "
@@ -617,6 +645,8 @@ class ScaleEstimator(stream.StreamKnobs):
         steps between them.  sampling="device": the batch streams through the device-resident stages in chunks
         (``id_triples``: per frame an (H,3) array of survivor-numbered vertex ids replacing the draw — a recorded
         reference run mapped to point ids; ``stage``: keep the per-frame stage outputs in ``self.last``)."""
+        if self.model_resident and id_triples is not None:
+            raise ValueError("id_triples belong to the RANSAC model: model='static_tri' draws no samples")
         if self.sampling == "device":
             return self._stream_device(feature3ds, feature2ds, id_triples, stage)
         if id_triples is not None:
@@ -638,6 +668,8 @@ class ScaleEstimator(stream.StreamKnobs):
     def _launch_flat_ransac(self, db, keep_ptr, dt2_ptr, frame_base, frame_ids, id_triples, stage, max_tri, ctx=None, large=False):
         """mvosr_flat_ransac_batch over a DeviceBatch — ``large``: mvosr_flat_ransac_large_batch, same parameters, same results on
         every frame both take —; returns the outputs' block (download queued)."""
+        if self.model_resident:
+            return self._launch_flat_static(db, keep_ptr, dt2_ptr, stage, max_tri, ctx or self.ctx)
         ctx, F, H = ctx or self.ctx, db.n_frames, self.N_HYP
         spec = [("raw_scale", F, np.float64), ("height_level", F, np.float64), ("model", (F, 4), np.float64),
                 ("best_ic", F, np.int32), ("used", F, np.int32), ("n_kept", F, np.int32), ("status", F, np.int32)]
@@ -677,6 +709,31 @@ class ScaleEstimator(stream.StreamKnobs):
         for blk in side:
             blk.mark(True)
         return out, flags, side
+
+    def _launch_flat_static(self, db, keep_ptr, dt2_ptr, stage, max_tri, ctx):
+        """model_resident=True: mvosr_flat_static_tri_batch in mvosr_flat_ransac_batch's place, over the same DeviceBatch, keep words
+        and statuses, with its own outputs' block (download queued).  Frame ids, id_triples and seeds do not enter: the road model
+        draws nothing."""
+        F = db.n_frames
+        out = ctx.block([("raw_scale", F, np.float64), ("height_level", F, np.float64), ("scale_norm", F, np.float64),
+                         ("n_used", F, np.int32), ("n_kept", F, np.int32), ("status", F, np.int32)])
+        o = _lib.StaticTriOutputs(out["scale_norm"].ptr, out["raw_scale"].ptr, out["height_level"].ptr, out["n_used"].ptr,
+                                  out["n_kept"].ptr, out["status"].ptr, None, None, None)
+        flags = None
+        if stage:
+            flags = ctx.block([("tri_flags", max(db.n_rows2, 1), np.uint8)])
+            o.tri_flags = flags["tri_flags"].ptr
+        k = self.constants
+        b = db.struct()
+        _lib.check(ctx.lib.mvosr_flat_static_tri_batch(ctx.handle, C.byref(b), keep_ptr, k.loose_deg, k.tight_deg, k.height_factor,
+                                                       STATIC_TRI_MIN_COUNT, float(self.absolute_reference), dt2_ptr, None, None,
+                                                       C.byref(o), int(max_tri)), "mvosr_flat_static_tri_batch")
+        if stage or not self.GPU_SIDE_DOWNLOADS:
+            out.prefetch()
+        else:
+            out.mark_done()
+        out.mark(True)
+        return out, flags, []
 
     def _chunk_dev_gpu(self, f3s, f2s, frame_base, id_triples, stage, tables=False, early_status=False):
         """One chunk, both triangulations on the device: pack (C packer into page-locked memory) -> ONE upload -> every
@@ -875,7 +932,7 @@ class ScaleEstimator(stream.StreamKnobs):
 
     @staticmethod
     def _collect(out, F):
-        return {k: out[k].download() for k in _FIELDS}
+        return {k: out[k].download() for k in (_FIELDS if "model" in out.views else _STATIC_FIELDS)}
 
     def _stage_outputs(self, st, host=False):
         """Per frame: the vote's mask (graph.py:35), the second triangulation's rows and flat_selection's flags."""
@@ -946,7 +1003,7 @@ class ScaleEstimator(stream.StreamKnobs):
         return res
 
     def _scatter(self, res, frames, sub, first, stage):
-        stream.scatter(res, frames, sub, _FIELDS, "host_errors", first)
+        stream.scatter(res, frames, sub, self._fields, "host_errors", first)
         if stage:
             for k in ("valid", "tris2", "tri_flags"):
                 for j, f in enumerate(frames):
@@ -977,7 +1034,7 @@ class ScaleEstimator(stream.StreamKnobs):
 
     def _finish_reruns(self, records, stage):
         """The call's re-runs after its last chunk: the started ones finish their steps, the others' frames go in one batch."""
-        stream.finish_all(records, lambda rest: self._merged_rerun(rest, stage), _FIELDS, "host_errors")
+        stream.finish_all(records, lambda rest: self._merged_rerun(rest, stage), self._fields, "host_errors")
 
     def _merged_rerun(self, records, stage):
         """The frames of the records whose re-run was not started, in ONE batch through the host's triangulations, scattered back."""
@@ -1071,8 +1128,8 @@ class ScaleEstimator(stream.StreamKnobs):
                                                         triples(ra + a, ra + b), stage))
         if oversized is not None and not results:
             raise self._oversized_error(*oversized, limit)
-        cat, host_errors = stream.concat(bounds, results, _FIELDS, "host_errors")
-        self.last = dict(zip(_FIELDS, cat))
+        cat, host_errors = stream.concat(bounds, results, self._fields, "host_errors")
+        self.last = dict(zip(self._fields, cat))
         raw, status, level = self.last["raw_scale"], self.last["status"], self.last["height_level"]
         if stage:
             for k in ("valid", "tris2", "tri_flags"):
@@ -1087,6 +1144,8 @@ class ScaleEstimator(stream.StreamKnobs):
             if oversized is not None:
                 raise host_errors[F]
             return raw, status, level, host_errors
+        if self.model_resident:
+            return self._push_static(raw, status, level, host_errors)
         return self._push_device(raw, status, level, host_errors)
 
     # ---- the two halves on their own: what a driver that shards a sequence over GPUs needs (offline.run_sequence_sharded) ----
@@ -1283,7 +1342,32 @@ class ScaleEstimator(stream.StreamKnobs):
         raw = np.asarray(raw, dtype=np.float64)
         status = np.asarray(status, dtype=np.int32)
         level = np.full(len(raw), np.nan) if level is None else np.asarray(level, dtype=np.float64)
+        if self.model == "static_tri":
+            return self._push_static(raw, status, level, host_errors or {})
         return self._push_device(raw, status, level, host_errors or {})
+
+    def _push_static(self, raw, status, level, host_errors):
+        """The cross-frame tail of model="static_tri" (rescale.py:181-187, ``_static_tri_carry``) over the frames before the first one
+        at which the reference raises; then that frame's exception, as ``_push_device`` raises it.  No slew limiter, no window:
+        ``scale_queue`` is not touched.  Returns ``(scales, zeros)``."""
+        F = len(raw)
+        bad = np.isin(status, (K.ST_ERR_SINGULAR, K.ST_ERR_MASK, K.ST_ERR_EMPTY))
+        for f in host_errors:
+            bad[f] = True
+        n_ok = int(np.argmax(bad)) if bad.any() else F
+        scales = self._static_tri_carry(raw, status, n_ok)
+        if n_ok:
+            self.height_level = level[n_ok - 1]                                             # :92
+        self._frame_counter += n_ok + (1 if n_ok < F else 0)
+        if n_ok < F:
+            if n_ok in host_errors and isinstance(host_errors[n_ok], Exception):
+                raise host_errors[n_ok]
+            if status[n_ok] == K.ST_ERR_SINGULAR:
+                raise np.linalg.LinAlgError("Singular matrix (frame %d of the batch)" % n_ok)  # :79
+            if status[n_ok] == K.ST_ERR_MASK:
+                raise _lib.MvosrLibraryError("triangulation with an out-of-range vertex id (frame %d of the batch)" % n_ok)
+            raise ValueError("frame %d of the batch has no triangles below the vanishing row" % n_ok)
+        return scales, np.zeros(F)
 
     def _push_device(self, raw, status, level, host_errors):
         """The cross-frame tail (rescale.py:169-178) on the device over the frames before the first one at which the
@@ -1406,7 +1490,11 @@ class RepeatedRuns:
         if not self.seeds:
             raise ValueError("RepeatedRuns: at least one case")
         self.cases = len(self.seeds)
+        if estimator_kw.get("model", "ransac") != "ransac":
+            raise ValueError("RepeatedRuns repeats the RANSAC model: model=%r draws no samples to repeat" % (estimator_kw["model"],))
         self.estimator = self._make_estimator(absolute_reference, window_size, estimator_kw)
+        if getattr(self.estimator, "model", "ransac") != "ransac":
+            raise ValueError("RepeatedRuns repeats the RANSAC model, not model=%r" % (self.estimator.model,))
         if self.estimator.sampling != "device":
             raise ValueError("RepeatedRuns needs a device-sampling mode: triangulation='gpu', or triangulation='scipy' with sampling='device'")
         self.tails = [_CaseTail(self.estimator.ctx, window_size) for _ in range(self.cases)]
@@ -1618,6 +1706,8 @@ class ConstantSweep:
         self.configs = list(configs)
         if not self.configs or not all(isinstance(k, RescaleConstants) for k in self.configs):
             raise ValueError("ConstantSweep: configs is a non-empty list of RescaleConstants")
+        if estimator_kw.get("model", "ransac") != "ransac":
+            raise ValueError("ConstantSweep sweeps the RANSAC model: model=%r has no RANSAC constants to sweep" % (estimator_kw["model"],))
         if "constants" in estimator_kw:
             raise TypeError("ConstantSweep takes its constants as configs")
         if seeds is not None:
