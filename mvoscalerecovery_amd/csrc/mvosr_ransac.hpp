@@ -4,6 +4,8 @@
 // /root/reference/src/thirdparty/Ransac/ransac.py:9-22, the sign rule and the height, the two counting loops and the ordered
 // compaction.  Device code only (the sequence's two key functions are host code as well); included after mvosr_device.hpp.  fp64,
 // compiled with -ffp-contract=off: the association order written here is the one every kernel's results are pinned to.
+// What the flat-selection kernels build from these — a frame's hypotheses, the fit's result, the survivors' compaction — and
+// their own rules (a row's bits, the level's search) is mvosr_flat.hpp, included after this file.
 #pragma once
 
 #include <hip/hip_runtime.h>

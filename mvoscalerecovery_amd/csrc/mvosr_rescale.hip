@@ -16,6 +16,7 @@
 #include "../../include/mvosr.h"
 #include "mvosr_device.hpp"
 #include "mvosr_ransac.hpp"
+#include "mvosr_flat.hpp"
 #include "mvosr_host.hpp"
 #include "mvosr_rescale_plan.hpp"
 
@@ -135,7 +136,9 @@ __global__ __launch_bounds__(kRsBlock) void graph_inliers_kernel(const GraphArgs
 // pitch < -85 and heights > level.  The median is the mean of the two middle order statistics; every triangle's height
 // and flags stay in LDS by row (no compacted list, no append counter), and the order statistic is found on the heights'
 // bit patterns by a 2048-bin histogram over [smallest, largest] loose height — narrowed to the bin that holds the rank
-// and repeated if needed — with wavefront 0 ranking the last <= 64 candidates directly.
+// and repeated if needed — with wavefront 0 ranking the last <= 64 candidates directly.  The rules — a row's bits, the level's
+// search, the survivors' compaction, the hypotheses and the fit's result — are mvosr_flat.hpp's, shared with the four sibling
+// kernels (mvosr_rescale_cases.hip, _sweep.hip, _large.hip, _static.hip); this kernel keeps its phases' order and its LDS traffic.
 // ---------------------------------------------------------------------------------------------
 struct FlatArgs {
     int64_t n_frames;
@@ -163,17 +166,17 @@ struct FlatArgs {
     int32_t *best_ic, *used, *hyp_counts;
 };
 
-constexpr int kFlatRows = 4;            // triangle rows a thread keeps in flight
-constexpr int kFlatDirect = 64;         // that few candidates left: wavefront 0 ranks them directly
 constexpr int kMaxHyp = 512;
 constexpr int kRansacPPT = 8;           // points per thread per chunk (chunks of 4096 points)
 
 constexpr int kFlatDevWaves = 16;   // the device-resident form holds 96 KB of LDS — one workgroup per CU —, so it brings its own occupancy: 16 wavefronts
 
+// (the second bound, wavefronts per SIMD: the stage form has always been allocated 96 vector registers — room for five wavefronts
+// per SIMD — but only because the allocator happened to end there: phase 1's four rows in flight sit at that edge, and moving
+// their loop into mvosr_flat.hpp moved it to 98, room for four.  Stated, it holds.  16 wavefronts need 4 per SIMD to launch at all.)
 template <bool DEV, int WAVES = kRsWaves>
-__global__ __launch_bounds__(WAVES *kWave) void flat_selection_kernel(const FlatArgs a) {
+__global__ __launch_bounds__(WAVES *kWave, WAVES == kRsWaves ? 5 : 4) void flat_selection_kernel(const FlatArgs a) {
     constexpr int BLK = WAVES * kWave;
-    static_assert(WAVES <= 16 && kFlatBins % BLK == 0, "flat_selection_kernel: misc slots / bins per thread");
     extern __shared__ __attribute__((aligned(16))) char smem[];
     const int64_t f = blockIdx.x;
     const int n_all = a.feat_cnt[f];
@@ -184,9 +187,9 @@ __global__ __launch_bounds__(WAVES *kWave) void flat_selection_kernel(const Flat
     const bool skip = DEV && a.dt_status && a.dt_status[f] != 0;
     // more features or rows than the launch's LDS was sized for (the header's max_feat, the call's max_tri): refused, LDS untouched
     const bool oversize = n_all > a.max_feat || tn > a.max_tri;
-    if (n_all <= 0 || tn <= 0 || skip || oversize) {
+    if (const int refused = flat_entry_status(n_all, tn, skip, oversize)) {
         if (tid == 0) {
-            a.status[f] = (!skip && oversize && n_all > 0 && tn > 0) ? MVOSR_ST_ERR_MASK : MVOSR_ST_ERR_EMPTY;
+            a.status[f] = refused;
             a.height_level[f] = nan(""); a.n_kept[f] = 0;
             if constexpr (DEV) {
                 a.raw_scale[f] = nan(""); a.best_ic[f] = 0; a.used[f] = 0;
@@ -212,30 +215,22 @@ __global__ __launch_bounds__(WAVES *kWave) void flat_selection_kernel(const Flat
 #define FS_STAMP(i) do {} while (0)
 #endif
     FS_STAMP(0);
-    if (tid < FM_WSUM) misc[tid] = 0;
-    if (tid == 0) { ext[0] = ~0ull; ext[1] = 0ull; ext[2] = ~0ull; }
-    // a thread's next kFlatRows triangle rows are in flight while it works on the current ones (and the first ones while
-    // the vertex planes stream in): a row is a dependent global load in front of nine LDS gathers and the LU chain
+    flat_state_init(misc, ext);
+    // (the first rows are in flight while the vertex planes stream in: mvosr_flat.hpp, flat_phase1)
     TriIds rows[kFlatRows];
-    auto load_rows = [&](int t0) {
-#pragma unroll
-        for (int j = 0; j < kFlatRows; ++j) rows[j] = load_tri(a.tri + 3 * tb, min(t0 + j * BLK, tn - 1));
-    };
-    load_rows(tid);
+    flat_load_rows<BLK>(a.tri + 3 * tb, tid, tn, rows);
     int n = n_all;                                               // features in LDS (the survivors)
     if (DEV && a.keep) {
-        // ordered compaction at load (rescale.py:134-135: feature3d[valid_id]): every wavefront owns a contiguous segment of
-        // the frame, counts its survivors, and after one barrier knows where its segment starts in LDS
-        int s0, s1;
-        ordered_segment(n_all, BLK, s0, s1);
+        // ordered compaction at load (rescale.py:134-135: feature3d[valid_id])
         // (a lane's features — up to four: 4 096 per frame on sixteen wavefronts — with their keep flags in one batch of loads,
         // before the count: flag, wait, coordinates, wait, twice over, was a tenth of this kernel's time with nothing else on the CU)
         constexpr int kOwn = 4;
-        const bool own = n_all <= kOwn * BLK;
-        double ox[kOwn], oy[kOwn], oz[kOwn];
-        unsigned okeep = 0u;
-        int c = 0;
-        if (own) {
+        if (n_all <= kOwn * BLK) {
+            int s0, s1;
+            ordered_segment(n_all, BLK, s0, s1);
+            double ox[kOwn], oy[kOwn], oz[kOwn];
+            unsigned okeep = 0u;
+            int c = 0;
 #pragma unroll
             for (int r = 0; r < kOwn; ++r) {
                 const int i = s0 + r * kWave + lane;
@@ -246,160 +241,33 @@ __global__ __launch_bounds__(WAVES *kWave) void flat_selection_kernel(const Flat
             }
 #pragma unroll
             for (int r = 0; r < kOwn; ++r) c += __popcll(__ballot((okeep >> r) & 1u));
-        } else
-        for (int i0 = s0; i0 < s1; i0 += kWave) {
-            const int i = i0 + lane;
-            c += __popcll(__ballot(i < s1 && a.keep[off + i] >= 0));
-        }
-        int base;
-        ordered_prefix<WAVES>(misc + FM_CW, c, base, n);
-        if (own) {
+            int base;
+            ordered_prefix<WAVES>(misc + FM_CW, c, base, n);
 #pragma unroll
             for (int r = 0; r < kOwn; ++r) {
                 const bool k = (okeep >> r) & 1u;
                 const int pos = ordered_rank(k, base);
                 if (k) { X[pos] = ox[r]; Y[pos] = oy[r]; Z[pos] = oz[r]; }
             }
-        } else
-        for (int i0 = s0; i0 < s1; i0 += kWave) {
-            const int i = i0 + lane;
-            const bool k = i < s1 && a.keep[off + i] >= 0;
-            const int pos = ordered_rank(k, base);
-            if (k) { X[pos] = a.x[off + i]; Y[pos] = a.y[off + i]; Z[pos] = a.z[off + i]; }
-        }
+        } else n = flat_compact_survivors<WAVES>(n_all, a.keep + off, a.x + off, a.y + off, a.z + off, X, Y, Z, misc + FM_CW);
     } else {
 #pragma unroll 4
         for (int i = tid; i < n_all; i += BLK) { X[i] = a.x[off + i]; Y[i] = a.y[off + i]; Z[i] = a.z[off + i]; }
     }
-    const double s_loose = sin(a.loose_deg * 3.141592653589793 / 180.0), s_tight = sin(a.tight_deg * 3.141592653589793 / 180.0);
+    const double s_loose = flat_sin_deg(a.loose_deg), s_tight = flat_sin_deg(a.tight_deg);
     __syncthreads();
     FS_STAMP(1);
     // phase 1: every triangle's height and flags into LDS (and the height to the output), the loose ones counted and bounded
     {
-        int k_mine = 0;
-        unsigned long long umin = ~0ull, umax = 0ull;
-        auto one_row = [&](const TriIds q, const int t) {
-            if (!ids_in_range(q.a, q.b, q.c, n)) {
-                misc[FM_BADID] = 1; Fl[t] = 0; Hh[t] = nan(""); if (!DEV || a.tri_height) a.tri_height[tb + t] = nan(""); return;
-            }
-            double mu, h;
-            if (!row_height_pitch(X, Y, Z, q, mu, h)) misc[FM_SINGULAR] = 1;
-            // pitch = asin(mu) * 180/pi (:83) is increasing in mu: away from the two thresholds the comparison is
-            // made on mu itself, within 1e-12 of one (or for NaN) on the reference's own expression
-            bool loose, tight;
-            if (fabs(mu - s_loose) > 1e-12 && fabs(mu - s_tight) > 1e-12) { loose = mu < s_loose; tight = mu < s_tight; }
-            else {
-                const double pitch = asin(mu) * 180.0 / 3.141592653589793;
-                loose = pitch < a.loose_deg; tight = pitch < a.tight_deg;
-            }
-            Hh[t] = h;
-            Fl[t] = (uint8_t)((loose ? 1 : 0) | (tight ? 2 : 0));                            // :85-86
-            if (!DEV || a.tri_height) a.tri_height[tb + t] = h;
-            if (loose) {
-                const unsigned long long u = (unsigned long long)__double_as_longlong(h);
-                ++k_mine; umin = u < umin ? u : umin; umax = u > umax ? u : umax;
-            }
-        };
-        for (int t0 = tid; t0 < tn; t0 += kFlatRows * BLK) {
-            TriIds cur[kFlatRows];
-#pragma unroll
-            for (int j = 0; j < kFlatRows; ++j) cur[j] = rows[j];
-            if (t0 + kFlatRows * BLK < tn) load_rows(t0 + kFlatRows * BLK);
-#pragma unroll
-            for (int j = 0; j < kFlatRows; ++j) if (t0 + j * BLK < tn) one_row(cur[j], t0 + j * BLK);
-        }
-        k_mine = wave_sum(k_mine);
-        umin = wave_min_u64(umin); umax = wave_max_u64(umax);
-        if (lane == 0 && k_mine) { atomicAdd(&misc[FM_K], k_mine); atomicMin(&ext[0], umin); atomicMax(&ext[1], umax); }
+        FlatLoose tally;
+        flat_phase1<BLK>(a.tri + 3 * tb, rows, tn, X, Y, Z, n, a.loose_deg, a.tight_deg, s_loose, s_tight, Hh, Fl,
+                         (!DEV || a.tri_height) ? a.tri_height + tb : nullptr, misc, tally);
+        tally.commit(misc, ext);
     }
     __syncthreads();
     FS_STAMP(2);
     const int k = misc[FM_K];
-    double level = nan("");                                      // median of an empty set is nan (nothing passes)
-    if (k > 0) {                                                                         // np.median, :91
-        // The lower middle order statistic (rank klo): histogram the candidates' bit patterns over [lo, hi] with bins of
-        // 2^shift patterns (<= 2048 bins), find the bin that holds the rank, narrow [lo, hi] to it, repeat — until a bin is a
-        // single pattern, or holds few enough candidates for wavefront 0 to rank them directly.  Real frames take one
-        // pass: their heights spread over a few thousand distinct patterns per bin at most.
-        const int klo = (k - 1) >> 1, khi = k >> 1;
-        unsigned long long lo = ext[0], hi = ext[1];
-        int rank = klo;
-        unsigned long long vlo_bits = lo;
-        for (;;) {
-            const unsigned long long range = hi - lo;
-            if (range == 0ull) { vlo_bits = lo; break; }
-            const int bits = 64 - __clzll((long long)range);                             // range < 2^bits
-            const int shift = bits > 11 ? bits - 11 : 0;
-            for (int b = tid; b < kFlatBins; b += BLK) hist[b] = 0;
-            __syncthreads();
-            #pragma unroll 4
-            for (int t = tid; t < tn; t += BLK) {
-                if (!(Fl[t] & 1)) continue;
-                const unsigned long long u = U[t];
-                if (u >= lo && u <= hi) atomicAdd(&hist[(int)((u - lo) >> shift)], 1);
-            }
-            __syncthreads();
-            {   // the bin whose cumulative count passes the rank: four bins per thread, wave scan, wave totals through LDS
-                constexpr int BPT = kFlatBins / BLK;                // bins per thread (4 with 512 threads, 2 with 1024)
-                const int b0 = hist[BPT * tid], b1 = BPT > 1 ? hist[BPT * tid + 1] : 0, b2 = BPT > 2 ? hist[BPT * tid + 2] : 0, b3 = BPT > 3 ? hist[BPT * tid + 3] : 0;
-                const int mine = (b0 + b1) + (b2 + b3);
-                int incl = wave_scan_incl(mine);
-                if (lane == kWave - 1) misc[FM_WSUM + wave] = incl;
-                __syncthreads();
-                int before = 0;
-#pragma unroll
-                for (int w = 0; w < WAVES; ++w) if (w < wave) before += misc[FM_WSUM + w];
-                incl += before;
-                const int excl = incl - mine;
-                if (rank >= excl && rank < incl) {               // exactly one thread
-                    int r = rank - excl, bin = BPT * tid, c = b0;
-                    if (r >= b0) { r -= b0; ++bin; c = b1; if (r >= b1) { r -= b1; ++bin; c = b2; if (r >= b2) { r -= b2; ++bin; c = b3; } } }
-                    misc[FM_BIN] = bin; misc[FM_RANK] = r; misc[FM_BINCNT] = c;
-                }
-                __syncthreads();
-            }
-            const int bin = misc[FM_BIN], c = misc[FM_BINCNT];
-            rank = misc[FM_RANK];
-            lo += (unsigned long long)bin << shift;
-            { const unsigned long long top = lo + ((1ull << shift) - 1ull); hi = top < hi ? top : hi; }
-            if (shift == 0) { vlo_bits = lo; break; }            // the bin is one pattern
-            if (c <= kFlatDirect) {
-                unsigned long long *list = reinterpret_cast<unsigned long long *>(hist);
-                __syncthreads();                                 // every thread has read misc / hist
-                #pragma unroll 4
-                for (int t = tid; t < tn; t += BLK) {
-                    if (!(Fl[t] & 1)) continue;
-                    const unsigned long long u = U[t];
-                    if (u >= lo && u <= hi) list[atomicAdd(&misc[FM_LIST], 1)] = u;
-                }
-                __syncthreads();
-                if (wave == 0) {
-                    const unsigned long long mine = lane < c ? list[lane] : ~0ull;
-                    int below = 0;
-                    for (int j = 0; j < c; ++j) { const unsigned long long v = list[j]; below += (v < mine || (v == mine && j < lane)) ? 1 : 0; }
-                    if (lane < c && below == rank) ext[3] = mine;
-                }
-                __syncthreads();
-                vlo_bits = ext[3];
-                break;
-            }
-            __syncthreads();                                     // hist is zeroed again at the top
-        }
-        const double vlo = __longlong_as_double((long long)vlo_bits);
-        double vhi = vlo;
-        if (khi != klo) {
-            int le = 0;
-            unsigned long long above = ~0ull;
-            #pragma unroll 4
-            for (int t = tid; t < tn; t += BLK) {
-                if (!(Fl[t] & 1)) continue;
-                const unsigned long long u = U[t];
-                if (u <= vlo_bits) ++le; else above = u < above ? u : above;
-            }
-            vhi = __longlong_as_double((long long)next_order_statistic(le, above, vlo_bits, khi, &misc[FM_LE], &ext[2]));
-        }
-        level = a.height_factor * ((klo == khi) ? vlo : (vlo + vhi) / 2.0);
-    }
+    const double level = flat_level_search<WAVES>(U, Fl, tn, k, ext, misc, hist, a.height_factor).level;   // np.median, :91
     FS_STAMP(3);
     if constexpr (!DEV) {
         int kept = 0;
@@ -461,19 +329,7 @@ __global__ __launch_bounds__(WAVES *kWave) void flat_selection_kernel(const Flat
             FS_STAMP(4);
             // the hypotheses' planes, one thread each (ransac.py:10-11, estimate_road_norm.py:13-15)
             const uint64_t key = ransac_frame_key(a.seed, (uint64_t)(a.frame_ids ? a.frame_ids[f] : a.frame_base + f));
-            for (int h = tid; h < H; h += BLK) {
-                int v0, v1, v2;
-                if (a.id_triples) {
-                    const int32_t *t = a.id_triples + ((int64_t)f * H + h) * 3;
-                    v0 = min(max(t[0], 0), n - 1); v1 = min(max(t[1], 0), n - 1); v2 = min(max(t[2], 0), n - 1);
-                } else {
-                    ransac_draw3(key, h, M, v0, v1, v2);         // (list positions: mvosr_ransac.hpp on a vertex drawn twice)
-                    v0 = L[v0]; v1 = L[v1]; v2 = L[v2];
-                }
-                const double4 m = ransac_unit_plane(X, Y, Z, v0, v1, v2);
-                mods[2 * h] = make_double2(m.x, m.y); mods[2 * h + 1] = make_double2(m.z, m.w);
-                cnts[h] = 0;
-            }
+            flat_build_hypotheses<BLK>(key, a.id_triples ? a.id_triples + (int64_t)f * H * 3 : nullptr, H, n, M, L, X, Y, Z, mods, cnts);
             __syncthreads();
             // Inlier counts (estimate_road_norm.py:17-18 over every list entry, repeats included).  The list names each of its
             // ~600 distinct vertices five or six times (once per kept triangle): a vertex is tested ONCE per hypothesis and
@@ -538,28 +394,15 @@ __global__ __launch_bounds__(WAVES *kWave) void flat_selection_kernel(const Flat
             if (a.hyp_counts) for (int h = tid; h < H; h += BLK) a.hyp_counts[(int64_t)f * H + h] = cnts[h];
         }
         if (wave == 0) {
-            int status = misc[FM_BADID] ? MVOSR_ST_ERR_MASK : (misc[FM_SINGULAR] ? MVOSR_ST_ERR_SINGULAR : (fit ? 0 : MVOSR_ST_RS_FEW));
-            int best = -1, best_ic = 0, used = 0;
-            double m[4] = {nan(""), nan(""), nan(""), nan("")};
-            double raw = nan("");
-            if (fit) {
-                RansacReplay rp = {-1, 0, H, 0};
-                ransac_replay(rp, cnts, 0, H, (double)M * a.goal_fraction);       // ransac.py:9-22; the goal: estimate_road_norm.py:68
-                best = rp.best; best_ic = rp.best_ic; used = rp.used;
-                if (best >= 0) {
-                    const double2 b0 = mods[2 * best], b1 = mods[2 * best + 1];
-                    const double4 bm = ransac_sign_rule(make_double4(b0.x, b0.y, b1.x, b1.y));   // rescale.py:159-161
-                    m[0] = bm.x; m[1] = bm.y; m[2] = bm.z; m[3] = bm.w;
-                    raw = a.absolute_reference / ransac_camera_height(bm);         // :158-167
-                } else status = MVOSR_ST_RS_FEW;                                   // (no hypothesis with an inlier: NaN planes only)
-            }
+            const int status = misc[FM_BADID] ? MVOSR_ST_ERR_MASK : (misc[FM_SINGULAR] ? MVOSR_ST_ERR_SINGULAR : (fit ? 0 : MVOSR_ST_RS_FEW));
+            const FlatRansacResult r = flat_ransac_result(fit, status, mods, cnts, H, (double)M * a.goal_fraction, a.absolute_reference);
             if (lane == 0) {
                 a.height_level[f] = level;
                 a.n_kept[f] = K;
-                a.status[f] = status;
-                a.raw_scale[f] = raw;
-                a.best_ic[f] = best_ic; a.used[f] = used;
-                for (int kk = 0; kk < 4; ++kk) a.model[4 * f + kk] = m[kk];
+                a.status[f] = r.status;
+                a.raw_scale[f] = r.raw;
+                a.best_ic[f] = r.best_ic; a.used[f] = r.used;
+                for (int kk = 0; kk < 4; ++kk) a.model[4 * f + kk] = r.m[kk];
             }
 #ifdef MVOSR_FS_STAMPS
             // diagnostic build: the results are overwritten by the phase durations (profiles/stamps_flat_dev.py)

@@ -10,8 +10,8 @@
 //   the point list from the rows whose flag has bit 2 (kept), in row order, three ids each, repeats included (rescale.py:101),
 //   and the counting form: the list's distinct vertices with their multiplicities;
 //   per case: the hypotheses from ransac_draw3 keyed by the CASE's seed, their counts, the replay rule, the sign rule and the raw
-//   scale (rescale.py:156-167) — the functions flat_selection_kernel<true>'s tail calls (mvosr_ransac.hpp), so that case c equals,
-//   bit for bit, what mvosr_flat_ransac_batch returns with rp->seed = case_seeds[c].
+//   scale (rescale.py:156-167) — flat_build_hypotheses and flat_ransac_result (mvosr_flat.hpp), which flat_selection_kernel<true>'s
+//   tail calls as well, so that case c equals, bit for bit, what mvosr_flat_ransac_batch returns with rp->seed = case_seeds[c].
 //
 // fp64, compiled with -ffp-contract=off.  The counts are integer sums: they depend neither on the counting form nor on the order
 // in which the distinct vertices were appended.
@@ -22,6 +22,7 @@
 #include "../../include/mvosr.h"
 #include "mvosr_device.hpp"
 #include "mvosr_ransac.hpp"
+#include "mvosr_flat.hpp"
 #include "mvosr_host.hpp"
 #include "mvosr_rescale_cases_plan.hpp"
 
@@ -80,8 +81,8 @@ __global__ __launch_bounds__(WAVES *kWave) void flat_ransac_cases_kernel(const C
     const bool skip = a.dt_status && a.dt_status[f] != 0;
     // more features or rows than the launch's LDS was sized for: refused, LDS untouched
     const bool oversize = n_all > a.max_feat || tn > a.max_tri;
-    if (n_all <= 0 || tn <= 0 || skip || oversize) {
-        cases_refuse(a, f, g, c_lo, c_hi, (!skip && oversize && n_all > 0 && tn > 0) ? MVOSR_ST_ERR_MASK : MVOSR_ST_ERR_EMPTY);
+    if (const int refused = flat_entry_status(n_all, tn, skip, oversize)) {
+        cases_refuse(a, f, g, c_lo, c_hi, refused);
         return;
     }
     const int H = a.n_hyp;
@@ -97,25 +98,8 @@ __global__ __launch_bounds__(WAVES *kWave) void flat_ransac_cases_kernel(const C
     int *misc = reinterpret_cast<int *>(smem + lds.misc);
     if (tid < CM_CW) misc[tid] = 0;
 
-    // ---- the survivors, compacted in order (rescale.py:134-135): every wavefront owns a contiguous segment of the frame
-    int n;
-    {
-        int s0, s1;
-        ordered_segment(n_all, BLK, s0, s1);
-        int c = 0;
-        for (int i0 = s0; i0 < s1; i0 += kWave) {
-            const int i = i0 + lane;
-            c += __popcll(__ballot(i < s1 && (!a.keep || a.keep[off + i] >= 0)));
-        }
-        int base;
-        ordered_prefix<WAVES>(misc + CM_CW, c, base, n);
-        for (int i0 = s0; i0 < s1; i0 += kWave) {
-            const int i = i0 + lane;
-            const bool k = i < s1 && (!a.keep || a.keep[off + i] >= 0);
-            const int pos = ordered_rank(k, base);
-            if (k) { X[pos] = a.x[off + i]; Y[pos] = a.y[off + i]; Z[pos] = a.z[off + i]; }
-        }
-    }
+    // ---- the survivors, compacted in order (rescale.py:134-135)
+    const int n = flat_compact_survivors<WAVES>(n_all, a.keep ? a.keep + off : nullptr, a.x + off, a.y + off, a.z + off, X, Y, Z, misc + CM_CW);
     // ---- the kept rows, in row order (rescale.py:94-96, :101): the same segmented compaction over the flags
     for (int v = tid; v < n_all; v += BLK) W[v] = 0;
     int t0w, t1w;
@@ -186,19 +170,7 @@ __global__ __launch_bounds__(WAVES *kWave) void flat_ransac_cases_kernel(const C
         const int64_t fc = f * C + c;
         // the hypotheses' planes, one thread each (ransac.py:10-11, estimate_road_norm.py:13-15)
         const uint64_t key = ransac_frame_key(a.case_seeds[c], fcnt);
-        for (int h = tid; h < H; h += BLK) {
-            int v0, v1, v2;
-            if (a.id_triples) {
-                const int32_t *t = a.id_triples + (fc * H + h) * 3;
-                v0 = min(max(t[0], 0), n - 1); v1 = min(max(t[1], 0), n - 1); v2 = min(max(t[2], 0), n - 1);
-            } else {
-                ransac_draw3(key, h, M, v0, v1, v2);
-                v0 = L[v0]; v1 = L[v1]; v2 = L[v2];
-            }
-            const double4 m = ransac_unit_plane(X, Y, Z, v0, v1, v2);
-            mods[2 * h] = make_double2(m.x, m.y); mods[2 * h + 1] = make_double2(m.z, m.w);
-            cnts[h] = 0;
-        }
+        flat_build_hypotheses<BLK>(key, a.id_triples ? a.id_triples + fc * H * 3 : nullptr, H, n, M, L, X, Y, Z, mods, cnts);
         __syncthreads();
         ransac_count_weighted<WAVES>(mods, cnts, H, n_items, a.threshold, packed,
             [&](int j, double &px, double &py, double &pz, int &wgt) { px = PX[j]; py = PY[j]; pz = PZ[j]; wgt = PW[j]; },
@@ -206,20 +178,10 @@ __global__ __launch_bounds__(WAVES *kWave) void flat_ransac_cases_kernel(const C
         __syncthreads();
         if (a.hyp_counts) for (int h = tid; h < H; h += BLK) a.hyp_counts[fc * H + h] = cnts[h];
         if (wave == 0) {
-            int status = 0;
-            double m[4] = {nan(""), nan(""), nan(""), nan("")};
-            double raw = nan("");
-            RansacReplay rp = {-1, 0, H, 0};
-            ransac_replay(rp, cnts, 0, H, goal);                                   // ransac.py:9-22
-            if (rp.best >= 0) {
-                const double2 b0 = mods[2 * rp.best], b1 = mods[2 * rp.best + 1];
-                const double4 bm = ransac_sign_rule(make_double4(b0.x, b0.y, b1.x, b1.y));   // rescale.py:159-161
-                m[0] = bm.x; m[1] = bm.y; m[2] = bm.z; m[3] = bm.w;
-                raw = a.absolute_reference / ransac_camera_height(bm);             // :158-167
-            } else status = MVOSR_ST_RS_FEW;                                       // (no hypothesis with an inlier: NaN planes only)
+            const FlatRansacResult r = flat_ransac_result(true, 0, mods, cnts, H, goal, a.absolute_reference);
             if (lane == 0) {
-                a.status[fc] = status; a.raw_scale[fc] = raw; a.best_ic[fc] = rp.best_ic; a.used[fc] = rp.used;
-                for (int kk = 0; kk < 4; ++kk) a.model[4 * fc + kk] = m[kk];
+                a.status[fc] = r.status; a.raw_scale[fc] = r.raw; a.best_ic[fc] = r.best_ic; a.used[fc] = r.used;
+                for (int kk = 0; kk < 4; ++kk) a.model[4 * fc + kk] = r.m[kk];
             }
         }
         __syncthreads();                                             // (the next case rewrites the planes and the counts)

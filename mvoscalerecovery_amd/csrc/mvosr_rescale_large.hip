@@ -19,6 +19,7 @@
 #include "../../include/mvosr.h"
 #include "mvosr_device.hpp"
 #include "mvosr_ransac.hpp"
+#include "mvosr_flat.hpp"
 #include "mvosr_host.hpp"
 #include "mvosr_rescale_large_plan.hpp"
 
@@ -26,10 +27,8 @@ namespace mvosr {
 
 constexpr int kLgBlock = kLargeWaves * kWave;
 constexpr int kLgMaxHyp = 512;
-constexpr int kLgDirect = 64;           // that few candidates left: wavefront 0 ranks them directly
 constexpr int kLgPPT = 4;               // list entries a thread holds while the hypotheses stream past (chunks of 4096 entries)
 static_assert(sizeof(double4) == kPlaneBytes, "a hypothesis' plane in the LDS plan");
-static_assert(kFlatBins % kLgBlock == 0 && kLargeWaves <= 16, "flat_ransac_large_kernel: bins per thread / misc slots");
 
 // ---------------------------------------------------------------------------------------------
 // The vote.  The rows are swept once per vertex tile: the tile's (total, good) tallies are 32-bit LDS words, a row adds at those
@@ -115,7 +114,8 @@ __global__ __launch_bounds__(kLgBlock) void graph_keep_large_kernel(const GraphL
 }
 
 // ---------------------------------------------------------------------------------------------
-// flat_selection + the RANSAC plane fit.  The phases are flat_selection_kernel<true>'s; the frame-sized arrays are global:
+// flat_selection + the RANSAC plane fit.  The phases are flat_selection_kernel<true>'s, and so is each phase's rule: both kernels
+// call mvosr_flat.hpp (this one the level's search in its ROLLED form).  The frame-sized arrays are global:
 //   X, Y, Z   the survivors, compacted in order into the workspace (keep == NULL: the batch's own planes, read in place)
 //   Hh, Fl    every row's height and flags: the caller's tri_height / tri_flags where given, else the workspace
 //   L         the point list: int32 vertex ids of the kept rows in row order (M = 3 K entries; M may exceed 65 535)
@@ -161,9 +161,9 @@ __global__ __launch_bounds__(kLgBlock) void flat_ransac_large_kernel(const FlatL
     const bool skip = a.dt_status && a.dt_status[f] != 0;
     // more features or rows than the header's max_feat / the call's max_tri (the workspace's row stride): refused, nothing touched
     const bool oversize = n_all > a.max_feat || tn > a.max_tri;
-    if (n_all <= 0 || tn <= 0 || skip || oversize) {
+    if (const int refused = flat_entry_status(n_all, tn, skip, oversize)) {
         if (tid == 0) {
-            LG_LATE(status)[f] = (!skip && oversize && n_all > 0 && tn > 0) ? MVOSR_ST_ERR_MASK : MVOSR_ST_ERR_EMPTY;
+            LG_LATE(status)[f] = refused;
             LG_LATE(height_level)[f] = nan(""); LG_LATE(n_kept)[f] = 0;
             LG_LATE(raw_scale)[f] = nan(""); LG_LATE(best_ic)[f] = 0; LG_LATE(used)[f] = 0;
             for (int k = 0; k < 4; ++k) LG_LATE(model)[4 * f + k] = nan("");
@@ -181,146 +181,36 @@ __global__ __launch_bounds__(kLgBlock) void flat_ransac_large_kernel(const FlatL
     uint8_t *Fl = a.tri_flags ? a.tri_flags + tb : a.wf + rbase;
     int32_t *L = a.wl + 3 * rbase;
     const int32_t *rows = a.tri + 3 * tb;
-    if (tid < FM_WSUM) misc[tid] = 0;
-    if (tid == 0) { ext[0] = ~0ull; ext[1] = 0ull; ext[2] = ~0ull; }
+    flat_state_init(misc, ext);
     // ---- ordered compaction of the survivors (rescale.py:134-135: feature3d[valid_id])
     int n = n_all;
     const double *X = a.x + off, *Y = a.y + off, *Z = a.z + off;
     if (a.keep) {
         double *CX = a.wx + off, *CY = a.wy + off, *CZ = a.wz + off;
-        const int32_t *kp = a.keep + off;
-        int s0, s1;
-        ordered_segment(n_all, BLK, s0, s1);
-        int c = 0;
-        for (int i0 = s0; i0 < s1; i0 += kWave) {
-            const int i = i0 + lane;
-            c += __popcll(__ballot(i < s1 && kp[i] >= 0));
-        }
-        int base;
-        ordered_prefix<WAVES>(misc + FM_CW, c, base, n);
-        for (int i0 = s0; i0 < s1; i0 += kWave) {
-            const int i = i0 + lane;
-            const bool k = i < s1 && kp[i] >= 0;
-            const int pos = ordered_rank(k, base);
-            if (k) { CX[pos] = X[i]; CY[pos] = Y[i]; CZ[pos] = Z[i]; }
-        }
+        n = flat_compact_survivors<WAVES>(n_all, a.keep + off, X, Y, Z, CX, CY, CZ, misc + FM_CW);
         X = CX; Y = CY; Z = CZ;
     }
-    const double s_loose = sin(a.loose_deg * 3.141592653589793 / 180.0), s_tight = sin(a.tight_deg * 3.141592653589793 / 180.0);
+    const double s_loose = flat_sin_deg(a.loose_deg), s_tight = flat_sin_deg(a.tight_deg);
     __syncthreads();
     // ---- phase 1: every row's height and flags, the loose ones counted and bounded
     {
-        int k_mine = 0;
-        unsigned long long umin = ~0ull, umax = 0ull;
-
+        FlatLoose tally;
         for (int t = tid; t < tn; t += BLK) {
-            const TriIds q = load_tri(rows, t);
-            if (!ids_in_range(q.a, q.b, q.c, n)) { misc[FM_BADID] = 1; Fl[t] = 0; Hh[t] = nan(""); continue; }
-            double mu, h;
-            if (!row_height_pitch(X, Y, Z, q, mu, h)) misc[FM_SINGULAR] = 1;
-            // (the comparison is flat_selection_kernel's: on mu away from the thresholds, on the reference's expression within 1e-12)
-            bool loose, tight;
-            if (fabs(mu - s_loose) > 1e-12 && fabs(mu - s_tight) > 1e-12) { loose = mu < s_loose; tight = mu < s_tight; }
-            else {
-                const double pitch = asin(mu) * 180.0 / 3.141592653589793;
-                loose = pitch < a.loose_deg; tight = pitch < a.tight_deg;
-            }
-            Hh[t] = h;
-            Fl[t] = (uint8_t)((loose ? 1 : 0) | (tight ? 2 : 0));                              // :85-86
-            if (loose) {
-                const unsigned long long u = (unsigned long long)__double_as_longlong(h);
-                ++k_mine; umin = u < umin ? u : umin; umax = u > umax ? u : umax;
-            }
+            const FlatRow r = flat_row(X, Y, Z, load_tri(rows, t), n);
+            if (r.bad_id) misc[FM_BADID] = 1;
+            if (r.singular) misc[FM_SINGULAR] = 1;
+            const unsigned bits = r.bad_id ? 0u : flat_row_bits(r.mu, s_loose, s_tight, a.loose_deg, a.tight_deg);
+            Hh[t] = r.h;
+            Fl[t] = (uint8_t)bits;
+            if (bits & 1u) tally.add(r.h);
         }
-        k_mine = wave_sum(k_mine);
-        umin = wave_min_u64(umin); umax = wave_max_u64(umax);
-        if (lane == 0 && k_mine) { atomicAdd(&misc[FM_K], k_mine); atomicMin(&ext[0], umin); atomicMax(&ext[1], umax); }
+        tally.commit(misc, ext);
     }
     __syncthreads();
     const int k = misc[FM_K];
-    double level = nan("");                                      // median of an empty set is nan (nothing passes)
-    if (k > 0) {                                                                               // np.median, :91
-        // the lower middle order statistic by histogram narrowing over the bit patterns (flat_selection_kernel), the heights read
-        // from global memory on every pass
-        const int klo = (k - 1) >> 1, khi = k >> 1;
-        unsigned long long lo = ext[0], hi = ext[1];
-        int rank = klo;
-        unsigned long long vlo_bits = lo;
-        for (;;) {
-            const unsigned long long range = hi - lo;
-            if (range == 0ull) { vlo_bits = lo; break; }
-            const int bits = 64 - __clzll((long long)range);                                   // range < 2^bits
-            const int shift = bits > 11 ? bits - 11 : 0;
-            for (int b = tid; b < kFlatBins; b += BLK) hist[b] = 0;
-            __syncthreads();
-            for (int t = tid; t < tn; t += BLK) {
-                if (!(Fl[t] & 1)) continue;
-                const unsigned long long u = (unsigned long long)__double_as_longlong(Hh[t]);
-                if (u >= lo && u <= hi) atomicAdd(&hist[(int)((u - lo) >> shift)], 1);
-            }
-            __syncthreads();
-            {   // the bin whose cumulative count passes the rank: two bins per thread, wave scan, wave totals through LDS
-                constexpr int BPT = kFlatBins / BLK;
-                static_assert(BPT == 2, "two bins per thread");
-                const int b0 = hist[BPT * tid], b1 = hist[BPT * tid + 1];
-                const int mine = b0 + b1;
-                int incl = wave_scan_incl(mine);
-                if (lane == kWave - 1) misc[FM_WSUM + wave] = incl;
-                __syncthreads();
-                int before = 0;
-#pragma unroll
-                for (int w = 0; w < WAVES; ++w) if (w < wave) before += misc[FM_WSUM + w];
-                incl += before;
-                const int excl = incl - mine;
-                if (rank >= excl && rank < incl) {               // exactly one thread
-                    int r = rank - excl, bin = BPT * tid, c = b0;
-                    if (r >= b0) { r -= b0; ++bin; c = b1; }
-                    misc[FM_BIN] = bin; misc[FM_RANK] = r; misc[FM_BINCNT] = c;
-                }
-                __syncthreads();
-            }
-            const int bin = misc[FM_BIN], c = misc[FM_BINCNT];
-            rank = misc[FM_RANK];
-            lo += (unsigned long long)bin << shift;
-            { const unsigned long long top = lo + ((1ull << shift) - 1ull); hi = top < hi ? top : hi; }
-            if (shift == 0) { vlo_bits = lo; break; }            // the bin is one pattern
-            if (c <= kLgDirect) {
-                unsigned long long *list = reinterpret_cast<unsigned long long *>(hist);
-                __syncthreads();                                 // every thread has read misc / hist
-                for (int t = tid; t < tn; t += BLK) {
-                    if (!(Fl[t] & 1)) continue;
-                    const unsigned long long u = (unsigned long long)__double_as_longlong(Hh[t]);
-                    if (u >= lo && u <= hi) list[atomicAdd(&misc[FM_LIST], 1)] = u;
-                }
-                __syncthreads();
-                if (wave == 0) {
-                    const unsigned long long mine = lane < c ? list[lane] : ~0ull;
-                    int below = 0;
-                    // (not unrolled: eight trips' compare masks at once were forty scalar registers — spilled; c <= 64, one wavefront)
-#pragma unroll 1
-                    for (int j = 0; j < c; ++j) { const unsigned long long v = list[j]; below += (v < mine || (v == mine && j < lane)) ? 1 : 0; }
-                    if (lane < c && below == rank) ext[3] = mine;
-                }
-                __syncthreads();
-                vlo_bits = ext[3];
-                break;
-            }
-            __syncthreads();                                     // hist is zeroed again at the top
-        }
-        const double vlo = __longlong_as_double((long long)vlo_bits);
-        double vhi = vlo;
-        if (khi != klo) {
-            int le = 0;
-            unsigned long long above = ~0ull;
-            for (int t = tid; t < tn; t += BLK) {
-                if (!(Fl[t] & 1)) continue;
-                const unsigned long long u = (unsigned long long)__double_as_longlong(Hh[t]);
-                if (u <= vlo_bits) ++le; else above = u < above ? u : above;
-            }
-            vhi = __longlong_as_double((long long)next_order_statistic(le, above, vlo_bits, khi, &misc[FM_LE], &ext[2]));
-        }
-        level = a.height_factor * ((klo == khi) ? vlo : (vlo + vhi) / 2.0);
-    }
+    // (the heights are read from global memory on every pass of the search)
+    const double level = flat_level_search<WAVES, true>(reinterpret_cast<const unsigned long long *>(Hh), Fl, tn, k, ext, misc, hist,
+                                                        a.height_factor).level;               // np.median, :91
     // ---- the kept rows (:94-96), wavefront by wavefront over contiguous row segments: the point list comes out in row order
     int s0, s1;
     ordered_segment(tn, BLK, s0, s1);
@@ -354,18 +244,7 @@ __global__ __launch_bounds__(kLgBlock) void flat_ransac_large_kernel(const FlatL
         __syncthreads();
         // the hypotheses' planes, one thread each (ransac.py:10-11, estimate_road_norm.py:13-15)
         const uint64_t key = ransac_frame_key(LG_LATE(seed), (uint64_t)(LG_LATE(frame_ids) ? LG_LATE(frame_ids)[f] : LG_LATE(frame_base) + f));
-        for (int h = tid; h < H; h += BLK) {
-            int v0, v1, v2;
-            if (LG_LATE(id_triples)) {
-                const int32_t *t = LG_LATE(id_triples) + ((int64_t)f * H + h) * 3;
-                v0 = min(max(t[0], 0), n - 1); v1 = min(max(t[1], 0), n - 1); v2 = min(max(t[2], 0), n - 1);
-            } else {
-                ransac_draw3(key, h, M, v0, v1, v2);             // (list positions: mvosr_ransac.hpp on a vertex drawn twice)
-                v0 = L[v0]; v1 = L[v1]; v2 = L[v2];
-            }
-            mods[h] = ransac_unit_plane(X, Y, Z, v0, v1, v2);
-            cnts[h] = 0;
-        }
+        flat_build_hypotheses<BLK>(key, LG_LATE(id_triples) ? LG_LATE(id_triples) + (int64_t)f * H * 3 : nullptr, H, n, M, L, X, Y, Z, mods, cnts);
         __syncthreads();
         // inlier counts over the list as it is, repeats included (estimate_road_norm.py:17-18): a thread's list entries in registers,
         // their coordinates gathered by id once, the hypotheses streamed past them from LDS (mvosr_ransac.hpp)
@@ -375,27 +254,15 @@ __global__ __launch_bounds__(kLgBlock) void flat_ransac_large_kernel(const FlatL
         if (LG_LATE(hyp_counts)) for (int h = tid; h < H; h += BLK) LG_LATE(hyp_counts)[(int64_t)f * H + h] = cnts[h];
     }
     if (wave == 0) {
-        int status = misc[FM_BADID] ? MVOSR_ST_ERR_MASK : (misc[FM_SINGULAR] ? MVOSR_ST_ERR_SINGULAR : (fit ? 0 : MVOSR_ST_RS_FEW));
-        int best = -1, best_ic = 0, used = 0;
-        double m[4] = {nan(""), nan(""), nan(""), nan("")};
-        double raw = nan("");
-        if (fit) {
-            RansacReplay rp = {-1, 0, H, 0};
-            ransac_replay(rp, cnts, 0, H, (double)M * LG_LATE(goal_fraction));           // ransac.py:9-22; the goal: estimate_road_norm.py:68
-            best = rp.best; best_ic = rp.best_ic; used = rp.used;
-            if (best >= 0) {
-                const double4 bm = ransac_sign_rule(mods[best]);                   // rescale.py:159-161
-                m[0] = bm.x; m[1] = bm.y; m[2] = bm.z; m[3] = bm.w;
-                raw = LG_LATE(absolute_reference) / ransac_camera_height(bm);             // :158-167
-            } else status = MVOSR_ST_RS_FEW;                                       // (no hypothesis with an inlier: NaN planes only)
-        }
+        const int status = misc[FM_BADID] ? MVOSR_ST_ERR_MASK : (misc[FM_SINGULAR] ? MVOSR_ST_ERR_SINGULAR : (fit ? 0 : MVOSR_ST_RS_FEW));
+        const FlatRansacResult r = flat_ransac_result(fit, status, mods, cnts, H, (double)M * LG_LATE(goal_fraction), LG_LATE(absolute_reference));
         if (lane == 0) {
             LG_LATE(height_level)[f] = level;
             LG_LATE(n_kept)[f] = K;
-            LG_LATE(status)[f] = status;
-            LG_LATE(raw_scale)[f] = raw;
-            LG_LATE(best_ic)[f] = best_ic; LG_LATE(used)[f] = used;
-            for (int kk = 0; kk < 4; ++kk) LG_LATE(model)[4 * f + kk] = m[kk];
+            LG_LATE(status)[f] = r.status;
+            LG_LATE(raw_scale)[f] = r.raw;
+            LG_LATE(best_ic)[f] = r.best_ic; LG_LATE(used)[f] = r.used;
+            for (int kk = 0; kk < 4; ++kk) LG_LATE(model)[4 * f + kk] = r.m[kk];
         }
     }
 }

@@ -40,7 +40,7 @@ template <typename U> MVOSR_HD inline U graph_large_tile(U asked, U max_feat) {
 template <typename U> struct FlatLargePlan {
     U ext;          // uint64[4] smallest / largest loose height (bits), smallest above the median, the ranked candidate
     U misc;         // int[FM_N]
-    U hist;         // int[kFlatBins]; later the short candidate list, uint64[64]
+    U hist;         // int[kFlatBins]; later the short candidate list, uint64[kFlatDirect]
     U mods;         // [n_hyp] unit (n, d), kPlaneBytes each, 32-aligned
     U cnts;         // int[n_hyp] inlier counts
     U total;

@@ -25,11 +25,13 @@
 namespace mvosr {
 
 constexpr int kRsWaves = 8;             // wavefronts of a workgroup (flat_selection_kernel's device-resident form brings 16)
-constexpr int kFlatBins = 2048;         // flat_selection_kernel: one histogram pass resolves 11 bits of the candidates' range
+constexpr int kFlatBins = 2048;         // the level's search (mvosr_flat.hpp): one histogram pass resolves 11 bits of the candidates' range
+constexpr int kFlatDirect = 64;         // ... and that few candidates left: wavefront 0 ranks them directly
 constexpr int kGrowBins = 256;          // grow_median: an 8-bit radix pass
 constexpr int kPlaneBytes = 4 * sizeof(double);   // a hypothesis' unit (n, d): one double4, or two double2
 
-// misc[] slots of flat_selection_kernel (slots below FM_WSUM are zeroed at the start)
+// misc[] slots of flat_selection_kernel and its siblings — the large kernel's and the static_tri kernel's plans hold the same
+// int[FM_N] — (slots below FM_WSUM are zeroed at the start; slot 9 is the static_tri kernel's FM_BADH)
 enum { FM_K = 0, FM_SINGULAR = 1, FM_BADID = 2, FM_KEPT = 3, FM_BIN = 4, FM_RANK = 5, FM_BINCNT = 6, FM_LE = 7, FM_LIST = 8, FM_ND = 9,
        FM_WSUM = 16 /* [16] per-wave bin totals */, FM_CW = 32 /* [16] per-wave counts of the ordered compactions */, FM_N = 48 };
 // misc[] slots of region_grow_kernel

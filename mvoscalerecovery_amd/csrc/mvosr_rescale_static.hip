@@ -6,12 +6,10 @@
 // survivors compacted by keep >= 0 in order, the second triangulation's rows with their counts, dt_status — and runs one frame per
 // workgroup, but its tail is the deterministic road model instead of the RANSAC plane:
 //
-//   phase 1   every row's (mu, height) by row_height_pitch, the device function flat_selection_kernel calls, and the row's two bits
-//             decided as that kernel decides them (on mu away from sin(threshold) by more than 1e-12, else on asin(mu) * 180 / pi);
-//             heights and flags stay in LDS by row.  The loose rows are counted and their heights' patterns bounded.
-//   level     np.median of the loose heights (:91): the lower middle order statistic by a 2048-bin histogram over the candidates'
-//             range, narrowed to the bin that holds the rank and repeated, wavefront 0 ranking the last <= 64 candidates directly;
-//             the upper one by one more sweep.  The histogram lives where the vertex planes were.
+//   phase 1   flat_phase1 (mvosr_flat.hpp), the loop flat_selection_kernel runs: every row's height and two bits, which stay in LDS
+//             by row.  The loose rows are counted and their heights' patterns bounded.
+//   level     flat_level_search (mvosr_flat.hpp): np.median of the loose heights (:91) with its two middle order statistics.  The
+//             search's histogram lives where the vertex planes were.
 //   model     one sweep over the rows: bit 2 and the kept count as flat_selection_kernel writes them, and of every loose row
 //             hi = 1 / h with its bin among the 19 (counted by comparison against k * 0.1, bin 18 closed) — per bin one ballot per
 //             wavefront step, a wavefront's 19 counts added to the workgroup's with integer LDS atomics.
@@ -30,6 +28,7 @@
 #include "../../include/mvosr.h"
 #include "mvosr_device.hpp"
 #include "mvosr_ransac.hpp"
+#include "mvosr_flat.hpp"
 #include "mvosr_host.hpp"
 #include "mvosr_rescale_static_plan.hpp"
 
@@ -53,8 +52,6 @@ struct StaticArgs {
     uint8_t *tri_flags;            // optional [rows] bit0: pitch < loose, bit1: pitch < tight, bit2: kept
 };
 
-constexpr int kStaticRows = 4;          // triangle rows a thread keeps in flight
-
 // np.histogram's bin of hi over the edges k * 0.1, k = 0..19: edges[k] <= hi < edges[k+1], the last bin closed, -1 outside
 // (static_tri_kernel's rule: (int)(10 hi) is off by at most one bin, the two comparisons decide)
 __device__ __forceinline__ int static_bin_of(double hi) {
@@ -69,7 +66,7 @@ __device__ __forceinline__ int static_bin_of(double hi) {
 template <bool GIVEN>
 __global__ __launch_bounds__(kStaticWaves *kWave) void flat_static_tri_kernel(const StaticArgs a) {
     constexpr int WAVES = kStaticWaves, BLK = WAVES * kWave;
-    static_assert(kStaticBins % BLK == 0 && kStaticModelBins <= 32, "flat_static_tri_kernel: bins per thread / the model's bins in the plan");
+    static_assert(kStaticModelBins <= 32, "flat_static_tri_kernel: the model's bins in the plan");
     extern __shared__ __attribute__((aligned(16))) char smem[];
     const int64_t f = blockIdx.x;
     const int n_all = a.feat_cnt[f];
@@ -80,9 +77,9 @@ __global__ __launch_bounds__(kStaticWaves *kWave) void flat_static_tri_kernel(co
     const bool skip = a.dt_status && a.dt_status[f] != 0;
     // more features or rows than the launch's LDS was sized for (the header's max_feat, the call's max_tri): refused, LDS untouched
     const bool oversize = n_all > a.max_feat || tn > a.max_tri;
-    if (n_all <= 0 || tn <= 0 || skip || oversize) {
+    if (const int refused = flat_entry_status(n_all, tn, skip, oversize)) {
         if (tid == 0) {
-            a.status[f] = (!skip && oversize && n_all > 0 && tn > 0) ? MVOSR_ST_ERR_MASK : MVOSR_ST_ERR_EMPTY;
+            a.status[f] = refused;
             a.height_level[f] = nan(""); a.n_kept[f] = 0;
             a.scale_norm[f] = nan(""); a.raw_scale[f] = nan(""); a.n_used[f] = 0;
         }
@@ -94,22 +91,16 @@ __global__ __launch_bounds__(kStaticWaves *kWave) void flat_static_tri_kernel(co
     int *misc = reinterpret_cast<int *>(smem + lds.misc);
     int *model = reinterpret_cast<int *>(smem + lds.model);
     int *hist = reinterpret_cast<int *>(smem + lds.hist);
-    if (tid < TM_WSUM) misc[tid] = 0;
+    flat_state_init(misc, ext);
     if (tid < 32) model[tid] = 0;
-    if (tid == 0) { ext[0] = ~0ull; ext[1] = 0ull; ext[2] = ~0ull; }
     // what the phases behind the first read: the rows' heights and flags, in LDS (fused) or in global memory (given)
     const double *Hh;
     const uint8_t *Fl;
-    int k_mine = 0;
-    unsigned long long umin = ~0ull, umax = 0ull;
+    FlatLoose tally;
     if constexpr (GIVEN) {
         Hh = a.height_in + tb;
         Fl = a.flags_in + tb;
-        for (int t = tid; t < tn; t += BLK) {
-            if (!(Fl[t] & 1)) continue;
-            const unsigned long long u = (unsigned long long)__double_as_longlong(Hh[t]);
-            ++k_mine; umin = u < umin ? u : umin; umax = u > umax ? u : umax;
-        }
+        for (int t = tid; t < tn; t += BLK) if (Fl[t] & 1) tally.add(Hh[t]);
         __syncthreads();                                         // (misc and ext are set: the tallies below add to them)
     } else {
         double *H1 = reinterpret_cast<double *>(smem + lds.heights);
@@ -119,160 +110,28 @@ __global__ __launch_bounds__(kStaticWaves *kWave) void flat_static_tri_kernel(co
         double *Z = reinterpret_cast<double *>(smem + lds.z);
         Hh = H1;
         Fl = F1;
-        // a thread's next kStaticRows triangle rows are in flight while it works on the current ones (and the first ones while the
-        // vertex planes stream in)
-        TriIds rows[kStaticRows];
-        auto load_rows = [&](int t0) {
-#pragma unroll
-            for (int j = 0; j < kStaticRows; ++j) rows[j] = load_tri(a.tri + 3 * tb, min(t0 + j * BLK, tn - 1));
-        };
-        load_rows(tid);
-        // ---- the survivors, compacted in order (rescale.py:134-135): every wavefront owns a contiguous segment of the frame
+        // (the first rows are in flight while the vertex planes stream in: mvosr_flat.hpp, flat_phase1)
+        TriIds rows[kFlatRows];
+        flat_load_rows<BLK>(a.tri + 3 * tb, tid, tn, rows);
+        // ---- the survivors, compacted in order (rescale.py:134-135)
         int n = n_all;
-        if (a.keep) {
-            int s0, s1;
-            ordered_segment(n_all, BLK, s0, s1);
-            int c = 0;
-            for (int i0 = s0; i0 < s1; i0 += kWave) {
-                const int i = i0 + lane;
-                c += __popcll(__ballot(i < s1 && a.keep[off + i] >= 0));
-            }
-            int base;
-            ordered_prefix<WAVES>(misc + TM_CW, c, base, n);
-            for (int i0 = s0; i0 < s1; i0 += kWave) {
-                const int i = i0 + lane;
-                const bool k = i < s1 && a.keep[off + i] >= 0;
-                const int pos = ordered_rank(k, base);
-                if (k) { X[pos] = a.x[off + i]; Y[pos] = a.y[off + i]; Z[pos] = a.z[off + i]; }
-            }
-        } else {
+        if (a.keep) n = flat_compact_survivors<WAVES>(n_all, a.keep + off, a.x + off, a.y + off, a.z + off, X, Y, Z, misc + FM_CW);
+        else {
 #pragma unroll 4
             for (int i = tid; i < n_all; i += BLK) { X[i] = a.x[off + i]; Y[i] = a.y[off + i]; Z[i] = a.z[off + i]; }
         }
-        const double s_loose = sin(a.loose_deg * 3.141592653589793 / 180.0), s_tight = sin(a.tight_deg * 3.141592653589793 / 180.0);
+        const double s_loose = flat_sin_deg(a.loose_deg), s_tight = flat_sin_deg(a.tight_deg);
         __syncthreads();
         // ---- phase 1: every row's height and flags into LDS, the loose ones counted and bounded (rescale.py:79-89)
-        auto one_row = [&](const TriIds q, const int t) {
-            if (!ids_in_range(q.a, q.b, q.c, n)) {
-                misc[TM_BADID] = 1; F1[t] = 0; H1[t] = nan(""); if (a.tri_height) a.tri_height[tb + t] = nan(""); return;
-            }
-            double mu, h;
-            if (!row_height_pitch(X, Y, Z, q, mu, h)) misc[TM_SINGULAR] = 1;
-            // pitch = asin(mu) * 180/pi (:83) is increasing in mu: away from the two thresholds the comparison is made on mu itself,
-            // within 1e-12 of one (or for NaN) on the reference's own expression
-            bool loose, tight;
-            if (fabs(mu - s_loose) > 1e-12 && fabs(mu - s_tight) > 1e-12) { loose = mu < s_loose; tight = mu < s_tight; }
-            else {
-                const double pitch = asin(mu) * 180.0 / 3.141592653589793;
-                loose = pitch < a.loose_deg; tight = pitch < a.tight_deg;
-            }
-            H1[t] = h;
-            F1[t] = (uint8_t)((loose ? 1 : 0) | (tight ? 2 : 0));                            // :85-86
-            if (a.tri_height) a.tri_height[tb + t] = h;
-            if (loose) {
-                const unsigned long long u = (unsigned long long)__double_as_longlong(h);
-                ++k_mine; umin = u < umin ? u : umin; umax = u > umax ? u : umax;
-            }
-        };
-        for (int t0 = tid; t0 < tn; t0 += kStaticRows * BLK) {
-            TriIds cur[kStaticRows];
-#pragma unroll
-            for (int j = 0; j < kStaticRows; ++j) cur[j] = rows[j];
-            if (t0 + kStaticRows * BLK < tn) load_rows(t0 + kStaticRows * BLK);
-#pragma unroll
-            for (int j = 0; j < kStaticRows; ++j) if (t0 + j * BLK < tn) one_row(cur[j], t0 + j * BLK);
-        }
+        flat_phase1<BLK>(a.tri + 3 * tb, rows, tn, X, Y, Z, n, a.loose_deg, a.tight_deg, s_loose, s_tight, H1, F1,
+                         a.tri_height ? a.tri_height + tb : nullptr, misc, tally);
     }
-    k_mine = wave_sum(k_mine);
-    umin = wave_min_u64(umin); umax = wave_max_u64(umax);
-    if (lane == 0 && k_mine) { atomicAdd(&misc[TM_K], k_mine); atomicMin(&ext[0], umin); atomicMax(&ext[1], umax); }
+    tally.commit(misc, ext);
     __syncthreads();                                             // (the planes are dead: their room is the histogram's)
-    const unsigned long long *U = reinterpret_cast<const unsigned long long *>(Hh);
-    const int k = misc[TM_K];
-    // ---- the level (:91): np.median of the loose heights, as flat_selection_kernel searches it
-    double level = nan("");                                      // median of an empty set is nan (nothing passes)
-    double vlo = nan(""), vhi = nan("");                         // the two middle order statistics (one, twice, for an odd k)
-    if (k > 0) {
-        const int klo = (k - 1) >> 1, khi = k >> 1;
-        unsigned long long lo = ext[0], hi = ext[1];
-        int rank = klo;
-        unsigned long long vlo_bits = lo;
-        for (;;) {
-            const unsigned long long range = hi - lo;
-            if (range == 0ull) { vlo_bits = lo; break; }
-            const int bits = 64 - __clzll((long long)range);                             // range < 2^bits
-            const int shift = bits > 11 ? bits - 11 : 0;
-            for (int b = tid; b < kStaticBins; b += BLK) hist[b] = 0;
-            __syncthreads();
-#pragma unroll 4
-            for (int t = tid; t < tn; t += BLK) {
-                if (!(Fl[t] & 1)) continue;
-                const unsigned long long u = U[t];
-                if (u >= lo && u <= hi) atomicAdd(&hist[(int)((u - lo) >> shift)], 1);
-            }
-            __syncthreads();
-            {   // the bin whose cumulative count passes the rank: two bins per thread, wave scan, wave totals through LDS
-                constexpr int BPT = kStaticBins / BLK;
-                static_assert(BPT == 2, "flat_static_tri_kernel: two bins per thread");
-                const int b0 = hist[BPT * tid], b1 = hist[BPT * tid + 1];
-                const int mine = b0 + b1;
-                int incl = wave_scan_incl(mine);
-                if (lane == kWave - 1) misc[TM_WSUM + wave] = incl;
-                __syncthreads();
-                int before = 0;
-#pragma unroll
-                for (int w = 0; w < WAVES; ++w) if (w < wave) before += misc[TM_WSUM + w];
-                incl += before;
-                const int excl = incl - mine;
-                if (rank >= excl && rank < incl) {               // exactly one thread
-                    int r = rank - excl, bin = BPT * tid, c = b0;
-                    if (r >= b0) { r -= b0; ++bin; c = b1; }
-                    misc[TM_BIN] = bin; misc[TM_RANK] = r; misc[TM_BINCNT] = c;
-                }
-                __syncthreads();
-            }
-            const int bin = misc[TM_BIN], c = misc[TM_BINCNT];
-            rank = misc[TM_RANK];
-            lo += (unsigned long long)bin << shift;
-            { const unsigned long long top = lo + ((1ull << shift) - 1ull); hi = top < hi ? top : hi; }
-            if (shift == 0) { vlo_bits = lo; break; }            // the bin is one pattern
-            if (c <= kStaticDirect) {
-                unsigned long long *list = reinterpret_cast<unsigned long long *>(hist);
-                __syncthreads();                                 // every thread has read misc / hist
-#pragma unroll 4
-                for (int t = tid; t < tn; t += BLK) {
-                    if (!(Fl[t] & 1)) continue;
-                    const unsigned long long u = U[t];
-                    if (u >= lo && u <= hi) list[atomicAdd(&misc[TM_LIST], 1)] = u;
-                }
-                __syncthreads();
-                if (wave == 0) {
-                    const unsigned long long mine = lane < c ? list[lane] : ~0ull;
-                    int below = 0;
-                    for (int j = 0; j < c; ++j) { const unsigned long long v = list[j]; below += (v < mine || (v == mine && j < lane)) ? 1 : 0; }
-                    if (lane < c && below == rank) ext[3] = mine;
-                }
-                __syncthreads();
-                vlo_bits = ext[3];
-                break;
-            }
-            __syncthreads();                                     // hist is zeroed again at the top
-        }
-        vlo = __longlong_as_double((long long)vlo_bits);
-        vhi = vlo;
-        if (khi != klo) {
-            int le = 0;
-            unsigned long long above = ~0ull;
-#pragma unroll 4
-            for (int t = tid; t < tn; t += BLK) {
-                if (!(Fl[t] & 1)) continue;
-                const unsigned long long u = U[t];
-                if (u <= vlo_bits) ++le; else above = u < above ? u : above;
-            }
-            vhi = __longlong_as_double((long long)next_order_statistic(le, above, vlo_bits, khi, &misc[TM_LE], &ext[2]));
-        }
-        level = a.height_factor * ((klo == khi) ? vlo : (vlo + vhi) / 2.0);
-    }
+    const int k = misc[FM_K];
+    // ---- the level (:91): np.median of the loose heights, with the two middle order statistics (one, twice, for an odd k)
+    const FlatLevel lv = flat_level_search<WAVES>(reinterpret_cast<const unsigned long long *>(Hh), Fl, tn, k, ext, misc, hist, a.height_factor);
+    const double level = lv.level, vlo = lv.vlo, vhi = lv.vhi;
     // ---- the kept rows (:94-96) and the road model's histogram (scale_calculator.py:296-297), one sweep, 64 rows a wavefront step
     {
         int kept = 0, mine = 0;
@@ -298,15 +157,15 @@ __global__ __launch_bounds__(kStaticWaves *kWave) void flat_static_tri_kernel(co
             }
         }
         kept = wave_sum(kept);
-        if (lane == 0 && kept) atomicAdd(&misc[TM_KEPT], kept);
+        if (lane == 0 && kept) atomicAdd(&misc[FM_KEPT], kept);
         if (lane < kStaticModelBins && mine) atomicAdd(&model[lane], mine);
-        if (__ballot(badh) != 0ull && lane == 0) misc[TM_BADH] = 1;
+        if (__ballot(badh) != 0ull && lane == 0) misc[FM_BADH] = 1;
     }
     __syncthreads();
     // ---- decide, as static_tri_kernel does (scale_calculator.py:299-310, :446-483)
     if (wave == 0) {
-        const int flat_err = misc[TM_BADID] ? MVOSR_ST_ERR_MASK : (misc[TM_SINGULAR] ? MVOSR_ST_ERR_SINGULAR : 0);
-        const bool refused = misc[TM_BADH] != 0;
+        const int flat_err = misc[FM_BADID] ? MVOSR_ST_ERR_MASK : (misc[FM_SINGULAR] ? MVOSR_ST_ERR_SINGULAR : 0);
+        const bool refused = misc[FM_BADH] != 0;
         const bool few = k == 0 || k <= a.min_count;             // rescale.py:181
         int d = lane < kStaticModelBins ? model[lane] : 0;
         d = d == 1 ? 0 : d;                                      // :299
@@ -333,7 +192,7 @@ __global__ __launch_bounds__(kStaticWaves *kWave) void flat_static_tri_kernel(co
         if (a.hist && lane < kStaticModelBins) a.hist[f * kStaticModelBins + lane] = (flat_err || refused || few) ? 0 : d;
         if (lane == 0) {
             a.height_level[f] = level;
-            a.n_kept[f] = misc[TM_KEPT];
+            a.n_kept[f] = misc[FM_KEPT];
             a.scale_norm[f] = scale_norm;
             a.raw_scale[f] = scale_norm * a.absolute_reference;   // rescale.py:183
             a.n_used[f] = flat_err ? 0 : k;

@@ -18,6 +18,8 @@
 #include <stddef.h>
 #include <stdint.h>
 
+#include "mvosr_rescale_plan.hpp"
+
 #ifdef __HIPCC__
 #define MVOSR_STATIC_HD __host__ __device__
 #else
@@ -27,13 +29,12 @@
 namespace mvosr {
 
 constexpr int kStaticWaves = 16;        // wavefronts of a workgroup: the frame holds most of a CU's LDS, one workgroup per CU
-constexpr int kStaticBins = 2048;       // the median search resolves 11 bits of the candidates' range a pass
-constexpr int kStaticDirect = 64;       // that few candidates left: wavefront 0 ranks them directly
 constexpr int kStaticModelBins = 19;    // the road model's histogram (scale_calculator.py:297)
 
-// misc[] slots of flat_static_tri_kernel (slots below TM_WSUM are zeroed at the start)
-enum { TM_K = 0, TM_SINGULAR = 1, TM_BADID = 2, TM_KEPT = 3, TM_BIN = 4, TM_RANK = 5, TM_BINCNT = 6, TM_LE = 7, TM_LIST = 8, TM_BADH = 9,
-       TM_WSUM = 16 /* [kStaticWaves] per-wave bin totals */, TM_CW = 32 /* [kStaticWaves] per-wave survivor counts */, TM_N = 48 };
+// misc[] of flat_static_tri_kernel: flat_selection_kernel's slots (FM_*, mvosr_rescale_plan.hpp), whose slot 9 — the plane fit's
+// FM_ND — is this kernel's "a counted height is no positive finite number"
+enum { FM_BADH = FM_ND };
+static_assert(kStaticWaves <= FM_CW - FM_WSUM && FM_CW + kStaticWaves <= FM_N, "flat_static_tri_kernel: per-wave slots in misc");
 
 template <typename U> MVOSR_STATIC_HD inline U static_align16(U v) { return (v + 15u) & ~(U)15u; }
 
@@ -41,7 +42,7 @@ template <typename U> struct StaticPlan {
     U heights;      // double[tn] every row's height, by row (>= 0 where a row is loose: the patterns order like the values)
     U flags;        // uint8[tn] every row's flags, by row
     U ext;          // uint64[4] smallest / largest loose height (bits), smallest above the median, the ranked candidate
-    U misc;         // int[TM_N]
+    U misc;         // int[FM_N]
     U model;        // int[32] the road model's 19 bins
     U work;         // work_bytes
     U total;
@@ -49,18 +50,18 @@ template <typename U> struct StaticPlan {
     // in work, phase 1:
     U x, y, z;      // double[n rounded up to even] each: the survivors, compacted in order
     // in work, from the barrier that ends phase 1:
-    U hist;         // int[kStaticBins]; later the short candidate list, uint64[kStaticDirect]
+    U hist;         // int[kFlatBins]; later the short candidate list, uint64[kFlatDirect]
 };
 template <typename U> MVOSR_STATIC_HD inline StaticPlan<U> static_plan(U n, U tn) {
     StaticPlan<U> p;
     const U plane = 8u * ((n + 1u) & ~(U)1u);
-    const U hist = 4u * (U)kStaticBins;
+    const U hist = 4u * (U)kFlatBins;
     p.work_bytes = 3u * plane > hist ? 3u * plane : hist;
     p.heights = 0;
     p.flags = p.heights + static_align16<U>(8u * tn);
     p.ext = p.flags + static_align16<U>(tn);
     p.misc = p.ext + 4u * 8u;
-    p.model = p.misc + 4u * (U)TM_N;
+    p.model = p.misc + 4u * (U)FM_N;
     p.work = p.model + 4u * 32u;
     p.total = p.work + p.work_bytes;
     p.x = p.work;

@@ -7,9 +7,8 @@
 // (mvosr_flat_ransac_batch) reads — the survivors compacted by keep >= 0 in order, the second triangulation's rows with their
 // counts, dt_status — and runs one frame per workgroup:
 //
-//   once per frame: every row's (mu, height) by row_height_pitch, the device function flat_selection_kernel calls, and from mu
-//   the row's two bits for every setting, decided as that kernel decides them (on mu away from sin(threshold) by more than
-//   1e-12, else on asin(mu) * 180 / pi);
+//   once per frame: every row's (mu, height) by flat_row, and from mu the row's two bits for every setting by flat_row_bits —
+//   the functions flat_selection_kernel's phase 1 calls (mvosr_flat.hpp);
 //   per setting, one wavefront each: the median of the loose rows' heights as np.median takes it — the two middle order
 //   statistics by an 8-bit radix select over the heights' patterns, a histogram per wavefront where the vertex planes were —,
 //   the level, bit 2, and the setting's flag plane.
@@ -24,6 +23,7 @@
 #include "../../include/mvosr.h"
 #include "mvosr_device.hpp"
 #include "mvosr_ransac.hpp"
+#include "mvosr_flat.hpp"
 #include "mvosr_host.hpp"
 #include "mvosr_rescale_sweep_plan.hpp"
 
@@ -102,8 +102,8 @@ __global__ __launch_bounds__(WAVES *kWave) void flat_selection_sweep_kernel(cons
     const bool skip = a.dt_status && a.dt_status[f] != 0;
     // more features or rows than the launch's LDS was sized for, or rows that do not lie inside a plane: refused, LDS untouched
     const bool oversize = n_all > a.max_feat || tn > a.max_tri || tb < 0 || tb + tn > plane_rows;
-    if (n_all <= 0 || tn <= 0 || skip || oversize) {
-        if (tid == 0) a.status[f] = (!skip && oversize && n_all > 0 && tn > 0) ? MVOSR_ST_ERR_MASK : MVOSR_ST_ERR_EMPTY;
+    if (const int refused = flat_entry_status(n_all, tn, skip, oversize)) {
+        if (tid == 0) a.status[f] = refused;
         for (int s = tid; s < S; s += BLK) { a.height_level[f * S + s] = nan(""); a.n_kept[f * S + s] = 0; }
         return;
     }
@@ -118,56 +118,26 @@ __global__ __launch_bounds__(WAVES *kWave) void flat_selection_sweep_kernel(cons
     double *Z = reinterpret_cast<double *>(smem + lds.z);
     if (tid < SM_CW) misc[tid] = 0;
     if (tid < S) {
-        thr[tid] = sin(a.loose_deg[tid] * 3.141592653589793 / 180.0);
-        thr[S + tid] = sin(a.tight_deg[tid] * 3.141592653589793 / 180.0);
+        thr[tid] = flat_sin_deg(a.loose_deg[tid]);
+        thr[S + tid] = flat_sin_deg(a.tight_deg[tid]);
     }
-    // ---- the survivors, compacted in order (rescale.py:134-135): every wavefront owns a contiguous segment of the frame
-    int n;
-    {
-        int s0, s1;
-        ordered_segment(n_all, BLK, s0, s1);
-        int c = 0;
-        for (int i0 = s0; i0 < s1; i0 += kWave) {
-            const int i = i0 + lane;
-            c += __popcll(__ballot(i < s1 && (!a.keep || a.keep[off + i] >= 0)));
-        }
-        int base;
-        ordered_prefix<WAVES>(misc + SM_CW, c, base, n);
-        for (int i0 = s0; i0 < s1; i0 += kWave) {
-            const int i = i0 + lane;
-            const bool k = i < s1 && (!a.keep || a.keep[off + i] >= 0);
-            const int pos = ordered_rank(k, base);
-            if (k) { X[pos] = a.x[off + i]; Y[pos] = a.y[off + i]; Z[pos] = a.z[off + i]; }
-        }
-    }
+    // ---- the survivors, compacted in order (rescale.py:134-135)
+    const int n = flat_compact_survivors<WAVES>(n_all, a.keep ? a.keep + off : nullptr, a.x + off, a.y + off, a.z + off, X, Y, Z, misc + SM_CW);
     __syncthreads();
     // ---- phase 1: every row's height and, per setting, its two bits (rescale.py:79-89)
     {
         int bad = 0, singular = 0;
         for (int t = tid; t < tn; t += BLK) {
-            const TriIds q = load_tri(a.tri + 3 * tb, t);
+            const FlatRow r = flat_row(X, Y, Z, load_tri(a.tri + 3 * tb, t), n);
             uint32_t bits = 0u;
-            double h = nan("");
-            if (!ids_in_range(q.a, q.b, q.c, n)) bad = 1;
+            if (r.bad_id) bad = 1;
             else {
-                double mu;
-                if (!row_height_pitch(X, Y, Z, q, mu, h)) singular = 1;
-                for (int s = 0; s < S; ++s) {
-                    // pitch = asin(mu) * 180/pi (:83) is increasing in mu: away from the setting's two thresholds the comparison
-                    // is made on mu itself, within 1e-12 of one (or for NaN) on the reference's own expression
-                    const double s_loose = thr[s], s_tight = thr[S + s];
-                    bool loose, tight;
-                    if (fabs(mu - s_loose) > 1e-12 && fabs(mu - s_tight) > 1e-12) { loose = mu < s_loose; tight = mu < s_tight; }
-                    else {
-                        const double pitch = asin(mu) * 180.0 / 3.141592653589793;
-                        loose = pitch < a.loose_deg[s]; tight = pitch < a.tight_deg[s];
-                    }
-                    bits |= ((loose ? 1u : 0u) | (tight ? 2u : 0u)) << (2 * s);              // :85-86
-                }
+                if (r.singular) singular = 1;
+                for (int s = 0; s < S; ++s) bits |= flat_row_bits(r.mu, thr[s], thr[S + s], a.loose_deg[s], a.tight_deg[s]) << (2 * s);
             }
-            Hh[t] = h;
+            Hh[t] = r.h;
             B[t] = bits;
-            if (a.tri_height) a.tri_height[tb + t] = h;
+            if (a.tri_height) a.tri_height[tb + t] = r.h;
         }
         if (bad) misc[SM_BADID] = 1;
         if (singular) misc[SM_SINGULAR] = 1;

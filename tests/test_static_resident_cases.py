@@ -98,9 +98,9 @@ static size_t static_end(long long n, long long tn) {
     const size_t plane = 8u * (size_t)n;
     std::vector<Region> r = {
         {"heights", q.heights, 8u * (size_t)tn, 8, 7u}, {"flags", q.flags, (size_t)tn, 1, 7u}, {"ext", q.ext, 32, 8, 7u},
-        {"misc", q.misc, 4u * TM_N, 4, 7u}, {"model", q.model, 4u * 32, 4, 7u},
+        {"misc", q.misc, 4u * FM_N, 4, 7u}, {"model", q.model, 4u * 32, 4, 7u},
         {"x", q.x, plane, 8, 1u}, {"y", q.y, plane, 8, 1u}, {"z", q.z, plane, 8, 1u},
-        {"hist", q.hist, 4u * kStaticBins, 8, 2u}, {"list", q.hist, 8u * kStaticDirect, 8, 2u}};
+        {"hist", q.hist, 4u * kFlatBins, 8, 2u}, {"list", q.hist, 8u * kFlatDirect, 8, 2u}};
     size_t end = 0;
     for (size_t i = 0; i < r.size(); ++i) {
         CHECK(r[i].off % r[i].align == 0, "%s at %zu needs %zu (n %lld tn %lld)", r[i].name, r[i].off, r[i].align, n, tn);
@@ -117,7 +117,7 @@ static size_t static_end(long long n, long long tn) {
     for (size_t o : {q.heights, q.flags, q.ext, q.misc, q.model, q.work, q.x, q.hist, q.total})
         CHECK(o % 16 == 0, "offset %zu is no multiple of 16 (n %lld tn %lld)", o, n, tn);
     CHECK(q.y % 8 == 0 && q.z % 8 == 0, "planes");
-    CHECK(TM_CW + kStaticWaves <= TM_N && TM_WSUM + kStaticWaves <= TM_CW && kStaticModelBins <= 32 && kStaticDirect * 8 <= kStaticBins * 4, "slots");
+    CHECK(FM_CW + kStaticWaves <= FM_N && FM_WSUM + kStaticWaves <= FM_CW && kStaticModelBins <= 32 && kFlatDirect * 8 <= kFlatBins * 4, "slots");
     return end;
 }
 
@@ -158,7 +158,7 @@ static void properties() {
             CHECK(n >= 342 ? mine <= theirs : mine <= 65536, "(%lld, %lld): %zu against %zu", n, tn, mine, theirs);
         }
     // the given form: nothing row-sized
-    CHECK(static_plan<size_t>(0, 0).total == 32 + 4u * TM_N + 128 + 4u * kStaticBins, "the plan at (0, 0): %zu", static_plan<size_t>(0, 0).total);
+    CHECK(static_plan<size_t>(0, 0).total == 32 + 4u * FM_N + 128 + 4u * kFlatBins, "the plan at (0, 0): %zu", static_plan<size_t>(0, 0).total);
 }
 
 int main(int argc, char **argv) {
