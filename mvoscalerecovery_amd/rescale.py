@@ -78,7 +78,8 @@ STATIC_TRI_MIN_COUNT = 12                             # rescale.py:181 (more tha
 SLEW = 0.3                                            # rescale.py:169-172
 _FIELDS = ("raw_scale", "height_level", "model", "best_ic", "used", "n_kept", "status")     # a chunk's results, per frame
 _STATIC_FIELDS = ("raw_scale", "height_level", "scale_norm", "n_used", "n_kept", "status")   # the same with model_resident=True
-MAX_HYP = 512                                         # mvosr_flat_ransac_batch's limit (include/mvosr.h)
+_REFUSED = (K.ST_ERR_SINGULAR, K.ST_ERR_MASK, K.ST_ERR_EMPTY)   # the flat selection refuses the frame as a whole: singular row, bad vertex id, no rows
+MAX_HYP = 512                                        # mvosr_flat_ransac_batch's limit (include/mvosr.h)
 
 
 @dataclasses.dataclass(frozen=True)
@@ -677,10 +678,7 @@ class ScaleEstimator(stream.StreamKnobs):
         side = []
         o = _lib.RescaleOutputs(out["raw_scale"].ptr, out["height_level"].ptr, out["model"].ptr, out["best_ic"].ptr,
                                 out["used"].ptr, out["n_kept"].ptr, out["status"].ptr, None, None, None)
-        flags = None
-        if stage:
-            flags = ctx.block([("tri_flags", max(db.n_rows2, 1), np.uint8)])
-            o.tri_flags = flags["tri_flags"].ptr
+        flags = self._flags_block(ctx, db, o, stage)
         d_ids = d_tr = None
         if frame_ids is not None:
             d_ids = ctx.block([("frame_ids", F, np.int64)])
@@ -698,17 +696,29 @@ class ScaleEstimator(stream.StreamKnobs):
                                            d_tr["id_triples"].ptr if d_tr is not None else None,
                                            d_ids["frame_ids"].ptr if d_ids is not None else None, dt2_ptr,
                                            C.byref(o), int(max_tri)), entry)
-        # (the results reach their page-locked image through a copy KERNEL: a hipMemcpyAsync queued here would park a copy engine behind
-        # this chunk's kernels, and an upload of the next chunk that lands on that engine waits with it — DeviceBlock.mark_done; the
-        # per-frame call with stage outputs keeps the queued download)
+        self._queue_download(out, stage)
+        for blk in side:
+            blk.mark(True)
+        return out, flags, side
+
+    @staticmethod
+    def _flags_block(ctx, db, o, stage):
+        """With ``stage``: a block for the launch's tri_flags plane, named in its outputs ``o``; else None."""
+        if not stage:
+            return None
+        flags = ctx.block([("tri_flags", max(db.n_rows2, 1), np.uint8)])
+        o.tri_flags = flags["tri_flags"].ptr
+        return flags
+
+    def _queue_download(self, out, stage):
+        """The results reach their page-locked image through a copy KERNEL: a hipMemcpyAsync queued here would park a copy engine behind
+        this chunk's kernels, and an upload of the next chunk that lands on that engine waits with it — DeviceBlock.mark_done; the
+        per-frame call with stage outputs keeps the queued download."""
         if stage or not self.GPU_SIDE_DOWNLOADS:
             out.prefetch()
         else:
             out.mark_done()
         out.mark(True)
-        for blk in side:
-            blk.mark(True)
-        return out, flags, side
 
     def _launch_flat_static(self, db, keep_ptr, dt2_ptr, stage, max_tri, ctx):
         """model_resident=True: mvosr_flat_static_tri_batch in mvosr_flat_ransac_batch's place, over the same DeviceBatch, keep words
@@ -719,20 +729,13 @@ class ScaleEstimator(stream.StreamKnobs):
                          ("n_used", F, np.int32), ("n_kept", F, np.int32), ("status", F, np.int32)])
         o = _lib.StaticTriOutputs(out["scale_norm"].ptr, out["raw_scale"].ptr, out["height_level"].ptr, out["n_used"].ptr,
                                   out["n_kept"].ptr, out["status"].ptr, None, None, None)
-        flags = None
-        if stage:
-            flags = ctx.block([("tri_flags", max(db.n_rows2, 1), np.uint8)])
-            o.tri_flags = flags["tri_flags"].ptr
+        flags = self._flags_block(ctx, db, o, stage)
         k = self.constants
         b = db.struct()
         _lib.check(ctx.lib.mvosr_flat_static_tri_batch(ctx.handle, C.byref(b), keep_ptr, k.loose_deg, k.tight_deg, k.height_factor,
                                                        STATIC_TRI_MIN_COUNT, float(self.absolute_reference), dt2_ptr, None, None,
                                                        C.byref(o), int(max_tri)), "mvosr_flat_static_tri_batch")
-        if stage or not self.GPU_SIDE_DOWNLOADS:
-            out.prefetch()
-        else:
-            out.mark_done()
-        out.mark(True)
+        self._queue_download(out, stage)
         return out, flags, []
 
     def _chunk_dev_gpu(self, f3s, f2s, frame_base, id_triples, stage, tables=False, early_status=False):
@@ -872,10 +875,8 @@ class ScaleEstimator(stream.StreamKnobs):
 
     def _chunk_dev_host(self, f3s, f2s, frame_base, frame_ids, id_triples, stage):
         """The same kernels on the host's triangulations (SciPy's rows in canonical form): triangulation="scipy" with
-        sampling="device", and the frames the device triangulation declined.  Synchronous: the four steps below, one after the other."""
+        sampling="device", and the frames the device triangulation declined.  Synchronous: the steps below, one after the other (``_host_rows2`` takes the two in the middle)."""
         rec = self._host_begin(f3s, f2s, frame_base)
-        self._host_keep_start(rec)
-        self._host_tri2_start(rec)
         self._host_flat_start(rec, frame_base, frame_ids, id_triples, stage)
         return self._host_collect(rec, stage)
 
@@ -908,20 +909,34 @@ class ScaleEstimator(stream.StreamKnobs):
         rec["masks"] = [keep[pf.frame_slice(f)] >= 0 for f in range(pf.n_frames)]
         rec["h2"] = packing.submit_tri2(pf, rec["masks"], self.delaunay_workers, slot=slot, background=background)   # :134-137
 
-    def _host_flat_start(self, rec, frame_base, frame_ids, id_triples, stage):
+    def _host_rows2(self, rec):
+        """A record of ``_host_begin`` through the vote and the second triangulations — the steps a re-run that advances on its own
+        (``_rerun``) has taken already are not taken again —, their rows attached and on the device; returns the launches' ``max_tri``."""
+        if "h1" in rec:
+            self._host_keep_start(rec)
+        if "h2" not in rec:
+            self._host_tri2_start(rec)
         pf, db = rec["pf"], rec["db"]
         packing.attach_tri2(pf, rec.pop("h2"), rec["masks"], self.delaunay_workers)
         db.set_tri2(pf)
         db.n_rows2 = int(pf.tri2_off[-1])
-        max_tri = int(np.max(np.diff(pf.tri2_off))) if pf.n_frames else 0
-        rec["out"], rec["flags"], side = self._launch_flat_ransac(db, rec["aux"]["keep"].ptr, None, frame_base, frame_ids, id_triples, stage,
-                                                                  max(max_tri, 1), ctx=rec["ctx"], large=rec.get("large", False))
+        return max(int(np.max(np.diff(pf.tri2_off))) if pf.n_frames else 0, 1)
+
+    def _host_flat_start(self, rec, frame_base, frame_ids, id_triples, stage):
+        max_tri = self._host_rows2(rec)
+        rec["out"], rec["flags"], side = self._launch_flat_ransac(rec["db"], rec["aux"]["keep"].ptr, None, frame_base, frame_ids, id_triples,
+                                                                  stage, max_tri, ctx=rec["ctx"], large=rec.get("large", False))
         rec["side"] = side + [rec["aux"]]
+        return max_tri
+
+    @staticmethod
+    def _host_errors(pf):
+        """A host chunk's errors by frame: the second triangulations', and over them the first triangulations'."""
+        return {**pf.extra["tri2_errors"], **pf.extra["tri1_errors"]}
 
     def _host_collect(self, rec, stage):
         pf = rec["pf"]
-        host_errors = dict(pf.extra["tri2_errors"])
-        host_errors.update(pf.extra["tri1_errors"])
+        host_errors = self._host_errors(pf)
         res = self._collect(rec["out"], pf.n_frames)
         st = {"pf": pf, "db": rec["db"], "out": rec["out"], "flags": rec["flags"], "side": rec["side"], "host_errors": host_errors, "keep": rec["keep"]}
         if stage:
@@ -1202,39 +1217,66 @@ class ScaleEstimator(stream.StreamKnobs):
         flat selection refuses as a whole (singular row, bad vertex id, no rows) is refused for every case here."""
         for k in out.views:
             res["case_" + k] = out[k].download()
-        bad = np.isin(res["status"], (K.ST_ERR_SINGULAR, K.ST_ERR_MASK, K.ST_ERR_EMPTY))
-        if bad.any():
-            res["case_status"][bad] = res["status"][bad][:, None]
-            res["case_raw_scale"][bad] = np.nan
-            res["case_model"][bad] = np.nan
-            res["case_best_ic"][bad] = 0
-            res["case_used"][bad] = 0
-            res["case_count_form"][bad] = 0
+        case = lambda *keys: [res["case_" + k] for k in keys]
+        ScaleEstimator._merge_refused(res["status"], case("raw_scale", "model"), case("best_ic", "used", "count_form"), case("status"))
         return res
+
+    @staticmethod
+    def _merge_refused(status, nan=(), zero=(), take=()):
+        """The frames whose ``status`` refuses them as a whole, in case arrays with the frames on their first axis: NaN in those of
+        ``nan``, 0 in those of ``zero``, the frame's status in every case of those of ``take``."""
+        bad = np.isin(status, _REFUSED)
+        if bad.any():
+            for a in nan:
+                a[bad] = np.nan
+            for a in zero:
+                a[bad] = 0
+            for a in take:
+                a[bad] = status[bad].reshape((-1,) + (1,) * (a.ndim - 1))
 
     def _cases_host(self, f3s, f2s, seeds, frame_base, frame_ids, id_triples, opts):
         """One chunk of the cases path on the host's triangulations: triangulation="scipy" with sampling="device", and the frames
         both device triangulations declined (``frame_ids``: their own sample counters)."""
         rec = self._host_begin(f3s, f2s, frame_base)
-        cases = None
         try:
-            self._host_keep_start(rec)
-            self._host_tri2_start(rec)
-            self._host_flat_start(rec, frame_base, frame_ids, None, True)
-            pf = rec["pf"]
-            max_tri = max(int(np.max(np.diff(pf.tri2_off))) if pf.n_frames else 0, 1)
+            max_tri = self._host_flat_start(rec, frame_base, frame_ids, None, True)
             cases, side = self._launch_cases(rec["db"], rec["aux"]["keep"].ptr, None, rec["flags"]["tri_flags"].ptr, seeds, frame_base,
                                              frame_ids, id_triples, max_tri, opts, ctx=rec["ctx"])
-            rec["side"] = rec["side"] + [side]
-            host_errors = dict(pf.extra["tri2_errors"])
-            host_errors.update(pf.extra["tri1_errors"])
-            res = self._collect_cases(self._collect(rec["out"], pf.n_frames), cases)
-            res["host_errors"] = host_errors
+            rec["side"] += [side, cases]
+            res = self._collect_cases(self._collect(rec["out"], rec["pf"].n_frames), cases)
+            res["host_errors"] = self._host_errors(rec["pf"])
             return res
         finally:
-            if cases is not None:
-                cases.free()
+            stream.wait_out(rec.get("h1"), rec.get("h2"))     # (a pool job must not write into a freed slot)
             stream.free_blocks(rec)
+
+    def _rerun_declined(self, res, s1, s2, f3s, f2s, host_chunk):
+        """The frames of a chunk that a device triangulation declined (``s1``, ``s2``: their statuses) through the host's, counted in
+        ``last_declined``: ``host_chunk(f3s, f2s, redo)`` runs them — ``redo``: their positions in the chunk, for their own sample
+        counters — and its results, errors included, are scattered into the chunk's ``res``."""
+        res["host_errors"] = {}
+        redo = np.nonzero((s1 != 0) | (s2 != 0))[0]
+        self.last_declined += len(redo)
+        if len(redo):
+            sub = host_chunk([f3s[f] for f in redo], [f2s[f] for f in redo], redo)
+            stream.scatter(res, redo, sub, [k for k in sub if k != "host_errors"], "host_errors")
+        return res
+
+    def _cases_chunks(self, f3s, f2s, fields, start, finish):
+        """The chunk pipeline of the repeated runs and of ``ConstantSweep``: an oversized frame refused up front, then chunks of one
+        size through ``stream.run`` — with triangulation="gpu" ``start(a, b)`` packs, uploads and launches a chunk before
+        ``finish(state, a, b)`` waits for the results of the one before it; else ``finish`` gets ``{"gpu": False}`` and runs the chunk on
+        the host's triangulations.  Returns the chunks' ``fields`` concatenated and ``host_errors`` keyed by frame of the call."""
+        over = self._first_oversized(f2s, [len(x) for x in f2s], 0)
+        if over is not None:
+            raise self._oversized_error(*over)
+        self.last_declined = 0
+        F, gpu = len(f3s), self.triangulation == "gpu"
+        step = stream.chunk_size(F, self.GPU_CHUNK, self.GPU_MIN_CHUNK, self.GPU_CHUNK_POINTS, [len(x) for x in f3s[:64]])[0] if gpu else 2048
+        bounds, _, results = stream.run(stream.fixed_plan(F, step), lambda a, b, tables, k: start(a, b) if gpu else {"gpu": False},
+                                        lambda st, a, b, last: finish(st, a, b), int(gpu), stream.free_blocks, [], lambda: None)
+        cat, host_errors = stream.concat(bounds, results, fields, "host_errors")
+        return dict(zip(fields, cat), host_errors=host_errors)
 
     def _cases_gpu_start(self, f3s, f2s, seeds, frame_base, id_triples, opts):
         st = self._chunk_dev_gpu(f3s, f2s, frame_base, None, True)
@@ -1244,7 +1286,7 @@ class ScaleEstimator(stream.StreamKnobs):
                 db.mark(False)
                 st["cases"], side = self._launch_cases(db, db.bufs["vote_counters"].ptr, db.bufs["dt2_status"].ptr, st["flags"]["tri_flags"].ptr,
                                                        seeds, frame_base, None, id_triples, 2 * int(db.max_feat), opts)
-                st["side"] = st["side"] + [side]
+                st["side"] += [side, st["cases"]]        # (the state's blocks: stream.free_blocks releases them with the rest)
                 db.mark()
             except Exception:
                 stream.free_blocks(st)
@@ -1254,25 +1296,11 @@ class ScaleEstimator(stream.StreamKnobs):
     def _cases_gpu_finish(self, st, f3s, f2s, seeds, frame_base, id_triples, opts):
         if not st["gpu"]:
             return self._cases_host(f3s, f2s, seeds, frame_base, None, id_triples, opts)
-        try:
-            res = self._collect_cases(self._collect(st["out"], len(f3s)), st["cases"])
-            s1, s2 = st["db"].triangulation_status()
-        finally:
-            if st.get("cases") is not None:
-                st.pop("cases").free()
-            stream.free_blocks(st)
-        res["host_errors"] = {}
-        redo = np.nonzero((s1 != 0) | (s2 != 0))[0]
-        self.last_declined += len(redo)
-        if len(redo):                                # both device triangulations declined: the host's, with the frames' own counters
-            sub = self._cases_host([f3s[f] for f in redo], [f2s[f] for f in redo], seeds, 0, frame_base + redo,
-                                   None if id_triples is None else [id_triples[f] for f in redo], opts)
-            for k, v in sub.items():
-                if k != "host_errors":
-                    res[k][redo] = v
-            for j, e in sub["host_errors"].items():
-                res["host_errors"][int(redo[j])] = e
-        return res
+        res = self._collect_cases(self._collect(st["out"], len(f3s)), st["cases"])
+        s1, s2 = st["db"].triangulation_status()
+        stream.free_blocks(st)                       # (the results are on the host; when a step above raises, stream.run frees the state)
+        return self._rerun_declined(res, s1, s2, f3s, f2s, lambda g3, g2, redo: self._cases_host(
+            g3, g2, seeds, 0, frame_base + redo, None if id_triples is None else [id_triples[f] for f in redo], opts))
 
     def raw_scale_cases_batch(self, feature3ds, feature2ds, seeds, frame_base=0, id_triples=None, cases_per_group=0, hyp_counts=False):
         """The per-frame half for ``C = len(seeds)`` sample sequences of the same frames at once (no cross-frame state touched): both
@@ -1298,42 +1326,14 @@ class ScaleEstimator(stream.StreamKnobs):
                  "n_kept": np.zeros(0, np.int32), "frame_status": np.zeros(0, np.int32), "count_form": np.zeros(0, np.int32), "host_errors": {}}
         if F == 0:
             return empty
-        over = self._first_oversized(feature2ds, [len(x) for x in feature2ds], 0)
-        if over is not None:
-            raise self._oversized_error(*over)
         base = self._frame_counter + int(frame_base)
-        self.last_declined = 0
-        triples = (lambda a, b: None) if id_triples is None else (lambda a, b: id_triples[a:b])
-        gpu = self.triangulation == "gpu"
-        step = stream.chunk_size(F, self.GPU_CHUNK, self.GPU_MIN_CHUNK, self.GPU_CHUNK_POINTS, [len(x) for x in feature3ds[:64]])[0] if gpu else 2048
-        bounds = [(a, min(F, a + step)) for a in range(0, F, step)]
-        results, pending = [], None
-        try:
-            for a, b in bounds:
-                if gpu:
-                    st = self._cases_gpu_start(feature3ds[a:b], feature2ds[a:b], seeds, base + a, triples(a, b), opts)
-                    if pending is not None:
-                        pa, pb, pst = pending
-                        pending = None
-                        results.append(self._cases_gpu_finish(pst, feature3ds[pa:pb], feature2ds[pa:pb], seeds, base + pa, triples(pa, pb), opts))
-                    pending = (a, b, st)
-                else:
-                    results.append(self._cases_host(feature3ds[a:b], feature2ds[a:b], seeds, base + a, None, triples(a, b), opts))
-            if pending is not None:
-                pa, pb, pst = pending
-                pending = None
-                results.append(self._cases_gpu_finish(pst, feature3ds[pa:pb], feature2ds[pa:pb], seeds, base + pa, triples(pa, pb), opts))
-        finally:
-            if pending is not None:
-                if pending[2].get("cases") is not None:
-                    pending[2].pop("cases").free()
-                stream.free_blocks(pending[2])
-        cat = lambda k: np.concatenate([r[k] for r in results])
-        out = {k: np.ascontiguousarray(np.moveaxis(cat("case_" + k), 1, 0)) for k in self._CASE_FIELDS}
-        if hyp_counts:
-            out["hyp_counts"] = np.ascontiguousarray(np.moveaxis(cat("case_hyp_counts"), 1, 0))
-        out.update(height_level=cat("height_level"), n_kept=cat("n_kept"), frame_status=cat("status"), count_form=cat("case_count_form"))
-        out["host_errors"] = {a + int(f): e for (a, b), r in zip(bounds, results) for f, e in r["host_errors"].items()}
+        chunk = lambda a, b: (feature3ds[a:b], feature2ds[a:b], seeds, base + a, None if id_triples is None else id_triples[a:b], opts)
+        cases = self._CASE_FIELDS + (("hyp_counts",) if hyp_counts else ())
+        r = self._cases_chunks(feature3ds, feature2ds, ["case_" + k for k in cases] + ["height_level", "n_kept", "status", "case_count_form"],
+                               lambda a, b: self._cases_gpu_start(*chunk(a, b)), lambda st, a, b: self._cases_gpu_finish(st, *chunk(a, b)))
+        out = {k: np.ascontiguousarray(np.moveaxis(r["case_" + k], 1, 0)) for k in cases}
+        out.update(height_level=r["height_level"], n_kept=r["n_kept"], frame_status=r["status"], count_form=r["case_count_form"],
+                   host_errors=r["host_errors"])
         return out
 
     def push_raw_scales(self, raw, status, level=None, host_errors=None):
@@ -1351,7 +1351,7 @@ class ScaleEstimator(stream.StreamKnobs):
         at which the reference raises; then that frame's exception, as ``_push_device`` raises it.  No slew limiter, no window:
         ``scale_queue`` is not touched.  Returns ``(scales, zeros)``."""
         F = len(raw)
-        bad = np.isin(status, (K.ST_ERR_SINGULAR, K.ST_ERR_MASK, K.ST_ERR_EMPTY))
+        bad = np.isin(status, _REFUSED)
         for f in host_errors:
             bad[f] = True
         n_ok = int(np.argmax(bad)) if bad.any() else F
@@ -1373,7 +1373,7 @@ class ScaleEstimator(stream.StreamKnobs):
         """The cross-frame tail (rescale.py:169-178) on the device over the frames before the first one at which the
         reference raises; then that frame's exception."""
         F = len(raw)
-        bad = np.isin(status, (K.ST_ERR_SINGULAR, K.ST_ERR_MASK, K.ST_ERR_EMPTY))
+        bad = np.isin(status, _REFUSED)
         for f in host_errors:
             bad[f] = True
         n_ok = int(np.argmax(bad)) if bad.any() else F
@@ -1752,39 +1752,36 @@ class ConstantSweep:
         return [RescaleConstants(**dict(zip(names, combo))) for combo in itertools.product(*values)]
 
     # ---- a chunk: the launches behind the second triangulation ---------------------------------------------------------------
-    def _launch(self, db, keep_ptr, dt2_ptr, rows, max_tri, frame_base, frame_ids, ctx=None):
+    def _launch(self, st, keep_ptr, dt2_ptr, max_tri, frame_base, frame_ids, ctx=None):
         """mvosr_flat_selection_sweep_batch over the distinct selections (16 a launch), then mvosr_flat_ransac_cases_batch once
-        per distinct pair on its selection's plane; the outputs' downloads queued.  ``rows``: rows of a flag plane."""
-        est = self.estimator
+        per distinct pair on its selection's plane; the outputs' downloads queued.  Every block joins the state's ``side`` list the
+        moment it exists (``stream.free_blocks`` releases them); ``st["launch"]`` names the outputs for ``_collect``."""
+        est, db = self.estimator, st["db"]
         ctx, F, S = ctx or est.ctx, db.n_frames, len(self._sels)
-        stride = max(int(rows), 1)
+        stride = max(int(db.n_rows2), 1)                             # rows of a flag plane
         flags = ctx.block([("tri_flags", (S, stride), np.uint8)])
-        blocks, groups, cases = [flags], [], []
+        side = st["side"] = [flags]
+        groups, cases = [], []
         b = db.struct()
-        try:
-            for g0 in range(0, S, self.max_settings):
-                sel = self._sels[g0:g0 + self.max_settings]
-                out = ctx.block([("height_level", (F, len(sel)), np.float64), ("n_kept", (F, len(sel)), np.int32), ("status", F, np.int32)])
-                blocks.append(out)
-                loose, tight, factor = (np.array([x[i] for x in sel], dtype=np.float64) for i in range(3))
-                _lib.check(ctx.lib.mvosr_flat_selection_sweep_batch(ctx.handle, C.byref(b), keep_ptr, dt2_ptr, len(sel), _lib.addr(loose),
-                                                                    _lib.addr(tight), _lib.addr(factor), flags["tri_flags"].ptr + g0 * stride,
-                                                                    out["height_level"].ptr, out["n_kept"].ptr, out["status"].ptr, None,
-                                                                    int(max_tri)), "mvosr_flat_selection_sweep_batch")
-                self.launches["sweep"] += 1
-                out.prefetch()
-                groups.append(out)
-            for (si, _), k in zip(self._pairs, self._pair_constants):
-                out, side = est._launch_cases(db, keep_ptr, dt2_ptr, flags["tri_flags"].ptr + si * stride, self.seeds, frame_base, frame_ids,
-                                              None, max_tri, {"constants": k}, ctx=ctx)
-                self.launches["cases"] += 1
-                blocks += [out, side]
-                cases.append(out)
-        except Exception:
-            for blk in blocks:
-                blk.free()
-            raise
-        return {"groups": groups, "cases": cases, "blocks": blocks}
+        for g0 in range(0, S, self.max_settings):
+            sel = self._sels[g0:g0 + self.max_settings]
+            out = ctx.block([("height_level", (F, len(sel)), np.float64), ("n_kept", (F, len(sel)), np.int32), ("status", F, np.int32)])
+            side.append(out)
+            loose, tight, factor = (np.array([x[i] for x in sel], dtype=np.float64) for i in range(3))
+            _lib.check(ctx.lib.mvosr_flat_selection_sweep_batch(ctx.handle, C.byref(b), keep_ptr, dt2_ptr, len(sel), _lib.addr(loose),
+                                                                _lib.addr(tight), _lib.addr(factor), flags["tri_flags"].ptr + g0 * stride,
+                                                                out["height_level"].ptr, out["n_kept"].ptr, out["status"].ptr, None,
+                                                                int(max_tri)), "mvosr_flat_selection_sweep_batch")
+            self.launches["sweep"] += 1
+            out.prefetch()
+            groups.append(out)
+        for (si, _), k in zip(self._pairs, self._pair_constants):
+            out, inputs = est._launch_cases(db, keep_ptr, dt2_ptr, flags["tri_flags"].ptr + si * stride, self.seeds, frame_base, frame_ids,
+                                           None, max_tri, {"constants": k}, ctx=ctx)
+            self.launches["cases"] += 1
+            side += [out, inputs]
+            cases.append(out)
+        st["launch"] = {"groups": groups, "cases": cases}
 
     @staticmethod
     def _collect(lp):
@@ -1796,10 +1793,7 @@ class ConstantSweep:
                "n_kept": np.concatenate([g["n_kept"].download() for g in groups], axis=1),
                "case_raw_scale": np.stack([c["raw_scale"].download() for c in cases], axis=1),          # (F, P, C)
                "case_status": np.stack([c["status"].download() for c in cases], axis=1)}
-        bad = np.isin(res["status"], (K.ST_ERR_SINGULAR, K.ST_ERR_MASK, K.ST_ERR_EMPTY))
-        if bad.any():
-            res["case_status"][bad] = res["status"][bad][:, None, None]
-            res["case_raw_scale"][bad] = np.nan
+        ScaleEstimator._merge_refused(res["status"], nan=[res["case_raw_scale"]], take=[res["case_status"]])
         return res
 
     def _chunk_host(self, f3s, f2s, frame_base, frame_ids):
@@ -1807,34 +1801,22 @@ class ConstantSweep:
         triangulations declined (``frame_ids``: their own sample counters)."""
         est = self.estimator
         rec = est._host_begin(f3s, f2s, frame_base)
-        lp = None
         try:
-            est._host_keep_start(rec)
-            est._host_tri2_start(rec)
-            pf, db = rec["pf"], rec["db"]
-            packing.attach_tri2(pf, rec.pop("h2"), rec["masks"], est.delaunay_workers)
-            db.set_tri2(pf)
-            db.n_rows2 = int(pf.tri2_off[-1])
-            max_tri = max(int(np.max(np.diff(pf.tri2_off))) if pf.n_frames else 0, 1)
-            lp = self._launch(db, rec["aux"]["keep"].ptr, None, db.n_rows2, max_tri, frame_base, frame_ids, ctx=rec["ctx"])
-            res = self._collect(lp)
-            res["host_errors"] = dict(pf.extra["tri2_errors"])
-            res["host_errors"].update(pf.extra["tri1_errors"])
+            max_tri = est._host_rows2(rec)
+            self._launch(rec, rec["aux"]["keep"].ptr, None, max_tri, frame_base, frame_ids, ctx=rec["ctx"])
+            res = self._collect(rec["launch"])
+            res["host_errors"] = est._host_errors(rec["pf"])
             return res
         finally:
-            for blk in (lp["blocks"] if lp else ()):
-                blk.free()
             stream.wait_out(rec.get("h1"), rec.get("h2"))
             stream.free_blocks(rec)
 
     def _gpu_start(self, f3s, f2s, frame_base):
-        est = self.estimator
-        st = est._chunk_dev_front(f3s, f2s, frame_base)
+        st = self.estimator._chunk_dev_front(f3s, f2s, frame_base)
         if st["gpu"]:
             db = st["db"]
             try:
-                st["launch"] = self._launch(db, db.bufs["vote_counters"].ptr, db.bufs["dt2_status"].ptr, db.n_rows2, 2 * int(db.max_feat),
-                                            frame_base, None)
+                self._launch(st, db.bufs["vote_counters"].ptr, db.bufs["dt2_status"].ptr, 2 * int(db.max_feat), frame_base, None)
                 db.prefetch_info()
                 db.mark()
             except Exception:
@@ -1842,33 +1824,14 @@ class ConstantSweep:
                 raise
         return st
 
-    @staticmethod
-    def _free(st):
-        if st.get("launch") is not None:
-            for blk in st.pop("launch")["blocks"]:
-                blk.free()
-        stream.free_blocks(st)
-
     def _gpu_finish(self, st, f3s, f2s, frame_base):
-        est = self.estimator
         if not st["gpu"]:
             return self._chunk_host(f3s, f2s, frame_base, None)
-        try:
-            res = self._collect(st["launch"])
-            s1, s2 = st["db"].triangulation_status()
-        finally:
-            self._free(st)
-        res["host_errors"] = {}
-        redo = np.nonzero((s1 != 0) | (s2 != 0))[0]
-        est.last_declined += len(redo)
-        if len(redo):                                    # both device triangulations declined: the host's, with the frames' own counters
-            sub = self._chunk_host([f3s[f] for f in redo], [f2s[f] for f in redo], 0, frame_base + redo)
-            for k, v in sub.items():
-                if k != "host_errors":
-                    res[k][redo] = v
-            for j, e in sub["host_errors"].items():
-                res["host_errors"][int(redo[j])] = e
-        return res
+        res = self._collect(st["launch"])
+        s1, s2 = st["db"].triangulation_status()
+        stream.free_blocks(st)                           # (the results are on the host; when a step above raises, stream.run frees the state)
+        # both device triangulations declined: the host's, with the frames' own counters
+        return self.estimator._rerun_declined(res, s1, s2, f3s, f2s, lambda g3, g2, redo: self._chunk_host(g3, g2, 0, frame_base + redo))
 
     def _raw_cases(self, f3, f2):
         """The per-frame half for every pair and case (no cross-frame state touched): ``raw_scale`` / ``status`` ``(P, C, F)``,
@@ -1879,39 +1842,14 @@ class ConstantSweep:
         if F == 0:
             return {"raw_scale": np.zeros((P, Cn, 0)), "status": np.zeros((P, Cn, 0), np.int32), "height_level": np.zeros((S, 0)),
                     "n_kept": np.zeros((S, 0), np.int32), "frame_status": np.zeros(0, np.int32), "host_errors": {}}
-        over = est._first_oversized(f2, [len(x) for x in f2], 0)
-        if over is not None:
-            raise est._oversized_error(*over)
         base = est._frame_counter
-        est.last_declined = 0
-        gpu = est.triangulation == "gpu"
-        step = stream.chunk_size(F, est.GPU_CHUNK, est.GPU_MIN_CHUNK, est.GPU_CHUNK_POINTS, [len(x) for x in f3[:64]])[0] if gpu else 2048
-        bounds = [(a, min(F, a + step)) for a in range(0, F, step)]
-        results, pending = [], None
-        try:
-            for a, b in bounds:
-                if gpu:
-                    st = self._gpu_start(f3[a:b], f2[a:b], base + a)
-                    if pending is not None:
-                        pa, pb, pst = pending
-                        pending = None
-                        results.append(self._gpu_finish(pst, f3[pa:pb], f2[pa:pb], base + pa))
-                    pending = (a, b, st)
-                else:
-                    results.append(self._chunk_host(f3[a:b], f2[a:b], base + a, None))
-            if pending is not None:
-                pa, pb, pst = pending
-                pending = None
-                results.append(self._gpu_finish(pst, f3[pa:pb], f2[pa:pb], base + pa))
-        finally:
-            if pending is not None:
-                self._free(pending[2])
-        cat = lambda k: np.concatenate([r[k] for r in results])
-        return {"raw_scale": np.ascontiguousarray(np.moveaxis(cat("case_raw_scale"), 0, 2)),
-                "status": np.ascontiguousarray(np.moveaxis(cat("case_status"), 0, 2)),
-                "height_level": np.ascontiguousarray(cat("height_level").T), "n_kept": np.ascontiguousarray(cat("n_kept").T),
-                "frame_status": cat("status"),
-                "host_errors": {a + int(f): e for (a, b), r in zip(bounds, results) for f, e in r["host_errors"].items()}}
+        chunk = lambda a, b: (f3[a:b], f2[a:b], base + a)
+        r = est._cases_chunks(f3, f2, ["case_raw_scale", "case_status", "height_level", "n_kept", "status"],
+                              lambda a, b: self._gpu_start(*chunk(a, b)), lambda st, a, b: self._gpu_finish(st, *chunk(a, b)))
+        return {"raw_scale": np.ascontiguousarray(np.moveaxis(r["case_raw_scale"], 0, 2)),
+                "status": np.ascontiguousarray(np.moveaxis(r["case_status"], 0, 2)),
+                "height_level": np.ascontiguousarray(r["height_level"].T), "n_kept": np.ascontiguousarray(r["n_kept"].T),
+                "frame_status": r["status"], "host_errors": r["host_errors"]}
 
     # ---- the sequence -----------------------------------------------------------------------------------------------------------
     def run(self, data, minimum_feature_for_scale=None):

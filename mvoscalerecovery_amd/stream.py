@@ -1,7 +1,7 @@
 """The streamed-chunk path both estimators share (scale_calculator.ScaleEstimator, rescale.ScaleEstimator): a batch goes through the
 device in chunks, each packed, uploaded and launched while the chunks before it run, and collected a few chunks later.
 
-``plan`` cuts a call into chunks, ``run`` keeps them in flight, and ``Rerun`` records carry the frames a chunk's device triangulation
+``plan`` cuts a call into chunks (``fixed_plan``: into equal ones), ``run`` keeps them in flight, and ``Rerun`` records carry the frames a chunk's device triangulation
 declined through the host's triangulations while later chunks run (``advance``), to be finished after the call's last chunk
 (``finish_all``).  What differs between the estimators comes in as values and callables."""
 import contextlib
@@ -93,6 +93,12 @@ def plan(F, tables_of, C, ramp, points, resident, stop=None):
             b = a + ((b - a) // res) * res
         yield a, b, (tuple(t[:b - a] for t in tb) if tb is not None else None)
         a, k = b, k + 1
+
+
+def fixed_plan(F, step):
+    """``plan`` without a look at the frames: chunks of ``step`` frames, no packer's tables."""
+    for a in range(0, F, step):
+        yield a, min(F, a + step), None
 
 
 def tables_of(feature3ds, feature2ds, **kw):

@@ -9,7 +9,9 @@ Everything here is integer or bit equality, no case left out of a comparison:
 * one frame of ~1800 features / ~3600 rows (wavefront and histogram-pass boundaries);
 * end to end on the golden sequence: ConstantSweep.run equals K separate RepeatedRuns(constants=...) runs in both device-sampling
   modes and over two calls; ScaleEstimator(constants=..., sampler=recorded) reproduces the patched reference's golden outputs;
-  scores / scale_scores equal the per-config ones.
+  scores / scale_scores equal the per-config ones;
+* the chunk pipeline: the sweep over four chunks with a declined frame in the first and the last equals the one-chunk run, and an
+  error in the middle of a call of the sweep or of the repeated runs leaves no device block alive.
 """
 import dataclasses
 
@@ -19,6 +21,7 @@ import pytest
 import flat_cases as fc
 import sweep_cases as sw
 from conftest import load_npz
+from gpu_helpers import _declining
 
 pytestmark = pytest.mark.gpu
 SEEDS = [11, 2 ** 63 + 5, 977]
@@ -314,3 +317,83 @@ def test_a_frame_at_which_the_reference_raises(gpu, mode):
     assert sweep.estimator._frame_counter == rr.estimator._frame_counter == 8 and sweep.scales().shape[2] == rr.scales().shape[1] == 0
     for c in range(3):
         assert sweep.tails[2][c].scale == rr.tails[c].scale and list(sweep.tails[2][c].scale_queue) == list(rr.tails[c].scale_queue)
+
+
+# ---- the chunk pipeline: several chunks, declined frames, an error mid-call ------------------------------------------------------------
+def _short_sequence(n, declined=()):
+    """``n`` processed frames of 120-300 features, the frames ``declined`` replaced by ones both device triangulations decline."""
+    from mvoscalerecovery_amd import synth
+    data = synth.synth_sequence_dict(n, base_seed=67, n_lo=120, n_hi=300, p_not_moving=0.0, p_too_few=0.0)
+    frames = _declining(list(zip(data["feature3ds"], data["feature2ds"])), declined)
+    data["feature3ds"], data["feature2ds"] = [f[0] for f in frames], [f[1] for f in frames]
+    return data
+
+
+@pytest.mark.parametrize("mode", list(MODES))
+def test_sweep_over_several_chunks_with_declined_frames(gpu, mode):
+    """One chunk against chunks of 4 frames, a declined frame in the first chunk and one in the last: the same bits, the declined
+    frames re-run once per chunk that holds one, and one set of launches per chunk and per re-run."""
+    from mvoscalerecovery_amd.rescale import ConstantSweep, RescaleConstants
+    F, step, declined = 14, 4, [1, 13]
+    data = _short_sequence(F, declined)
+    configs = [RescaleConstants(), RescaleConstants(loose_deg=-75.0)]
+    runs = []
+    for chunk in (None, step):
+        sweep = ConstantSweep(sw.ABS_REF, configs, window_size=sw.WINDOW, seeds=SEEDS[:2], delaunay_workers=0, **MODES[mode])
+        if chunk is not None:
+            sweep.estimator.GPU_CHUNK = sweep.estimator.GPU_MIN_CHUNK = chunk
+        runs.append((sweep, sweep.run(data)))
+    (one, want), (chunked, got) = runs
+    assert got["raw_scale"].shape == (2, 2, F) and len(chunked._sels) == 2 and len(chunked._pairs) == 2
+    for key in ("scales", "error", "raw_scale", "status"):
+        assert _same(got[key], want[key]), (mode, key)
+    assert not _same(got["raw_scale"][0], got["raw_scale"][1])       # the selection constant bites on these frames
+    if mode == "gpu":
+        assert one.estimator.last_declined == chunked.estimator.last_declined == 2
+        bounds = [(a, min(F, a + step)) for a in range(0, F, step)]
+        launched = len(bounds) + len({k for k, (a, b) in enumerate(bounds) for f in declined if a <= f < b})
+        assert (len(bounds), launched) == (4, 6)
+    else:
+        launched = 1                                                 # the host's triangulations: chunks of 2048 frames, nothing to re-run
+    assert chunked.launches == {"sweep": launched, "cases": len(chunked._pairs) * launched}
+    assert one.launches == {"sweep": 1 + (mode == "gpu"), "cases": 2 * (1 + (mode == "gpu"))}
+
+
+@pytest.mark.parametrize("pipeline", ["repeats", "sweep"])
+def test_error_mid_call_releases_every_block(gpu, pipeline, monkeypatch):
+    """``_launch_cases`` raises on its third call, while a chunk is being started and the chunk before it is queued: the exception
+    leaves the call, no device block of the call stays alive, and the estimator's next call equals a fresh estimator's."""
+    from mvoscalerecovery_amd.rescale import ConstantSweep, RescaleConstants, ScaleEstimator
+    data = _short_sequence(12)
+    f3s, f2s = data["feature3ds"], data["feature2ds"]
+
+    def make():
+        if pipeline == "sweep":
+            sweep = ConstantSweep(sw.ABS_REF, [RescaleConstants(), RescaleConstants(loose_deg=-75.0)], window_size=sw.WINDOW, seeds=SEEDS[:2],
+                                  triangulation="gpu", delaunay_workers=0)
+            est, call = sweep.estimator, lambda: sweep._raw_cases(f3s, f2s)
+        else:
+            est = ScaleEstimator(sw.ABS_REF, window_size=sw.WINDOW, ransac_seed=0, triangulation="gpu", delaunay_workers=0)
+            call = lambda: est.raw_scale_cases_batch(f3s, f2s, SEEDS[:2])
+        est.GPU_CHUNK = est.GPU_MIN_CHUNK = 4
+        return est, call
+    est, call = make()
+    call()                                                           # (the estimator's context has its caches from here on)
+    before = est.ctx.alloc_stats()["live_blocks"]
+    real, calls = est._launch_cases, [0]
+
+    def failing(*a, **k):
+        calls[0] += 1
+        if calls[0] == 3:
+            raise RuntimeError("launch failed")
+        return real(*a, **k)
+    monkeypatch.setattr(est, "_launch_cases", failing)
+    with pytest.raises(RuntimeError, match="launch failed"):
+        call()
+    monkeypatch.undo()
+    assert calls[0] == 3 and est.ctx.alloc_stats()["live_blocks"] == before
+    got, want = call(), make()[1]()
+    assert set(got) == set(want) and sorted(got["host_errors"]) == sorted(want["host_errors"]) == []
+    for key in want:
+        if key != "host_errors":
+            assert _same(got[key], want[key]), key
