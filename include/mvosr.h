@@ -38,7 +38,8 @@ extern "C" {
 /* (mvosr_point_cloud_batch and its three structs were added WITHOUT raising this number: the change is purely additive —
  * no existing struct or signature moved — and a binding resolves every symbol it declares when it loads the library, so a
  * library older than its binding fails loudly at load time anyway.  mvosr_height_pitch_batch, its two structs and
- * mvosr_height_pitch_lds_bytes were added the same way.) */
+ * mvosr_height_pitch_lds_bytes were added the same way, and so were mvosr_height_pitch_tail_batch, its two records and its two
+ * size functions.) */
 
 /* error codes (function return values) */
 enum mvosr_err {
@@ -1157,6 +1158,64 @@ typedef struct mvosr_height_pitch_outputs {
 int mvosr_height_pitch_batch(mvosr_ctx *ctx, const mvosr_batch *b, const mvosr_height_pitch_params *p, const double *frame_prior,
                              const int32_t *triples, const mvosr_height_pitch_outputs *o);
 size_t mvosr_height_pitch_lds_bytes(int max_feat, int n_hyp);
+
+/* ---- the estimator's frame-to-frame carry (calculate_height_pitch.py:140, :163-167, :202-203) for a chunk of frames ---------- */
+
+/* one frame of a chunk, as the script's lists take it (56 bytes) */
+typedef struct mvosr_height_pitch_tail_frame {
+    double ransac_height, refined_mean, refined_std, height_t_mean, refined_pitch;
+    int32_t n_inliers;           /* with the five doubles: the six values of the script's result files */
+    int32_t n_selected;          /* the frame's own list length */
+    int32_t carried;             /* 1: fewer than min_points list points, the values are the previous frame's (:163-165) */
+    int32_t source;              /* the last fitted frame of the chunk at or before this one; -1: none, the carry-in's */
+} mvosr_height_pitch_tail_frame;
+
+/* the header of a carry record (64 bytes); behind it, at the offsets mvosr_height_pitch_carry_bytes' layout gives for the
+ * record's capacity `cap` rounded up to even: y[cap] at 64, z[cap] at 64 + 8 cap (doubles), index[cap] at 64 + 16 cap (int32) —
+ * the back-projected Y and Z (:68, :66) and the feature indices of the last fitted frame's inliers, in feature order */
+typedef struct mvosr_height_pitch_carry {
+    double ransac_height, refined_mean, refined_std, height_t_mean, refined_pitch;
+    int32_t n_inliers;           /* ... the previous frame's six values (its height_t_mean enters no result) */
+    int32_t has_prev;            /* 0: no frame yet — a carried frame raises (:167) */
+    int32_t count;               /* entries of y, z and index */
+    int32_t halted;              /* 1: a chunk before this one ended in an error; every later tail passes the record on untouched */
+    int64_t reserved;
+} mvosr_height_pitch_carry;
+
+enum mvosr_hpt_error {           /* the high half of the error word, in the host loop's order of precedence per frame */
+    MVOSR_HPT_ERR_SINGULAR = 1,  /* MVOSR_ST_ERR_SINGULAR: the script raises LinAlgError (:83) */
+    MVOSR_HPT_ERR_MASK = 2,      /* MVOSR_ST_ERR_MASK */
+    MVOSR_HPT_ERR_EMPTY = 3,     /* MVOSR_ST_ERR_EMPTY */
+    MVOSR_HPT_ERR_NO_MODEL = 4,  /* MVOSR_ST_RS_FEW with n_selected >= min_points: no sample of the RANSAC had an inlier */
+    MVOSR_HPT_ERR_NO_PREVIOUS = 5, /* a carried frame with no frame before it: the script's IndexError (:167) */
+    MVOSR_HPT_ERR_STATUS = 6,    /* a status the estimator does not know, or status 0 on a frame outside (0, max_feat] */
+    MVOSR_HPT_ERR_UPSTREAM = 7   /* the carry-in is halted (or its count exceeds carry_cap): no frame of this chunk is final */
+};
+
+/*
+ * The body of the estimator's host loop for one chunk of frames in sequence order, behind mvosr_height_pitch_batch on the
+ * context's stream: two launches (hpt_resolve_kernel: one workgroup; hpt_carry_kernel: n_frames + 1 workgroups), no host
+ * synchronisation.  b: n_frames, feat_off, feat_cnt, v, z (depth) and max_feat as mvosr_height_pitch_batch read them; p: focus,
+ * cy, min_points; frame_prior: the same [F][4]; o: that launch's outputs, the mask included (all device pointers).
+ *   A frame with status 0 is final as the kernel wrote it.  A frame with MVOSR_ST_RS_FEW and n_selected < min_points is CARRIED:
+ *   it copies ransac_height, refined_mean, refined_std, refined_pitch and n_inliers of the most recent frame before it (in the
+ *   chunk, or the carry-in's), keeps its own n_selected, and its height_t_mean is np.mean(Z sin + Y cos) over the inliers of the
+ *   most recent FITTED frame with its OWN prior's sin and cos (frame_prior[f][2..3]): Y = depth * (v - cy) / focus, the products and
+ *   the sum rounded separately, the terms in feature order, the sum in np.add.reduce's pairwise order, divided by the count — the
+ *   host's double to the last bit.
+ *   *error (int64): -1, or kind << 32 | the first frame at which the host must raise (an mvosr_hpt_error; per frame singular, mask /
+ *   empty, no model, then a carried frame with no previous).  Frames from that one on are not final.
+ *   carry_out: the state after the last frame before the error, or after the chunk's last frame — the next chunk's carry_in; halted
+ *   when the chunk had an error.  A halted carry_in is copied to carry_out, *error = MVOSR_HPT_ERR_UPSTREAM << 32, frames untouched.
+ * carry_in != carry_out, both mvosr_height_pitch_carry_bytes(carry_cap) bytes; max_feat <= carry_cap <= 8192 (one buffer of
+ * np.add.reduce), else MVOSR_ERR_ARG / MVOSR_ERR_TOO_LARGE.  LDS: mvosr_height_pitch_tail_lds_bytes(carry_cap) = 8 carry_cap +
+ * ~2.2 KB.  The results do not depend on how a sequence is cut into chunks.
+ */
+int mvosr_height_pitch_tail_batch(mvosr_ctx *ctx, const mvosr_batch *b, const mvosr_height_pitch_params *p, const double *frame_prior,
+                                  const mvosr_height_pitch_outputs *o, const void *carry_in, void *carry_out, int32_t carry_cap,
+                                  mvosr_height_pitch_tail_frame *frames, int64_t *error);
+size_t mvosr_height_pitch_tail_lds_bytes(int max_feat);
+size_t mvosr_height_pitch_carry_bytes(int carry_cap);
 
 /* ---- the RANSAC evaluation runs (/root/reference/src/calculate_height_pitch_eval.py, calculate_height_pitch_eval_line.py) ---- */
 

@@ -161,6 +161,24 @@ class HeightPitchOutputs(C.Structure):
                 ("mask", C.c_void_p), ("point_list", C.c_void_p), ("hyp_counts", C.c_void_p)]
 
 
+class HeightPitchTailFrame(C.Structure):
+    """mvosr_height_pitch_tail_frame"""
+    _fields_ = [("ransac_height", C.c_double), ("refined_mean", C.c_double), ("refined_std", C.c_double), ("height_t_mean", C.c_double),
+                ("refined_pitch", C.c_double), ("n_inliers", C.c_int32), ("n_selected", C.c_int32), ("carried", C.c_int32),
+                ("source", C.c_int32)]
+
+
+class HeightPitchCarry(C.Structure):
+    """mvosr_height_pitch_carry"""
+    _fields_ = [("ransac_height", C.c_double), ("refined_mean", C.c_double), ("refined_std", C.c_double), ("height_t_mean", C.c_double),
+                ("refined_pitch", C.c_double), ("n_inliers", C.c_int32), ("has_prev", C.c_int32), ("count", C.c_int32),
+                ("halted", C.c_int32), ("reserved", C.c_int64)]
+
+
+# enum mvosr_hpt_error
+HPT_ERR_SINGULAR, HPT_ERR_MASK, HPT_ERR_EMPTY, HPT_ERR_NO_MODEL, HPT_ERR_NO_PREVIOUS, HPT_ERR_STATUS, HPT_ERR_UPSTREAM = 1, 2, 3, 4, 5, 6, 7
+
+
 class HeightPitchEvalParams(C.Structure):
     """mvosr_height_pitch_eval_params"""
     _fields_ = HeightPitchParams._fields_ + [("model", C.c_int32), ("n_cases", C.c_int32), ("cases_per_group", C.c_int32)]
@@ -295,6 +313,10 @@ SYMBOLS = {
     "mvosr_plane_inliers": (C.c_int, [_P, C.c_int64, _P, _P, _P, _P, C.c_double, _P]),
     "mvosr_height_pitch_batch": (C.c_int, [_P, C.POINTER(Batch), C.POINTER(HeightPitchParams), _P, _P, C.POINTER(HeightPitchOutputs)]),
     "mvosr_height_pitch_lds_bytes": (C.c_size_t, [C.c_int, C.c_int]),
+    "mvosr_height_pitch_tail_batch": (C.c_int, [_P, C.POINTER(Batch), C.POINTER(HeightPitchParams), _P, C.POINTER(HeightPitchOutputs), _P, _P,
+                                                C.c_int32, _P, _P]),
+    "mvosr_height_pitch_tail_lds_bytes": (C.c_size_t, [C.c_int]),
+    "mvosr_height_pitch_carry_bytes": (C.c_size_t, [C.c_int]),
     "mvosr_height_pitch_eval_batch": (C.c_int, [_P, C.POINTER(Batch), C.POINTER(HeightPitchEvalParams), _P, _P,
                                                 C.POINTER(HeightPitchEvalOutputs)]),
     "mvosr_height_pitch_eval_lds_bytes": (C.c_size_t, [C.c_int, C.c_int, C.c_int]),

@@ -10,7 +10,7 @@
 //   unit 1 + k               window w: one lane per segment i = 0, step, 2 step .. < n - w takes np.sum(e[i : i + w]) — the pairwise
 //                            recursion over the slice's LENGTH, whatever its offset — then |.| / w, parks it, and the workgroup takes
 //                            np.mean of the parked list.  No segment: NaN, as np.mean([]).
-//   block_np_sum             np.add.reduce of a list in memory: per 8192-element chunk one thread per node of the recursion — the
+//   block_np_sum             (mvosr_npsum.hpp) np.add.reduce of a list in memory: per 8192-element chunk one thread per node of the recursion — the
 //                            leaves (<= 128 elements, np_leaf_sum) side by side, then the inner nodes level by level, each the sum
 //                            of its two halves — and the chunk added to the running total, left to right from 0.  No
 //                            floating-point atomics: the same bytes every run.
@@ -28,7 +28,7 @@
 namespace mvosr {
 
 static_assert(kSsMaxWindows == MVOSR_SCALE_MAX_WINDOWS && kSsMaxThresholds == MVOSR_SCALE_MAX_THRESHOLDS, "include/mvosr.h states the caps");
-static_assert(kSsMaxWindow <= kNpBufSize && kSsNodes == (1 << kNpDepth) && kSsNodes <= kSsBlock, "a window's sum; a chunk's recursion, one thread a node");
+static_assert(kSsMaxWindow <= kNpBufSize && kSsNodes == kNpNodes && kSsNodes <= kSsBlock, "a window's sum; a chunk's recursion, one thread a node");
 
 // The recursion of @TYPE@_pairwise_sum over n <= kNpBufSize elements in post-order: visit(lo, len, true) for a leaf (<= 128
 // elements), visit(lo, len, false) for an inner node once both halves — the first rounded down to a multiple of 8 — are done.
@@ -58,47 +58,6 @@ __device__ __forceinline__ double ss_slice_sum(const double *a, int n) {
         else { const double r = val[--vp], l = val[--vp]; val[vp++] = l + r; }
     });
     return val[0];
-}
-
-// The node with heap index h (the root is 0, the halves of node h are 2h + 1 and 2h + 2) of the recursion over m <= kNpBufSize
-// elements: its slice [lo, lo + len), or len = 0 where the tree has no such node (an ancestor is a leaf).  A slice at depth d
-// has at most m / 2^d + 15 elements, so the leaves lie at depth 7 at the latest: h < kSsNodes.
-__device__ __forceinline__ void ss_heap_node(int h, int m, int &lo, int &len) {
-    const int depth = 31 - __clz(h + 1);
-    lo = 0;
-    len = m;
-    for (int d = depth - 1; d >= 0; --d) {                      // the bits of h + 1 below the leading one: 0 the first half, 1 the second
-        if (len <= 128) { len = 0; return; }
-        int m2 = len / 2;
-        m2 -= m2 % 8;
-        if (((h + 1) >> d) & 1) { lo += m2; len -= m2; } else len = m2;
-    }
-}
-
-// np.add.reduce(a[0 : n]) by the workgroup; `node`: kSsNodes doubles of LDS, `slot`: one.  Workgroup-uniform call; what `a`
-// holds was written before a barrier.  Per chunk, thread h is node h of the recursion: the leaves are summed side by side, then
-// every inner node adds its two halves, the deepest first — the recursion's own additions, none of them in another order.
-__device__ __forceinline__ double block_np_sum(const double *a, int64_t n, double *node, double *slot) {
-    const int t = threadIdx.x;
-    const int depth = 31 - __clz(t + 1);
-    if (t == 0) *slot = 0.0;                                     // the reduction starts from add's identity
-    __syncthreads();
-    for (int64_t c0 = 0; c0 < n; c0 += kNpBufSize) {
-        const int m = (int)((n - c0) < (int64_t)kNpBufSize ? (n - c0) : (int64_t)kNpBufSize);
-        int lo, len;
-        ss_heap_node(t, m, lo, len);
-        if (len > 0 && len <= 128) node[t] = np_leaf_sum(a + c0 + lo, len, 0.0, false);
-        __syncthreads();
-        for (int d = kNpDepth - 2; d >= 0; --d) {
-            if (len > 128 && depth == d && 2 * t + 2 < kSsNodes) node[t] = node[2 * t + 1] + node[2 * t + 2];
-            __syncthreads();
-        }
-        if (t == 0) *slot = *slot + node[0];
-        __syncthreads();
-    }
-    const double res = *slot;
-    __syncthreads();
-    return res;
 }
 
 struct ScaleErrArgs {

@@ -13,8 +13,11 @@ The reference is a Python-2 script over text dumps that writes six result files 
 ONE kernel launch for a batch of frames (``mvosr_height_pitch_batch``) and the script's cross-frame state —
 a frame with fewer than 12 list points repeats the previous frame's plane and inliers (:163-165) — is kept by
 :class:`HeightPitchEstimator`.  The triangulation's rows are built on the host (SciPy) or on the device and visit the
-host either way in this version.  The line RANSAC of :146 is printed by the base script and never used there: the estimator
-does not compute it (the evaluation's line model does)."""
+host either way on the default path; ``HeightPitchEstimator(triangulation="gpu", resident=True)`` keeps a call's frames on the
+device from their upload to the six result values — rows in HBM between ``mvosr_delaunay_batch`` and the kernel, the cross-frame
+state applied by ``mvosr_height_pitch_tail_batch``, chunks streamed on the shared pipeline (``stream.py``).
+The line RANSAC of :146 is printed by the base script and never used there: the estimator does not compute it (the evaluation's
+line model does)."""
 from __future__ import annotations
 
 import collections
@@ -24,7 +27,7 @@ import os
 
 import numpy as np
 
-from . import _lib, packing
+from . import _lib, packing, stream
 
 FOCUS, CX, CY = 718.856, 607.1928, 185.2157        # calculate_height_pitch.py:15-17
 PI_SCRIPT = 3.1415926                               # :63, :91
@@ -104,6 +107,80 @@ def _delaunay_rows(ctx, pts2d, triangulation, workers):
     return rows
 
 
+def _pack_planes(pts):
+    """``_pack_frames``' feature planes and offsets from ONE concatenate over the frames -> (planes (3, total), feat_off, feat_cnt)."""
+    cnt = np.fromiter((len(p) for p in pts), dtype=np.int32, count=len(pts))
+    even = (cnt.astype(np.int64) + 1) & ~1
+    off = np.concatenate([[0], np.cumsum(even)[:-1]]).astype(np.int64)              # even segment starts
+    planes = np.zeros((3, max(int(off[-1] + even[-1]), 2)), dtype=np.float64)
+    start = np.concatenate([[0], np.cumsum(cnt.astype(np.int64))[:-1]])
+    where = np.repeat(off - start, cnt) + np.arange(int(cnt.sum()), dtype=np.int64)
+    planes[:, where] = np.concatenate(pts).T
+    return planes, off, cnt
+
+
+# mvosr_height_pitch_tail_frame, mvosr_height_pitch_carry (include/mvosr.h)
+TAIL_FRAME = np.dtype([(k, "<f8") for k in ("ransac_height", "refined_mean", "refined_std", "height_t_mean", "refined_pitch")] +
+                      [(k, "<i4") for k in ("n_inliers", "n_selected", "carried", "source")])
+CARRY_HEADER = np.dtype([(k, "<f8") for k in ("ransac_height", "refined_mean", "refined_std", "height_t_mean", "refined_pitch")] +
+                        [(k, "<i4") for k in ("n_inliers", "has_prev", "count", "halted")] + [("reserved", "<i8")])
+
+
+def carry_record(cap, prev=None, inliers=None, index=None):
+    """A carry record of capacity ``cap`` as bytes: the header, then y, z and index (mvosr_height_pitch_carry).  ``prev``: the
+    previous frame's six values (anything with RESULT_FIELDS' attributes), ``inliers`` its (k, 3) back-projected inliers."""
+    cap, y0 = (int(cap) + 1) & ~1, CARRY_HEADER.itemsize
+    rec = np.zeros(-(-(y0 + 20 * cap) // 16) * 16, dtype=np.uint8)
+    if prev is not None:
+        h = rec[:y0].view(CARRY_HEADER)
+        for k in RESULT_FIELDS:
+            h[k] = getattr(prev, k)
+        k = len(inliers)
+        h["has_prev"], h["count"] = 1, k
+        rec[y0:y0 + 8 * k].view(np.float64)[:] = inliers[:, 1]
+        rec[y0 + 8 * cap:y0 + 8 * cap + 8 * k].view(np.float64)[:] = inliers[:, 2]
+        if index is not None:
+            rec[y0 + 16 * cap:y0 + 16 * cap + 4 * k].view(np.int32)[:] = index
+    return rec
+
+
+def carry_fields(rec, cap):
+    """(header (a CARRY_HEADER scalar), y, z, index) of a carry record's bytes, the arrays cut to the header's count."""
+    cap, y0 = (int(cap) + 1) & ~1, CARRY_HEADER.itemsize
+    h = rec[:y0].view(CARRY_HEADER)[0]
+    k = int(h["count"])
+    return (h, rec[y0:y0 + 8 * k].view(np.float64), rec[y0 + 8 * cap:y0 + 8 * cap + 8 * k].view(np.float64),
+            rec[y0 + 16 * cap:y0 + 16 * cap + 4 * k].view(np.int32))
+
+
+def resident_rows_stage(ctx, pts, extra_in=(), extra_arrays=None):
+    """A chunk's frames uploaded ONCE and triangulated on the device, the rows left in HBM for the kernel that consumes them:
+    -> dict with ``din`` (feat_off, feat_cnt, u, v, z, tri_off = 2 feat_off, and ``extra_in``'s arrays), ``tri`` (canonical rows at
+    3 tri_off[f], room for 2 n), ``dt`` (tri_cnt, dt_status, dt_used), ``off``, ``cnt`` and ``total``.  Everything is queued on the
+    context's stream; nothing is waited for.  (The evaluation objects' kernels honour ``tri1_cnt`` too: this stage is theirs to take.)"""
+    planes, off, cnt = _pack_planes(pts)
+    F, total = len(pts), planes.shape[1]
+    din = ctx.block([("feat_off", F, np.int64), ("feat_cnt", F, np.int32), ("u", total, np.float64), ("v", total, np.float64),
+                     ("z", total, np.float64), ("tri_off", F, np.int64)] + list(extra_in))
+    tri = dt = None
+    try:
+        tri = ctx.block([("tri", 6 * total, np.int32)])
+        dt = ctx.block([("tri_cnt", F, np.int32), ("dt_status", F, np.int32), ("dt_used", F, np.int32)])
+        arrays = {"feat_off": off, "feat_cnt": cnt, "u": planes[0], "v": planes[1], "z": planes[2], "tri_off": 2 * off}
+        arrays.update(extra_arrays or {})
+        din.upload(arrays)
+        dt.zero()
+        _lib.check(ctx.lib.mvosr_delaunay_batch(ctx.handle, F, din["feat_off"].ptr, din["feat_cnt"].ptr, din["u"].ptr, din["v"].ptr, None,
+                                                int(cnt.max()), din["tri_off"].ptr, tri["tri"].ptr, dt["tri_cnt"].ptr, dt["dt_used"].ptr,
+                                                dt["dt_status"].ptr), "mvosr_delaunay_batch")
+    except BaseException:
+        for blk in (din, tri, dt):
+            if blk is not None:
+                blk.free()
+        raise
+    return {"din": din, "tri": tri, "dt": dt, "off": off, "cnt": cnt, "total": total}
+
+
 def _batch_header(din, F, max_feat, total_feat):
     b = _lib.Batch()
     b.n_frames, b.feat_off, b.feat_cnt = F, din["feat_off"].ptr, din["feat_cnt"].ptr
@@ -117,10 +194,22 @@ class HeightPitchEstimator:
     """The script's frame loop as an object: ``process`` / ``process_batch`` take frames in sequence order and keep what the
     script carries from one frame to the next; the six result lists grow as the script's do."""
 
+    # the resident path's chunks (the streamed path's knobs, stream.StreamKnobs; tests and profiles override them per instance)
+    GPU_CHUNK = stream.StreamKnobs.GPU_CHUNK
+    GPU_MIN_CHUNK = stream.StreamKnobs.GPU_MIN_CHUNK
+    GPU_CHUNK_POINTS = stream.StreamKnobs.GPU_CHUNK_POINTS
+    GPU_PIPELINE = stream.StreamKnobs.GPU_PIPELINE
+    GPU_SIDE_DOWNLOADS = stream.StreamKnobs.GPU_SIDE_DOWNLOADS
+
     def __init__(self, focus=FOCUS, cx=CX, cy=CY, max_iterations=500, threshold=0.005, inlier_threshold=0.01, seed=None, device=0,
-                 triangulation="scipy", delaunay_workers=0):
+                 triangulation="scipy", delaunay_workers=0, resident=False):
         if triangulation not in ("scipy", "gpu"):
             raise ValueError("triangulation must be 'scipy' or 'gpu'")
+        # resident: opt-in (DESIGN.md §3.26).  False: every path, message and state below is what it was.
+        if resident and triangulation != "gpu":
+            raise ValueError("resident=True belongs to triangulation='gpu': the rows stay where the device triangulation wrote them")
+        self.resident = bool(resident)
+        self.declined_total = 0                        # resident path: frames whose rows came from the host (or that have no rows: < 3 points)
         self.ctx = _lib.default_context(device)
         self.focus, self.cx, self.cy = float(focus), float(cx), float(cy)
         self.max_iterations, self.threshold, self.inlier_threshold = int(max_iterations), float(threshold), float(inlier_threshold)
@@ -214,6 +303,10 @@ class HeightPitchEstimator:
         ests = [float(e) for e in np.asarray(estimated_pitches, dtype=np.float64).reshape(-1)]
         if len(ests) != len(points3d_list):
             raise ValueError("one estimated pitch per frame")
+        if self.resident:
+            if tris is not None:
+                raise ValueError("resident=True triangulates on the device: tris= belongs to the staged path")
+            return self._process_resident(points3d_list, ests, triples)
         res = self.launch(points3d_list, [frame_prior(e) for e in ests], triples=triples, tris=tris)
         self.last = res
         out = []
@@ -247,6 +340,200 @@ class HeightPitchEstimator:
 
     def process(self, points3d, estimated_pitch):
         return self.process_batch([points3d], [estimated_pitch])[0]
+
+    # ---- the device-resident path (resident=True) --------------------------------------------------------------
+    def _resident_start(self, call, a, b, k):
+        """Chunk ``k`` = frames ``a:b`` of the call: ONE upload, then the triangulation, the kernel and the tail queued on the
+        estimator's stream, and the download of the chunk's small records behind them.  Nothing is waited for."""
+        ctx, H, F = self.ctx, self.max_iterations, b - a
+        extra, arrays = [("prior", (F, 4), np.float64)], {"prior": call["priors"][a:b]}
+        if call["triples"] is not None:
+            tr = np.full((F, H, 3), -1, dtype=np.int32)                             # (-1: outside every list, the sample is spent)
+            for f, t in enumerate(call["triples"][a:b]):
+                if t is not None and len(t):
+                    t = np.asarray(t, dtype=np.int32).reshape(-1, 3)[:H]
+                    tr[f, :len(t)] = t
+            extra.append(("triples", (F, H, 3), np.int32))
+            arrays["triples"] = tr
+        st = resident_rows_stage(ctx, call["pts"][a:b], extra, arrays)
+        st.update(k=k, a=a, b=b, side=[st["din"], st["tri"], st["dt"]])             # (side: the blocks stream.free_blocks releases)
+        call["inflight"].append(st)
+        try:
+            din, total, max_feat = st["din"], st["total"], int(st["cnt"].max())
+            out = ctx.block([("ransac_height", F, np.float64), ("model", (F, 4), np.float64), ("best_ic", F, np.int32), ("used", F, np.int32),
+                             ("n_selected", F, np.int32), ("n_inliers", F, np.int32), ("refined_normal", (F, 3), np.float64),
+                             ("refined_pitch", F, np.float64), ("refined_mean", F, np.float64), ("refined_std", F, np.float64),
+                             ("height_t_mean", F, np.float64), ("status", F, np.int32), ("mask", total, np.uint8)])
+            st["out"] = out
+            small = st["small"] = ctx.block([("frames", F, TAIL_FRAME), ("error", 1, np.int64)])
+            st["side"].append(small)
+            out.zero()
+            hb = st["header"] = _lib.Batch()
+            hb.n_frames, hb.feat_off, hb.feat_cnt = F, din["feat_off"].ptr, din["feat_cnt"].ptr
+            hb.x, hb.v, hb.z = din["u"].ptr, din["v"].ptr, din["z"].ptr
+            hb.tri1_off, hb.tri1, hb.tri1_cnt = din["tri_off"].ptr, st["tri"]["tri"].ptr, st["dt"]["tri_cnt"].ptr
+            hb.max_feat, hb.total_feat = max_feat, total
+            st["params"] = _lib.HeightPitchParams(self.focus, self.cx, self.cy, MIN_POINTS, H, self.threshold, GOAL_FRACTION, self.inlier_threshold,
+                                                  self.seed, int(call["frame_base"] + a))
+            st["outputs"] = _lib.HeightPitchOutputs(*[(out[n].ptr if n in out else None) for n, _ in _lib.HeightPitchOutputs._fields_])
+            self._resident_kernel(st)
+            while len(call["chain"]) < k + 2:                                            # chunk k: chain[k] -> chain[k + 1]
+                call["chain"].append(ctx.empty(len(call["carry0"]), np.uint8))
+            self._resident_tail(call, st, F)
+            for blk in (din, st["tri"], out):
+                blk.mark(True)
+        except BaseException:
+            call["inflight"].remove(st)
+            stream.free_blocks(st)
+            raise
+        return st
+
+    def _resident_kernel(self, st):
+        ctx, din = self.ctx, st["din"]
+        _lib.check(ctx.lib.mvosr_height_pitch_batch(ctx.handle, C.byref(st["header"]), C.byref(st["params"]), din["prior"].ptr,
+                                                    din["triples"].ptr if "triples" in din else None, C.byref(st["outputs"])),
+                   "mvosr_height_pitch_batch")
+
+    def _resident_tail(self, call, st, n_frames, download=True):
+        """``mvosr_height_pitch_tail_batch`` over the chunk's first ``n_frames`` frames, then (``download``) the chunk's small records on
+        their way to page-locked memory — through the pipeline's side download (a copy kernel) where the knob allows it, as the rescale path."""
+        ctx, small = self.ctx, st["small"]
+        hb = _lib.Batch.from_buffer_copy(st["header"])
+        hb.n_frames = int(n_frames)
+        _lib.check(ctx.lib.mvosr_height_pitch_tail_batch(ctx.handle, C.byref(hb), C.byref(st["params"]), st["din"]["prior"].ptr,
+                                                         C.byref(st["outputs"]), call["chain"][st["k"]].ptr, call["chain"][st["k"] + 1].ptr,
+                                                         call["cap"], small["frames"].ptr, small["error"].ptr),
+                   "mvosr_height_pitch_tail_batch")
+        for blk in (st["dt"], small) if download else ():
+            blk.mark(False)
+            if self.GPU_SIDE_DOWNLOADS:
+                blk.mark_done()
+            else:
+                blk.prefetch()
+            blk.mark(True)
+
+    def _resident_redo(self, call, st, declined):
+        """The frames of the chunk the device triangulation declined: SciPy's rows in canonical form into the frames' own slots of
+        the chunk's row slab, ``tri_cnt`` patched, the kernel run again over the chunk, and the tails of this chunk and of every chunk
+        queued behind it (their carry-in changed).  A SciPy exception: -> (its frame, the exception), the tail run over the frames
+        before it only."""
+        ctx, lib, off = self.ctx, self.ctx.lib, st["off"]
+        stop = None
+        rows = packing.delaunay_many([np.ascontiguousarray(call["pts"][st["a"] + f][:, 0:2]) for f in declined], self.delaunay_workers)
+        for blk in (st["din"], st["tri"], st["out"]):
+            blk.mark(False)
+        for f, t in zip(declined, rows):
+            if isinstance(t, Exception):
+                stop = (f, t)
+                break
+            t = np.ascontiguousarray(packing.canonical_rows(t), dtype=np.int32)
+            assert len(t) <= 2 * int(st["cnt"][f])                                  # (a planar triangulation of n points: at most 2n - 5 rows)
+            n_rows = np.array([len(t)], dtype=np.int32)
+            _lib.check(lib.mvosr_memcpy_h2d(ctx.handle, st["tri"]["tri"].ptr + 24 * int(off[f]), _lib.addr(t), t.nbytes), "h2d")
+            _lib.check(lib.mvosr_memcpy_h2d(ctx.handle, st["dt"]["tri_cnt"].ptr + 4 * f, _lib.addr(n_rows), 4), "h2d")
+        self._resident_kernel(st)
+        n = st["b"] - st["a"] if stop is None else stop[0]
+        if n > 0:
+            self._resident_tail(call, st, n)
+        if stop is None:
+            for later in call["inflight"]:
+                if later["k"] > st["k"]:
+                    self._resident_tail(call, later, later["b"] - later["a"])
+        for blk in (st["din"], st["tri"], st["out"]):
+            blk.mark(True)
+        return stop
+
+    def _resident_collect(self, call, st):
+        """Wait for the chunk's records, send its declined frames through the host, apply the records to the object's state in
+        sequence order, and raise where the host loop raises."""
+        cnt, F = st["cnt"], st["b"] - st["a"]
+        dt_status = st["dt"]["dt_status"].download()
+        declined = [f for f in range(F) if dt_status[f] != 0 and cnt[f] >= 3]
+        self.declined_total += len(declined) + int(np.count_nonzero(cnt < 3))
+        stop = self._resident_redo(call, st, declined) if declined else None
+        n = F if stop is None else stop[0]
+        frames = st["small"]["frames"].download()[:n] if n else np.zeros(0, dtype=TAIL_FRAME)
+        err = int(st["small"]["error"].download()[0]) if n else -1
+        kind, bad = (err >> 32, err & 0xffffffff) if err >= 0 else (0, n)
+        call["records"].append(frames[:bad])
+        call["dt_status"].append(dt_status)
+        call["errors"].append(err)
+        out = call["out"]
+        for f in range(bad):
+            r = frames[f]
+            res = FrameResult(float(r["ransac_height"]), float(r["refined_mean"]), float(r["refined_std"]), float(r["height_t_mean"]),
+                              float(r["refined_pitch"]), int(r["n_inliers"]), int(r["n_selected"]), bool(r["carried"]))
+            if not res.carried:
+                call["last_fit"] = st["a"] + f
+            self.frame_count += 1
+            for k in RESULT_FIELDS:
+                self.results[k].append(getattr(res, k))
+            out.append(res)
+        if bad:
+            call["carry_at"] = st["k"] + 1
+        call["inflight"].remove(st)
+        stream.free_blocks(st)
+        if kind == _lib.HPT_ERR_SINGULAR:
+            raise np.linalg.LinAlgError("Singular matrix")                           # :83
+        if kind in (_lib.HPT_ERR_MASK, _lib.HPT_ERR_EMPTY):
+            raise ValueError("frame %d: %s" % (self.frame_count, "no features or no triangles" if kind == _lib.HPT_ERR_EMPTY else
+                                               "a triangle names a vertex outside the frame"))
+        if kind == _lib.HPT_ERR_NO_MODEL:
+            raise ValueError("frame %d: no sample of the RANSAC had an inlier" % self.frame_count)
+        if kind == _lib.HPT_ERR_NO_PREVIOUS:                                         # :167 indexes the 1-D norm_prev of :45 with two indices
+            raise IndexError("too many indices for array: array is 1-dimensional, but 2 were indexed")
+        if kind:
+            raise RuntimeError("frame %d: the tail stopped with error %d" % (self.frame_count, kind))
+        if stop is not None:
+            raise stop[1]
+        return n
+
+    def _resident_call(self, points3d_list, ests, triples):
+        """A call's state: its frames as float64 arrays, the priors, the carry-in record from the object's ``_prev`` — after the
+        refusals, which come before anything of the call runs, with the staged path's message."""
+        ctx, H = self.ctx, self.max_iterations
+        pts = [np.ascontiguousarray(np.asarray(p, dtype=np.float64).reshape(-1, 3)) for p in points3d_list]
+        F = len(pts)
+        max_feat = max(len(p) for p in pts)
+        need = int(ctx.lib.mvosr_height_pitch_lds_bytes(max_feat, H))
+        if need > ctx.lds_per_block:
+            raise ValueError("a frame of %d features needs %d bytes of LDS, the device has %d" % (max_feat, need, ctx.lds_per_block))
+        if max_feat > packing.delaunay_gpu_max_points():
+            raise ValueError("a frame of %d features is beyond the device triangulation's %d" % (max_feat, packing.delaunay_gpu_max_points()))
+        prev, inl = self._prev if self._prev is not None else (None, None)
+        cap = (max(max_feat, 0 if inl is None else len(inl), 2) + 1) & ~1
+        return {"pts": pts, "priors": np.array([frame_prior(e) for e in ests], dtype=np.float64).reshape(F, 4), "triples": triples,
+                "frame_base": self.frame_count, "cap": cap, "carry0": carry_record(cap, prev, inl), "chain": [], "inflight": [],
+                "records": [], "dt_status": [], "errors": [], "out": [], "last_fit": None, "carry_at": 0}
+
+    def _process_resident(self, points3d_list, ests, triples):
+        """``process_batch`` with the call's frames device-resident: chunks of the call through ``stream.run``, per chunk ONE upload,
+        ``mvosr_delaunay_batch`` -> ``mvosr_height_pitch_batch`` -> ``mvosr_height_pitch_tail_batch`` on the estimator's stream, and
+        a few dozen bytes per frame back.  The object's host state is what the staged path leaves, after an exception too."""
+        if not len(points3d_list):
+            return []
+        call = self._resident_call(points3d_list, ests, triples)
+        ctx, cap, F = self.ctx, call["cap"], len(points3d_list)
+        inl = None if self._prev is None else self._prev[1]
+        step = stream.chunk_size(F, self.GPU_CHUNK, self.GPU_MIN_CHUNK, self.GPU_CHUNK_POINTS, [len(p) for p in call["pts"][:64]])[0]
+        try:
+            call["chain"].append(ctx.to_device(call["carry0"]))
+            stream.run(stream.fixed_plan(F, step), lambda a, b, tables, k: self._resident_start(call, a, b, k),
+                       lambda st, a, b, last: self._resident_collect(call, st), self.GPU_PIPELINE,
+                       lambda st: stream.free_blocks(st), [], lambda: None)
+        finally:
+            try:
+                if call["out"]:                                                      # the carry: one frame's inliers
+                    if call["last_fit"] is not None:
+                        index = carry_fields(call["chain"][call["carry_at"]].download(), cap)[3]
+                        inl = back_project(points3d_list[call["last_fit"]], self.focus, self.cx, self.cy)[index]
+                    self._prev = (call["out"][-1], inl)
+            finally:
+                for buf in call["chain"]:
+                    buf.free()
+                self.last = {"records": np.concatenate(call["records"]) if call["records"] else np.zeros(0, dtype=TAIL_FRAME),
+                             "dt_status": call["dt_status"], "errors": call["errors"]}
+        return call["out"]
 
     def run_sequence(self, frames, motion_ts):
         """The script's run: ``frames[i]`` is dump ``i + 1`` (:50, :60) and its prior ``get_pitch(motion_ts[0:i + 2])`` (:62).
