@@ -39,7 +39,7 @@ extern "C" {
  * no existing struct or signature moved — and a binding resolves every symbol it declares when it loads the library, so a
  * library older than its binding fails loudly at load time anyway.  mvosr_height_pitch_batch, its two structs and
  * mvosr_height_pitch_lds_bytes were added the same way, and so were mvosr_height_pitch_tail_batch, its two records and its two
- * size functions.) */
+ * size functions, and mvosr_height_pitch_eval_tail_batch with its record, its two structs and its size function.) */
 
 /* error codes (function return values) */
 enum mvosr_err {
@@ -1331,6 +1331,69 @@ int mvosr_height_pitch_eval_budgets_batch(mvosr_ctx *ctx, const mvosr_batch *b, 
                                           int n_budgets, const double *frame_prior, const int32_t *samples,
                                           const mvosr_height_pitch_eval_budgets_outputs *o);
 size_t mvosr_height_pitch_eval_budgets_lds_bytes(int max_feat, int n_hyp_max, int n_budgets, int model);
+
+/* ---- the evaluation runs' cross-frame rules (_eval.py:71-79, :184-188, :223-224) for a chunk of frames ----------------------- */
+
+/* the header of an evaluation carry record (16 bytes).  Behind it, with E = n_cases * n_budgets and element (c, b) at
+ * c * n_budgets + b: eight double[E] at 16 + 8 E k — k = 0..5 the six values in the result files' order (ransac_height,
+ * refined_mean, refined_std, height_t_mean, refined_pitch, n_inliers), k = 6 sum_y, k = 7 sum_z — and uint8 degenerate[E] at
+ * 16 + 64 E: the state after the last frame, the sums and the flag those of the last FITTED frame.  The record is
+ * mvosr_height_pitch_eval_carry_bytes(n_cases, n_budgets) bytes (a multiple of 16).  An empty record: has_prev = halted = 0,
+ * n_cases and n_budgets filled in, everything behind the header zero. */
+typedef struct mvosr_height_pitch_eval_carry {
+    int32_t has_prev;            /* 0: no fitted frame yet — a carried frame raises (:188) */
+    int32_t halted;              /* 1: a chunk before this one ended in an error; every later tail passes the record on untouched */
+    int32_t n_cases, n_budgets;  /* what the record was written for; a tail called with other numbers treats it as halted */
+} mvosr_height_pitch_eval_carry;
+
+/* what the evaluation launch wrote (device pointers): mvosr_height_pitch_eval_batch's [F][C] arrays are [F][C][B] with B = 1 */
+typedef struct mvosr_height_pitch_eval_tail_inputs {
+    const int32_t *n_selected;   /* [F] */
+    const int32_t *status;       /* [F][C][B] */
+    const double *ransac_height, *refined_mean, *refined_std, *height_t_mean, *refined_pitch;   /* [F][C][B] */
+    const int32_t *n_inliers;    /* [F][C][B] */
+    const double *sum_y, *sum_z; /* [F][C][B] */
+    const int32_t *used, *best;  /* [F][C][B]; each may be NULL: the output of the same name must then be NULL too */
+} mvosr_height_pitch_eval_tail_inputs;
+
+/* what the host's run returns (device pointers), [B][C][F] with F = n_frames of the call, frames fastest */
+typedef struct mvosr_height_pitch_eval_tail_outputs {
+    double *ransac_height, *refined_mean, *refined_std, *height_t_mean, *refined_pitch, *n_inliers;   /* [B][C][F], n_inliers as a double */
+    uint8_t *degenerate;         /* [B][C][F] 1: the refined values are NaN (MVOSR_ST_HP_REFINE_DEGENERATE of the frame or of its source) */
+    int32_t *used, *best;        /* [B][C][F] optional; a carried frame: 0 and -1 */
+    uint8_t *carried;            /* [F] 1: fewer than min_points list points */
+    int32_t *frame_class;        /* [F] 0 fitted, -1 carried, else an mvosr_hpt_error kind | budget index << 8 (the index: no-model only) */
+    int32_t *source;             /* [F] the last fitted frame of the chunk at or before this one; -1: none, the carry-in's */
+    int64_t *error;              /* one word, see below */
+} mvosr_height_pitch_eval_tail_outputs;
+
+/*
+ * The cross-frame rules of RansacEvaluation.run / RansacBudgetSweep.run for one chunk of frames in sequence order, behind the
+ * evaluation launch on the context's stream: three launches (hpe_class_kernel: one wavefront per frame; hpe_resolve_kernel: one
+ * workgroup; hpe_apply_kernel: one thread per (frame, case, budget)), no host synchronisation, no atomics.
+ *   Class of frame f, from its C * B status words and n_selected[f]: any MVOSR_ST_ERR_SINGULAR -> singular; else any
+ *   MVOSR_ST_ERR_EMPTY -> empty, else any MVOSR_ST_ERR_MASK -> mask; else, with n_selected >= min_points, any MVOSR_ST_RS_FEW ->
+ *   no-model at the smallest budget index that has one; else a word that is none of 0, MVOSR_ST_HP_REFINE_DEGENERATE,
+ *   MVOSR_ST_RS_FEW -> status; else n_selected < min_points -> CARRIED; else FITTED.  A carried frame with no fitted frame before
+ *   it in the chunk and has_prev = 0 in the carry-in is the no-previous error.  (The kinds: enum mvosr_hpt_error.)
+ *   A fitted frame's element (c, b) takes the launch's six values, degenerate = status & MVOSR_ST_HP_REFINE_DEGENERATE != 0, used and best.
+ *   A carried frame's element takes ransac_height, refined_mean, refined_std, refined_pitch, n_inliers and degenerate of its SOURCE —
+ *   the last fitted frame before it, in the chunk or the carry-in's — used = 0, best = -1, and
+ *   height_t_mean = degenerate ? NaN (0x7ff8000000000000) : (sum_z * sin + sum_y * cos) / (double)n_inliers with the source's sums
+ *   and the frame's own frame_prior[f][2], [3]: two products, one sum, one division, each rounded (no fused multiply-add).
+ *   *error: -1, or frame | kind << 32 | budget index << 40 for the first frame at which the host must raise (the index: no-model
+ *   only, else 0).  Frames from that one on are not written (carried, frame_class and source are).
+ *   carry_out: the state after the last frame before the error, or after the chunk's last frame; halted when the chunk had an
+ *   error.  A halted carry_in is copied to carry_out, *error = MVOSR_HPT_ERR_UPSTREAM << 32, and nothing else is written; one
+ *   written for other n_cases / n_budgets is not read behind its header: the same, with an empty halted record as carry_out.
+ * frame_prior: [F][4] as the evaluation launch took it.  carry_in != carry_out.  1 <= n_cases <= 1024, 1 <= n_budgets <= 16,
+ * min_points >= 3, n_frames < 2^31 - 64 (else MVOSR_ERR_ARG / MVOSR_ERR_TOO_LARGE); n_frames <= 0: MVOSR_OK, nothing is written.
+ * The results do not depend on how a sequence is cut into chunks.
+ */
+int mvosr_height_pitch_eval_tail_batch(mvosr_ctx *ctx, int64_t n_frames, int32_t n_cases, int32_t n_budgets, int32_t min_points,
+                                       const mvosr_height_pitch_eval_tail_inputs *in, const double *frame_prior, const void *carry_in,
+                                       void *carry_out, const mvosr_height_pitch_eval_tail_outputs *out);
+size_t mvosr_height_pitch_eval_carry_bytes(int n_cases, int n_budgets);
 
 /* ---- dense depth maps from the triangle planes (/root/reference/src/reconstruct.py) ------------------ */
 

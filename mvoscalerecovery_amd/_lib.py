@@ -201,6 +201,25 @@ class HeightPitchEvalBudgetsOutputs(C.Structure):
                 ("sum_z", C.c_void_p), ("status", C.c_void_p), ("best", C.c_void_p), ("point_list", C.c_void_p), ("hyp_counts", C.c_void_p)]
 
 
+class HeightPitchEvalCarry(C.Structure):
+    """mvosr_height_pitch_eval_carry"""
+    _fields_ = [("has_prev", C.c_int32), ("halted", C.c_int32), ("n_cases", C.c_int32), ("n_budgets", C.c_int32)]
+
+
+class HeightPitchEvalTailInputs(C.Structure):
+    """mvosr_height_pitch_eval_tail_inputs"""
+    _fields_ = [("n_selected", C.c_void_p), ("status", C.c_void_p), ("ransac_height", C.c_void_p), ("refined_mean", C.c_void_p),
+                ("refined_std", C.c_void_p), ("height_t_mean", C.c_void_p), ("refined_pitch", C.c_void_p), ("n_inliers", C.c_void_p),
+                ("sum_y", C.c_void_p), ("sum_z", C.c_void_p), ("used", C.c_void_p), ("best", C.c_void_p)]
+
+
+class HeightPitchEvalTailOutputs(C.Structure):
+    """mvosr_height_pitch_eval_tail_outputs"""
+    _fields_ = [("ransac_height", C.c_void_p), ("refined_mean", C.c_void_p), ("refined_std", C.c_void_p), ("height_t_mean", C.c_void_p),
+                ("refined_pitch", C.c_void_p), ("n_inliers", C.c_void_p), ("degenerate", C.c_void_p), ("used", C.c_void_p),
+                ("best", C.c_void_p), ("carried", C.c_void_p), ("frame_class", C.c_void_p), ("source", C.c_void_p), ("error", C.c_void_p)]
+
+
 HP_MODEL_PLANE, HP_MODEL_LINE = 0, 1      # enum mvosr_hp_model
 ST_HP_REFINE_DEGENERATE = 0x100           # MVOSR_ST_HP_REFINE_DEGENERATE
 
@@ -323,6 +342,9 @@ SYMBOLS = {
     "mvosr_height_pitch_eval_budgets_batch": (C.c_int, [_P, C.POINTER(Batch), C.POINTER(HeightPitchEvalParams), _P, C.c_int, _P, _P,
                                                         C.POINTER(HeightPitchEvalBudgetsOutputs)]),
     "mvosr_height_pitch_eval_budgets_lds_bytes": (C.c_size_t, [C.c_int, C.c_int, C.c_int, C.c_int]),
+    "mvosr_height_pitch_eval_tail_batch": (C.c_int, [_P, C.c_int64, C.c_int32, C.c_int32, C.c_int32, C.POINTER(HeightPitchEvalTailInputs), _P, _P, _P,
+                                                     C.POINTER(HeightPitchEvalTailOutputs)]),
+    "mvosr_height_pitch_eval_carry_bytes": (C.c_size_t, [C.c_int, C.c_int]),
     "mvosr_triangle_model_batch": (C.c_int, [_P, C.POINTER(Batch), C.c_int, _P, _P, _P]),
     "mvosr_dense_depth_batch": (C.c_int, [_P, C.POINTER(Batch), C.c_int, _P, _P, C.POINTER(Camera), C.POINTER(DepthOutputs), C.c_int64, C.c_int64]),
     "mvosr_point_cloud_batch": (C.c_int, [_P, C.POINTER(CloudInputs), C.POINTER(Camera), C.POINTER(CloudParams), C.POINTER(CloudOutputs)]),

@@ -16,6 +16,8 @@ a frame with fewer than 12 list points repeats the previous frame's plane and in
 host either way on the default path; ``HeightPitchEstimator(triangulation="gpu", resident=True)`` keeps a call's frames on the
 device from their upload to the six result values — rows in HBM between ``mvosr_delaunay_batch`` and the kernel, the cross-frame
 state applied by ``mvosr_height_pitch_tail_batch``, chunks streamed on the shared pipeline (``stream.py``).
+``RansacEvaluation`` / ``RansacBudgetSweep(triangulation="gpu", resident=True)`` are on the same path with a tail of their own,
+``mvosr_height_pitch_eval_tail_batch``, which writes the (budgets, cases, frames) arrays ``run`` returns.
 The line RANSAC of :146 is printed by the base script and never used there: the estimator does not compute it (the evaluation's
 line model does)."""
 from __future__ import annotations
@@ -39,6 +41,8 @@ ST_RS_FEW, ST_ERR_SINGULAR, ST_ERR_MASK, ST_ERR_EMPTY = 11, 7, 8, 9
 RESULT_FILES = ("result_heights_line_ransac.txt", "refined_camera_height_means.txt", "refined_camera_height_stds.txt",
                 "refined_camera_height_t_means.txt", "refined_pitch.txt", "inlier_numbers.txt")
 RESULT_FIELDS = ("ransac_height", "refined_mean", "refined_std", "height_t_mean", "refined_pitch", "n_inliers")
+
+RESIDENT_ERROR = "resident=True belongs to triangulation='gpu': the rows stay where the device triangulation wrote them"
 
 FrameResult = collections.namedtuple("FrameResult", RESULT_FIELDS + ("n_selected", "carried"))
 
@@ -157,7 +161,7 @@ def resident_rows_stage(ctx, pts, extra_in=(), extra_arrays=None):
     """A chunk's frames uploaded ONCE and triangulated on the device, the rows left in HBM for the kernel that consumes them:
     -> dict with ``din`` (feat_off, feat_cnt, u, v, z, tri_off = 2 feat_off, and ``extra_in``'s arrays), ``tri`` (canonical rows at
     3 tri_off[f], room for 2 n), ``dt`` (tri_cnt, dt_status, dt_used), ``off``, ``cnt`` and ``total``.  Everything is queued on the
-    context's stream; nothing is waited for.  (The evaluation objects' kernels honour ``tri1_cnt`` too: this stage is theirs to take.)"""
+    context's stream; nothing is waited for.  (The estimator's chunks and the evaluation objects' both start here.)"""
     planes, off, cnt = _pack_planes(pts)
     F, total = len(pts), planes.shape[1]
     din = ctx.block([("feat_off", F, np.int64), ("feat_cnt", F, np.int32), ("u", total, np.float64), ("v", total, np.float64),
@@ -179,6 +183,23 @@ def resident_rows_stage(ctx, pts, extra_in=(), extra_arrays=None):
                 blk.free()
         raise
     return {"din": din, "tri": tri, "dt": dt, "off": off, "cnt": cnt, "total": total}
+
+
+def patch_declined_rows(ctx, st, pts, declined, workers):
+    """The frames ``declined`` of a :func:`resident_rows_stage` chunk (``pts``: their points) through SciPy: the rows in canonical form
+    into the frames' own slots of the chunk's row slab, ``tri_cnt`` patched.  A SciPy exception: -> (its frame, the exception), the
+    frames behind it left as they were; else None."""
+    lib, off = ctx.lib, st["off"]
+    rows = packing.delaunay_many([np.ascontiguousarray(p[:, 0:2]) for p in pts], workers)
+    for f, t in zip(declined, rows):
+        if isinstance(t, Exception):
+            return f, t
+        t = np.ascontiguousarray(packing.canonical_rows(t), dtype=np.int32)
+        assert len(t) <= 2 * int(st["cnt"][f])                                      # (a planar triangulation of n points: at most 2n - 5 rows)
+        n_rows = np.array([len(t)], dtype=np.int32)
+        _lib.check(lib.mvosr_memcpy_h2d(ctx.handle, st["tri"]["tri"].ptr + 24 * int(off[f]), _lib.addr(t), t.nbytes), "h2d")
+        _lib.check(lib.mvosr_memcpy_h2d(ctx.handle, st["dt"]["tri_cnt"].ptr + 4 * f, _lib.addr(n_rows), 4), "h2d")
+    return None
 
 
 def _batch_header(din, F, max_feat, total_feat):
@@ -207,7 +228,7 @@ class HeightPitchEstimator:
             raise ValueError("triangulation must be 'scipy' or 'gpu'")
         # resident: opt-in.  False: every path, message and state below is what it was.
         if resident and triangulation != "gpu":
-            raise ValueError("resident=True belongs to triangulation='gpu': the rows stay where the device triangulation wrote them")
+            raise ValueError(RESIDENT_ERROR)
         self.resident = bool(resident)
         self.declined_total = 0                        # resident path: frames whose rows came from the host (or that have no rows: < 3 points)
         self.ctx = _lib.default_context(device)
@@ -417,20 +438,9 @@ class HeightPitchEstimator:
         the chunk's row slab, ``tri_cnt`` patched, the kernel run again over the chunk, and the tails of this chunk and of every chunk
         queued behind it (their carry-in changed).  A SciPy exception: -> (its frame, the exception), the tail run over the frames
         before it only."""
-        ctx, lib, off = self.ctx, self.ctx.lib, st["off"]
-        stop = None
-        rows = packing.delaunay_many([np.ascontiguousarray(call["pts"][st["a"] + f][:, 0:2]) for f in declined], self.delaunay_workers)
         for blk in (st["din"], st["tri"], st["out"]):
             blk.mark(False)
-        for f, t in zip(declined, rows):
-            if isinstance(t, Exception):
-                stop = (f, t)
-                break
-            t = np.ascontiguousarray(packing.canonical_rows(t), dtype=np.int32)
-            assert len(t) <= 2 * int(st["cnt"][f])                                  # (a planar triangulation of n points: at most 2n - 5 rows)
-            n_rows = np.array([len(t)], dtype=np.int32)
-            _lib.check(lib.mvosr_memcpy_h2d(ctx.handle, st["tri"]["tri"].ptr + 24 * int(off[f]), _lib.addr(t), t.nbytes), "h2d")
-            _lib.check(lib.mvosr_memcpy_h2d(ctx.handle, st["dt"]["tri_cnt"].ptr + 4 * f, _lib.addr(n_rows), 4), "h2d")
+        stop = patch_declined_rows(self.ctx, st, [call["pts"][st["a"] + f] for f in declined], declined, self.delaunay_workers)
         self._resident_kernel(st)
         n = st["b"] - st["a"] if stop is None else stop[0]
         if n > 0:
@@ -605,6 +615,20 @@ def _eval_frame_rules(i, est, st, n_sel, value, prev, budget=None):
     return cur, False
 
 
+def _pack_samples(samples, F, Cn, H):
+    """Recorded samples of ``F`` frames as the (F, Cn, H, 3) array both evaluation launches upload."""
+    sm = np.full((F, Cn, H, 3), -1, dtype=np.int32)                                 # (-1: outside every list, the sample is spent)
+    for f, t in enumerate(samples):
+        if t is None:
+            continue
+        t = np.asarray(t, dtype=np.int32)
+        if t.ndim != 3 or t.shape[0] != Cn or t.shape[2] not in (2, 3):
+            raise ValueError("samples[%d] must be shaped (cases, h, 2 or 3)" % f)
+        h = min(H, t.shape[1])
+        sm[f, :, :h, :t.shape[2]] = t[:, :h]
+    return sm
+
+
 def _eval_launch(ev, H, budgets, points3d_list, priors, samples, tris, frame_base, stage, max_feat, timing, cases_per_group):
     """The launch of both evaluation objects: ``budgets`` None — ``mvosr_height_pitch_eval_batch`` with ``H`` hypotheses, (F, C) per
     quantity; a tuple — ``mvosr_height_pitch_eval_budgets_batch``, ``H`` its last, (F, C, B) per quantity and ``best``."""
@@ -623,17 +647,8 @@ def _eval_launch(ev, H, budgets, points3d_list, priors, samples, tris, frame_bas
         raise ValueError("a frame of %d features needs %d bytes of LDS, the device has %d" % (max_feat, need, ctx.lds_per_block))
     spec_in, arrays, off, toff, planes, T = _pack_frames(pts, rows, priors)
     if samples is not None:
-        sm = np.full((F, Cn, H, 3), -1, dtype=np.int32)                             # (-1: outside every list, the sample is spent)
-        for f, t in enumerate(samples):
-            if t is None:
-                continue
-            t = np.asarray(t, dtype=np.int32)
-            if t.ndim != 3 or t.shape[0] != Cn or t.shape[2] not in (2, 3):
-                raise ValueError("samples[%d] must be shaped (cases, h, 2 or 3)" % f)
-            h = min(H, t.shape[1])
-            sm[f, :, :h, :t.shape[2]] = t[:, :h]
         spec_in.append(("samples", (F, Cn, H, 3), np.int32))
-        arrays["samples"] = sm
+        arrays["samples"] = _pack_samples(samples, F, Cn, H)
     FC = (F, Cn) if budgets is None else (F, Cn, len(budgets))
     spec_out = [("ransac_height", FC, np.float64), ("model", FC + (4,), np.float64), ("best_ic", FC, np.int32), ("used", FC, np.int32),
                 ("n_selected", F, np.int32), ("n_inliers", FC, np.int32), ("refined_normal", FC + (3,), np.float64),
@@ -694,17 +709,274 @@ def _eval_launch(ev, H, budgets, points3d_list, priors, samples, tris, frame_bas
     return res
 
 
+# ---- the evaluation runs on the device-resident path (resident=True) ------------------------------------------
+EVAL_CARRY_HEADER = np.dtype([(k, "<i4") for k in ("has_prev", "halted", "n_cases", "n_budgets")])   # mvosr_height_pitch_eval_carry
+EVAL_CARRY_VALUES = RESULT_FIELDS + ("sum_y", "sum_z")
+
+
+def eval_carry_bytes(n_cases, n_budgets):
+    """``mvosr_height_pitch_eval_carry_bytes``: the header, eight double[E], uint8[E], rounded up to 16."""
+    E = int(n_cases) * int(n_budgets)
+    return -(-(EVAL_CARRY_HEADER.itemsize + 65 * E) // 16) * 16
+
+
+def eval_carry_record(n_cases, n_budgets, prev=None, halted=False):
+    """An evaluation carry record as bytes (mvosr_height_pitch_eval_carry and its arrays).  ``prev``: None — the empty record —, or
+    a dict of (n_cases, n_budgets) arrays under EVAL_CARRY_VALUES' names and ``degenerate``: the state after the last frame."""
+    Cn, B = int(n_cases), int(n_budgets)
+    E, y0 = Cn * B, EVAL_CARRY_HEADER.itemsize
+    rec = np.zeros(eval_carry_bytes(Cn, B), dtype=np.uint8)
+    h = rec[:y0].view(EVAL_CARRY_HEADER)
+    h["has_prev"], h["halted"], h["n_cases"], h["n_budgets"] = int(prev is not None), int(bool(halted)), Cn, B
+    if prev is not None:
+        val = rec[y0:y0 + 64 * E].view(np.float64).reshape(8, E)
+        for k, name in enumerate(EVAL_CARRY_VALUES):
+            val[k] = np.asarray(prev[name], dtype=np.float64).reshape(E)
+        rec[y0 + 64 * E:y0 + 65 * E] = np.asarray(prev["degenerate"]).reshape(E) != 0
+    return rec
+
+
+def eval_carry_fields(rec):
+    """(header (an EVAL_CARRY_HEADER scalar), dict name -> (n_cases, n_budgets) array) of an evaluation carry record's bytes."""
+    rec, y0 = np.asarray(rec, dtype=np.uint8), EVAL_CARRY_HEADER.itemsize
+    h = rec[:y0].view(EVAL_CARRY_HEADER)[0]
+    Cn, B = int(h["n_cases"]), int(h["n_budgets"])
+    E = Cn * B
+    val = rec[y0:y0 + 64 * E].view(np.float64).reshape(8, Cn, B)
+    out = {name: val[k].copy() for k, name in enumerate(EVAL_CARRY_VALUES)}
+    out["degenerate"] = rec[y0 + 64 * E:y0 + 65 * E].reshape(Cn, B) != 0
+    return h, out
+
+
+def eval_tail_error(err):
+    """The tail's error word -> (kind, budget index, frame); kind 0: none."""
+    err = int(err)
+    return (0, 0, -1) if err < 0 else ((err >> 32) & 0xff, (err >> 40) & 0xff, err & 0xffffffff)
+
+
+def _eval_resident_refusals(ev, H, budgets, frames, runs):
+    """What is refused before anything of a resident run is queued, run by run in sequence order, with the staged launch's message."""
+    ctx, lib = ev.ctx, ev.ctx.lib
+    for idx in runs:
+        max_feat = max(int(np.asarray(frames[i]).size) // 3 for i in idx)
+        need = int(lib.mvosr_height_pitch_eval_lds_bytes(max_feat, H, EVAL_MODELS[ev.model])) if budgets is None else \
+            int(lib.mvosr_height_pitch_eval_budgets_lds_bytes(max_feat, H, len(budgets), EVAL_MODELS[ev.model]))
+        if need > ctx.lds_per_block:
+            raise ValueError("a frame of %d features needs %d bytes of LDS, the device has %d" % (max_feat, need, ctx.lds_per_block))
+        if max_feat > packing.delaunay_gpu_max_points():
+            raise ValueError("a frame of %d features is beyond the device triangulation's %d" % (max_feat, packing.delaunay_gpu_max_points()))
+
+
+def _eval_resident_start(ev, call, a, b, k):
+    """Chunk ``k`` = dumps ``a:b`` (one run of non-empty dumps): ONE upload, then the triangulation, the evaluation launch and the
+    tail queued on the context's stream, and the download of the chunk's results behind them.  Nothing is waited for."""
+    ctx, Cn, H, budgets, F = ev.ctx, ev.cases, call["H"], call["budgets"], b - a
+    B = call["B"]
+    extra, arrays = [("prior", (F, 4), np.float64)], {"prior": call["priors"][a:b]}
+    if call["samples"] is not None:
+        extra.append(("samples", (F, Cn, H, 3), np.int32))
+        arrays["samples"] = _pack_samples(call["samples"][a:b], F, Cn, H)
+    st = resident_rows_stage(ctx, call["pts"][a:b], extra, arrays)
+    st.update(k=k, a=a, b=b, side=[st["din"], st["tri"], st["dt"]])                 # (side: the blocks stream.free_blocks releases)
+    call["inflight"].append(st)
+    try:
+        din, total, max_feat = st["din"], st["total"], int(st["cnt"].max())
+        FC = (F, Cn) if budgets is None else (F, Cn, B)
+        out = st["out"] = ctx.block([("ransac_height", FC, np.float64), ("model", FC + (4,), np.float64), ("best_ic", FC, np.int32), ("used", FC, np.int32),
+                                     ("n_selected", F, np.int32), ("n_inliers", FC, np.int32), ("refined_normal", FC + (3,), np.float64),
+                                     ("refined_pitch", FC, np.float64), ("refined_mean", FC, np.float64), ("refined_std", FC, np.float64),
+                                     ("height_t_mean", FC, np.float64), ("sum_y", FC, np.float64), ("sum_z", FC, np.float64), ("status", FC, np.int32)] +
+                                    ([("best", FC, np.int32)] if budgets is not None else []))
+        BCF = (B, Cn, F)
+        small = st["small"] = ctx.block([(n, BCF, np.float64) for n in RESULT_FIELDS] + [("degenerate", BCF, np.uint8)] +
+                                        ([("used", BCF, np.int32), ("best", BCF, np.int32)] if budgets is not None else []) +
+                                        [("carried", F, np.uint8), ("frame_class", F, np.int32), ("source", F, np.int32), ("error", 1, np.int64)])
+        st["side"].append(small)
+        out.zero()
+        hb = st["header"] = _lib.Batch()
+        hb.n_frames, hb.feat_off, hb.feat_cnt = F, din["feat_off"].ptr, din["feat_cnt"].ptr
+        hb.x, hb.v, hb.z = din["u"].ptr, din["v"].ptr, din["z"].ptr
+        hb.tri1_off, hb.tri1, hb.tri1_cnt = din["tri_off"].ptr, st["tri"]["tri"].ptr, st["dt"]["tri_cnt"].ptr
+        hb.max_feat, hb.total_feat = max_feat, total
+        st["params"] = _lib.HeightPitchEvalParams(ev.focus, ev.cx, ev.cy, MIN_POINTS, H, ev.threshold, GOAL_FRACTION, ev.inlier_threshold,
+                                                  ev.seed, int(a), EVAL_MODELS[ev.model], Cn, ev.cases_per_group)
+        o = st["outputs"] = _lib.HeightPitchEvalOutputs() if budgets is None else _lib.HeightPitchEvalBudgetsOutputs()
+        for n, _ in o._fields_:                                                       # (list_mask, point_list, hyp_counts: NULL — run() reads none)
+            if n in out:
+                setattr(o, n, out[n].ptr)
+        ti = st["tail_in"] = _lib.HeightPitchEvalTailInputs()
+        for n, _ in ti._fields_:
+            setattr(ti, n, out[n].ptr if n in out and (budgets is not None or n != "used") else None)
+        to = st["tail_out"] = _lib.HeightPitchEvalTailOutputs()
+        for n, _ in to._fields_:
+            setattr(to, n, small[n].ptr if n in small else None)
+        _eval_resident_kernel(ev, call, st)
+        while len(call["chain"]) < k + 2:                                              # chunk k: chain[k] -> chain[k + 1]
+            call["chain"].append(ctx.empty(len(call["carry0"]), np.uint8))
+        _eval_resident_tail(ev, call, st, F)
+        for blk in (din, st["tri"], out):
+            blk.mark(True)
+    except BaseException:
+        call["inflight"].remove(st)
+        stream.free_blocks(st)
+        raise
+    return st
+
+
+def _eval_resident_kernel(ev, call, st):
+    ctx, din = ev.ctx, st["din"]
+    sp = din["samples"].ptr if "samples" in din else None
+    if call["budgets"] is None:
+        _lib.check(ctx.lib.mvosr_height_pitch_eval_batch(ctx.handle, C.byref(st["header"]), C.byref(st["params"]), din["prior"].ptr, sp,
+                                                         C.byref(st["outputs"])), "mvosr_height_pitch_eval_batch")
+    else:
+        _lib.check(ctx.lib.mvosr_height_pitch_eval_budgets_batch(ctx.handle, C.byref(st["header"]), C.byref(st["params"]), call["bud"], call["B"],
+                                                                 din["prior"].ptr, sp, C.byref(st["outputs"])),
+                   "mvosr_height_pitch_eval_budgets_batch")
+
+
+def _eval_resident_tail(ev, call, st, n_frames, download=True):
+    """``mvosr_height_pitch_eval_tail_batch`` over the chunk's first ``n_frames`` frames, then (``download``) the chunk's result block and
+    the triangulation's status words on their way to page-locked memory, as ``HeightPitchEstimator._resident_tail``."""
+    ctx, small = ev.ctx, st["small"]
+    _lib.check(ctx.lib.mvosr_height_pitch_eval_tail_batch(ctx.handle, int(n_frames), ev.cases, call["B"], MIN_POINTS, C.byref(st["tail_in"]),
+                                                          st["din"]["prior"].ptr, call["chain"][st["k"]].ptr, call["chain"][st["k"] + 1].ptr,
+                                                          C.byref(st["tail_out"])), "mvosr_height_pitch_eval_tail_batch")
+    st["tail_frames"] = int(n_frames)
+    for blk in (st["dt"], small) if download else ():
+        blk.mark(False)
+        if ev.GPU_SIDE_DOWNLOADS:
+            blk.mark_done()
+        else:
+            blk.prefetch()
+        blk.mark(True)
+
+
+def _eval_resident_redo(ev, call, st, declined):
+    """``HeightPitchEstimator._resident_redo``'s scheme: SciPy's rows into the declined frames' slots, the evaluation launch again
+    over the chunk, then this chunk's tail and the tail of every chunk queued behind it (their carry-in changed)."""
+    for blk in (st["din"], st["tri"], st["out"]):
+        blk.mark(False)
+    stop = patch_declined_rows(ev.ctx, st, [call["pts"][st["a"] + f] for f in declined], declined, ev.delaunay_workers)
+    _eval_resident_kernel(ev, call, st)
+    n = st["b"] - st["a"] if stop is None else stop[0]
+    if n > 0:
+        _eval_resident_tail(ev, call, st, n)
+    if stop is None:
+        for later in call["inflight"]:
+            if later["k"] > st["k"]:
+                _eval_resident_tail(ev, call, later, later["b"] - later["a"])
+    for blk in (st["din"], st["tri"], st["out"]):
+        blk.mark(True)
+    return stop
+
+
+def _eval_resident_collect(ev, call, st):
+    """Wait for the chunk's results, send its declined frames through the host, copy the final frames into the call's arrays and
+    raise where the host loop raises."""
+    cnt, F, a, budgets = st["cnt"], st["b"] - st["a"], st["a"], call["budgets"]
+    dt_status = st["dt"]["dt_status"].download()
+    declined = [f for f in range(F) if dt_status[f] != 0 and cnt[f] >= 3]
+    ev.declined_total += len(declined) + int(np.count_nonzero(cnt < 3))
+    stop = _eval_resident_redo(ev, call, st, declined) if declined else None
+    n = F if stop is None else stop[0]
+    small = st["small"]
+    err = int(small["error"].download()[0]) if n else -1
+    kind, bud, bad = eval_tail_error(err)
+    bad = n if not kind else bad
+    call["dt_status"].append(dt_status)
+    call["errors"].append(err)
+    if bad:
+        B, Cn = call["B"], ev.cases
+        part = lambda name: small[name].download().reshape(-1)[:B * Cn * n].reshape(B, Cn, n)[:, :, :bad]   # (laid out for the n frames the tail ran over)
+        for name in RESULT_FIELDS:
+            call["out"][name][:, :, a:a + bad] = part(name)
+        ev.degenerate.reshape(B, Cn, -1)[:, :, a:a + bad] = part("degenerate") != 0
+        ev.carried[a:a + bad] = small["carried"].download()[:bad] != 0
+        if budgets is not None:
+            ev.used[:, :, a:a + bad], ev.best[:, :, a:a + bad] = part("used"), part("best")
+    call["inflight"].remove(st)
+    stream.free_blocks(st)
+    i = a + bad                                                                      # the dump the host loop raises at
+    if kind == _lib.HPT_ERR_SINGULAR:
+        raise np.linalg.LinAlgError("Singular matrix")                               # :101
+    if kind in (_lib.HPT_ERR_MASK, _lib.HPT_ERR_EMPTY):
+        raise ValueError("frame %d: %s" % (i, "no features or no triangles" if kind == _lib.HPT_ERR_EMPTY else
+                                           "a triangle names a vertex outside the frame"))
+    if kind == _lib.HPT_ERR_NO_MODEL:
+        raise ValueError("frame %d: no sample of the RANSAC had an inlier" % i + ("" if budgets is None else " at budget %d" % budgets[bud]))
+    if kind == _lib.HPT_ERR_NO_PREVIOUS:                                             # :188 indexes the 1-D norm_prev of :55 with two indices
+        raise IndexError("too many indices for array: array is 1-dimensional, but 2 were indexed")
+    if kind:
+        raise RuntimeError("frame %d: the tail stopped with error %d" % (i, kind))
+    if stop is not None:
+        raise stop[1]
+    return n
+
+
+def _eval_resident_call(ev, H, budgets, frames, ests, samples):
+    """A resident run's state: the frames as float64 arrays, the priors, the empty carry record, and the arrays ``run`` returns —
+    the object's ``carried`` / ``degenerate`` (/ ``used`` / ``best``) set up as the staged run sets them up."""
+    n, Cn, B = len(frames), ev.cases, 1 if budgets is None else len(budgets)
+    ev.carried = np.zeros(n, dtype=bool)
+    ev.degenerate = np.zeros((Cn, n) if budgets is None else (B, Cn, n), dtype=bool)
+    if budgets is not None:
+        ev.used, ev.best = np.zeros((B, Cn, n), dtype=np.int32), np.full((B, Cn, n), -1, dtype=np.int32)
+    empty = np.zeros((0, 3), dtype=np.float64)
+    return {"pts": [np.ascontiguousarray(np.asarray(p, dtype=np.float64).reshape(-1, 3)) if np.asarray(p).size else empty for p in frames],
+            "priors": np.array([frame_prior(e) for e in ests], dtype=np.float64).reshape(n, 4), "samples": samples, "H": H, "B": B,
+            "budgets": budgets, "bud": None if budgets is None else (C.c_int32 * B)(*budgets), "carry0": eval_carry_record(Cn, B),
+            "chain": [], "inflight": [], "dt_status": [], "errors": [], "out": {k: np.zeros((B, Cn, n), dtype=np.float64) for k in RESULT_FIELDS}}
+
+
+def _eval_resident_run(ev, H, budgets, frames, motion_ts, samples, batch):
+    """``run`` of both evaluation objects with the frames device-resident: the runs of non-empty dumps as chunks through ``stream.run``,
+    per chunk ONE upload, ``mvosr_delaunay_batch`` -> the evaluation launch -> ``mvosr_height_pitch_eval_tail_batch`` on the context's
+    stream, and the (B, cases, frames) arrays ``run`` returns coming back as they are.  -> dict field -> (B, cases, frames)."""
+    ctx, n = ev.ctx, len(frames)
+    ests = estimated_pitches(motion_ts, 1, n) if n else np.zeros(0)
+    runs = _nonempty_runs(frames, batch)
+    _eval_resident_refusals(ev, H, budgets, frames, runs)
+    call = _eval_resident_call(ev, H, budgets, frames, ests, samples)
+    if not runs:
+        return call["out"]
+    try:
+        call["chain"].append(ctx.to_device(call["carry0"]))
+        stream.run(((idx[0], idx[-1] + 1, None) for idx in runs), lambda a, b, tables, k: _eval_resident_start(ev, call, a, b, k),
+                   lambda st, a, b, last: _eval_resident_collect(ev, call, st), ev.GPU_PIPELINE,
+                   lambda st: stream.free_blocks(st), [], lambda: None)
+    finally:
+        for buf in call["chain"]:
+            buf.free()
+        ev.last = {"dt_status": call["dt_status"], "errors": call["errors"]}
+    return call["out"]
+
+
 class RansacEvaluation:
     """``calculate_height_pitch_eval.py`` (model "plane") and ``calculate_height_pitch_eval_line.py`` ("line"): the sequence run
     ``cases`` times with ``iterations`` hypotheses per frame, every case with a sample sequence of its own.  One launch per batch of
-    frames covers all cases; the scripts' cross-frame rules are applied per case on the host."""
+    frames covers all cases; the scripts' cross-frame rules are applied per case on the host — or, with ``triangulation="gpu",
+    resident=True``, on the device, the frames resident from their upload to the arrays ``run`` returns: the same
+    results, ``carried`` and ``degenerate`` byte for byte; ``tris=`` is refused there, and ``last`` holds status and error words only."""
+
+
+    # the device-resident path (resident=True; DESIGN.md §3.27): off unless asked for, its chunk pipeline's knobs (stream.StreamKnobs;
+    # tests and profiles override them per instance) and its count of frames whose rows came from the host (or that have < 3 points)
+    resident = False
+    declined_total = 0
+    GPU_PIPELINE = stream.StreamKnobs.GPU_PIPELINE
+    GPU_SIDE_DOWNLOADS = stream.StreamKnobs.GPU_SIDE_DOWNLOADS
 
     def __init__(self, model, iterations, cases=10, focus=FOCUS, cx=CX, cy=CY, threshold=0.005, inlier_threshold=0.01, seed=None,
-                 device=0, triangulation="scipy", cases_per_group=None, delaunay_workers=0):
+                 device=0, triangulation="scipy", cases_per_group=None, delaunay_workers=0, resident=False):
         if model not in EVAL_MODELS:
             raise ValueError("model must be 'plane' or 'line'")
         if triangulation not in ("scipy", "gpu"):
             raise ValueError("triangulation must be 'scipy' or 'gpu'")
+        if resident:                                   # opt-in; without it no attribute of the instance is new
+            if triangulation != "gpu":
+                raise ValueError(RESIDENT_ERROR)
+            self.resident, self.declined_total = True, 0
         if not 1 <= int(iterations) <= MAX_EVAL_ITERATIONS:
             raise ValueError("iterations must be in 1..%d" % MAX_EVAL_ITERATIONS)
         if int(cases) < 1:
@@ -737,6 +1009,12 @@ class RansacEvaluation:
         the new prior (:184-186, :223); a first fitted frame with too few points raises ``IndexError`` (:188), a singular row
         ``np.linalg.LinAlgError`` (:101).  Where the refinement's sample names a vertex twice, the refined values are NaN
         (``self.degenerate``); the RANSAC height and the inlier number are not affected."""
+        if self.resident:
+            if tris is not None:
+                raise ValueError("resident=True triangulates on the device: tris= belongs to the staged path")
+            out = _eval_resident_run(self, self.iterations, None, frames, motion_ts, samples, batch)
+            self.results = {k: v[0] for k, v in out.items()}
+            return self.results
         n, Cn = len(frames), self.cases
         ests = estimated_pitches(motion_ts, 1, n) if n else np.zeros(0)
         out = {k: np.zeros((Cn, n), dtype=np.float64) for k in RESULT_FIELDS}
@@ -809,14 +1087,27 @@ class RansacBudgetSweep:
     :class:`RansacEvaluation` at every iteration budget of ``budgets`` from ONE launch per batch of frames
     (``mvosr_height_pitch_eval_budgets_batch``).  The sample sequence of a (frame, case) does not depend on the
     budget, so the run at budget b is the first b hypotheses of the run at the largest: row k of every result equals, bit for bit,
-    ``RansacEvaluation(model, budgets[k], cases, seed=seed, ...)`` on the same inputs (recorded ``samples`` cut to that budget)."""
+    ``RansacEvaluation(model, budgets[k], cases, seed=seed, ...)`` on the same inputs (recorded ``samples`` cut to that budget).
+    ``triangulation="gpu", resident=True``: as :class:`RansacEvaluation`'s, ``used`` and ``best`` included."""
+
+
+    # the device-resident path (resident=True; DESIGN.md §3.27): off unless asked for, its chunk pipeline's knobs (stream.StreamKnobs;
+    # tests and profiles override them per instance) and its count of frames whose rows came from the host (or that have < 3 points)
+    resident = False
+    declined_total = 0
+    GPU_PIPELINE = stream.StreamKnobs.GPU_PIPELINE
+    GPU_SIDE_DOWNLOADS = stream.StreamKnobs.GPU_SIDE_DOWNLOADS
 
     def __init__(self, model, budgets, cases=10, focus=FOCUS, cx=CX, cy=CY, threshold=0.005, inlier_threshold=0.01, seed=None,
-                 device=0, triangulation="scipy", cases_per_group=None, delaunay_workers=0):
+                 device=0, triangulation="scipy", cases_per_group=None, delaunay_workers=0, resident=False):
         if model not in EVAL_MODELS:
             raise ValueError("model must be 'plane' or 'line'")
         if triangulation not in ("scipy", "gpu"):
             raise ValueError("triangulation must be 'scipy' or 'gpu'")
+        if resident:                                   # opt-in; without it no attribute of the instance is new
+            if triangulation != "gpu":
+                raise ValueError(RESIDENT_ERROR)
+            self.resident, self.declined_total = True, 0
         self.budgets = check_budgets(budgets)
         if int(cases) < 1:
             raise ValueError("cases must be at least 1")
@@ -849,6 +1140,11 @@ class RansacBudgetSweep:
         dump, the carried frame under the new prior, the first frame's ``IndexError``, ``LinAlgError`` — apply per (budget, case).
         Where a single run would raise "no sample of the RANSAC had an inlier", so does this, naming the frame and the smallest
         such budget."""
+        if self.resident:
+            if tris is not None:
+                raise ValueError("resident=True triangulates on the device: tris= belongs to the staged path")
+            self.results = _eval_resident_run(self, self.budgets[-1], self.budgets, frames, motion_ts, samples, batch)
+            return self.results
         n, Cn, B = len(frames), self.cases, len(self.budgets)
         ests = estimated_pitches(motion_ts, 1, n) if n else np.zeros(0)
         out = {k: np.zeros((B, Cn, n), dtype=np.float64) for k in RESULT_FIELDS}
