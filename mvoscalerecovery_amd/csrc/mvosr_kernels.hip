@@ -24,6 +24,7 @@
 #include <stdint.h>
 #include <stdlib.h>
 #include <string.h>
+#include <type_traits>
 
 #include "../../include/mvosr.h"
 #include "mvosr_device.hpp"
@@ -459,11 +460,16 @@ struct PitchTest {
 
 // One triangle of the first sweep (:229-240): bit 0 = pitch_deg < thr (flat), bit 1 = pitch_deg >= thr,
 // bit 2 = exactly singular.  `h` is the triangle's mean y' (only written out in FULL mode).
-template <bool FULL>
-__device__ __forceinline__ int classify_triangle(double x0, double y0, double z0, double x1, double y1, double z1,
-                                                 double x2, double y2, double z2, double h, const PitchTest &pt,
-                                                 double *g_normals, double *g_pitch, double *g_heights, int64_t tg) {
-    bool is_flat = false, is_steep = false, is_singular = false;
+//
+// classify_row is the test itself: it returns bits 0 and 1 only, and the reference's formulation's own word (bits 0 to 2;
+// bit 3 is the fact that it ran) is handed to `on_rare` INSIDE the branch that evaluated it.  That branch holds a call (or, FULL, the
+// outputs' stores) and stays a branch, so a caller that accumulates the rare bits there pays nothing for them on a
+// decided row; returned in the row's word they are merged behind the branch and masked, compared and selected per row.
+template <bool FULL, class Rare>
+__device__ __forceinline__ int classify_row(double x0, double y0, double z0, double x1, double y1, double z1,
+                                            double x2, double y2, double z2, double h, const PitchTest &pt,
+                                            double *g_normals, double *g_pitch, double *g_heights, int64_t tg, Rare on_rare) {
+    bool is_flat = false, is_steep = false;
     bool decided = false;
     if constexpr (!FULL) {
         // The plane n.p = 1 through the vertices has n = c / det with c = (p1-p0) x (p2-p0) and
@@ -492,7 +498,6 @@ __device__ __forceinline__ int classify_triangle(double x0, double y0, double z0
     if (!decided) {
         double nx, ny, nz, pitch;
         const int r = pitch_reference<FULL>(x0, y0, z0, x1, y1, z1, x2, y2, z2, pt.thr_deg, nx, ny, nz, pitch);
-        is_singular = r & 4;
         is_flat = r & 1;
         is_steep = r & 2;
         if constexpr (FULL) {
@@ -500,10 +505,21 @@ __device__ __forceinline__ int classify_triangle(double x0, double y0, double z0
             if (g_pitch) g_pitch[tg] = pitch;
             if (g_heights) g_heights[tg] = h;
         }
+        // bit 3: decided by the reference's own formulation — the one place where the ROTATION of the row (the order LAPACK's LU sees the
+        // vertices in) can move the outcome: a caller whose rows are stand-ins for SciPy's (same triangles, other rotation) redoes the frame
+        on_rare(r);
     }
-    // bit 3: decided by the reference's own formulation — the one place where the ROTATION of the row (the order LAPACK's LU sees the
-    // vertices in) can move the outcome: a caller whose rows are stand-ins for SciPy's (same triangles, other rotation) redoes the frame
-    return (is_flat ? 1 : 0) | (is_steep ? 2 : 0) | (is_singular ? 4 : 0) | (decided ? 0 : 8);
+    return (is_flat ? 1 : 0) | (is_steep ? 2 : 0);
+}
+// The row's whole word: bits 0, 1 and, merged behind the rare branch, 2 and 3.
+template <bool FULL>
+__device__ __forceinline__ int classify_triangle(double x0, double y0, double z0, double x1, double y1, double z1,
+                                                 double x2, double y2, double z2, double h, const PitchTest &pt,
+                                                 double *g_normals, double *g_pitch, double *g_heights, int64_t tg) {
+    bool is_singular = false, decided = true;
+    const int r = classify_row<FULL>(x0, y0, z0, x1, y1, z1, x2, y2, z2, h, pt, g_normals, g_pitch, g_heights, tg,
+                                     [&](int bits) { is_singular = bits & 4; decided = false; });
+    return r | (is_singular ? 4 : 0) | (decided ? 0 : 8);
 }
 
 // The heights of the frame's STEEP triangles (pitch_deg >= thr, :239) in the row order of tri2, one at a time and
@@ -658,6 +674,110 @@ struct LdsFetch {            // rows of tri2 index the compacted survivors in LD
 // that magnitude)
 constexpr double kLevelGuard = 1e-12;
 
+// phase_select's per-thread bookkeeping: which of my rows are flat, the steep rows' sums and count, and what a frame is
+// refused or redone for.  Two forms with the same results, bit for bit (the floating-point operations, their operands
+// and their order are the same); kLeanRows says which one a kernel takes.
+//
+// The per-row form: every row updates every item.
+template <int MODE, int FW>
+struct RowBook {
+    unsigned long long flat = 0ull;          // bit kk: my kk-th triangle has pitch_deg < thr
+    unsigned long long flat_hi = 0ull;       // bits 64..127 (FW == 2: dense frames, up to 128 triangles per thread)
+    double hsum = 0.0, hcnt = 0.0, habs = 0.0;
+    int npitch = 0, singular = 0, bad = 0;
+    int undecided = 0;       // HOT: a triangle inside the pitch test's band (classified by the reference's formulation): the frame joins the redo list
+    __device__ __forceinline__ void refuse() { bad = 1; }
+    __device__ __forceinline__ void out_of_range() { bad = 1; }
+    template <bool FULL>
+    __device__ __forceinline__ void row(double x0, double y0, double z0, double x1, double y1, double z1, double x2, double y2, double z2,
+                                        double h, const PitchTest &pt, double *g_normals, double *g_pitch, double *g_heights, int64_t tg, int kk) {
+        const int r = classify_triangle<FULL>(x0, y0, z0, x1, y1, z1, x2, y2, z2, h, pt, g_normals, g_pitch, g_heights, tg);
+        const bool is_flat = r & 1, is_steep = r & 2;
+        if (r & 4) singular = 1;
+        if constexpr (MODE == MODE_HOT) { if (r & 8) undecided = 1; }
+        if (is_steep) { hsum += h; hcnt += 1.0; if constexpr (MODE == MODE_HOT) habs += fabs(h); }     // :240
+        if (is_flat) {
+            if (FW == 1 || kk < 64) flat |= 1ull << (kk & 63); else flat_hi |= 1ull << (kk & 63);
+            ++npitch;
+        }
+    }
+    __device__ __forceinline__ void end_trip(int) {}
+    template <int B>
+    __device__ __forceinline__ void close(int, int) {}
+    __device__ __forceinline__ void begin_marks() {}
+    __device__ __forceinline__ bool flat_at(int kk) const {
+        const unsigned long long fw = (FW == 1 || kk < 64) ? flat : flat_hi;
+        return (fw >> (kk & 63)) & 1ull;
+    }
+    __device__ __forceinline__ void end_mark_trip(int) {}
+};
+
+// The lean form, for the product (HOT) kernels with one 64-bit flag word per thread: a decided row costs a select and the
+// sums' adds, and one select and one shift-or for its flag.
+//  - The row index kk is the same for the whole workgroup, so the flag word is two 32-bit halves: the half in use is `cur`, a
+//    row's flag goes into it with a scalar shift, and a uniform branch files it behind row 31 (never taken when a thread
+//    has at most 32 rows, as in the product shapes).
+//  - The steep rows are not counted: they are my rows less the flat ones (a popcount, once) and the rare "neither" ones.
+//    A small integer is exact as a double and sums of such are exact in any order.
+//  - The sums take one select and plain adds: they start at +0.0, a sum of doubles that starts there is never -0.0, so
+//    adding +0.0 for a row that is not steep leaves every bit as it is.  (Not h times 0 or 1: inf * 0 is NaN.)
+//  - What no decided row touches lives in `rare` and is written behind the rare branches only: the number of my rows that
+//    are neither flat nor steep (out-of-range ids, NaN pitch; at most 64: the low byte, so that a row adds an inline
+//    constant) and three flags above it (undecided: a triangle inside the pitch test's band, the frame joins the redo list).
+constexpr int kRareNeither = 1, kRareNeitherMask = 0xFF, kRareSingular = 0x100, kRareUndecided = 0x200, kRareBad = 0x400;
+struct LeanRowBook {
+    unsigned lo = 0u, hi = 0u;      // rows 0..31 and 32..63, once filed
+    unsigned cur = 0u;
+    double hsum = 0.0, hcnt = 0.0, habs = 0.0;
+    int rare = 0;
+    int npitch = 0, singular = 0, bad = 0, undecided = 0;      // (formed by close())
+    __device__ __forceinline__ void refuse() { rare = kRareBad; }
+    __device__ __forceinline__ void out_of_range() {
+        asm volatile("" : "+v"(rare));           // (a skipped region, as in div3)
+        rare = (rare | kRareBad) + kRareNeither;
+    }
+    template <bool FULL>
+    __device__ __forceinline__ void row(double x0, double y0, double z0, double x1, double y1, double z1, double x2, double y2, double z2,
+                                        double h, const PitchTest &pt, double *g_normals, double *g_pitch, double *g_heights, int64_t tg, int kk) {
+        asm volatile("" :: "v"(h));      // (formed here: sunk behind the test, the three y' stay live across the rare branch's call)
+        const int r = classify_row<FULL>(x0, y0, z0, x1, y1, z1, x2, y2, z2, h, pt, g_normals, g_pitch, g_heights, tg, [&](int bits) {
+            rare = (rare | ((bits & 4) ? kRareSingular : 0) | kRareUndecided) + ((bits & 3) ? 0 : kRareNeither);
+        });
+        const bool is_flat = r & 1, is_steep = r & 2;
+        const double hs = is_steep ? h : 0.0;                                                          // :240
+        hsum += hs;
+        habs += fabs(hs);
+        cur |= (is_flat ? 1u : 0u) << (kk & 31);
+    }
+    // behind the trip of rows kk0 .. kk0 + kTC - 1.  (At the end of the low half's last trip, not at the start of the high
+    // half's first: a test that singles out the first trip makes the compiler peel it, and the sweep's body is in the
+    // listing twice.  A skipped region, as in div3: if-converted, the filing's moves run in every trip.)
+    __device__ __forceinline__ void end_trip(int kk0) {
+        static_assert(32 % kTC == 0, "a trip's rows share one flag half");
+        if (kk0 + kTC == 32) { asm volatile("" : "+v"(cur)); lo = cur; cur = 0u; }
+    }
+    // behind the sweep: the half the last trip was in, the counts and the flags
+    template <int B>
+    __device__ __forceinline__ void close(int t2_count, int tid) {
+        if (t2_count > 32 * B) hi = cur; else lo |= cur;              // (uniform; exactly 32 B rows: filed already, cur is 0)
+        npitch = __popc(lo) + __popc(hi);
+        const int my_rows = (t2_count + B - 1 - tid) / B;           // t = tid, tid + B, ... below t2_count
+        hcnt = (double)(my_rows - npitch - (rare & kRareNeitherMask));
+        singular = rare & kRareSingular ? 1 : 0;
+        bad = rare & kRareBad ? 1 : 0;
+        undecided = rare & kRareUndecided ? 1 : 0;
+    }
+    __device__ __forceinline__ void begin_marks() { cur = lo; }
+    __device__ __forceinline__ bool flat_at(int kk) const { return (cur >> (kk & 31)) & 1u; }
+    __device__ __forceinline__ void end_mark_trip(int kk0) {
+        if (kk0 + kTC == 32) { asm volatile("" : "+v"(cur)); cur = hi; }
+    }
+};
+// The lean form where the compiled kernel needs no more registers with it than with the per-row form (profiles/valu_report.py;
+// LABNOTES 3.1): the product's 4- and 8-wavefront HOT kernels.
+template <int WAVES, int MODE, int FW>
+constexpr bool kLeanRows = MODE == MODE_HOT && FW == 1 && (WAVES == 4 || WAVES == 8);
+
 template <int WAVES, int MODE, int FW = 1>
 __device__ __forceinline__ SelectResult phase_select(const Smem &s, int n_valid, const int32_t *tri2, int64_t t2_begin,
                                                      int t2_count, TriChunk<WAVES * kWave> &tc, PitchTest pt,
@@ -666,16 +786,14 @@ __device__ __forceinline__ SelectResult phase_select(const Smem &s, int n_valid,
     constexpr int B = WAVES * kWave;
     constexpr bool FULL = MODE == MODE_FULL;
     const int tid = threadIdx.x;
-    unsigned long long flat = 0ull;          // bit kk: my kk-th triangle has pitch_deg < thr
-    unsigned long long flat_hi = 0ull;       // bits 64..127 (FW == 2: dense frames, up to 128 triangles per thread)
-    double hsum = 0.0, hcnt = 0.0, habs = 0.0;
-    int npitch = 0, singular = 0, bad = 0;
-    int undecided = 0;       // HOT: a triangle inside the pitch test's band (classified by the reference's formulation): the frame joins the redo list
+    typename std::conditional<kLeanRows<WAVES, MODE, FW>, LeanRowBook, RowBook<MODE, FW>>::type bk;
+    double &hsum = bk.hsum, &hcnt = bk.hcnt, &habs = bk.habs;
+    int &npitch = bk.npitch, &singular = bk.singular, &bad = bk.bad;
     // more rows than the per-thread flag words can name (not a triangulation of this frame's points): refuse
-    if (t2_count > 64 * FW * B) { bad = 1; t2_count = 0; }
+    if (t2_count > 64 * FW * B) { bk.refuse(); t2_count = 0; }
     // One triangle of the first sweep (:229-240).
     auto test_triangle = [&](int t, int kk, const TriIds q) {
-    if ((unsigned)q.a >= (unsigned)n_valid || (unsigned)q.b >= (unsigned)n_valid || (unsigned)q.c >= (unsigned)n_valid) { bad = 1; return; }
+    if ((unsigned)q.a >= (unsigned)n_valid || (unsigned)q.b >= (unsigned)n_valid || (unsigned)q.c >= (unsigned)n_valid) { bk.out_of_range(); return; }
     const double2 p0 = s.P[q.a], p1 = s.P[q.b], p2 = s.P[q.c];      // {x, z'}
     const double y0 = s.Y[q.a], y1 = s.Y[q.b], y2 = s.Y[q.c];
     const double x0 = p0.x, z0 = p0.y, x1 = p1.x, z1 = p1.y, x2 = p2.x, z2 = p2.y;
@@ -683,15 +801,7 @@ __device__ __forceinline__ SelectResult phase_select(const Smem &s, int n_valid,
     // with a flat triangle inside it is redone in the EXACT variant), which is ~10^4 roundings wide — so the division
     // by 3 per triangle, and its rounding, are left out of both sweeps.
     const double h = MODE == MODE_HOT ? (y0 + y1) + y2 : div3((y0 + y1) + y2);
-    const int r = classify_triangle<FULL>(x0, y0, z0, x1, y1, z1, x2, y2, z2, h, pt, g_normals, g_pitch, g_heights, t2_begin + t);
-    const bool is_flat = r & 1, is_steep = r & 2;
-    if (r & 4) singular = 1;
-    if constexpr (MODE == MODE_HOT) { if (r & 8) undecided = 1; }
-    if (is_steep) { hsum += h; hcnt += 1.0; if constexpr (MODE == MODE_HOT) habs += fabs(h); }     // :240
-    if (is_flat) {
-        if (FW == 1 || kk < 64) flat |= 1ull << (kk & 63); else flat_hi |= 1ull << (kk & 63);
-        ++npitch;
-    }
+    bk.template row<FULL>(x0, y0, z0, x1, y1, z1, x2, y2, z2, h, pt, g_normals, g_pitch, g_heights, t2_begin + t, kk);
     };
     // `tc` comes with the first chunk of tri2 in flight (phase_vote issued it before the compaction); its wait is
     // taken in front of the loop.  The next chunk streams in while the current one is processed: inside the
@@ -706,8 +816,10 @@ __device__ __forceinline__ SelectResult phase_select(const Smem &s, int n_valid,
             const int t = base + k * B + tid;
             if (t < t2_count) test_triangle(t, base / B + k, tc.q[k]);
         }
+        bk.end_trip(base / B);       // (in front of the chunk's copy: the trip's wait for the next rows stays the last thing in it)
         if (more) tc = tn;
     }
+    bk.template close<B>(t2_count, tid);
     // second sweep: its first chunk is re-read now, under the reduction's barrier (unless the whole
     // triangulation was one chunk and is still in registers)
     const bool in_regs = t2_count <= kTC * B;
@@ -726,10 +838,10 @@ __device__ __forceinline__ SelectResult phase_select(const Smem &s, int n_valid,
         else
             hl = exact_height_level<FULL>(tri2 + 3 * t2_begin, t2_count, (int)hcnt, pt, LdsFetch{s.P, s.Y, n_valid});
     }
-    int ntv = 0, near = undecided;
+    int ntv = 0, near = bk.undecided;
+    bk.begin_marks();
     auto mark_triangle = [&](int kk, int qa, int qb, int qc) {
-        const unsigned long long fw = (FW == 1 || kk < 64) ? flat : flat_hi;
-        if (!((fw >> (kk & 63)) & 1ull)) return;
+        if (!bk.flat_at(kk)) return;
         const double y0 = s.Y[qa], y1 = s.Y[qb], y2 = s.Y[qc];
         const double h = MODE == MODE_HOT ? (y0 + y1) + y2 : div3((y0 + y1) + y2);           // HOT: 3h against 3 * level
         if constexpr (MODE == MODE_HOT) { if (fabs(h - hl) <= guard) near = 1; }
@@ -750,6 +862,7 @@ __device__ __forceinline__ SelectResult phase_select(const Smem &s, int n_valid,
         for (int k = 0; k < kTC; ++k) {
             if (base + k * B + tid < t2_count) mark_triangle(base / B + k, tc.q[k].a, tc.q[k].b, tc.q[k].c);
         }
+        bk.end_mark_trip(base / B);
         if (more) tc = tn;
     }
     bad |= bad_in;
