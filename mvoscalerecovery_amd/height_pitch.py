@@ -15,7 +15,8 @@ a frame with fewer than 12 list points repeats the previous frame's plane and in
 :class:`HeightPitchEstimator`.  The triangulation's rows are built on the host (SciPy) or on the device and visit the
 host either way on the default path; ``HeightPitchEstimator(triangulation="gpu", resident=True)`` keeps a call's frames on the
 device from their upload to the six result values — rows in HBM between ``mvosr_delaunay_batch`` and the kernel, the cross-frame
-state applied by ``mvosr_height_pitch_tail_batch``, chunks streamed on the shared pipeline (``stream.py``).
+state applied by ``mvosr_height_pitch_tail_batch``, chunks streamed on the shared pipeline by the one resident driver
+(``stream.py``, ``hp_resident.py``).
 ``RansacEvaluation`` / ``RansacBudgetSweep(triangulation="gpu", resident=True)`` are on the same path with a tail of their own,
 ``mvosr_height_pitch_eval_tail_batch``, which writes the (budgets, cases, frames) arrays ``run`` returns.
 The line RANSAC of :146 is printed by the base script and never used there: the estimator does not compute it (the evaluation's
@@ -30,6 +31,7 @@ import os
 import numpy as np
 
 from . import _lib, packing, stream
+from .hp_resident import ResidentCall, _pack_planes, batch_header, frame_error, patch_declined_rows, resident_rows_stage  # noqa: F401
 
 FOCUS, CX, CY = 718.856, 607.1928, 185.2157        # calculate_height_pitch.py:15-17
 PI_SCRIPT = 3.1415926                               # :63, :91
@@ -111,18 +113,6 @@ def _delaunay_rows(ctx, pts2d, triangulation, workers):
     return rows
 
 
-def _pack_planes(pts):
-    """``_pack_frames``' feature planes and offsets from ONE concatenate over the frames -> (planes (3, total), feat_off, feat_cnt)."""
-    cnt = np.fromiter((len(p) for p in pts), dtype=np.int32, count=len(pts))
-    even = (cnt.astype(np.int64) + 1) & ~1
-    off = np.concatenate([[0], np.cumsum(even)[:-1]]).astype(np.int64)              # even segment starts
-    planes = np.zeros((3, max(int(off[-1] + even[-1]), 2)), dtype=np.float64)
-    start = np.concatenate([[0], np.cumsum(cnt.astype(np.int64))[:-1]])
-    where = np.repeat(off - start, cnt) + np.arange(int(cnt.sum()), dtype=np.int64)
-    planes[:, where] = np.concatenate(pts).T
-    return planes, off, cnt
-
-
 # mvosr_height_pitch_tail_frame, mvosr_height_pitch_carry (include/mvosr.h)
 TAIL_FRAME = np.dtype([(k, "<f8") for k in ("ransac_height", "refined_mean", "refined_std", "height_t_mean", "refined_pitch")] +
                       [(k, "<i4") for k in ("n_inliers", "n_selected", "carried", "source")])
@@ -157,58 +147,95 @@ def carry_fields(rec, cap):
             rec[y0 + 16 * cap:y0 + 16 * cap + 4 * k].view(np.int32))
 
 
-def resident_rows_stage(ctx, pts, extra_in=(), extra_arrays=None):
-    """A chunk's frames uploaded ONCE and triangulated on the device, the rows left in HBM for the kernel that consumes them:
-    -> dict with ``din`` (feat_off, feat_cnt, u, v, z, tri_off = 2 feat_off, and ``extra_in``'s arrays), ``tri`` (canonical rows at
-    3 tri_off[f], room for 2 n), ``dt`` (tri_cnt, dt_status, dt_used), ``off``, ``cnt`` and ``total``.  Everything is queued on the
-    context's stream; nothing is waited for.  (The estimator's chunks and the evaluation objects' both start here.)"""
-    planes, off, cnt = _pack_planes(pts)
-    F, total = len(pts), planes.shape[1]
-    din = ctx.block([("feat_off", F, np.int64), ("feat_cnt", F, np.int32), ("u", total, np.float64), ("v", total, np.float64),
-                     ("z", total, np.float64), ("tri_off", F, np.int64)] + list(extra_in))
-    tri = dt = None
-    try:
-        tri = ctx.block([("tri", 6 * total, np.int32)])
-        dt = ctx.block([("tri_cnt", F, np.int32), ("dt_status", F, np.int32), ("dt_used", F, np.int32)])
-        arrays = {"feat_off": off, "feat_cnt": cnt, "u": planes[0], "v": planes[1], "z": planes[2], "tri_off": 2 * off}
-        arrays.update(extra_arrays or {})
-        din.upload(arrays)
-        dt.zero()
-        _lib.check(ctx.lib.mvosr_delaunay_batch(ctx.handle, F, din["feat_off"].ptr, din["feat_cnt"].ptr, din["u"].ptr, din["v"].ptr, None,
-                                                int(cnt.max()), din["tri_off"].ptr, tri["tri"].ptr, dt["tri_cnt"].ptr, dt["dt_used"].ptr,
-                                                dt["dt_status"].ptr), "mvosr_delaunay_batch")
-    except BaseException:
-        for blk in (din, tri, dt):
-            if blk is not None:
-                blk.free()
-        raise
-    return {"din": din, "tri": tri, "dt": dt, "off": off, "cnt": cnt, "total": total}
-
-
-def patch_declined_rows(ctx, st, pts, declined, workers):
-    """The frames ``declined`` of a :func:`resident_rows_stage` chunk (``pts``: their points) through SciPy: the rows in canonical form
-    into the frames' own slots of the chunk's row slab, ``tri_cnt`` patched.  A SciPy exception: -> (its frame, the exception), the
-    frames behind it left as they were; else None."""
-    lib, off = ctx.lib, st["off"]
-    rows = packing.delaunay_many([np.ascontiguousarray(p[:, 0:2]) for p in pts], workers)
-    for f, t in zip(declined, rows):
-        if isinstance(t, Exception):
-            return f, t
-        t = np.ascontiguousarray(packing.canonical_rows(t), dtype=np.int32)
-        assert len(t) <= 2 * int(st["cnt"][f])                                      # (a planar triangulation of n points: at most 2n - 5 rows)
-        n_rows = np.array([len(t)], dtype=np.int32)
-        _lib.check(lib.mvosr_memcpy_h2d(ctx.handle, st["tri"]["tri"].ptr + 24 * int(off[f]), _lib.addr(t), t.nbytes), "h2d")
-        _lib.check(lib.mvosr_memcpy_h2d(ctx.handle, st["dt"]["tri_cnt"].ptr + 4 * f, _lib.addr(n_rows), 4), "h2d")
-    return None
-
-
 def _batch_header(din, F, max_feat, total_feat):
-    b = _lib.Batch()
-    b.n_frames, b.feat_off, b.feat_cnt = F, din["feat_off"].ptr, din["feat_cnt"].ptr
-    b.x, b.v, b.z = din["u"].ptr, din["v"].ptr, din["z"].ptr
-    b.tri1_off, b.tri1 = din["tri1_off"].ptr, din["tri1"].ptr
-    b.max_feat, b.total_feat = max_feat, total_feat
-    return b
+    return batch_header(din, F, max_feat, total_feat, din["tri1_off"].ptr, din["tri1"].ptr)
+
+
+# ---- what the staged launches and the resident chunks of all three objects share ------------------------------------------------
+def _refuse_lds(ctx, max_feat, need):
+    if need > ctx.lds_per_block:
+        raise ValueError("a frame of %d features needs %d bytes of LDS, the device has %d" % (max_feat, need, ctx.lds_per_block))
+
+
+def _refuse_beyond_triangulation(max_feat):
+    if max_feat > packing.delaunay_gpu_max_points():
+        raise ValueError("a frame of %d features is beyond the device triangulation's %d" % (max_feat, packing.delaunay_gpu_max_points()))
+
+
+def _refuse_tris(tris):
+    if tris is not None:
+        raise ValueError("resident=True triangulates on the device: tris= belongs to the staged path")
+
+
+def _float_frame(p):
+    return np.ascontiguousarray(np.asarray(p, dtype=np.float64).reshape(-1, 3))
+
+
+def _staged_frames(obj, points3d_list, tris, max_feat):
+    """A staged launch's frames as float64 arrays, their rows (``tris``, or the object's triangulation's) and the ``max_feat`` the
+    batch header states -> (pts, rows, max_feat)."""
+    pts = [_float_frame(p) for p in points3d_list]
+    rows = [np.ascontiguousarray(np.asarray(t, dtype=np.int32).reshape(-1, 3)) for t in tris] if tris is not None \
+        else _delaunay_rows(obj.ctx, [np.ascontiguousarray(p[:, 0:2]) for p in pts], obj.triangulation, obj.delaunay_workers)
+    return pts, rows, max(len(p) for p in pts) if max_feat is None else int(max_feat)
+
+
+def _staged_launch(ctx, spec_in, arrays, spec_out, call_of, timing):
+    """One staged launch: the inputs uploaded, the outputs zeroed, ``call_of(din, dout)()`` once — and, ``timing`` > 0, that often
+    again between two events (``kernel_ms``: one launch's share) —, every output downloaded -> dict of host arrays."""
+    din, dout = ctx.block(spec_in), ctx.block(spec_out)
+    try:
+        din.upload(arrays)
+        dout.zero()
+        call = call_of(din, dout)
+        call()
+        kernel_ms = None
+        if timing > 0:
+            ev = ctx.event(), ctx.event()
+            ctx.record(ev[0])
+            for _ in range(int(timing)):
+                call()
+            ctx.record(ev[1])
+            kernel_ms = ctx.elapsed_ms(*ev) / int(timing)
+            for e in ev:
+                ctx.lib.mvosr_event_destroy(ctx.handle, e)
+        res = {k: dout[k].download() for k, _, _ in spec_out}
+        if kernel_ms is not None:
+            res["kernel_ms"] = kernel_ms
+    finally:
+        din.free()
+        dout.free()
+    return res
+
+
+def _status_kind(st, n_sel):
+    """A frame's status words (one, or one per case) and its list's length as the tails' error kind (MVOSR_HPT_ERR_*), in the
+    order the host loops ask; 0: none of these."""
+    if np.any(st == ST_ERR_SINGULAR):
+        return _lib.HPT_ERR_SINGULAR
+    if np.any(st == ST_ERR_EMPTY):
+        return _lib.HPT_ERR_EMPTY
+    if np.any(st == ST_ERR_MASK):
+        return _lib.HPT_ERR_MASK
+    return _lib.HPT_ERR_NO_MODEL if np.any(st == ST_RS_FEW) and n_sel >= MIN_POINTS else 0
+
+
+def _pack_triples(triples, F, H):
+    """Recorded samples of ``F`` frames as the (F, H, 3) array the estimator's launches upload."""
+    tr = np.full((F, H, 3), -1, dtype=np.int32)                                     # (-1: outside every list, the sample is spent)
+    for f, t in enumerate(triples):
+        if t is not None and len(t):
+            t = np.asarray(t, dtype=np.int32).reshape(-1, 3)[:H]
+            tr[f, :len(t)] = t
+    return tr
+
+
+def _out_spec(F, total):
+    """``mvosr_height_pitch_batch``'s outputs over ``F`` frames whose feature planes are ``total`` long."""
+    return [("ransac_height", F, np.float64), ("model", (F, 4), np.float64), ("best_ic", F, np.int32), ("used", F, np.int32),
+            ("n_selected", F, np.int32), ("n_inliers", F, np.int32), ("refined_normal", (F, 3), np.float64),
+            ("refined_pitch", F, np.float64), ("refined_mean", F, np.float64), ("refined_std", F, np.float64),
+            ("height_t_mean", F, np.float64), ("status", F, np.int32), ("mask", total, np.uint8)]
 
 
 class HeightPitchEstimator:
@@ -243,10 +270,6 @@ class HeightPitchEstimator:
         self.results = {k: [] for k in RESULT_FIELDS}
         self.last = None                               # the last launch's per-frame device outputs (parity tests)
 
-    # ---- rows
-    def _rows_for(self, pts2d):
-        return _delaunay_rows(self.ctx, pts2d, self.triangulation, self.delaunay_workers)
-
     # ---- one launch
     def launch(self, points3d_list, priors, triples=None, tris=None, frame_base=None, stage=False, max_feat=None, timing=0):
         """``mvosr_height_pitch_batch`` over the frames -> dict of per-frame host arrays (``mask`` / ``point_list``: lists).
@@ -254,62 +277,27 @@ class HeightPitchEstimator:
         positions (None / shorter: the missing samples are spent).  ``stage``: also ``hyp_counts`` and ``point_list``.
         ``max_feat``: what the batch header states (default: the largest frame; a larger frame is refused by the kernel).
         ``timing`` > 0: the launch is repeated that often on the resident batch between two events; ``kernel_ms`` is one launch's share."""
-        ctx, lib = self.ctx, self.ctx.lib
-        pts = [np.ascontiguousarray(np.asarray(p, dtype=np.float64).reshape(-1, 3)) for p in points3d_list]
-        F, H = len(pts), self.max_iterations
+        ctx, lib, F, H = self.ctx, self.ctx.lib, len(points3d_list), self.max_iterations
         if F == 0:
             return None
-        rows = [np.ascontiguousarray(np.asarray(t, dtype=np.int32).reshape(-1, 3)) for t in tris] if tris is not None \
-            else self._rows_for([np.ascontiguousarray(p[:, 0:2]) for p in pts])
-        cnt = np.array([len(p) for p in pts], dtype=np.int32)
-        max_feat = int(cnt.max()) if max_feat is None else int(max_feat)
-        need = int(lib.mvosr_height_pitch_lds_bytes(max_feat, H))
-        if need > ctx.lds_per_block:
-            raise ValueError("a frame of %d features needs %d bytes of LDS, the device has %d" % (max_feat, need, ctx.lds_per_block))
+        pts, rows, max_feat = _staged_frames(self, points3d_list, tris, max_feat)
+        _refuse_lds(ctx, max_feat, int(lib.mvosr_height_pitch_lds_bytes(max_feat, H)))
         spec_in, arrays, off, toff, planes, T = _pack_frames(pts, rows, priors)
         if triples is not None:
-            tr = np.full((F, H, 3), -1, dtype=np.int32)                             # (-1: outside every list, the sample is spent)
-            for f, t in enumerate(triples):
-                if t is not None and len(t):
-                    t = np.asarray(t, dtype=np.int32).reshape(-1, 3)[:H]
-                    tr[f, :len(t)] = t
             spec_in.append(("triples", (F, H, 3), np.int32))
-            arrays["triples"] = tr
-        spec_out = [("ransac_height", F, np.float64), ("model", (F, 4), np.float64), ("best_ic", F, np.int32), ("used", F, np.int32),
-                    ("n_selected", F, np.int32), ("n_inliers", F, np.int32), ("refined_normal", (F, 3), np.float64),
-                    ("refined_pitch", F, np.float64), ("refined_mean", F, np.float64), ("refined_std", F, np.float64),
-                    ("height_t_mean", F, np.float64), ("status", F, np.int32), ("mask", planes.shape[1], np.uint8)]
-        if stage:
-            spec_out += [("point_list", 3 * T, np.int32), ("hyp_counts", (F, H), np.int32)]
-        din, dout = ctx.block(spec_in), ctx.block(spec_out)
-        try:
-            din.upload(arrays)
-            dout.zero()
+            arrays["triples"] = _pack_triples(triples, F, H)
+        spec_out = _out_spec(F, planes.shape[1]) + ([("point_list", 3 * T, np.int32), ("hyp_counts", (F, H), np.int32)] if stage else [])
+
+        def call_of(din, dout):
             b = _batch_header(din, F, max_feat, planes.shape[1])
             p = _lib.HeightPitchParams(self.focus, self.cx, self.cy, MIN_POINTS, H, self.threshold, GOAL_FRACTION, self.inlier_threshold,
                                        self.seed, int(self.frame_count if frame_base is None else frame_base))
             o = _lib.HeightPitchOutputs(*[(dout[k].ptr if k in dout else None) for k, _ in _lib.HeightPitchOutputs._fields_])
-            def call():
-                _lib.check(lib.mvosr_height_pitch_batch(ctx.handle, C.byref(b), C.byref(p), din["prior"].ptr,
-                                                        din["triples"].ptr if triples is not None else None, C.byref(o)),
-                           "mvosr_height_pitch_batch")
-            call()
-            kernel_ms = None
-            if timing > 0:
-                ev = ctx.event(), ctx.event()
-                ctx.record(ev[0])
-                for _ in range(int(timing)):
-                    call()
-                ctx.record(ev[1])
-                kernel_ms = ctx.elapsed_ms(*ev) / int(timing)
-                for e in ev:
-                    lib.mvosr_event_destroy(ctx.handle, e)
-            res = {k: dout[k].download() for k, _, _ in spec_out}
-            if kernel_ms is not None:
-                res["kernel_ms"] = kernel_ms
-        finally:
-            din.free()
-            dout.free()
+            return lambda: _lib.check(lib.mvosr_height_pitch_batch(ctx.handle, C.byref(b), C.byref(p), din["prior"].ptr,
+                                                                   din["triples"].ptr if triples is not None else None, C.byref(o)),
+                                      "mvosr_height_pitch_batch")
+        res = _staged_launch(ctx, spec_in, arrays, spec_out, call_of, timing)
+        cnt = arrays["feat_cnt"]
         res["mask"] = [res["mask"][off[f]:off[f] + cnt[f]].astype(bool) for f in range(F)]
         if stage:
             res["point_list"] = [res["point_list"][3 * toff[f]:3 * toff[f] + max(int(res["n_selected"][f]), 0)] for f in range(F)]
@@ -325,25 +313,19 @@ class HeightPitchEstimator:
         if len(ests) != len(points3d_list):
             raise ValueError("one estimated pitch per frame")
         if self.resident:
-            if tris is not None:
-                raise ValueError("resident=True triangulates on the device: tris= belongs to the staged path")
+            _refuse_tris(tris)
             return self._process_resident(points3d_list, ests, triples)
         res = self.launch(points3d_list, [frame_prior(e) for e in ests], triples=triples, tris=tris)
         self.last = res
         out = []
         for f, est in enumerate(ests):
-            st = int(res["status"][f])
-            if st == ST_ERR_SINGULAR:
-                raise np.linalg.LinAlgError("Singular matrix")                       # :83
-            if st in (ST_ERR_MASK, ST_ERR_EMPTY):
-                raise ValueError("frame %d: %s" % (self.frame_count, "no features or no triangles" if st == ST_ERR_EMPTY else
-                                                   "a triangle names a vertex outside the frame"))
-            n_sel = int(res["n_selected"][f])
-            if st == ST_RS_FEW and n_sel >= MIN_POINTS:
-                raise ValueError("frame %d: no sample of the RANSAC had an inlier" % self.frame_count)
+            st, n_sel = int(res["status"][f]), int(res["n_selected"][f])
+            kind = _status_kind(st, n_sel)
+            if kind:
+                raise frame_error(kind, self.frame_count)
             if st == ST_RS_FEW:
-                if self._prev is None:                                               # :167 indexes the 1-D norm_prev of :45 with two indices
-                    raise IndexError("too many indices for array: array is 1-dimensional, but 2 were indexed")
+                if self._prev is None:
+                    raise frame_error(_lib.HPT_ERR_NO_PREVIOUS, self.frame_count)
                 prev, inl = self._prev
                 # :163-165 and the surviving `inliers`: everything repeats, but :202-203 see the new prior
                 h_t = float(np.mean(inl[:, 2] * math.sin(est) + inl[:, 1] * math.cos(est)))
@@ -363,158 +345,14 @@ class HeightPitchEstimator:
         return self.process_batch([points3d], [estimated_pitch])[0]
 
     # ---- the device-resident path (resident=True) --------------------------------------------------------------
-    def _resident_start(self, call, a, b, k):
-        """Chunk ``k`` = frames ``a:b`` of the call: ONE upload, then the triangulation, the kernel and the tail queued on the
-        estimator's stream, and the download of the chunk's small records behind them.  Nothing is waited for."""
-        ctx, H, F = self.ctx, self.max_iterations, b - a
-        extra, arrays = [("prior", (F, 4), np.float64)], {"prior": call["priors"][a:b]}
-        if call["triples"] is not None:
-            tr = np.full((F, H, 3), -1, dtype=np.int32)                             # (-1: outside every list, the sample is spent)
-            for f, t in enumerate(call["triples"][a:b]):
-                if t is not None and len(t):
-                    t = np.asarray(t, dtype=np.int32).reshape(-1, 3)[:H]
-                    tr[f, :len(t)] = t
-            extra.append(("triples", (F, H, 3), np.int32))
-            arrays["triples"] = tr
-        st = resident_rows_stage(ctx, call["pts"][a:b], extra, arrays)
-        st.update(k=k, a=a, b=b, side=[st["din"], st["tri"], st["dt"]])             # (side: the blocks stream.free_blocks releases)
-        call["inflight"].append(st)
-        try:
-            din, total, max_feat = st["din"], st["total"], int(st["cnt"].max())
-            out = ctx.block([("ransac_height", F, np.float64), ("model", (F, 4), np.float64), ("best_ic", F, np.int32), ("used", F, np.int32),
-                             ("n_selected", F, np.int32), ("n_inliers", F, np.int32), ("refined_normal", (F, 3), np.float64),
-                             ("refined_pitch", F, np.float64), ("refined_mean", F, np.float64), ("refined_std", F, np.float64),
-                             ("height_t_mean", F, np.float64), ("status", F, np.int32), ("mask", total, np.uint8)])
-            st["out"] = out
-            small = st["small"] = ctx.block([("frames", F, TAIL_FRAME), ("error", 1, np.int64)])
-            st["side"].append(small)
-            out.zero()
-            hb = st["header"] = _lib.Batch()
-            hb.n_frames, hb.feat_off, hb.feat_cnt = F, din["feat_off"].ptr, din["feat_cnt"].ptr
-            hb.x, hb.v, hb.z = din["u"].ptr, din["v"].ptr, din["z"].ptr
-            hb.tri1_off, hb.tri1, hb.tri1_cnt = din["tri_off"].ptr, st["tri"]["tri"].ptr, st["dt"]["tri_cnt"].ptr
-            hb.max_feat, hb.total_feat = max_feat, total
-            st["params"] = _lib.HeightPitchParams(self.focus, self.cx, self.cy, MIN_POINTS, H, self.threshold, GOAL_FRACTION, self.inlier_threshold,
-                                                  self.seed, int(call["frame_base"] + a))
-            st["outputs"] = _lib.HeightPitchOutputs(*[(out[n].ptr if n in out else None) for n, _ in _lib.HeightPitchOutputs._fields_])
-            self._resident_kernel(st)
-            while len(call["chain"]) < k + 2:                                            # chunk k: chain[k] -> chain[k + 1]
-                call["chain"].append(ctx.empty(len(call["carry0"]), np.uint8))
-            self._resident_tail(call, st, F)
-            for blk in (din, st["tri"], out):
-                blk.mark(True)
-        except BaseException:
-            call["inflight"].remove(st)
-            stream.free_blocks(st)
-            raise
-        return st
-
-    def _resident_kernel(self, st):
-        ctx, din = self.ctx, st["din"]
-        _lib.check(ctx.lib.mvosr_height_pitch_batch(ctx.handle, C.byref(st["header"]), C.byref(st["params"]), din["prior"].ptr,
-                                                    din["triples"].ptr if "triples" in din else None, C.byref(st["outputs"])),
-                   "mvosr_height_pitch_batch")
-
-    def _resident_tail(self, call, st, n_frames, download=True):
-        """``mvosr_height_pitch_tail_batch`` over the chunk's first ``n_frames`` frames, then (``download``) the chunk's small records on
-        their way to page-locked memory — through the pipeline's side download (a copy kernel) where the knob allows it, as the rescale path."""
-        ctx, small = self.ctx, st["small"]
-        hb = _lib.Batch.from_buffer_copy(st["header"])
-        hb.n_frames = int(n_frames)
-        _lib.check(ctx.lib.mvosr_height_pitch_tail_batch(ctx.handle, C.byref(hb), C.byref(st["params"]), st["din"]["prior"].ptr,
-                                                         C.byref(st["outputs"]), call["chain"][st["k"]].ptr, call["chain"][st["k"] + 1].ptr,
-                                                         call["cap"], small["frames"].ptr, small["error"].ptr),
-                   "mvosr_height_pitch_tail_batch")
-        for blk in (st["dt"], small) if download else ():
-            blk.mark(False)
-            if self.GPU_SIDE_DOWNLOADS:
-                blk.mark_done()
-            else:
-                blk.prefetch()
-            blk.mark(True)
-
-    def _resident_redo(self, call, st, declined):
-        """The frames of the chunk the device triangulation declined: SciPy's rows in canonical form into the frames' own slots of
-        the chunk's row slab, ``tri_cnt`` patched, the kernel run again over the chunk, and the tails of this chunk and of every chunk
-        queued behind it (their carry-in changed).  A SciPy exception: -> (its frame, the exception), the tail run over the frames
-        before it only."""
-        for blk in (st["din"], st["tri"], st["out"]):
-            blk.mark(False)
-        stop = patch_declined_rows(self.ctx, st, [call["pts"][st["a"] + f] for f in declined], declined, self.delaunay_workers)
-        self._resident_kernel(st)
-        n = st["b"] - st["a"] if stop is None else stop[0]
-        if n > 0:
-            self._resident_tail(call, st, n)
-        if stop is None:
-            for later in call["inflight"]:
-                if later["k"] > st["k"]:
-                    self._resident_tail(call, later, later["b"] - later["a"])
-        for blk in (st["din"], st["tri"], st["out"]):
-            blk.mark(True)
-        return stop
-
-    def _resident_collect(self, call, st):
-        """Wait for the chunk's records, send its declined frames through the host, apply the records to the object's state in
-        sequence order, and raise where the host loop raises."""
-        cnt, F = st["cnt"], st["b"] - st["a"]
-        dt_status = st["dt"]["dt_status"].download()
-        declined = [f for f in range(F) if dt_status[f] != 0 and cnt[f] >= 3]
-        self.declined_total += len(declined) + int(np.count_nonzero(cnt < 3))
-        stop = self._resident_redo(call, st, declined) if declined else None
-        n = F if stop is None else stop[0]
-        frames = st["small"]["frames"].download()[:n] if n else np.zeros(0, dtype=TAIL_FRAME)
-        err = int(st["small"]["error"].download()[0]) if n else -1
-        kind, bad = (err >> 32, err & 0xffffffff) if err >= 0 else (0, n)
-        call["records"].append(frames[:bad])
-        call["dt_status"].append(dt_status)
-        call["errors"].append(err)
-        out = call["out"]
-        for f in range(bad):
-            r = frames[f]
-            res = FrameResult(float(r["ransac_height"]), float(r["refined_mean"]), float(r["refined_std"]), float(r["height_t_mean"]),
-                              float(r["refined_pitch"]), int(r["n_inliers"]), int(r["n_selected"]), bool(r["carried"]))
-            if not res.carried:
-                call["last_fit"] = st["a"] + f
-            self.frame_count += 1
-            for k in RESULT_FIELDS:
-                self.results[k].append(getattr(res, k))
-            out.append(res)
-        if bad:
-            call["carry_at"] = st["k"] + 1
-        call["inflight"].remove(st)
-        stream.free_blocks(st)
-        if kind == _lib.HPT_ERR_SINGULAR:
-            raise np.linalg.LinAlgError("Singular matrix")                           # :83
-        if kind in (_lib.HPT_ERR_MASK, _lib.HPT_ERR_EMPTY):
-            raise ValueError("frame %d: %s" % (self.frame_count, "no features or no triangles" if kind == _lib.HPT_ERR_EMPTY else
-                                               "a triangle names a vertex outside the frame"))
-        if kind == _lib.HPT_ERR_NO_MODEL:
-            raise ValueError("frame %d: no sample of the RANSAC had an inlier" % self.frame_count)
-        if kind == _lib.HPT_ERR_NO_PREVIOUS:                                         # :167 indexes the 1-D norm_prev of :45 with two indices
-            raise IndexError("too many indices for array: array is 1-dimensional, but 2 were indexed")
-        if kind:
-            raise RuntimeError("frame %d: the tail stopped with error %d" % (self.frame_count, kind))
-        if stop is not None:
-            raise stop[1]
-        return n
-
     def _resident_call(self, points3d_list, ests, triples):
-        """A call's state: its frames as float64 arrays, the priors, the carry-in record from the object's ``_prev`` — after the
-        refusals, which come before anything of the call runs, with the staged path's message."""
-        ctx, H = self.ctx, self.max_iterations
-        pts = [np.ascontiguousarray(np.asarray(p, dtype=np.float64).reshape(-1, 3)) for p in points3d_list]
-        F = len(pts)
+        """A call's state (:class:`_EstimatorCall`) — after the refusals, which come before anything of the call runs, with the
+        staged path's message."""
+        pts = [_float_frame(p) for p in points3d_list]
         max_feat = max(len(p) for p in pts)
-        need = int(ctx.lib.mvosr_height_pitch_lds_bytes(max_feat, H))
-        if need > ctx.lds_per_block:
-            raise ValueError("a frame of %d features needs %d bytes of LDS, the device has %d" % (max_feat, need, ctx.lds_per_block))
-        if max_feat > packing.delaunay_gpu_max_points():
-            raise ValueError("a frame of %d features is beyond the device triangulation's %d" % (max_feat, packing.delaunay_gpu_max_points()))
-        prev, inl = self._prev if self._prev is not None else (None, None)
-        cap = (max(max_feat, 0 if inl is None else len(inl), 2) + 1) & ~1
-        return {"pts": pts, "priors": np.array([frame_prior(e) for e in ests], dtype=np.float64).reshape(F, 4), "triples": triples,
-                "frame_base": self.frame_count, "cap": cap, "carry0": carry_record(cap, prev, inl), "chain": [], "inflight": [],
-                "records": [], "dt_status": [], "errors": [], "out": [], "last_fit": None, "carry_at": 0}
+        _refuse_lds(self.ctx, max_feat, int(self.ctx.lib.mvosr_height_pitch_lds_bytes(max_feat, self.max_iterations)))
+        _refuse_beyond_triangulation(max_feat)
+        return _EstimatorCall(self, pts, max_feat, ests, triples)
 
     def _process_resident(self, points3d_list, ests, triples):
         """``process_batch`` with the call's frames device-resident: chunks of the call through ``stream.run``, per chunk ONE upload,
@@ -522,28 +360,10 @@ class HeightPitchEstimator:
         a few dozen bytes per frame back.  The object's host state is what the staged path leaves, after an exception too."""
         if not len(points3d_list):
             return []
-        call = self._resident_call(points3d_list, ests, triples)
-        ctx, cap, F = self.ctx, call["cap"], len(points3d_list)
-        inl = None if self._prev is None else self._prev[1]
-        step = stream.chunk_size(F, self.GPU_CHUNK, self.GPU_MIN_CHUNK, self.GPU_CHUNK_POINTS, [len(p) for p in call["pts"][:64]])[0]
-        try:
-            call["chain"].append(ctx.to_device(call["carry0"]))
-            stream.run(stream.fixed_plan(F, step), lambda a, b, tables, k: self._resident_start(call, a, b, k),
-                       lambda st, a, b, last: self._resident_collect(call, st), self.GPU_PIPELINE,
-                       lambda st: stream.free_blocks(st), [], lambda: None)
-        finally:
-            try:
-                if call["out"]:                                                      # the carry: one frame's inliers
-                    if call["last_fit"] is not None:
-                        index = carry_fields(call["chain"][call["carry_at"]].download(), cap)[3]
-                        inl = back_project(points3d_list[call["last_fit"]], self.focus, self.cx, self.cy)[index]
-                    self._prev = (call["out"][-1], inl)
-            finally:
-                for buf in call["chain"]:
-                    buf.free()
-                self.last = {"records": np.concatenate(call["records"]) if call["records"] else np.zeros(0, dtype=TAIL_FRAME),
-                             "dt_status": call["dt_status"], "errors": call["errors"]}
-        return call["out"]
+        call, F = self._resident_call(points3d_list, ests, triples), len(points3d_list)
+        step = stream.chunk_size(F, self.GPU_CHUNK, self.GPU_MIN_CHUNK, self.GPU_CHUNK_POINTS, [len(p) for p in call.pts[:64]])[0]
+        call.run(stream.fixed_plan(F, step))
+        return call.out
 
     def run_sequence(self, frames, motion_ts):
         """The script's run: ``frames[i]`` is dump ``i + 1`` (:50, :60) and its prior ``get_pitch(motion_ts[0:i + 2])`` (:62).
@@ -558,6 +378,89 @@ class HeightPitchEstimator:
         """The six files under the script's names, as its ``np.savetxt`` calls write them (:228-244)."""
         for name, arr in zip(RESULT_FILES, self.result_arrays()):
             np.savetxt(os.path.join(directory, name), arr)
+
+
+class _EstimatorCall(ResidentCall):
+    """A ``process_batch`` call of the estimator ``est`` on the resident path: the priors, the carry-in record from the object's
+    ``_prev``, and what :class:`ResidentCall` leaves to its user — ``mvosr_height_pitch_batch``, ``mvosr_height_pitch_tail_batch``,
+    and the chunks' records as ``FrameResult``s into the object's lists."""
+
+    def __init__(self, est, pts, max_feat, ests, triples):
+        prev, inl = est._prev if est._prev is not None else (None, None)
+        self.cap = (max(max_feat, 0 if inl is None else len(inl), 2) + 1) & ~1
+        super().__init__(est, pts, carry_record(self.cap, prev, inl))
+        self.priors = np.array([frame_prior(e) for e in ests], dtype=np.float64).reshape(len(pts), 4)
+        self.triples, self.frame_base = triples, est.frame_count
+        self.records, self.out = [], []                # per chunk the final records; the call's FrameResults
+        self.last_fit, self.carry_at = None, 0         # the last fitted frame, and the chain record behind the last final frame
+
+    def inputs(self, a, b):
+        F, H = b - a, self.owner.max_iterations
+        extra, arrays = [("prior", (F, 4), np.float64)], {"prior": self.priors[a:b]}
+        if self.triples is not None:
+            extra.append(("triples", (F, H, 3), np.int32))
+            arrays["triples"] = _pack_triples(self.triples[a:b], F, H)
+        return extra, arrays
+
+    def block_specs(self, st):
+        F = st["b"] - st["a"]
+        return _out_spec(F, st["total"]), [("frames", F, TAIL_FRAME), ("error", 1, np.int64)]
+
+    def structs(self, st):
+        est, out = self.owner, st["out"]
+        st["params"] = _lib.HeightPitchParams(est.focus, est.cx, est.cy, MIN_POINTS, est.max_iterations, est.threshold, GOAL_FRACTION,
+                                              est.inlier_threshold, est.seed, int(self.frame_base + st["a"]))
+        st["outputs"] = _lib.HeightPitchOutputs(*[(out[n].ptr if n in out else None) for n, _ in _lib.HeightPitchOutputs._fields_])
+
+    def kernel(self, st):
+        ctx, din = self.ctx, st["din"]
+        _lib.check(ctx.lib.mvosr_height_pitch_batch(ctx.handle, C.byref(st["header"]), C.byref(st["params"]), din["prior"].ptr,
+                                                    din["triples"].ptr if "triples" in din else None, C.byref(st["outputs"])),
+                   "mvosr_height_pitch_batch")
+
+    def launch_tail(self, st, n_frames):
+        ctx, small = self.ctx, st["small"]
+        hb = _lib.Batch.from_buffer_copy(st["header"])
+        hb.n_frames = n_frames
+        _lib.check(ctx.lib.mvosr_height_pitch_tail_batch(ctx.handle, C.byref(hb), C.byref(st["params"]), st["din"]["prior"].ptr,
+                                                         C.byref(st["outputs"]), self.chain[st["k"]].ptr, self.chain[st["k"] + 1].ptr,
+                                                         self.cap, small["frames"].ptr, small["error"].ptr),
+                   "mvosr_height_pitch_tail_batch")
+
+    def decode(self, err, n):
+        return (err >> 32, err & 0xffffffff, None) if err >= 0 else (0, n, None)
+
+    def apply(self, st, n, bad):
+        est = self.owner
+        frames = st["small"]["frames"].download()[:bad] if n else np.zeros(0, dtype=TAIL_FRAME)
+        self.records.append(frames)
+        for f, r in enumerate(frames):
+            res = FrameResult(float(r["ransac_height"]), float(r["refined_mean"]), float(r["refined_std"]), float(r["height_t_mean"]),
+                              float(r["refined_pitch"]), int(r["n_inliers"]), int(r["n_selected"]), bool(r["carried"]))
+            if not res.carried:
+                self.last_fit = st["a"] + f
+            est.frame_count += 1
+            for k in RESULT_FIELDS:
+                est.results[k].append(getattr(res, k))
+            self.out.append(res)
+        if bad:
+            self.carry_at = st["k"] + 1
+
+    def error_frame(self, st, bad):
+        return self.owner.frame_count
+
+    def epilogue(self):
+        est = self.owner
+        try:
+            if self.out:                                                             # the carry: one frame's inliers
+                inl = None if est._prev is None else est._prev[1]
+                if self.last_fit is not None:
+                    index = carry_fields(self.chain[self.carry_at].download(), self.cap)[3]
+                    inl = back_project(self.pts[self.last_fit], est.focus, est.cx, est.cy)[index]
+                est._prev = (self.out[-1], inl)
+        finally:
+            est.last = {"records": np.concatenate(self.records) if self.records else np.zeros(0, dtype=TAIL_FRAME),
+                        "dt_status": self.dt_status, "errors": self.errors}
 
 
 # ---- the evaluation runs ---------------------------------------------------------------------------------------------------
@@ -595,16 +498,12 @@ def _eval_frame_rules(i, est, st, n_sel, value, prev, budget=None):
     """The scripts' cross-frame rules for frame ``i`` of ONE run (one budget): ``st`` (cases,) the launch's statuses, ``n_sel`` the
     list's length, ``value(name)`` -> (cases,) the launch's output, ``prev`` the last fitted frame's dict (None: none yet) ->
     (the frame's dict: the six values, sum_y, sum_z, degenerate — per case, carried).  Raises what the scripts raise."""
-    if np.any(st == ST_ERR_SINGULAR):
-        raise np.linalg.LinAlgError("Singular matrix")                               # :101
-    if np.any((st == ST_ERR_MASK) | (st == ST_ERR_EMPTY)):
-        raise ValueError("frame %d: %s" % (i, "no features or no triangles" if np.any(st == ST_ERR_EMPTY) else
-                                           "a triangle names a vertex outside the frame"))
-    if np.any(st == ST_RS_FEW) and n_sel >= MIN_POINTS:
-        raise ValueError("frame %d: no sample of the RANSAC had an inlier" % i + ("" if budget is None else " at budget %d" % budget))
+    kind = _status_kind(st, n_sel)
+    if kind:
+        raise frame_error(kind, i, budget)
     if n_sel < MIN_POINTS:
-        if prev is None:                                                             # :188 indexes the 1-D norm_prev of :55 with two indices
-            raise IndexError("too many indices for array: array is 1-dimensional, but 2 were indexed")
+        if prev is None:
+            raise frame_error(_lib.HPT_ERR_NO_PREVIOUS, i)
         cur = dict(prev)
         # :184-186 and the surviving `inliers`: everything repeats, but :223-224 see the new prior
         cur["height_t_mean"] = np.where(prev["degenerate"], np.nan,
@@ -629,77 +528,73 @@ def _pack_samples(samples, F, Cn, H):
     return sm
 
 
+def _eval_lds_bytes(ev, max_feat, H, budgets):
+    lib, model = ev.ctx.lib, EVAL_MODELS[ev.model]
+    return int(lib.mvosr_height_pitch_eval_lds_bytes(max_feat, H, model)) if budgets is None else \
+        int(lib.mvosr_height_pitch_eval_budgets_lds_bytes(max_feat, H, len(budgets), model))
+
+
+def _eval_out_spec(F, Cn, budgets):
+    """The evaluation launch's outputs over ``F`` frames: (F, C) per quantity, or with ``budgets`` (F, C, B) and ``best``."""
+    FC = (F, Cn) if budgets is None else (F, Cn, len(budgets))
+    return [("ransac_height", FC, np.float64), ("model", FC + (4,), np.float64), ("best_ic", FC, np.int32), ("used", FC, np.int32),
+            ("n_selected", F, np.int32), ("n_inliers", FC, np.int32), ("refined_normal", FC + (3,), np.float64),
+            ("refined_pitch", FC, np.float64), ("refined_mean", FC, np.float64), ("refined_std", FC, np.float64),
+            ("height_t_mean", FC, np.float64), ("sum_y", FC, np.float64), ("sum_z", FC, np.float64), ("status", FC, np.int32)] + \
+        ([("best", FC, np.int32)] if budgets is not None else [])
+
+
+def _eval_structs(ev, H, budgets, frame_base, G, block, list_stride=0):
+    """-> (the evaluation launch's parameters, its outputs over ``block`` — what the block does not hold stays NULL)."""
+    p = _lib.HeightPitchEvalParams(ev.focus, ev.cx, ev.cy, MIN_POINTS, H, ev.threshold, GOAL_FRACTION, ev.inlier_threshold,
+                                   ev.seed, int(frame_base), EVAL_MODELS[ev.model], ev.cases, G)
+    o = _lib.HeightPitchEvalOutputs() if budgets is None else _lib.HeightPitchEvalBudgetsOutputs()
+    for k, _ in o._fields_:
+        if k == "list_stride":
+            o.list_stride = list_stride
+        elif k in block:
+            setattr(o, k, block[k].ptr)
+    return p, o
+
+
+def _eval_kernel(ctx, bud, header, params, din, outputs):
+    """The evaluation launch over the uploaded block ``din``: ``bud`` None — ``mvosr_height_pitch_eval_batch``; the budgets as a C
+    array — ``mvosr_height_pitch_eval_budgets_batch``."""
+    sp = din["samples"].ptr if "samples" in din else None
+    if bud is None:
+        _lib.check(ctx.lib.mvosr_height_pitch_eval_batch(ctx.handle, C.byref(header), C.byref(params), din["prior"].ptr, sp, C.byref(outputs)),
+                   "mvosr_height_pitch_eval_batch")
+    else:
+        _lib.check(ctx.lib.mvosr_height_pitch_eval_budgets_batch(ctx.handle, C.byref(header), C.byref(params), bud, len(bud), din["prior"].ptr,
+                                                                 sp, C.byref(outputs)), "mvosr_height_pitch_eval_budgets_batch")
+
+
+def _budget_array(budgets):
+    return None if budgets is None else (C.c_int32 * len(budgets))(*budgets)
+
+
 def _eval_launch(ev, H, budgets, points3d_list, priors, samples, tris, frame_base, stage, max_feat, timing, cases_per_group):
     """The launch of both evaluation objects: ``budgets`` None — ``mvosr_height_pitch_eval_batch`` with ``H`` hypotheses, (F, C) per
     quantity; a tuple — ``mvosr_height_pitch_eval_budgets_batch``, ``H`` its last, (F, C, B) per quantity and ``best``."""
-    ctx, lib = ev.ctx, ev.ctx.lib
-    pts = [np.ascontiguousarray(np.asarray(p, dtype=np.float64).reshape(-1, 3)) for p in points3d_list]
-    F, Cn = len(pts), ev.cases
+    ctx, F, Cn = ev.ctx, len(points3d_list), ev.cases
     if F == 0:
         return None
-    rows = [np.ascontiguousarray(np.asarray(t, dtype=np.int32).reshape(-1, 3)) for t in tris] if tris is not None \
-        else _delaunay_rows(ctx, [np.ascontiguousarray(p[:, 0:2]) for p in pts], ev.triangulation, ev.delaunay_workers)
-    cnt = np.array([len(p) for p in pts], dtype=np.int32)
-    max_feat = int(cnt.max()) if max_feat is None else int(max_feat)
-    need = int(lib.mvosr_height_pitch_eval_lds_bytes(max_feat, H, EVAL_MODELS[ev.model])) if budgets is None else \
-        int(lib.mvosr_height_pitch_eval_budgets_lds_bytes(max_feat, H, len(budgets), EVAL_MODELS[ev.model]))
-    if need > ctx.lds_per_block:
-        raise ValueError("a frame of %d features needs %d bytes of LDS, the device has %d" % (max_feat, need, ctx.lds_per_block))
+    pts, rows, max_feat = _staged_frames(ev, points3d_list, tris, max_feat)
+    _refuse_lds(ctx, max_feat, _eval_lds_bytes(ev, max_feat, H, budgets))
     spec_in, arrays, off, toff, planes, T = _pack_frames(pts, rows, priors)
     if samples is not None:
         spec_in.append(("samples", (F, Cn, H, 3), np.int32))
         arrays["samples"] = _pack_samples(samples, F, Cn, H)
-    FC = (F, Cn) if budgets is None else (F, Cn, len(budgets))
-    spec_out = [("ransac_height", FC, np.float64), ("model", FC + (4,), np.float64), ("best_ic", FC, np.int32), ("used", FC, np.int32),
-                ("n_selected", F, np.int32), ("n_inliers", FC, np.int32), ("refined_normal", FC + (3,), np.float64),
-                ("refined_pitch", FC, np.float64), ("refined_mean", FC, np.float64), ("refined_std", FC, np.float64),
-                ("height_t_mean", FC, np.float64), ("sum_y", FC, np.float64), ("sum_z", FC, np.float64), ("status", FC, np.int32)]
-    if budgets is not None:
-        spec_out.append(("best", FC, np.int32))
+    spec_out = _eval_out_spec(F, Cn, budgets)
     if stage:
         spec_out += ([("list_mask", (Cn, 3 * T), np.uint8)] if budgets is None else []) + \
             [("point_list", 3 * T, np.int32), ("hyp_counts", (F, Cn, H), np.int32)]
-    din, dout = ctx.block(spec_in), ctx.block(spec_out)
-    try:
-        din.upload(arrays)
-        dout.zero()
-        b = _batch_header(din, F, max_feat, planes.shape[1])
-        G = ev.cases_per_group if cases_per_group is None else int(cases_per_group)
-        p = _lib.HeightPitchEvalParams(ev.focus, ev.cx, ev.cy, MIN_POINTS, H, ev.threshold, GOAL_FRACTION, ev.inlier_threshold,
-                                       ev.seed, int(frame_base), EVAL_MODELS[ev.model], Cn, G)
-        o = _lib.HeightPitchEvalOutputs() if budgets is None else _lib.HeightPitchEvalBudgetsOutputs()
-        for k, tp in o._fields_:
-            if k == "list_stride":
-                o.list_stride = 3 * T
-            elif k in dout:
-                setattr(o, k, dout[k].ptr)
-        sp = din["samples"].ptr if samples is not None else None
-        if budgets is None:
-            def call():
-                _lib.check(lib.mvosr_height_pitch_eval_batch(ctx.handle, C.byref(b), C.byref(p), din["prior"].ptr, sp, C.byref(o)),
-                           "mvosr_height_pitch_eval_batch")
-        else:
-            bud = (C.c_int32 * len(budgets))(*budgets)
-            def call():
-                _lib.check(lib.mvosr_height_pitch_eval_budgets_batch(ctx.handle, C.byref(b), C.byref(p), bud, len(budgets), din["prior"].ptr,
-                                                                     sp, C.byref(o)), "mvosr_height_pitch_eval_budgets_batch")
-        call()
-        kernel_ms = None
-        if timing > 0:
-            ev2 = ctx.event(), ctx.event()
-            ctx.record(ev2[0])
-            for _ in range(int(timing)):
-                call()
-            ctx.record(ev2[1])
-            kernel_ms = ctx.elapsed_ms(*ev2) / int(timing)
-            for e in ev2:
-                lib.mvosr_event_destroy(ctx.handle, e)
-        res = {k: dout[k].download() for k, _, _ in spec_out}
-        if kernel_ms is not None:
-            res["kernel_ms"] = kernel_ms
-    finally:
-        din.free()
-        dout.free()
+
+    def call_of(din, dout):
+        b, bud = _batch_header(din, F, max_feat, planes.shape[1]), _budget_array(budgets)
+        p, o = _eval_structs(ev, H, budgets, frame_base, ev.cases_per_group if cases_per_group is None else int(cases_per_group), dout, 3 * T)
+        return lambda: _eval_kernel(ctx, bud, b, p, din, o)
+    res = _staged_launch(ctx, spec_in, arrays, spec_out, call_of, timing)
     if stage:
         nsel = [max(int(m), 0) for m in res["n_selected"]]
         if budgets is None:
@@ -754,211 +649,102 @@ def eval_tail_error(err):
     return (0, 0, -1) if err < 0 else ((err >> 32) & 0xff, (err >> 40) & 0xff, err & 0xffffffff)
 
 
-def _eval_resident_refusals(ev, H, budgets, frames, runs):
-    """What is refused before anything of a resident run is queued, run by run in sequence order, with the staged launch's message."""
-    ctx, lib = ev.ctx, ev.ctx.lib
-    for idx in runs:
-        max_feat = max(int(np.asarray(frames[i]).size) // 3 for i in idx)
-        need = int(lib.mvosr_height_pitch_eval_lds_bytes(max_feat, H, EVAL_MODELS[ev.model])) if budgets is None else \
-            int(lib.mvosr_height_pitch_eval_budgets_lds_bytes(max_feat, H, len(budgets), EVAL_MODELS[ev.model]))
-        if need > ctx.lds_per_block:
-            raise ValueError("a frame of %d features needs %d bytes of LDS, the device has %d" % (max_feat, need, ctx.lds_per_block))
-        if max_feat > packing.delaunay_gpu_max_points():
-            raise ValueError("a frame of %d features is beyond the device triangulation's %d" % (max_feat, packing.delaunay_gpu_max_points()))
+class _EvalCall(ResidentCall):
+    """A ``run`` of an evaluation object ``ev`` on the resident path: the dumps as float64 arrays, the priors, the empty carry record,
+    the (B, cases, frames) arrays ``run`` returns (``out``) — the object's ``carried`` / ``degenerate`` (/ ``used`` / ``best``) set up as
+    the staged run sets them up — and what :class:`ResidentCall` leaves to its user: the evaluation launch,
+    ``mvosr_height_pitch_eval_tail_batch``, and the chunks' results as slices of those arrays."""
 
+    def __init__(self, ev, H, budgets, frames, ests, samples):
+        n, Cn, B = len(frames), ev.cases, 1 if budgets is None else len(budgets)
+        ev.carried = np.zeros(n, dtype=bool)
+        ev.degenerate = np.zeros((Cn, n) if budgets is None else (B, Cn, n), dtype=bool)
+        if budgets is not None:
+            ev.used, ev.best = np.zeros((B, Cn, n), dtype=np.int32), np.full((B, Cn, n), -1, dtype=np.int32)
+        empty = np.zeros((0, 3), dtype=np.float64)
+        super().__init__(ev, [_float_frame(p) if np.asarray(p).size else empty for p in frames], eval_carry_record(Cn, B))
+        self.priors = np.array([frame_prior(e) for e in ests], dtype=np.float64).reshape(n, 4)
+        self.samples, self.H, self.B, self.budgets, self.bud = samples, H, B, budgets, _budget_array(budgets)
+        self.out = {k: np.zeros((B, Cn, n), dtype=np.float64) for k in RESULT_FIELDS}
 
-def _eval_resident_start(ev, call, a, b, k):
-    """Chunk ``k`` = dumps ``a:b`` (one run of non-empty dumps): ONE upload, then the triangulation, the evaluation launch and the
-    tail queued on the context's stream, and the download of the chunk's results behind them.  Nothing is waited for."""
-    ctx, Cn, H, budgets, F = ev.ctx, ev.cases, call["H"], call["budgets"], b - a
-    B = call["B"]
-    extra, arrays = [("prior", (F, 4), np.float64)], {"prior": call["priors"][a:b]}
-    if call["samples"] is not None:
-        extra.append(("samples", (F, Cn, H, 3), np.int32))
-        arrays["samples"] = _pack_samples(call["samples"][a:b], F, Cn, H)
-    st = resident_rows_stage(ctx, call["pts"][a:b], extra, arrays)
-    st.update(k=k, a=a, b=b, side=[st["din"], st["tri"], st["dt"]])                 # (side: the blocks stream.free_blocks releases)
-    call["inflight"].append(st)
-    try:
-        din, total, max_feat = st["din"], st["total"], int(st["cnt"].max())
-        FC = (F, Cn) if budgets is None else (F, Cn, B)
-        out = st["out"] = ctx.block([("ransac_height", FC, np.float64), ("model", FC + (4,), np.float64), ("best_ic", FC, np.int32), ("used", FC, np.int32),
-                                     ("n_selected", F, np.int32), ("n_inliers", FC, np.int32), ("refined_normal", FC + (3,), np.float64),
-                                     ("refined_pitch", FC, np.float64), ("refined_mean", FC, np.float64), ("refined_std", FC, np.float64),
-                                     ("height_t_mean", FC, np.float64), ("sum_y", FC, np.float64), ("sum_z", FC, np.float64), ("status", FC, np.int32)] +
-                                    ([("best", FC, np.int32)] if budgets is not None else []))
-        BCF = (B, Cn, F)
-        small = st["small"] = ctx.block([(n, BCF, np.float64) for n in RESULT_FIELDS] + [("degenerate", BCF, np.uint8)] +
-                                        ([("used", BCF, np.int32), ("best", BCF, np.int32)] if budgets is not None else []) +
-                                        [("carried", F, np.uint8), ("frame_class", F, np.int32), ("source", F, np.int32), ("error", 1, np.int64)])
-        st["side"].append(small)
-        out.zero()
-        hb = st["header"] = _lib.Batch()
-        hb.n_frames, hb.feat_off, hb.feat_cnt = F, din["feat_off"].ptr, din["feat_cnt"].ptr
-        hb.x, hb.v, hb.z = din["u"].ptr, din["v"].ptr, din["z"].ptr
-        hb.tri1_off, hb.tri1, hb.tri1_cnt = din["tri_off"].ptr, st["tri"]["tri"].ptr, st["dt"]["tri_cnt"].ptr
-        hb.max_feat, hb.total_feat = max_feat, total
-        st["params"] = _lib.HeightPitchEvalParams(ev.focus, ev.cx, ev.cy, MIN_POINTS, H, ev.threshold, GOAL_FRACTION, ev.inlier_threshold,
-                                                  ev.seed, int(a), EVAL_MODELS[ev.model], Cn, ev.cases_per_group)
-        o = st["outputs"] = _lib.HeightPitchEvalOutputs() if budgets is None else _lib.HeightPitchEvalBudgetsOutputs()
-        for n, _ in o._fields_:                                                       # (list_mask, point_list, hyp_counts: NULL — run() reads none)
-            if n in out:
-                setattr(o, n, out[n].ptr)
+    def inputs(self, a, b):
+        F, Cn = b - a, self.owner.cases
+        extra, arrays = [("prior", (F, 4), np.float64)], {"prior": self.priors[a:b]}
+        if self.samples is not None:
+            extra.append(("samples", (F, Cn, self.H, 3), np.int32))
+            arrays["samples"] = _pack_samples(self.samples[a:b], F, Cn, self.H)
+        return extra, arrays
+
+    def block_specs(self, st):
+        F, BCF = st["b"] - st["a"], (self.B, self.owner.cases, st["b"] - st["a"])
+        return (_eval_out_spec(F, self.owner.cases, self.budgets),
+                [(n, BCF, np.float64) for n in RESULT_FIELDS] + [("degenerate", BCF, np.uint8)] +
+                ([("used", BCF, np.int32), ("best", BCF, np.int32)] if self.budgets is not None else []) +
+                [("carried", F, np.uint8), ("frame_class", F, np.int32), ("source", F, np.int32), ("error", 1, np.int64)])
+
+    def structs(self, st):
+        ev, out, small = self.owner, st["out"], st["small"]
+        # (list_mask, point_list, hyp_counts: NULL — run() reads none)
+        st["params"], st["outputs"] = _eval_structs(ev, self.H, self.budgets, st["a"], ev.cases_per_group, out)
         ti = st["tail_in"] = _lib.HeightPitchEvalTailInputs()
         for n, _ in ti._fields_:
-            setattr(ti, n, out[n].ptr if n in out and (budgets is not None or n != "used") else None)
+            setattr(ti, n, out[n].ptr if n in out and (self.budgets is not None or n != "used") else None)
         to = st["tail_out"] = _lib.HeightPitchEvalTailOutputs()
         for n, _ in to._fields_:
             setattr(to, n, small[n].ptr if n in small else None)
-        _eval_resident_kernel(ev, call, st)
-        while len(call["chain"]) < k + 2:                                              # chunk k: chain[k] -> chain[k + 1]
-            call["chain"].append(ctx.empty(len(call["carry0"]), np.uint8))
-        _eval_resident_tail(ev, call, st, F)
-        for blk in (din, st["tri"], out):
-            blk.mark(True)
-    except BaseException:
-        call["inflight"].remove(st)
-        stream.free_blocks(st)
-        raise
-    return st
 
+    def kernel(self, st):
+        _eval_kernel(self.ctx, self.bud, st["header"], st["params"], st["din"], st["outputs"])
 
-def _eval_resident_kernel(ev, call, st):
-    ctx, din = ev.ctx, st["din"]
-    sp = din["samples"].ptr if "samples" in din else None
-    if call["budgets"] is None:
-        _lib.check(ctx.lib.mvosr_height_pitch_eval_batch(ctx.handle, C.byref(st["header"]), C.byref(st["params"]), din["prior"].ptr, sp,
-                                                         C.byref(st["outputs"])), "mvosr_height_pitch_eval_batch")
-    else:
-        _lib.check(ctx.lib.mvosr_height_pitch_eval_budgets_batch(ctx.handle, C.byref(st["header"]), C.byref(st["params"]), call["bud"], call["B"],
-                                                                 din["prior"].ptr, sp, C.byref(st["outputs"])),
-                   "mvosr_height_pitch_eval_budgets_batch")
+    def launch_tail(self, st, n_frames):
+        ctx = self.ctx
+        _lib.check(ctx.lib.mvosr_height_pitch_eval_tail_batch(ctx.handle, n_frames, self.owner.cases, self.B, MIN_POINTS, C.byref(st["tail_in"]),
+                                                              st["din"]["prior"].ptr, self.chain[st["k"]].ptr, self.chain[st["k"] + 1].ptr,
+                                                              C.byref(st["tail_out"])), "mvosr_height_pitch_eval_tail_batch")
 
+    def decode(self, err, n):
+        kind, bud, bad = eval_tail_error(err)
+        return kind, bad if kind else n, self.budgets[bud] if self.budgets is not None else None
 
-def _eval_resident_tail(ev, call, st, n_frames, download=True):
-    """``mvosr_height_pitch_eval_tail_batch`` over the chunk's first ``n_frames`` frames, then (``download``) the chunk's result block and
-    the triangulation's status words on their way to page-locked memory, as ``HeightPitchEstimator._resident_tail``."""
-    ctx, small = ev.ctx, st["small"]
-    _lib.check(ctx.lib.mvosr_height_pitch_eval_tail_batch(ctx.handle, int(n_frames), ev.cases, call["B"], MIN_POINTS, C.byref(st["tail_in"]),
-                                                          st["din"]["prior"].ptr, call["chain"][st["k"]].ptr, call["chain"][st["k"] + 1].ptr,
-                                                          C.byref(st["tail_out"])), "mvosr_height_pitch_eval_tail_batch")
-    st["tail_frames"] = int(n_frames)
-    for blk in (st["dt"], small) if download else ():
-        blk.mark(False)
-        if ev.GPU_SIDE_DOWNLOADS:
-            blk.mark_done()
-        else:
-            blk.prefetch()
-        blk.mark(True)
-
-
-def _eval_resident_redo(ev, call, st, declined):
-    """``HeightPitchEstimator._resident_redo``'s scheme: SciPy's rows into the declined frames' slots, the evaluation launch again
-    over the chunk, then this chunk's tail and the tail of every chunk queued behind it (their carry-in changed)."""
-    for blk in (st["din"], st["tri"], st["out"]):
-        blk.mark(False)
-    stop = patch_declined_rows(ev.ctx, st, [call["pts"][st["a"] + f] for f in declined], declined, ev.delaunay_workers)
-    _eval_resident_kernel(ev, call, st)
-    n = st["b"] - st["a"] if stop is None else stop[0]
-    if n > 0:
-        _eval_resident_tail(ev, call, st, n)
-    if stop is None:
-        for later in call["inflight"]:
-            if later["k"] > st["k"]:
-                _eval_resident_tail(ev, call, later, later["b"] - later["a"])
-    for blk in (st["din"], st["tri"], st["out"]):
-        blk.mark(True)
-    return stop
-
-
-def _eval_resident_collect(ev, call, st):
-    """Wait for the chunk's results, send its declined frames through the host, copy the final frames into the call's arrays and
-    raise where the host loop raises."""
-    cnt, F, a, budgets = st["cnt"], st["b"] - st["a"], st["a"], call["budgets"]
-    dt_status = st["dt"]["dt_status"].download()
-    declined = [f for f in range(F) if dt_status[f] != 0 and cnt[f] >= 3]
-    ev.declined_total += len(declined) + int(np.count_nonzero(cnt < 3))
-    stop = _eval_resident_redo(ev, call, st, declined) if declined else None
-    n = F if stop is None else stop[0]
-    small = st["small"]
-    err = int(small["error"].download()[0]) if n else -1
-    kind, bud, bad = eval_tail_error(err)
-    bad = n if not kind else bad
-    call["dt_status"].append(dt_status)
-    call["errors"].append(err)
-    if bad:
-        B, Cn = call["B"], ev.cases
+    def apply(self, st, n, bad):
+        if not bad:
+            return
+        ev, small, a, B, Cn = self.owner, st["small"], st["a"], self.B, self.owner.cases
         part = lambda name: small[name].download().reshape(-1)[:B * Cn * n].reshape(B, Cn, n)[:, :, :bad]   # (laid out for the n frames the tail ran over)
         for name in RESULT_FIELDS:
-            call["out"][name][:, :, a:a + bad] = part(name)
+            self.out[name][:, :, a:a + bad] = part(name)
         ev.degenerate.reshape(B, Cn, -1)[:, :, a:a + bad] = part("degenerate") != 0
         ev.carried[a:a + bad] = small["carried"].download()[:bad] != 0
-        if budgets is not None:
+        if self.budgets is not None:
             ev.used[:, :, a:a + bad], ev.best[:, :, a:a + bad] = part("used"), part("best")
-    call["inflight"].remove(st)
-    stream.free_blocks(st)
-    i = a + bad                                                                      # the dump the host loop raises at
-    if kind == _lib.HPT_ERR_SINGULAR:
-        raise np.linalg.LinAlgError("Singular matrix")                               # :101
-    if kind in (_lib.HPT_ERR_MASK, _lib.HPT_ERR_EMPTY):
-        raise ValueError("frame %d: %s" % (i, "no features or no triangles" if kind == _lib.HPT_ERR_EMPTY else
-                                           "a triangle names a vertex outside the frame"))
-    if kind == _lib.HPT_ERR_NO_MODEL:
-        raise ValueError("frame %d: no sample of the RANSAC had an inlier" % i + ("" if budgets is None else " at budget %d" % budgets[bud]))
-    if kind == _lib.HPT_ERR_NO_PREVIOUS:                                             # :188 indexes the 1-D norm_prev of :55 with two indices
-        raise IndexError("too many indices for array: array is 1-dimensional, but 2 were indexed")
-    if kind:
-        raise RuntimeError("frame %d: the tail stopped with error %d" % (i, kind))
-    if stop is not None:
-        raise stop[1]
-    return n
 
+    def error_frame(self, st, bad):
+        return st["a"] + bad                                                         # the dump the host loop raises at
 
-def _eval_resident_call(ev, H, budgets, frames, ests, samples):
-    """A resident run's state: the frames as float64 arrays, the priors, the empty carry record, and the arrays ``run`` returns —
-    the object's ``carried`` / ``degenerate`` (/ ``used`` / ``best``) set up as the staged run sets them up."""
-    n, Cn, B = len(frames), ev.cases, 1 if budgets is None else len(budgets)
-    ev.carried = np.zeros(n, dtype=bool)
-    ev.degenerate = np.zeros((Cn, n) if budgets is None else (B, Cn, n), dtype=bool)
-    if budgets is not None:
-        ev.used, ev.best = np.zeros((B, Cn, n), dtype=np.int32), np.full((B, Cn, n), -1, dtype=np.int32)
-    empty = np.zeros((0, 3), dtype=np.float64)
-    return {"pts": [np.ascontiguousarray(np.asarray(p, dtype=np.float64).reshape(-1, 3)) if np.asarray(p).size else empty for p in frames],
-            "priors": np.array([frame_prior(e) for e in ests], dtype=np.float64).reshape(n, 4), "samples": samples, "H": H, "B": B,
-            "budgets": budgets, "bud": None if budgets is None else (C.c_int32 * B)(*budgets), "carry0": eval_carry_record(Cn, B),
-            "chain": [], "inflight": [], "dt_status": [], "errors": [], "out": {k: np.zeros((B, Cn, n), dtype=np.float64) for k in RESULT_FIELDS}}
+    def epilogue(self):
+        self.owner.last = {"dt_status": self.dt_status, "errors": self.errors}
 
 
 def _eval_resident_run(ev, H, budgets, frames, motion_ts, samples, batch):
     """``run`` of both evaluation objects with the frames device-resident: the runs of non-empty dumps as chunks through ``stream.run``,
     per chunk ONE upload, ``mvosr_delaunay_batch`` -> the evaluation launch -> ``mvosr_height_pitch_eval_tail_batch`` on the context's
-    stream, and the (B, cases, frames) arrays ``run`` returns coming back as they are.  -> dict field -> (B, cases, frames)."""
-    ctx, n = ev.ctx, len(frames)
+    stream, and the (B, cases, frames) arrays ``run`` returns coming back as they are.  -> dict field -> (B, cases, frames).
+    What is refused is refused before anything of the run is queued, run by run in sequence order, with the staged launch's message."""
+    n = len(frames)
     ests = estimated_pitches(motion_ts, 1, n) if n else np.zeros(0)
     runs = _nonempty_runs(frames, batch)
-    _eval_resident_refusals(ev, H, budgets, frames, runs)
-    call = _eval_resident_call(ev, H, budgets, frames, ests, samples)
-    if not runs:
-        return call["out"]
-    try:
-        call["chain"].append(ctx.to_device(call["carry0"]))
-        stream.run(((idx[0], idx[-1] + 1, None) for idx in runs), lambda a, b, tables, k: _eval_resident_start(ev, call, a, b, k),
-                   lambda st, a, b, last: _eval_resident_collect(ev, call, st), ev.GPU_PIPELINE,
-                   lambda st: stream.free_blocks(st), [], lambda: None)
-    finally:
-        for buf in call["chain"]:
-            buf.free()
-        ev.last = {"dt_status": call["dt_status"], "errors": call["errors"]}
-    return call["out"]
+    for idx in runs:
+        max_feat = max(int(np.asarray(frames[i]).size) // 3 for i in idx)
+        _refuse_lds(ev.ctx, max_feat, _eval_lds_bytes(ev, max_feat, H, budgets))
+        _refuse_beyond_triangulation(max_feat)
+    call = _EvalCall(ev, H, budgets, frames, ests, samples)
+    if runs:
+        call.run((idx[0], idx[-1] + 1, None) for idx in runs)
+    return call.out
 
 
-class RansacEvaluation:
-    """``calculate_height_pitch_eval.py`` (model "plane") and ``calculate_height_pitch_eval_line.py`` ("line"): the sequence run
-    ``cases`` times with ``iterations`` hypotheses per frame, every case with a sample sequence of its own.  One launch per batch of
-    frames covers all cases; the scripts' cross-frame rules are applied per case on the host — or, with ``triangulation="gpu",
-    resident=True``, on the device, the frames resident from their upload to the arrays ``run`` returns (DESIGN.md §3.27): the same
-    results, ``carried`` and ``degenerate`` byte for byte; ``tris=`` is refused there, and ``last`` holds status and error words only."""
-
+class _RansacRuns:
+    """What :class:`RansacEvaluation` and :class:`RansacBudgetSweep` share before their first launch."""
 
     # the device-resident path (resident=True; DESIGN.md §3.27): off unless asked for, its chunk pipeline's knobs (stream.StreamKnobs;
     # tests and profiles override them per instance) and its count of frames whose rows came from the host (or that have < 3 points)
@@ -967,8 +753,10 @@ class RansacEvaluation:
     GPU_PIPELINE = stream.StreamKnobs.GPU_PIPELINE
     GPU_SIDE_DOWNLOADS = stream.StreamKnobs.GPU_SIDE_DOWNLOADS
 
-    def __init__(self, model, iterations, cases=10, focus=FOCUS, cx=CX, cy=CY, threshold=0.005, inlier_threshold=0.01, seed=None,
-                 device=0, triangulation="scipy", cases_per_group=None, delaunay_workers=0, resident=False):
+    def _init(self, hypotheses, model, cases, focus, cx, cy, threshold, inlier_threshold, seed, device, triangulation, cases_per_group,
+              delaunay_workers, resident):
+        """The constructors' checks and attributes; ``hypotheses()`` is the object's own check of its iterations or budgets, in its
+        place among the checks."""
         if model not in EVAL_MODELS:
             raise ValueError("model must be 'plane' or 'line'")
         if triangulation not in ("scipy", "gpu"):
@@ -977,21 +765,37 @@ class RansacEvaluation:
             if triangulation != "gpu":
                 raise ValueError(RESIDENT_ERROR)
             self.resident, self.declined_total = True, 0
-        if not 1 <= int(iterations) <= MAX_EVAL_ITERATIONS:
-            raise ValueError("iterations must be in 1..%d" % MAX_EVAL_ITERATIONS)
+        hypotheses()
         if int(cases) < 1:
             raise ValueError("cases must be at least 1")
         self.ctx = _lib.default_context(device)
-        self.model, self.iterations, self.cases = model, int(iterations), int(cases)
+        self.model, self.cases = model, int(cases)
         self.focus, self.cx, self.cy = float(focus), float(cx), float(cy)
         self.threshold, self.inlier_threshold = float(threshold), float(inlier_threshold)
         self.seed = int.from_bytes(os.urandom(8), "little") if seed is None else int(seed) & (2 ** 64 - 1)
         self.triangulation, self.delaunay_workers = triangulation, delaunay_workers
         self.cases_per_group = 0 if cases_per_group is None else int(cases_per_group)  # (0: the library's default, one case per workgroup)
-        self.results = None                            # field -> (cases, frames) after run()
+        self.results = None                            # field -> (cases, frames) after run(); the sweep's: (B, cases, frames)
         self.carried = None                            # (frames,) bool
-        self.degenerate = None                         # (cases, frames) bool: the refinement's sample named a vertex twice
+        self.degenerate = None                         # shaped like a result, bool: the refinement's sample named a vertex twice
         self.last = None
+
+
+class RansacEvaluation(_RansacRuns):
+    """``calculate_height_pitch_eval.py`` (model "plane") and ``calculate_height_pitch_eval_line.py`` ("line"): the sequence run
+    ``cases`` times with ``iterations`` hypotheses per frame, every case with a sample sequence of its own.  One launch per batch of
+    frames covers all cases; the scripts' cross-frame rules are applied per case on the host — or, with ``triangulation="gpu",
+    resident=True``, on the device, the frames resident from their upload to the arrays ``run`` returns (DESIGN.md §3.27): the same
+    results, ``carried`` and ``degenerate`` byte for byte; ``tris=`` is refused there, and ``last`` holds status and error words only."""
+
+    def __init__(self, model, iterations, cases=10, focus=FOCUS, cx=CX, cy=CY, threshold=0.005, inlier_threshold=0.01, seed=None,
+                 device=0, triangulation="scipy", cases_per_group=None, delaunay_workers=0, resident=False):
+        def hypotheses():
+            if not 1 <= int(iterations) <= MAX_EVAL_ITERATIONS:
+                raise ValueError("iterations must be in 1..%d" % MAX_EVAL_ITERATIONS)
+            self.iterations = int(iterations)
+        self._init(hypotheses, model, cases, focus, cx, cy, threshold, inlier_threshold, seed, device, triangulation, cases_per_group,
+                   delaunay_workers, resident)
 
     # ---- one launch
     def launch(self, points3d_list, priors, samples=None, tris=None, frame_base=0, stage=False, max_feat=None, timing=0, cases_per_group=None):
@@ -1010,8 +814,7 @@ class RansacEvaluation:
         ``np.linalg.LinAlgError`` (:101).  Where the refinement's sample names a vertex twice, the refined values are NaN
         (``self.degenerate``); the RANSAC height and the inlier number are not affected."""
         if self.resident:
-            if tris is not None:
-                raise ValueError("resident=True triangulates on the device: tris= belongs to the staged path")
+            _refuse_tris(tris)
             out = _eval_resident_run(self, self.iterations, None, frames, motion_ts, samples, batch)
             self.results = {k: v[0] for k, v in out.items()}
             return self.results
@@ -1082,7 +885,7 @@ def check_budgets(budgets):
     return out
 
 
-class RansacBudgetSweep:
+class RansacBudgetSweep(_RansacRuns):
     """What the two evaluation scripts are run for — how many RANSAC iterations the road-plane fit needs: the runs of
     :class:`RansacEvaluation` at every iteration budget of ``budgets`` from ONE launch per batch of frames
     (``mvosr_height_pitch_eval_budgets_batch``).  The sample sequence of a (frame, case) does not depend on the
@@ -1090,40 +893,14 @@ class RansacBudgetSweep:
     ``RansacEvaluation(model, budgets[k], cases, seed=seed, ...)`` on the same inputs (recorded ``samples`` cut to that budget).
     ``triangulation="gpu", resident=True``: as :class:`RansacEvaluation`'s, ``used`` and ``best`` included."""
 
-
-    # the device-resident path (resident=True; DESIGN.md §3.27): off unless asked for, its chunk pipeline's knobs (stream.StreamKnobs;
-    # tests and profiles override them per instance) and its count of frames whose rows came from the host (or that have < 3 points)
-    resident = False
-    declined_total = 0
-    GPU_PIPELINE = stream.StreamKnobs.GPU_PIPELINE
-    GPU_SIDE_DOWNLOADS = stream.StreamKnobs.GPU_SIDE_DOWNLOADS
-
     def __init__(self, model, budgets, cases=10, focus=FOCUS, cx=CX, cy=CY, threshold=0.005, inlier_threshold=0.01, seed=None,
                  device=0, triangulation="scipy", cases_per_group=None, delaunay_workers=0, resident=False):
-        if model not in EVAL_MODELS:
-            raise ValueError("model must be 'plane' or 'line'")
-        if triangulation not in ("scipy", "gpu"):
-            raise ValueError("triangulation must be 'scipy' or 'gpu'")
-        if resident:                                   # opt-in; without it no attribute of the instance is new
-            if triangulation != "gpu":
-                raise ValueError(RESIDENT_ERROR)
-            self.resident, self.declined_total = True, 0
-        self.budgets = check_budgets(budgets)
-        if int(cases) < 1:
-            raise ValueError("cases must be at least 1")
-        self.ctx = _lib.default_context(device)
-        self.model, self.cases = model, int(cases)
-        self.focus, self.cx, self.cy = float(focus), float(cx), float(cy)
-        self.threshold, self.inlier_threshold = float(threshold), float(inlier_threshold)
-        self.seed = int.from_bytes(os.urandom(8), "little") if seed is None else int(seed) & (2 ** 64 - 1)
-        self.triangulation, self.delaunay_workers = triangulation, delaunay_workers
-        self.cases_per_group = 0 if cases_per_group is None else int(cases_per_group)
-        self.results = None                            # field -> (B, cases, frames) after run()
-        self.carried = None                            # (frames,) bool
-        self.degenerate = None                         # (B, cases, frames) bool
+        def hypotheses():
+            self.budgets = check_budgets(budgets)
+        self._init(hypotheses, model, cases, focus, cx, cy, threshold, inlier_threshold, seed, device, triangulation, cases_per_group,
+                   delaunay_workers, resident)
         self.used = None                               # (B, cases, frames) hypotheses replayed; 0 on empty and carried frames
         self.best = None                               # (B, cases, frames) the best hypothesis' number; -1 on empty and carried frames
-        self.last = None
 
     # ---- one launch
     def launch(self, points3d_list, priors, samples=None, tris=None, frame_base=0, stage=False, max_feat=None, timing=0, cases_per_group=None):
@@ -1141,8 +918,7 @@ class RansacBudgetSweep:
         Where a single run would raise "no sample of the RANSAC had an inlier", so does this, naming the frame and the smallest
         such budget."""
         if self.resident:
-            if tris is not None:
-                raise ValueError("resident=True triangulates on the device: tris= belongs to the staged path")
+            _refuse_tris(tris)
             self.results = _eval_resident_run(self, self.budgets[-1], self.budgets, frames, motion_ts, samples, batch)
             return self.results
         n, Cn, B = len(frames), self.cases, len(self.budgets)

@@ -21,37 +21,13 @@ import numpy as np
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path[:0] = [ROOT, os.path.join(ROOT, "tests")]
 
-from mvoscalerecovery_amd import height_pitch as hp, stream, synth      # noqa: E402
+from mvoscalerecovery_amd import height_pitch as hp, synth              # noqa: E402
 import heightpitch_cases as hc                                           # noqa: E402
+from resident_tail import tail_us                                        # noqa: E402
 
 
 def spread(ts):
     return {"median_s": statistics.median(ts), "min_s": min(ts), "max_s": max(ts), "runs": len(ts)}
-
-
-def tail_us(est, frames, ests, repeats):
-    """One launch of the tail over the frames as ONE resident chunk, by device events -> (us per launch, carried frames)."""
-    ctx = est.ctx
-    call = est._resident_call(frames, ests, None)
-    call["chain"].append(ctx.to_device(call["carry0"]))
-    st = est._resident_start(call, 0, len(frames), 0)
-    try:
-        carried = int(st["small"]["frames"].download()["carried"].sum())
-        assert int(st["small"]["error"].download()[0]) == -1
-        ev = ctx.event(), ctx.event()
-        ctx.record(ev[0])
-        for _ in range(repeats):
-            est._resident_tail(call, st, len(frames), download=False)
-        ctx.record(ev[1])
-        ctx.sync()
-        us = 1e3 * ctx.elapsed_ms(*ev) / repeats
-        for e in ev:
-            ctx.lib.mvosr_event_destroy(ctx.handle, e)
-    finally:
-        stream.free_blocks(st)
-        for buf in call["chain"]:
-            buf.free()
-    return us, carried
 
 
 def main():
@@ -99,7 +75,7 @@ def main():
     few = [(np.stack([rng.uniform(0, 1241, 2000), rng.uniform(0, 376, 2000), np.full(2000, 20.0)], 1) if i % 10 == 5 else p) for i, p in enumerate(sub)]
     out["tail"] = {}
     for name, fr in (("carried_0_percent", sub), ("carried_10_percent", few)):
-        us, carried = tail_us(est, fr, ests, 50)
+        us, carried = tail_us(est._resident_call(fr, ests, None), len(fr), 50, lambda st: int(st["small"]["frames"].download()["carried"].sum()))
         out["tail"][name] = {"us_per_launch": us, "frames": len(fr), "carried": carried}
     out["note"] = "wall clock around run_sequence on a fresh object per run; no hardware counters were read"
     with open(a.out, "w") as fh:

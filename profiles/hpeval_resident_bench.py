@@ -21,8 +21,9 @@ import numpy as np
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path[:0] = [ROOT, os.path.join(ROOT, "tests")]
 
-from mvoscalerecovery_amd import height_pitch as hp, stream, synth      # noqa: E402
+from mvoscalerecovery_amd import height_pitch as hp, synth              # noqa: E402
 import heightpitch_cases as hc                                           # noqa: E402
+from resident_tail import tail_us                                        # noqa: E402
 
 BUDGETS = (25, 50, 100, 200, 500, 1000, 2000)
 ITERATIONS, CASES = 500, 10
@@ -36,31 +37,6 @@ def make(kind, resident):
     if kind == "sweep":
         return hp.RansacBudgetSweep("plane", BUDGETS, cases=CASES, seed=1, triangulation="gpu", resident=resident)
     return hp.RansacEvaluation("plane", ITERATIONS, cases=CASES, seed=1, triangulation="gpu", resident=resident)
-
-
-def tail_us(ev, frames, motion, repeats):
-    """One call of the tail over the frames as ONE resident chunk, by device events -> (us per call, carried frames)."""
-    ctx, n = ev.ctx, len(frames)
-    call = hp._eval_resident_call(ev, ev.budgets[-1], ev.budgets, frames, hp.estimated_pitches(motion, 1, n), None)
-    call["chain"].append(ctx.to_device(call["carry0"]))
-    st = hp._eval_resident_start(ev, call, 0, n, 0)
-    try:
-        carried = int(st["small"]["carried"].download().sum())
-        assert int(st["small"]["error"].download()[0]) == -1
-        e = ctx.event(), ctx.event()
-        ctx.record(e[0])
-        for _ in range(repeats):
-            hp._eval_resident_tail(ev, call, st, n, download=False)
-        ctx.record(e[1])
-        ctx.sync()
-        us = 1e3 * ctx.elapsed_ms(*e) / repeats
-        for x in e:
-            ctx.lib.mvosr_event_destroy(ctx.handle, x)
-    finally:
-        stream.free_blocks(st)
-        for buf in call["chain"]:
-            buf.free()
-    return us, carried
 
 
 def main():
@@ -113,7 +89,8 @@ def main():
     few = [(np.stack([rng.uniform(0, 1241, 2000), rng.uniform(0, 376, 2000), np.full(2000, 20.0)], 1) if i % 10 == 5 else p) for i, p in enumerate(sub)]
     out["tail"] = {}
     for name, fr in (("carried_0_percent", sub), ("carried_10_percent", few)):
-        us, carried = tail_us(ev, fr, motion[:513], 50)
+        call = hp._EvalCall(ev, ev.budgets[-1], ev.budgets, fr, hp.estimated_pitches(motion[:513], 1, len(fr)), None)
+        us, carried = tail_us(call, len(fr), 50, lambda st: int(st["small"]["carried"].download().sum()))
         out["tail"][name] = {"us_per_call": us, "launches_per_call": 3, "frames": len(fr), "elements_per_frame": CASES * len(BUDGETS), "carried": carried}
     out["note"] = ("wall clock around run() on a fresh object per run; the staged side is the code this change does not touch; "
                    "no hardware counters were read, so what bounds the tail's kernels was not measured")

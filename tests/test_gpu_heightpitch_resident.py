@@ -281,6 +281,43 @@ def test_declined_frame_takes_the_hosts_rows(golden, chunk):
     assert "rows" not in res.last and all(isinstance(v, (np.ndarray, list)) and len(v) <= 5 for v in res.last.values())   # self.last carries none
 
 
+def flat_row_frame():
+    """Six pixels on one image row, pixel 4 an exact copy of pixel 1: the repeated pixel makes the device triangulation decline the
+    frame, and the host's Qhull then finds every point on one line ("Initial simplex is flat")."""
+    pts = np.array([[100.0 + 10 * i, 200.0, 10.0 + i] for i in range(6)])
+    pts[4, 0:2] = pts[1, 0:2]
+    return pts
+
+
+@pytest.mark.parametrize("place", [0, 1])
+def test_scipy_raises_on_a_declined_frame(golden, staged, place):
+    """The declined frame is the first (``place`` 0: no tail runs again) or the second (1: the tail runs again over one frame) of the
+    second chunk of two, with two more chunks queued behind it: SciPy's exception leaves the call, and the object is left as the
+    staged path is after the frames before the bad one."""
+    from scipy.spatial import QhullError
+    bad = 2 + place
+    frames = [f for f in golden["frames"][:8]]
+    frames[bad] = flat_row_frame()
+    ests = [float(e) for e in golden["priors"][:8]]
+    res, ref = estimator(True, 2), estimator(False)
+    assert res.GPU_PIPELINE == 2
+    before = res.ctx.alloc_stats()
+    with pytest.raises(QhullError):
+        res.process_batch(frames, ests)
+    after = res.ctx.alloc_stats()
+    print("alloc_stats before", before, "after", after, "dt_status", res.last["dt_status"], "errors", res.last["errors"])
+    assert res.last["dt_status"][1][place] != 0                                      # the device did decline it (MVOSR_DT_DEGENERATE)
+    assert res.declined_total == 1
+    assert ref.process_batch(frames[:bad], ests[:bad]) == staged[1][:bad]
+    same_state(res, ref)
+    assert res.frame_count == bad and len(res.last["records"]) == bad
+    # (the counters of alloc_stats only grow; what a call can leave behind is a live block)
+    assert after["live_blocks"] == before["live_blocks"]
+    more = (golden["frames"][8:10], [float(e) for e in golden["priors"][8:10]])
+    assert res.process_batch(*more) == ref.process_batch(*more)
+    same_state(res, ref)
+
+
 # ---- 7. refusals ----------------------------------------------------------------------------------------------------------------
 def test_refusals(golden):
     from mvoscalerecovery_amd.height_pitch import HeightPitchEstimator

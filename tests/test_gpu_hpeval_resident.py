@@ -278,6 +278,32 @@ def test_declined_frame_takes_the_hosts_rows(golden, kind):
     assert all(isinstance(v, list) and len(v) == 4 for v in res.last.values())       # status and error words, no lists, no masks
 
 
+@pytest.mark.parametrize("place", [0, 1])
+@pytest.mark.parametrize("kind", ["eval", "sweep"])
+def test_scipy_raises_on_a_declined_frame(golden, kind, place):
+    """Six pixels on one image row, pixel 4 an exact copy of pixel 1 — the device triangulation declines the frame and the host's Qhull
+    finds every point on one line —, as the first (``place`` 0: no tail runs again) or the second (1: the tail runs again over one frame)
+    dump of the second chunk of two, two more chunks queued behind it: SciPy's exception leaves the run, ``results`` is what it was."""
+    from scipy.spatial import QhullError
+    g = golden["plane"]["seq"]
+    frames = [f for f in g["frames"]]
+    bad = np.array([[100.0 + 10 * i, 200.0, 10.0 + i] for i in range(6)])
+    bad[4, 0:2] = bad[1, 0:2]
+    frames[2 + place] = bad
+    res = make(kind, "plane", True)
+    assert res.GPU_PIPELINE == 2 and len(frames) == 8
+    kept = res.results = {"kept": np.zeros(1)}
+    before = res.ctx.alloc_stats()
+    with pytest.raises(QhullError):
+        res.run(frames, g["motion"][:, 3::4], batch=2)
+    after = res.ctx.alloc_stats()
+    print("alloc_stats before", before, "after", after, "dt_status", res.last["dt_status"], "errors", res.last["errors"])
+    assert res.last["dt_status"][1][place] != 0                                      # the device did decline it (MVOSR_DT_DEGENERATE)
+    assert res.declined_total == 1 and res.results is kept
+    # (the counters of alloc_stats only grow; what a run can leave behind is a live block)
+    assert after["live_blocks"] == before["live_blocks"]
+
+
 # ---- 5. refusals ----------------------------------------------------------------------------------------------------------------
 @pytest.mark.parametrize("kind", ["eval", "sweep"])
 def test_refusals(golden, kind):

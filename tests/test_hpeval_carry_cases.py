@@ -202,3 +202,27 @@ def test_resident_belongs_to_the_device_triangulation():
         hp.HeightPitchEstimator(resident=True)
     assert str(info.value) == message
     assert hp.RansacEvaluation.resident is False and hp.RansacBudgetSweep.resident is False
+
+
+@pytest.mark.parametrize("budget", [None, 20])
+def test_error_kinds_map_to_the_scripts_exceptions(budget):
+    """``hp_resident.frame_error`` — the resident paths' one mapping — gives, kind by kind, the type and text ``_eval_frame_rules``
+    raises for the corresponding status word, spelled out here once more; kind 0 is no error."""
+    from mvoscalerecovery_amd import _lib, height_pitch as hp
+    from mvoscalerecovery_amd.hp_resident import frame_error
+    at = "" if budget is None else " at budget 20"
+    index_text = "too many indices for array: array is 1-dimensional, but 2 were indexed"
+    cases = [(_lib.HPT_ERR_SINGULAR, hp.ST_ERR_SINGULAR, 0, np.linalg.LinAlgError, "Singular matrix"),
+             (_lib.HPT_ERR_MASK, hp.ST_ERR_MASK, 0, ValueError, "frame 7: a triangle names a vertex outside the frame"),
+             (_lib.HPT_ERR_EMPTY, hp.ST_ERR_EMPTY, 0, ValueError, "frame 7: no features or no triangles"),
+             (_lib.HPT_ERR_NO_MODEL, hp.ST_RS_FEW, hp.MIN_POINTS, ValueError, "frame 7: no sample of the RANSAC had an inlier" + at),
+             (_lib.HPT_ERR_NO_PREVIOUS, hp.ST_RS_FEW, hp.MIN_POINTS - 1, IndexError, index_text)]
+    for kind, status, n_sel, exc, text in cases:
+        got = frame_error(kind, 7, budget)
+        assert type(got) is exc and str(got) == text, kind
+        with pytest.raises(exc) as info:
+            hp._eval_frame_rules(7, 0.0, np.array([0, status, 0]), n_sel, None, None, budget)
+        assert type(info.value) is exc and str(info.value) == text, kind
+    got = frame_error(_lib.HPT_ERR_STATUS, 7, budget)
+    assert type(got) is RuntimeError and str(got) == "frame 7: the tail stopped with error 6"
+    assert frame_error(0, 7, budget) is None
